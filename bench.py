@@ -7,6 +7,10 @@ reference); the N normalised partial points are all-gathered (RCCL via torch.dis
 op) and summed.  One "step" = one full MSM over all N*2^20 points.  Inputs are resident in HBM before the timed region.
 
 Prints ONE JSON line (rank 0).  `value` = algorithmic GB/s = 96 B/point * points / wall time.
+
+A plain run sets up, warms up, times the --steps steps and prints the line (its `roofline` comes from the timed steps' own events).
+Every other leg (the resident-scalars comparisons, the CPU baseline, the NTT / config-5 / prove extras, and at N GPUs the prover replicas
+and config 5) runs only under --full.  --dump-outputs DIR writes the last timed step's result for output-for-output comparison of builds.
 """
 import argparse
 import gc
@@ -371,7 +375,16 @@ def main():
     ap.add_argument("--config5-reference", action="store_true", help="also time the whole 2^26-point MSM of BASELINE configs[4] on ONE GPU (6 GB of inputs; the strong-scaling reference for the 8 x 2^23 run)")
     ap.add_argument("--no-northstar", action="store_true", help="skip the second prove leg (37 payloads, m = 2^20: the north star's 2^20-constraint case)")
     ap.add_argument("--prove-logm", type=int, default=18, help="log2 of the evaluation domain of the prove leg: 18 = 8 payloads (BASELINE configs[3]), 20 = 37 payloads (the north star's 2^20-constraint case)")
+    ap.add_argument("--full", action="store_true", help="run every leg beside the headline steps (resident-scalars legs, CPU baseline, extras; at N GPUs the prover "
+                                                        "replicas and config 5); --headline-only, --no-cpu-baseline and --no-extras drop parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's result point to DIR/msm_g1_point.npy: its 12 64-bit limbs (X, Y, Z as the C ABI "
+                                                          "returns them) as 24 little-endian 32-bit words in float64, shape (3, 8), exact")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    resident_legs = args.full and not args.headline_only
+    with_cpu = args.full and not args.no_cpu_baseline
+    with_extras = args.full and not args.no_extras
     gc.disable()        # the interpreter's cyclic collector pauses for tens of ms every few hundred calls (tools/prove_outliers.py): not the product's latency
 
     # stdout carries exactly ONE JSON line: libraries that print banners (RCCL prints its version on first use) go to stderr
@@ -459,13 +472,16 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "msm_g1_point.npy"), np.asarray(result, dtype=np.uint64).view(np.uint32).astype(np.float64).reshape(3, 8))
     kern_ms, launches = zkg.timing_dominant_ms()
     kern_ms = kern_ms * launches / max(1, args.steps)                        # the accumulation's launches of one step (one per piece) added up
     same_everywhere = all_ranks_same(torch, dist, result, use_dist)          # outside the timed region
     # the same step with the scalars already in HBM (rounds 1-3's headline), and with ONE upload followed by the resident call (what the
     # piece-wise entry point replaces) — reported beside `value`, same result required
     resident = None
-    if world == 1 and not args.headline_only:
+    if world == 1 and resident_legs:
         for _ in range(4):                                   # (the job's buffers grow from the pieces' sizes to the whole vector's on the first calls)
             step_resident()
         zkg.timing_reset()
@@ -541,7 +557,7 @@ def main():
         except Exception:
             pass
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and with_cpu:
         # CPU baseline: the oracle's restatement of libff multi_exp<BDLO12> (kind "port": reference libsnark is an absent submodule),
         # timed on this host on the SAME 2^logn-point workload; also used to check the GPU result.
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -561,11 +577,11 @@ def main():
                                           f"({cpu_dt:.2f} s) — mirrors the reference default MULTICORE=OFF",
                                 "value_all_cores": round(BYTES_PER_POINT * sample_n / cpu_dt_mt / 1e9, 5), "cores_all": threads,
                                 "seconds_all_cores": round(cpu_dt_mt, 3), "gpu_matches_cpu": parity and bool(np.array_equal(ref_mt, ref))}
-    if rank == 0 and world == 1 and not args.no_extras:
-        line["extras"] = extras(zkg, torch, args, not args.no_cpu_baseline)
+    if rank == 0 and world == 1 and with_extras:
+        line["extras"] = extras(zkg, torch, args, with_cpu)
         line["proofs_per_sec"] = line["extras"]["groth16_prove"]["proofs_per_sec"]          # the other half of BASELINE.json's metric
         line["proofs_per_sec_three_callers"] = line["extras"]["groth16_prove"]["three_callers_one_key"]["proofs_per_sec"]   # same key, three host threads
-    if (world > 1 or (use_dist and os.environ.get("ZKG_BENCH_TEST_REPLICAS"))) and not args.no_extras:      # the env switch lets one GPU rehearse this branch
+    if (world > 1 or (use_dist and os.environ.get("ZKG_BENCH_TEST_REPLICAS"))) and with_extras:      # the env switch lets one GPU rehearse this branch
         # the prover does not shard (replicas only): every rank proves the same 8-payload credential on its own GPU
         # with its own resident key; the job's proofs/sec is the sum over ranks
         try:
@@ -578,7 +594,7 @@ def main():
         if rank == 0 and int(pps[1].item()) == world:
             line["proofs_per_sec"] = round(float(pps[0].item()), 3)
             line["proofs_per_sec_note"] = f"{world} independent prover replicas (one per GPU), zklaim gadget, 8 payloads, m = 2^18"
-    if (world > 1 or (use_dist and os.environ.get("ZKG_BENCH_TEST_REPLICAS"))) and not args.no_extras:      # (the env switch lets one GPU rehearse this branch)
+    if (world > 1 or (use_dist and os.environ.get("ZKG_BENCH_TEST_REPLICAS"))) and with_extras:      # (the env switch lets one GPU rehearse this branch)
         # BASELINE configs[4]: 2^23 points per GPU (2^26 at 8 GPUs), same exchange; every rank takes part, rank 0 reports
         # (msm_leg agrees on every rank's setup before its first collective and returns None on all ranks if one of them failed)
         c5 = msm_leg(zkg, torch, dist, 23, 0x100 * rank, 3, use_dist, world)

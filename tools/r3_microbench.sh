@@ -22,7 +22,7 @@ assert n >= 4
 print(f"29-bit product: {n} vectors equal a*b*2^-261 mod q")
 PY
 cat $OUT/mul_variants.txt
-timeout -k 10 300 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE --output-format csv -d $OUT/grbm -o g -- python3 bench.py --no-cpu-baseline --no-extras --steps 10 --warmup 3 > $OUT/bench_grbm.json 2> $OUT/bench_grbm.err || { echo "grbm failed"; tail -5 $OUT/bench_grbm.err; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE --output-format csv -d $OUT/grbm -o g -- python3 bench.py --full --no-cpu-baseline --no-extras --steps 10 --warmup 3 > $OUT/bench_grbm.json 2> $OUT/bench_grbm.err || { echo "grbm failed"; tail -5 $OUT/bench_grbm.err; exit 1; }
 python3 - $OUT/grbm <<'PY'
 import csv, glob, sys, collections
 rows = []

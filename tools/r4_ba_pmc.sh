@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 L=${1:-3}
 OUT=gpurun_out/r4_ba
 mkdir -p $OUT
-pass() { tag=$1; shift; timeout -k 10 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/pmc_$tag -o p -- python3 bench.py --no-cpu-baseline --no-extras --steps 3 --warmup 1 > $OUT/pmc_$tag.json 2> $OUT/pmc_$tag.err || { tail -5 $OUT/pmc_$tag.err; exit 1; }; }
+pass() { tag=$1; shift; timeout -k 10 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/pmc_$tag -o p -- python3 bench.py --full --no-cpu-baseline --no-extras --steps 3 --warmup 1 > $OUT/pmc_$tag.json 2> $OUT/pmc_$tag.err || { tail -5 $OUT/pmc_$tag.err; exit 1; }; }
 export ZKG_ACCUM_BA=$L
 pass ba_fetch FETCH_SIZE
 pass ba_write WRITE_SIZE

@@ -6,7 +6,7 @@ OUT=gpurun_out/r4_pieces2
 mkdir -p $OUT
 timeout -k 10 300 python -m pytest tests/test_gpu_msm.py -m gpu -x -q -k "host_scalars or vs_oracle or adversarial" > $OUT/tests.log 2>&1 || { tail -20 $OUT/tests.log; exit 1; }
 tail -2 $OUT/tests.log
-run() { tag=$1; shift; env "$@" timeout -k 10 300 python3 bench.py --no-extras --no-cpu-baseline --steps 20 --warmup 5 > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err || { tail -5 $OUT/bench_$tag.err; exit 1; }; }
+run() { tag=$1; shift; env "$@" timeout -k 10 300 python3 bench.py --full --no-extras --no-cpu-baseline --steps 20 --warmup 5 > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err || { tail -5 $OUT/bench_$tag.err; exit 1; }; }
 run one_p3 ZKG_MSM_PIECES_ONE_STREAM=1 ZKG_MSM_PIECES=3
 for p in 2 3 4 5; do run two_p$p ZKG_MSM_PIECES=$p; done
 python3 - <<'PY'

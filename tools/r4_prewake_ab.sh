@@ -10,7 +10,7 @@ timeout -k 10 300 python -m pytest tests/test_gpu_msm.py -m gpu -x -q -k "host_s
 tail -1 $OUT/tests.log
 for tag in pre none pre none; do
   if [ $tag = pre ]; then export ZKG_POOL_PREWAKE=1; else unset ZKG_POOL_PREWAKE; fi
-  timeout -k 10 300 python3 bench.py --no-extras --no-cpu-baseline --steps 40 --warmup 5 > $OUT/bench_$tag.json 2> $OUT/err_$tag.log || { tail -5 $OUT/err_$tag.log; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --no-extras --no-cpu-baseline --steps 40 --warmup 5 > $OUT/bench_$tag.json 2> $OUT/err_$tag.log || { tail -5 $OUT/err_$tag.log; exit 1; }
   python3 -c "
 import json; j=json.load(open('$OUT/bench_$tag.json')); print('$tag: value', j['value'], 'median', j['ms_per_step_stats']['median'], 'min', j['ms_per_step_stats']['min'], 'resident median', j['scalars_resident']['ms_per_step']['median'])"
   ZKG_DEBUG_TIMING=1 timeout -k 10 200 python3 bench.py --no-extras --no-cpu-baseline --headline-only --steps 6 --warmup 3 2>&1 | grep -i "job finish" | tail -2 | sed "s/^/$tag /"

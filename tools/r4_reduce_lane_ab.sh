@@ -9,7 +9,7 @@ timeout -k 10 500 python -m pytest tests/test_gpu_msm.py tests/test_gpu_baseline
 tail -2 $OUT/tests.log
 for tag in lane pair lane pair; do
   if [ $tag = pair ]; then export ZKG_REDUCE_PAIR=1; else unset ZKG_REDUCE_PAIR; fi
-  timeout -k 10 300 python3 bench.py --no-extras --no-cpu-baseline --steps 30 --warmup 5 > $OUT/bench_$tag.json 2> $OUT/err_$tag.log || { tail -5 $OUT/err_$tag.log; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --no-extras --no-cpu-baseline --steps 30 --warmup 5 > $OUT/bench_$tag.json 2> $OUT/err_$tag.log || { tail -5 $OUT/err_$tag.log; exit 1; }
   python3 -c "
 import json; j=json.load(open('$OUT/bench_$tag.json')); print('$tag: value', j['value'], 'median', j['ms_per_step_stats']['median'], 'resident median', j['scalars_resident']['ms_per_step']['median'])"
 done

@@ -18,23 +18,23 @@ fi
 bash tools/pmc_collect.sh > $OUT/pmc_collect.log 2>&1 || { tail -5 $OUT/pmc_collect.log; exit 1; }
 cp profiles/pmc_traffic.json $OUT/pmc_traffic.json
 echo "pmc done"
-timeout -k 10 700 python bench.py > $OUT/${R}_bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+timeout -k 10 700 python bench.py --full > $OUT/${R}_bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 echo "bench done"
 # headline MSM: per-kernel durations of the same command (no CPU legs, no extras)
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kstats -o b -- python3 bench.py --no-cpu-baseline --no-extras --steps 5 > $OUT/${R}_bench_under_rocprof.json 2> $OUT/rocprof.err || exit 1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kstats -o b -- python3 bench.py --full --no-cpu-baseline --no-extras --steps 5 > $OUT/${R}_bench_under_rocprof.json 2> $OUT/rocprof.err || exit 1
 cp $OUT/kstats/b_kernel_stats.csv $OUT/${R}_bench_kernel_stats.csv
 # ... and of the headline step alone (no resident-scalars legs: every launch belongs to a piece-wise step)
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kstats_h -o b -- python3 bench.py --no-cpu-baseline --no-extras --headline-only --steps 10 > $OUT/${R}_bench_headline_only_under_rocprof.json 2> $OUT/rocprof_h.err || exit 1
 cp $OUT/kstats_h/b_kernel_stats.csv $OUT/${R}_bench_headline_only_kernel_stats.csv
 # SQ counters of the accumulation and the reduction (own --pmc pass)
-timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_SALU --output-format csv -d $OUT/sq -o p -- python3 bench.py --no-cpu-baseline --no-extras --steps 3 --warmup 1 > $OUT/sq_bench.json 2> $OUT/sq.err || { tail -5 $OUT/sq.err; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_SALU --output-format csv -d $OUT/sq -o p -- python3 bench.py --full --no-cpu-baseline --no-extras --steps 3 --warmup 1 > $OUT/sq_bench.json 2> $OUT/sq.err || { tail -5 $OUT/sq.err; exit 1; }
 python3 - $OUT/sq <<'PY' > $OUT/${R}_accum_reduce_sq_counters.txt
 import csv, glob, sys, collections
 agg = collections.defaultdict(lambda: collections.defaultdict(list))
 for f in glob.glob(sys.argv[1] + "/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         agg[r["Kernel_Name"].split("(")[0].replace("void ", "").strip()][r["Counter_Name"]].append(float(r["Counter_Value"]))
-print("SQ counters per launch (averages over the launches of `bench.py --no-cpu-baseline --no-extras --steps 3 --warmup 1`: the piece-wise headline steps — one accumulation launch per piece (four), beside the next piece's sort — and the resident-scalars legs — one launch, alone)")
+print("SQ counters per launch (averages over the launches of `bench.py --full --no-cpu-baseline --no-extras --steps 3 --warmup 1`: the piece-wise headline steps — one accumulation launch per piece (four), beside the next piece's sort — and the resident-scalars legs — one launch, alone)")
 for k, v in sorted(agg.items()):
     if "accum29" in k or "reduce29" in k or "k_rx" in k or "k_digits" in k:
         wc = sum(v["SQ_WAVE_CYCLES"]) / len(v["SQ_WAVE_CYCLES"])
