@@ -282,6 +282,26 @@ size_t zkg_keypair_vk_blob(const zkg_keypair *kp, uint8_t *out, size_t cap);
 int zkg_groth16_verify(const uint8_t *vk_blob, size_t vk_len, const uint64_t *primary_input, size_t n_inputs,
                        const uint8_t *proof, size_t proof_len);
 int zkg_pairing_probe(const uint64_t a[4], const uint64_t b[4], uint8_t out[384]);   /* e(a*G1, b*G2), for bilinearity tests */
+/* ---- batch verification on the GPU.  One item = one zkg_groth16_verify call; items may name different keys (grouped by the
+ *      vk's bytes).  verdicts[i] = what zkg_groth16_verify would return for items[i] (0 valid, 1 invalid, 2 malformed vk), except
+ *      with probability at most (number of combined checks) * 2^-128: the proofs of one key are checked together as one random
+ *      linear combination (128-bit weights drawn from std::random_device on every call), a failed combination is bisected, and
+ *      whatever the combination cannot decide soundly (malformed or unusual keys, wrong sizes, bad encodings, B outside G2) goes
+ *      through zkg_groth16_verify's own code.  Synchronous; host pointers; safe to call from several threads at once.
+ *      Returns ZKG_OK when every verdict was written, ZKG_ERROR on a null argument, a HIP failure or no GPU (zkg_init).    */
+typedef struct zkg_verify_item {
+    const uint8_t  *vk_blob;       size_t vk_len;      /* as zkg_groth16_verify                          */
+    const uint64_t *primary_input; size_t n_inputs;    /* n_inputs x 4 limbs, Montgomery Fr              */
+    const uint8_t  *proof;         size_t proof_len;   /* ZKG_PROOF_BYTES, libsnark compressed layout    */
+} zkg_verify_item;
+int zkg_groth16_verify_batch(const zkg_verify_item *items, size_t count, uint8_t *verdicts);
+/* test hook: what the calling thread's last zkg_groth16_verify_batch did — out[0] combined checks, out[1] items decided by
+ * zkg_groth16_verify's own code, out[2] of those, items whose B failed the GPU's G2 membership test ([r]B == O)                  */
+void zkg_verify_batch_stats(size_t out[3]);
+/* reduced pairing product FE(prod_i ML(g1[i], g2[i])) of n affine pairs (8 / 16 Montgomery limbs each, all-zero = infinity, which
+ * contributes 1), serialised as zkg_pairing_probe's output.  Miller loops and their product on the GPU, the final exponentiation on
+ * the host.  ZKG_ERROR for a point off its curve or a coordinate >= q.                                                          */
+int zkg_pairing_product(const uint64_t *g1_affine, const uint64_t *g2_affine, size_t n, uint8_t out[384]);
 /* test hook: Frobenius maps and the last chunk of the final exponentiation against plain square-and-multiply by q^k and by
  * the integer e (nlimbs x u32, little-endian); 0 = all agree */
 int zkg_pairing_selfcheck(const uint32_t *e, int nlimbs);

@@ -23,6 +23,7 @@ DECLARED_SYMBOLS = [
     "zkg_compat_reset", "zkg_field_op", "zkg_init_multi", "zkg_msm_g1_shards_upload", "zkg_msm_g1_shards_free", "zkg_msm_g1_shards_count",
     "zkg_msm_g1_multi", "zkg_g1_add_quad29", "zkg_crs_shard_h", "zkg_msm_g1_bases_upload", "zkg_msm_g1_resident", "zkg_msm_g1_bases_free",
     "zkg_prover_peak_in_flight", "zkg_msm_g1_host_scalars", "zkg_multi_rccl_calls", "zkg_g1_add_pair29",
+    "zkg_groth16_verify_batch", "zkg_pairing_product", "zkg_verify_batch_stats",
 ]
 # the reference's own seam, exported with its original names (zklaim.h:257-259)
 COMPAT_SYMBOLS = ["libsnark_trusted_setup", "libsnark_prove", "libsnark_verify"]
@@ -581,6 +582,47 @@ def groth16_verify(vk_blob, primary_input, proof):
 def pairing_probe(a, b):
     out = np.zeros(384, np.uint8)
     lib().zkg_pairing_probe(_p(_u64(a)), _p(_u64(b)), _p(out))
+    return out.tobytes()
+
+
+class VerifyItem(C.Structure):
+    _fields_ = [("vk_blob", C.c_void_p), ("vk_len", C.c_size_t), ("primary_input", C.c_void_p), ("n_inputs", C.c_size_t),
+                ("proof", C.c_void_p), ("proof_len", C.c_size_t)]
+
+
+def groth16_verify_batch(items):
+    """items: (vk_blob, primary_input, proof) triples.  Returns a uint8 array: verdicts[i] == groth16_verify(*items[i]) (0 valid,
+    1 invalid, 2 malformed key), checked on the GPU as random linear combinations per key.  Raises ZkgError when the call fails."""
+    L = lib()
+    L.zkg_groth16_verify_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+    arr = (VerifyItem * max(1, len(items)))()
+    keep = []
+    for k, (vk_blob, primary_input, proof) in enumerate(items):
+        vk = np.frombuffer(bytes(vk_blob), np.uint8); pr = np.frombuffer(bytes(proof), np.uint8); x = _u64(primary_input)
+        keep += [vk, pr, x]
+        arr[k] = VerifyItem(vk.ctypes.data if vk.size else None, vk.size, x.ctypes.data if x.size else None, x.size // 4,
+                            pr.ctypes.data if pr.size else None, pr.size)
+    verdicts = np.full(max(1, len(items)), 0xFF, np.uint8)
+    _check(L.zkg_groth16_verify_batch(C.cast(arr, C.c_void_p), len(items), _p(verdicts)), "zkg_groth16_verify_batch")
+    return verdicts[:len(items)]
+
+
+def verify_batch_stats():
+    """(combined checks, items decided by the single verifier's code, of those: B outside G2) of this thread's last groth16_verify_batch"""
+    out = (C.c_size_t * 3)()
+    lib().zkg_verify_batch_stats(out)
+    return tuple(int(v) for v in out)
+
+
+def pairing_product(g1, g2):
+    """FE(prod_i ML(g1[i], g2[i])): g1 (n, 8), g2 (n, 16) affine Montgomery limbs (all-zero = infinity); 384 bytes as pairing_probe"""
+    a = _u64(g1).reshape(-1, 8); b = _u64(g2).reshape(-1, 16)
+    if a.shape[0] != b.shape[0]:
+        raise ZkgError("pairing_product: g1 and g2 differ in length")
+    out = np.zeros(384, np.uint8)
+    L = lib()
+    L.zkg_pairing_product.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    _check(L.zkg_pairing_product(_p(a) if a.size else None, _p(b) if b.size else None, a.shape[0], _p(out)), "zkg_pairing_product")
     return out.tobytes()
 
 

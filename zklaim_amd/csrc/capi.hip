@@ -280,7 +280,8 @@ __global__ __launch_bounds__(64) void k_add_quad29(const XYZZ<Fq> *a, const XYZZ
 }
 
 static std::mutex g_init_mu;
-static int g_device = -1;
+static std::atomic<int> g_device{-1};                     // written under g_init_mu, read by entry points on any thread
+int initialised_device() { return g_device.load(); }
 static void kernels_configure() { (void)ntt_configure(); (void)msm_configure(); }
 
 }  // namespace zk
@@ -308,6 +309,7 @@ void zkg_shutdown(void) {
     (void)hipDeviceSynchronize();
     ntt_release_all();
     msm_release_all();
+    verify_release_all();
     g_device = -1;
 }
 const char *zkg_last_error(void) { std::lock_guard<std::mutex> lk(g_err_mu); static std::string copy; copy = g_error; return copy.c_str(); }

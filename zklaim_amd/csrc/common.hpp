@@ -186,6 +186,22 @@ int msm_configure();
 int compress_g1_records(const G1Affine *d_in, size_t n, uint8_t *d_out, hipStream_t s);
 int compress_kc_records(const G2Affine *d_g2, const G1Affine *d_g1, const uint32_t *d_idx, size_t nidx, uint8_t *d_out, hipStream_t s);
 
+// ---------------- batch verification kernels (verify.hip) ----------------
+// one lane per item.  ok[i] = 1 iff [r]B_i == O; out[i] = w_i P_i (w: n x 4 u32, 128-bit weights, little-endian) in affine form;
+// Miller values ML(P_i, Q_i) as 384-byte Fq12 (1 where a point is infinity or use[i] == 0; use optional)
+static constexpr size_t VERIFY_PROD_BLOCKS = 64;         // the range product's first launch: at most this many partial Fq12
+int verify_g2_subgroup(const G2Affine *d_B, size_t n, uint8_t *d_ok, hipStream_t s);
+int verify_g1_mul128(const G1Affine *d_in, const uint32_t *d_w, size_t nw, size_t n, G1Affine *d_out, hipStream_t s);   // lane i: weight i mod nw
+int verify_miller(const G1Affine *d_P, const G2Affine *d_Q, const uint8_t *d_use, size_t n, void *d_out, hipStream_t s);
+int verify_fq12_product(const void *d_in, size_t lo, size_t hi, void *d_partial, void *d_out, hipStream_t s);   // d_out[0] = prod d_in[lo, hi)
+int initialised_device();                                // the device zkg_init selected, -1 before (capi.hip)
+// a batch call's device workspace: grow-only buffer, two streams (the subgroup check runs beside the scalar multiplications), two events
+struct VerifyWorkspace { DevBuf buf; hipStream_t s = nullptr, s2 = nullptr; hipEvent_t ev = nullptr, ev2 = nullptr; };
+VerifyWorkspace *verify_workspace_acquire();             // a free one or a new one; null on a HIP failure (message set)
+void verify_workspace_release(VerifyWorkspace *w);       // back to the free list (null: nothing)
+void verify_workspace_destroy(VerifyWorkspace *w);
+void verify_release_all();                               // zkg_shutdown: the free workspaces' buffers, streams and events
+
 // ---------------- ABI encodings (capi.cpp) ----------------
 void store_norm(uint64_t *out, const G1 &p);   // normalised jac, 12 limbs
 void store_norm(uint64_t *out, const G2 &p);   // 24 limbs

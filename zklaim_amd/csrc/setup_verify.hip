@@ -23,9 +23,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <random>
+#include <sys/random.h>
 
 using namespace zk;
 using zk::pairing::Fq12;
+using zk::pairing::Fq6;
 
 struct zkg_keypair {
     // the (possibly swapped) constraint system stored in the pk
@@ -337,6 +339,7 @@ struct PreparedVk {
     Fq12 alpha_beta; G2Affine gamma_g2, delta_g2; G1Affine ic0; size_t domain = 0;
     std::vector<size_t> idx; std::vector<G1Affine> ic;                          // gamma_ABC: indices and decompressed values
     std::vector<pairing::LineCoeff> gamma_lines, delta_lines;                   // empty when the point is infinity
+    mutable std::once_flag batch_once; mutable bool batchable = false;          // vk_batchable, computed on the first batch call that meets the key
 };
 static int prepare_vk(const uint8_t *vk_blob, size_t vk_len, PreparedVk &v) {   // 0, or 2 = malformed (message set)
     ser::Reader rd{vk_blob, vk_blob + vk_len};
@@ -386,36 +389,42 @@ static std::shared_ptr<const PreparedVk> prepared_vk(const uint8_t *vk_blob, siz
     return v;
 }
 
+// sum_k x_k * IC_k over the key's gamma_ABC entries (Montgomery scalars x_k from scalar_of(k, x)), in up to 16 chunks on the host pool.
+// A chunk shares its doublings (Straus, one bit at a time: 254 doublings and on average 127 mixed additions per point instead of a
+// double-and-add per point): 0.67 -> 0.3 ms at 20 payloads' 102 inputs.
+static G1 ic_combination(const PreparedVk &vk, const std::function<void(size_t, Fr &)> &scalar_of) {
+    const size_t nidx = vk.idx.size();
+    const int chunks = (int)std::min<size_t>(16, nidx);
+    std::vector<G1> part(std::max(chunks, 1), G1::inf());
+    host_parallel_for(chunks, [&](int c) {
+        const size_t lo = nidx * (size_t)c / chunks, hi = nidx * (size_t)(c + 1) / chunks, cnt = hi - lo;
+        std::vector<uint32_t> e(8 * cnt);
+        for (size_t k = lo; k < hi; ++k) { Fr x; scalar_of(k, x); fr_limbs(x, &e[8 * (k - lo)]); }
+        const G1Affine *pt = vk.ic.data() + lo;
+        G1 a = G1::inf();
+        for (int bit = 255; bit >= 0; --bit) {
+            a = a.dbl();
+            for (size_t j = 0; j < cnt; ++j) if ((e[8 * j + (bit >> 5)] >> (bit & 31)) & 1u) a.madd(pt[j]);
+        }
+        part[c] = a;
+    });
+    G1 acc = G1::inf();
+    for (int c = 0; c < chunks; ++c) acc.add(part[c]);
+    return acc;
+}
+
 static int groth16_verify_impl(const uint8_t *vk_blob, size_t vk_len, const uint64_t *primary_input, size_t n_inputs, const uint8_t *proof, size_t proof_len) {
     if (!vk_blob || !proof || (n_inputs && !primary_input)) { set_error("zkg_groth16_verify: null argument"); return 2; }
     int rc = 0;
     const std::shared_ptr<const PreparedVk> vk = prepared_vk(vk_blob, vk_len, rc);
     if (!vk) return rc;
-    const size_t nidx = vk->idx.size();
     if (vk->domain != n_inputs) return 1;                                       // strong input consistency: sizes must agree
     if (proof_len != ZKG_PROOF_BYTES) return 1;
     G1Affine pA, pC; G2Affine pB;
     if (!ser::get_g1(proof, pA) || !ser::get_g2(proof + 34, pB) || !ser::get_g1(proof + 100, pC)) return 1;     // is_well_formed
     // acc = IC_0 + sum_i input_i * IC_{i+1}
     G1 acc = G1::from_affine(vk->ic0);
-    {   // sum_i input_i * IC_{i+1} in up to 16 chunks on the host pool.  A chunk shares its doublings (Straus, one bit at a time: 254 doublings
-        // and on average 127 mixed additions per point instead of a double-and-add per point): 0.67 -> 0.3 ms at 20 payloads' 102 inputs.
-        const int chunks = (int)std::min<size_t>(16, nidx);
-        std::vector<G1> part(std::max(chunks, 1), G1::inf());
-        host_parallel_for(chunks, [&](int c) {
-            const size_t lo = nidx * (size_t)c / chunks, hi = nidx * (size_t)(c + 1) / chunks, cnt = hi - lo;
-            std::vector<uint32_t> e(8 * cnt);
-            for (size_t k = lo; k < hi; ++k) { Fr x; memcpy(x.v, primary_input + 4 * vk->idx[k], 32); fr_limbs(x, &e[8 * (k - lo)]); }
-            const G1Affine *pt = vk->ic.data() + lo;
-            G1 a = G1::inf();
-            for (int bit = 255; bit >= 0; --bit) {
-                a = a.dbl();
-                for (size_t j = 0; j < cnt; ++j) if ((e[8 * j + (bit >> 5)] >> (bit & 31)) & 1u) a.madd(pt[j]);
-            }
-            part[c] = a;
-        });
-        for (int c = 0; c < chunks; ++c) acc.add(part[c]);
-    }
+    acc.add(ic_combination(*vk, [&](size_t k, Fr &x) { memcpy(x.v, primary_input + 4 * vk->idx[k], 32); }));
     // e(A, B) == e(alpha, beta) * e(acc, gamma) * e(C, delta)   <=>   FE( ML(A,B) * ML(-acc, gamma) * ML(-C, delta) ) == alpha_beta
     // (three loops in lock-step; the lines of gamma and delta come from the prepared key, only B's are computed here)
     G1Affine accA = acc.to_affine();
@@ -430,6 +439,280 @@ int zkg_groth16_verify(const uint8_t *vk_blob, size_t vk_len, const uint64_t *pr
     try { return groth16_verify_impl(vk_blob, vk_len, primary_input, n_inputs, proof, proof_len); }       // nothing propagates through the C boundary
     catch (const std::exception &e) { set_error(std::string("zkg_groth16_verify: ") + e.what()); return 2; }
     catch (...) { set_error("zkg_groth16_verify: unexpected exception"); return 2; }
+}
+
+// ---- batch verification (zkg_groth16_verify_batch).  For the N proofs of one key, with fresh 128-bit weights r_i:
+//   FE( prod_i ML(r_i A_i, B_i) * ML(-sum_i r_i acc_i, gamma) * ML(-sum_i r_i C_i, delta) ) == alpha_beta ^ (sum_i r_i),
+//   sum_i r_i acc_i = (sum_i r_i) IC_0 + sum_j s_j IC_j,  s_j = sum_i r_i x_ij.
+// The GPU (verify.hip) checks B_i in G2, computes r_i A_i and r_i C_i and the per-proof Miller values, and multiplies the Miller values of
+// any index range; the host adds the r_i C_i, forms the s_j, runs the two Miller loops on the key's prepared lines, one final exponentiation
+// and one GT power.  A failed range is halved until VERIFY_LEAF proofs or fewer are left, which zkg_groth16_verify's own code decides.
+static constexpr size_t VERIFY_LEAF = 4;
+
+static bool limbs_below(const uint32_t *x, const uint32_t *m) {            // x < m, 8 little-endian u32 limbs
+    for (int i = 7; i >= 0; --i) if (x[i] != m[i]) return x[i] < m[i];
+    return false;
+}
+static bool coords_canonical(const uint8_t *rec, int nfq) {                // the x coordinate's limbs of a compressed point are < q
+    if (rec[0] == '1') return true;                                         // infinity: nothing else is read
+    for (int k = 0; k < nfq; ++k) { uint32_t x[8]; memcpy(x, rec + 1 + 32 * k, 32); if (!limbs_below(x, FqParams::P)) return false; }
+    return true;
+}
+// what the combination needs of a key beyond what the single verifier checks: gamma and delta in G2, alpha_beta of order r (then it lies
+// in the cyclotomic subgroup, and alpha_beta^(sum r_i) can be taken with cyclotomic squarings)
+static bool vk_batchable(const PreparedVk &vk) {
+    const uint32_t *r = FrParams::P;
+    auto canon = [](const Fq &x) { return limbs_below(x.v, FqParams::P); };  // the single verifier reads limbs >= q too; only canonical keys enter
+    auto canon2 = [&](const Fq2 &x) { return canon(x.c0) && canon(x.c1); };
+    for (const Fq6 *h : {&vk.alpha_beta.c0, &vk.alpha_beta.c1}) if (!canon2(h->c0) || !canon2(h->c1) || !canon2(h->c2)) return false;
+    if (!canon2(vk.gamma_g2.x) || !canon2(vk.gamma_g2.y) || !canon2(vk.delta_g2.x) || !canon2(vk.delta_g2.y) || !canon(vk.ic0.x) || !canon(vk.ic0.y)) return false;
+    for (const G1Affine &q : vk.ic) if (!canon(q.x) || !canon(q.y)) return false;
+    if (!G2::from_affine(vk.gamma_g2).mul(r, 8).is_inf() || !G2::from_affine(vk.delta_g2).mul(r, 8).is_inf()) return false;
+    return vk.alpha_beta.pow(r, 8) == Fq12::one();
+}
+
+static bool vk_batchable_cached(const PreparedVk &vk) {
+    std::call_once(vk.batch_once, [&] { vk.batchable = vk_batchable(vk); });
+    return vk.batchable;
+}
+
+// 16 * n random bytes from the OS in as few requests as it allows (std::random_device on x86 issues one RDSEED per 32 bits: 4 per weight,
+// ~0.1 ms per proof on a host whose cores share the RDSEED unit); std::random_device where getrandom is not available
+static void draw_weights(uint32_t *w, size_t n) {
+    uint8_t *p = reinterpret_cast<uint8_t *>(w);
+    size_t left = 16 * n;
+    while (left) {
+        const ssize_t got = getrandom(p, left, 0);
+        if (got <= 0) break;
+        p += got; left -= (size_t)got;
+    }
+    if (left) { std::random_device rd; for (size_t i = 16 * n - left; i < 16 * n; i += 4) { uint32_t v = rd(); memcpy(reinterpret_cast<uint8_t *>(w) + i, &v, 4); } }
+    for (size_t i = 0; i < n; ++i)                                              // nonzero weights (a zero draw has probability 2^-128)
+        while (!(w[4 * i] | w[4 * i + 1] | w[4 * i + 2] | w[4 * i + 3])) { std::random_device rd; for (int j = 0; j < 4; ++j) w[4 * i + j] = rd(); }
+}
+
+// what the last zkg_groth16_verify_batch call of this thread did (zkg_verify_batch_stats)
+static thread_local size_t t_batch_stats[3] = {0, 0, 0};
+
+namespace {
+struct BatchGroup {
+    const uint8_t *blob; size_t len; uint64_t digest;
+    std::shared_ptr<const PreparedVk> vk; bool batchable = false;
+    std::vector<size_t> items;                                              // item indices, then the positions [lo, hi) of those that enter
+    size_t lo = 0, hi = 0;
+};
+struct WorkspaceLease {                       // returned to the free list on every way out (after the call's streams are idle)
+    VerifyWorkspace *w = nullptr;
+    ~WorkspaceLease() { if (w) { (void)hipStreamSynchronize(w->s); (void)hipStreamSynchronize(w->s2); verify_workspace_release(w); } }
+};
+}  // namespace
+
+static int verify_batch_impl(const zkg_verify_item *items, size_t count, uint8_t *verdicts) {
+    if (initialised_device() < 0) { set_error("zkg_groth16_verify_batch: zkg_init not called (no GPU: there is no CPU path)"); return ZKG_ERROR; }
+    if (count && (!items || !verdicts)) { set_error("zkg_groth16_verify_batch: null argument"); return ZKG_ERROR; }
+    size_t n_combined = 0, n_outside_g2 = 0;
+    t_batch_stats[0] = t_batch_stats[1] = t_batch_stats[2] = 0;
+    if (!count) return ZKG_OK;
+    // ZKG_VERIFY_BATCH_LAPS=1: the host clock at the end of each stage, on stderr (where a batch's time goes)
+    static const bool laps = getenv("ZKG_VERIFY_BATCH_LAPS") && atoi(getenv("ZKG_VERIFY_BATCH_LAPS")) != 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::string lap_line;
+    auto lap = [&](const char *what) {
+        if (laps) lap_line += std::string(" ") + what + "=" + std::to_string(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    };
+    struct PrintLaps { const std::string &l; size_t n; ~PrintLaps() { if (!l.empty()) fprintf(stderr, "[verify_batch] n=%zu ms:%s\n", n, l.c_str()); } } print_laps{lap_line, count};
+    std::vector<char> own(count, 0);                                        // decided by the single verifier's code
+    // 1. group by the key's bytes
+    std::vector<BatchGroup> groups; std::multimap<uint64_t, size_t> by_digest;
+    for (size_t i = 0; i < count; ++i) {
+        const zkg_verify_item &it = items[i];
+        if (!it.vk_blob) { own[i] = 1; continue; }
+        const uint64_t d = vk_digest(it.vk_blob, it.vk_len);
+        size_t g = groups.size();
+        for (auto r = by_digest.equal_range(d); r.first != r.second; ++r.first) {
+            const BatchGroup &c = groups[r.first->second];
+            if (c.len == it.vk_len && memcmp(c.blob, it.vk_blob, it.vk_len) == 0) { g = r.first->second; break; }
+        }
+        if (g == groups.size()) { groups.push_back(BatchGroup{it.vk_blob, it.vk_len, d}); by_digest.emplace(d, g); }
+        groups[g].items.push_back(i);
+    }
+    // 2. per key: prepared form (shared with zkg_groth16_verify's cache) and the checks the weights rely on, once per key
+    host_parallel_for((int)groups.size(), [&](int g) {
+        BatchGroup &G = groups[g];
+        try {
+            int rc = 0;
+            G.vk = prepared_vk(G.blob, G.len, rc);
+            G.batchable = G.vk && vk_batchable_cached(*G.vk);
+        } catch (...) { G.vk = nullptr; G.batchable = false; }              // the single verifier decides these items (and meets the same failure)
+    });
+    for (const BatchGroup &G : groups) if (!G.batchable) for (size_t i : G.items) own[i] = 1;
+    lap("keys");
+    // 3. per proof: sizes, encodings and inputs as the single verifier reads them; the proof's points decoded on the host pool
+    std::vector<G1Affine> hA(count), hC(count); std::vector<G2Affine> hB(count);
+    std::vector<int> group_of(count, -1);
+    for (size_t g = 0; g < groups.size(); ++g) for (size_t i : groups[g].items) group_of[i] = (int)g;
+    host_parallel_for((int)std::min<size_t>(64, count), [&](int c) {
+        for (size_t i = count * (size_t)c / std::min<size_t>(64, count); i < count * (size_t)(c + 1) / std::min<size_t>(64, count); ++i) {
+            if (own[i]) continue;
+            const zkg_verify_item &it = items[i];
+            const BatchGroup &G = groups[group_of[i]];
+            bool ok = it.proof && it.proof_len == ZKG_PROOF_BYTES && it.n_inputs == G.vk->domain && (!it.n_inputs || it.primary_input);
+            for (size_t j = 0; ok && j < it.n_inputs; ++j) {
+                uint32_t x[8]; memcpy(x, it.primary_input + 4 * j, 32);
+                ok = limbs_below(x, FrParams::P);
+            }
+            ok = ok && coords_canonical(it.proof, 1) && coords_canonical(it.proof + 34, 2) && coords_canonical(it.proof + 100, 1) &&
+                 ser::get_g1(it.proof, hA[i]) && ser::get_g2(it.proof + 34, hB[i]) && ser::get_g1(it.proof + 100, hC[i]);
+            if (!ok) own[i] = 1;
+        }
+    });
+    lap("decode");
+    // 4. layout: the entering proofs of each key at contiguous positions, a weight per position
+    std::vector<size_t> item_at;
+    for (BatchGroup &G : groups) {
+        G.lo = item_at.size();
+        for (size_t i : G.items) if (!own[i]) item_at.push_back(i);
+        G.hi = item_at.size();
+    }
+    const size_t N = item_at.size();
+    std::vector<G1Affine> pA(N), pC(N), rC(N); std::vector<G2Affine> pB(N); std::vector<uint32_t> w(4 * N); std::vector<Fr> wm(N);
+    draw_weights(w.data(), N);                                              // fresh on every call; no seed crosses the ABI
+    for (size_t p = 0; p < N; ++p) {
+        Fr x = Fr::zero(); memcpy(x.v, &w[4 * p], 16); wm[p] = x.to_mont();
+        pA[p] = hA[item_at[p]]; pB[p] = hB[item_at[p]]; pC[p] = hC[item_at[p]];
+    }
+    lap("weights");
+    std::vector<uint8_t> in_g2(N, 1);
+    std::vector<size_t> decide_alone;
+    if (N) {
+        // 5. the GPU part: B in G2 (second stream) beside r_i A_i and r_i C_i (one launch), then the Miller values
+        const size_t o_A = 0, o_C = o_A + 64 * N, o_B = o_C + 64 * N, o_rA = o_B + 128 * N, o_rC = o_rA + 64 * N, o_M = o_rC + 64 * N,
+                     o_part = o_M + 384 * N, o_out = o_part + 384 * VERIFY_PROD_BLOCKS, o_w = o_out + 384, o_ok = o_w + 16 * N, total = o_ok + N + 16;
+        WorkspaceLease lease;
+        if (!(lease.w = verify_workspace_acquire()) || lease.w->buf.reserve(total)) return ZKG_ERROR;
+        uint8_t *d = lease.w->buf.as<uint8_t>(); hipStream_t s = lease.w->s, s2 = lease.w->s2;
+        ZK_HIP(hipMemcpyAsync(d + o_B, pB.data(), 128 * N, hipMemcpyHostToDevice, s));
+        ZK_HIP(hipEventRecord(lease.w->ev, s));
+        ZK_HIP(hipStreamWaitEvent(s2, lease.w->ev, 0));
+        if (verify_g2_subgroup((const G2Affine *)(d + o_B), N, d + o_ok, s2)) return ZKG_ERROR;
+        ZK_HIP(hipEventRecord(lease.w->ev2, s2));
+        ZK_HIP(hipMemcpyAsync(d + o_A, pA.data(), 64 * N, hipMemcpyHostToDevice, s));      // A and C back to back: one launch for both
+        ZK_HIP(hipMemcpyAsync(d + o_C, pC.data(), 64 * N, hipMemcpyHostToDevice, s));
+        ZK_HIP(hipMemcpyAsync(d + o_w, w.data(), 16 * N, hipMemcpyHostToDevice, s));
+        if (verify_g1_mul128((const G1Affine *)(d + o_A), (const uint32_t *)(d + o_w), N, 2 * N, (G1Affine *)(d + o_rA), s)) return ZKG_ERROR;
+        ZK_HIP(hipStreamWaitEvent(s, lease.w->ev2, 0));
+        if (verify_miller((const G1Affine *)(d + o_rA), (const G2Affine *)(d + o_B), d + o_ok, N, d + o_M, s)) return ZKG_ERROR;
+        ZK_HIP(hipMemcpyAsync(in_g2.data(), d + o_ok, N, hipMemcpyDeviceToHost, s));
+        ZK_HIP(hipMemcpyAsync(rC.data(), d + o_rC, 64 * N, hipMemcpyDeviceToHost, s));
+        lap("upload_launch");
+        ZK_HIP(hipStreamSynchronize(s));
+        lap("gpu");
+        for (size_t p = 0; p < N; ++p) if (!in_g2[p]) { own[item_at[p]] = 1; ++n_outside_g2; }     // its Miller value is 1: the ranges stay contiguous
+        // 6. one combined check per range; a failed range is halved
+        auto combined = [&](const BatchGroup &G, size_t lo, size_t hi, bool &pass) -> int {
+            Fq12 prod;
+            if (verify_fq12_product(d + o_M, lo, hi, d + o_part, d + o_out, s)) return ZKG_ERROR;
+            ZK_HIP(hipMemcpyAsync(&prod, d + o_out, 384, hipMemcpyDeviceToHost, s));
+            std::vector<size_t> in;                                         // (the host work below runs while the product is computed)
+            for (size_t p = lo; p < hi; ++p) if (in_g2[p]) in.push_back(p);
+            Fr rsum = Fr::zero();
+            for (size_t p : in) rsum += wm[p];
+            const int chunks = (int)std::min<size_t>(16, in.size());
+            std::vector<G1> part(std::max(chunks, 1), G1::inf());
+            host_parallel_for(chunks, [&](int c) {
+                G1 a = G1::inf();
+                for (size_t t = in.size() * c / chunks; t < in.size() * (c + 1) / chunks; ++t) a.madd(rC[in[t]]);
+                part[c] = a;
+            });
+            G1 csum = G1::inf();
+            for (const G1 &q : part) csum.add(q);
+            const PreparedVk &vk = *G.vk;
+            G1 acc = G1::from_affine(vk.ic0);
+            { uint32_t e[8]; fr_limbs(rsum, e); acc = acc.mul(e, 8); }
+            acc.add(ic_combination(vk, [&](size_t k, Fr &x) {              // s_k = sum_i r_i x_ik
+                Fr sk = Fr::zero();
+                for (size_t p : in) { Fr xi; memcpy(xi.v, items[item_at[p]].primary_input + 4 * vk.idx[k], 32); sk += wm[p] * xi; }
+                x = sk;
+            }));
+            std::vector<G1Affine> Ps; std::vector<G2Affine> Qs; std::vector<const std::vector<pairing::LineCoeff> *> prep;
+            auto ml = [&](const G1Affine &P, const G2Affine &Q, const std::vector<pairing::LineCoeff> *lines) { if (!P.is_inf() && !Q.is_inf()) { Ps.push_back(P); Qs.push_back(Q); prep.push_back(lines); } };
+            ml(acc.to_affine().neg(), vk.gamma_g2, &vk.gamma_lines); ml(csum.to_affine().neg(), vk.delta_g2, &vk.delta_lines);
+            Fq12 f = Ps.empty() ? Fq12::one() : pairing::multi_miller_loop(Ps.data(), Qs.data(), (int)Ps.size(), prep.data());
+            uint32_t e[8]; fr_limbs(rsum, e);
+            const Fq12 rhs = vk.alpha_beta.cyclotomic_pow(e, 8);
+            ZK_HIP(hipStreamSynchronize(s));
+            pass = pairing::final_exponentiation(prod * f) == rhs;
+            return ZKG_OK;
+        };
+        std::function<int(const BatchGroup &, size_t, size_t)> decide = [&](const BatchGroup &G, size_t lo, size_t hi) -> int {
+            size_t n_in = 0;
+            for (size_t p = lo; p < hi; ++p) n_in += in_g2[p];
+            if (!n_in) return ZKG_OK;
+            bool pass = false;
+            ++n_combined;
+            if (int rc = combined(G, lo, hi, pass)) return rc;
+            if (pass) { for (size_t p = lo; p < hi; ++p) if (in_g2[p]) verdicts[item_at[p]] = 0; return ZKG_OK; }
+            if (n_in <= VERIFY_LEAF) { for (size_t p = lo; p < hi; ++p) if (in_g2[p]) own[item_at[p]] = 1; return ZKG_OK; }
+            const size_t mid = lo + (hi - lo) / 2;
+            if (int rc = decide(G, lo, mid)) return rc;
+            return decide(G, mid, hi);
+        };
+        for (const BatchGroup &G : groups)
+            if (G.hi > G.lo) if (int rc = decide(G, G.lo, G.hi)) return rc;
+        lap("checks");
+    }
+    // 7. everything the combination did not decide: the single verifier's code, on the host pool
+    for (size_t i = 0; i < count; ++i) if (own[i]) decide_alone.push_back(i);
+    host_parallel_for((int)decide_alone.size(), [&](int t) {
+        const zkg_verify_item &it = items[decide_alone[t]];
+        int v;
+        try { v = groth16_verify_impl(it.vk_blob, it.vk_len, it.primary_input, it.n_inputs, it.proof, it.proof_len); } catch (...) { v = 2; }
+        verdicts[decide_alone[t]] = (uint8_t)v;
+    });
+    lap("alone");
+    t_batch_stats[0] = n_combined; t_batch_stats[1] = decide_alone.size(); t_batch_stats[2] = n_outside_g2;
+    return ZKG_OK;
+}
+
+void zkg_verify_batch_stats(size_t out[3]) { if (out) for (int i = 0; i < 3; ++i) out[i] = t_batch_stats[i]; }
+
+int zkg_groth16_verify_batch(const zkg_verify_item *items, size_t count, uint8_t *verdicts) {
+    try { return verify_batch_impl(items, count, verdicts); }
+    catch (const std::exception &e) { set_error(std::string("zkg_groth16_verify_batch: ") + e.what()); return ZKG_ERROR; }
+    catch (...) { set_error("zkg_groth16_verify_batch: unexpected exception"); return ZKG_ERROR; }
+}
+
+static int pairing_product_impl(const uint64_t *g1_affine, const uint64_t *g2_affine, size_t n, uint8_t out[384]) {
+    if (initialised_device() < 0) { set_error("zkg_pairing_product: zkg_init not called (no GPU: there is no CPU path)"); return ZKG_ERROR; }
+    if (!out || (n && (!g1_affine || !g2_affine))) { set_error("zkg_pairing_product: null argument"); return ZKG_ERROR; }
+    std::vector<G1Affine> P(n); std::vector<G2Affine> Q(n);
+    if (n) { memcpy(P.data(), g1_affine, 64 * n); memcpy(Q.data(), g2_affine, 128 * n); }
+    for (size_t i = 0; i < n; ++i) {
+        const bool canon = limbs_below(P[i].x.v, FqParams::P) && limbs_below(P[i].y.v, FqParams::P) && limbs_below(Q[i].x.c0.v, FqParams::P) &&
+                           limbs_below(Q[i].x.c1.v, FqParams::P) && limbs_below(Q[i].y.c0.v, FqParams::P) && limbs_below(Q[i].y.c1.v, FqParams::P);
+        if (!canon || !pairing::on_curve_g1(P[i]) || !pairing::on_curve_g2(Q[i])) { set_error("zkg_pairing_product: point " + std::to_string(i) + " is not on its curve"); return ZKG_ERROR; }
+    }
+    Fq12 prod = Fq12::one();
+    if (n) {
+        const size_t o_P = 0, o_Q = 64 * n, o_M = o_Q + 128 * n, o_part = o_M + 384 * n, o_out = o_part + 384 * VERIFY_PROD_BLOCKS, total = o_out + 384;
+        WorkspaceLease lease;
+        if (!(lease.w = verify_workspace_acquire()) || lease.w->buf.reserve(total)) return ZKG_ERROR;
+        uint8_t *d = lease.w->buf.as<uint8_t>(); hipStream_t s = lease.w->s;
+        ZK_HIP(hipMemcpyAsync(d + o_P, P.data(), 64 * n, hipMemcpyHostToDevice, s));
+        ZK_HIP(hipMemcpyAsync(d + o_Q, Q.data(), 128 * n, hipMemcpyHostToDevice, s));
+        if (verify_miller((const G1Affine *)(d + o_P), (const G2Affine *)(d + o_Q), nullptr, n, d + o_M, s) ||
+            verify_fq12_product(d + o_M, 0, n, d + o_part, d + o_out, s)) return ZKG_ERROR;
+        ZK_HIP(hipMemcpyAsync(&prod, d + o_out, 384, hipMemcpyDeviceToHost, s));
+        ZK_HIP(hipStreamSynchronize(s));
+    }
+    ser::put_fq12(out, pairing::final_exponentiation(prod));
+    return ZKG_OK;
+}
+
+int zkg_pairing_product(const uint64_t *g1_affine, const uint64_t *g2_affine, size_t n, uint8_t out[384]) {
+    try { return pairing_product_impl(g1_affine, g2_affine, n, out); }
+    catch (const std::exception &e) { set_error(std::string("zkg_pairing_product: ") + e.what()); return ZKG_ERROR; }
+    catch (...) { set_error("zkg_pairing_product: unexpected exception"); return ZKG_ERROR; }
 }
 
 // bilinearity probe for the tests: writes e(a*G1, b*G2) (384 B) for canonical scalars a, b
