@@ -233,6 +233,26 @@ int zkg_groth16_prove(const zkg_crs *crs, const uint64_t *witness, const uint64_
  * variable's tag byte is claimed once; no proof is written). */
 int zkg_groth16_prove_sparse(const zkg_crs *crs, const uint8_t *tags, const uint32_t *full_index, const uint64_t *full_values, size_t count,
                              const uint64_t r[4], const uint64_t s[4], int check_satisfied, uint8_t *proof_out, size_t *proof_len);
+/* ---- many proofs of ONE resident key in one call.  An item is one zkg_groth16_prove (witness != NULL) or one zkg_groth16_prove_sparse
+ *      (witness == NULL) call with its own (r, s); status[i] and the ZKG_PROOF_BYTES at proofs_out + i * ZKG_PROOF_BYTES are exactly what that
+ *      call returns and writes for item i alone — proof bytes are deterministic given (key, witness, r, s).  An unsatisfied witness (with
+ *      check_satisfied) is ZKG_UNSATISFIED for that item only, a bad sparse listing or a null pointer inside an item ZKG_ERROR for that item
+ *      only; the other items are still proved and nothing is written for a failed one.  Keys on a radix-2 domain up to 2^17 without H
+ *      shards are proved in chunks of zkg_prove_batch_chunk items whose GPU work is ONE launch sequence (the kernels carry a proof
+ *      dimension; the H multi-exponentiations of a chunk share one sort, accumulation, fold and reduction); other keys go through the
+ *      single-proof path item by item.  Synchronous; host pointers; safe from several threads and beside zkg_groth16_prove* on the same key.
+ *      Returns ZKG_OK when every status was written (count == 0 included: nothing is touched), ZKG_ERROR for a null argument or a HIP failure. */
+typedef struct zkg_prove_item {
+    const uint64_t *witness;                 /* dense form: n x 4 limbs as zkg_groth16_prove, or NULL for the sparse form */
+    const uint8_t  *tags; const uint32_t *full_index; const uint64_t *full_values; size_t count;   /* as zkg_groth16_prove_sparse */
+    const uint64_t *r, *s;                   /* 4 limbs each, Montgomery Fr */
+} zkg_prove_item;
+int zkg_groth16_prove_batch(const zkg_crs *crs, const zkg_prove_item *items, size_t count, int check_satisfied,
+                            uint8_t *proofs_out /* count x ZKG_PROOF_BYTES */, int *status /* count entries */);
+/* test hook: what the calling thread's last zkg_groth16_prove_batch did — out[0] items that went through batched launches, out[1] items
+ * that went through the single-proof path, out[2] batched chunks launched.  Counters, not clocks. */
+void zkg_prove_batch_stats(size_t out[3]);
+size_t zkg_prove_batch_chunk(const zkg_crs *crs);   /* proofs per batched chunk for this key; 0 = this key takes the single-proof path */
 /* coefficients_for_H (m+1 Fr, Montgomery) of r1cs_to_qap_witness_map, for parity tests */
 int zkg_qap_witness_h(const zkg_crs *crs, const uint64_t *witness, uint64_t *h_out);
 /* per-stage device milliseconds of the last zkg_groth16_prove on this crs (the stages run on their own streams, so the entries

@@ -1,0 +1,130 @@
+"""Proofs per second of zkg_groth16_prove_batch against the single-proof path, in one process on one box (host clock around the synchronous
+calls; kernel times come from a separate `rocprofv3 --kernel-trace --stats` run, see --trace-only).  For every k (payloads) and P (batch size),
+P distinct credentials of one key, sparse witnesses, fresh (r, s):
+  sequential    P Crs.prove_sparse calls one after another                       (leg a)
+  three_callers three threads on the key's prover slots, --caller-proofs proofs each: the figure of tools/prove_throughput.py, once per k  (leg b)
+  batch         one Crs.prove_batch of the P items                              (leg c)
+--reps timed repetitions each after one warm-up; min / median / max proofs/s.  The batch's bytes are compared with the sequential leg's.
+Prints a table and one JSON line; --out writes the JSON to a file.  --commit names the source state in the JSON.
+Usage: python tools/prove_batch_time.py [--ks 1 2 4] [--ps 1 2 4 8 16 32] [--reps 5] [--out profiles/prove_batch_time.json]
+       rocprofv3 --kernel-trace --stats -d DIR -- python tools/prove_batch_time.py --trace-only single|batch
+                                           (key setup, then 11 times one proof / one batch of 16 at k = 1: the runs to trace, no counters with them)
+       python tools/prove_batch_time.py --merge-stats SINGLE_kernel_stats.csv BATCH_kernel_stats.csv profiles/prove_batch_kernel_stats.csv"""
+import argparse
+import json
+import os
+import sys
+import threading
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402
+import zklaim_amd as zkg  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--ks", nargs="*", type=int, default=[1, 2, 4])
+ap.add_argument("--ps", nargs="*", type=int, default=[1, 2, 4, 8, 16, 32])
+ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--caller-proofs", type=int, default=40)
+ap.add_argument("--commit", default=None)
+ap.add_argument("--note", action="append", default=[], help="free text recorded in the JSON (e.g. the parent build's prove_throughput lines)")
+ap.add_argument("--out", default=None)
+ap.add_argument("--trace-only", choices=["single", "batch"], default=None)
+ap.add_argument("--merge-stats", nargs=3, metavar=("SINGLE_CSV", "BATCH_CSV", "OUT_CSV"), default=None)
+cli = ap.parse_args()
+TRACE_CALLS = 11
+
+
+def key_and_items(k, count):
+    keep = []
+    items = []
+    ck0 = None
+    for v in range(count):
+        pls = [dict(attrs=[1990 + i, 7 * i, 42, i, 5], refs=[2100, 7 * i, 41, 0, 5], ops=["less", "eq", "greater", "noop", "greater_or_eq"], salt=0x5A4B + i + 131 * v)
+               for i in range(k)]
+        ck = zkg.ZklaimCircuit(zkg.make_ctx(pls, keep))
+        rs = bench.splitmix_fr(2, 9 + v)
+        items.append(ck.sparse_witness() + (rs[0], rs[1]))
+        if ck0 is None:
+            ck0 = ck
+    kp = zkg.Keypair(ck0.r1cs, bench.splitmix_fr(5, 77))
+    return zkg.Crs(kp.pk), items, keep + [kp]
+
+
+def rates(fn, proofs, reps):
+    fn()                                                        # warm-up
+    out = []
+    for _ in range(reps):
+        t0 = time.perf_counter(); fn(); out.append(proofs / (time.perf_counter() - t0))
+    out.sort()
+    return {"min": round(out[0], 1), "median": round(out[len(out) // 2], 1), "max": round(out[-1], 1)}
+
+
+if cli.merge_stats:
+    # two rocprofv3 *_kernel_stats.csv (the --trace-only single / batch runs) side by side, per kernel and per call of the traced loop
+    import csv
+    single, batch, out = cli.merge_stats
+    rows = {}
+    for col, path in ((0, single), (1, batch)):
+        for r in csv.DictReader(open(path)):
+            rows.setdefault(r["Name"], [[0, 0], [0, 0]])[col] = [int(r["Calls"]), int(r["TotalDurationNs"])]
+    with open(out, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["Name", "single_launches", "single_total_us", "batch16_launches", "batch16_total_us", "traced_calls_each"])
+        for name, (a, b) in sorted(rows.items(), key=lambda kv: -kv[1][1][1]):
+            w.writerow([name, a[0], round(a[1] / 1e3, 1), b[0], round(b[1] / 1e3, 1), TRACE_CALLS])
+    sys.exit(0)
+zkg.init(0)
+if cli.trace_only:
+    crs, items, keep = key_and_items(1, 16)
+    for _ in range(TRACE_CALLS):                                # (the first call is the warm-up: witness tables, workspaces)
+        if cli.trace_only == "single":
+            assert crs.prove_sparse(*items[0])[0] == 0
+        else:
+            assert all(g[0] == 0 for g in crs.prove_batch(items))
+    crs.free()
+    zkg.shutdown()
+    sys.exit(0)
+
+res = {"tool": "prove_batch_time", "commit": cli.commit, "reps": cli.reps, "device": zkg.device_info() if hasattr(zkg, "device_info") else None,
+       "notes": cli.note, "results": {}}
+for k in cli.ks:
+    crs, items, keep = key_and_items(k, max(cli.ps))
+    chunk = crs.prove_batch_chunk()
+    expect = [crs.prove_sparse(*it) for it in items]
+    assert all(e[0] == 0 for e in expect)
+    bad = []
+
+    def caller():
+        for j in range(cli.caller_proofs):
+            if crs.prove_sparse(*items[j % len(items)]) != expect[j % len(items)]:
+                bad.append(j)
+
+    def three_callers():
+        th = [threading.Thread(target=caller) for _ in range(3)]
+        for t in th:
+            t.start()
+        for t in th:
+            t.join()
+
+    rk = {"chunk": chunk, "three_callers": rates(three_callers, 3 * cli.caller_proofs, cli.reps), "P": {}}
+    assert not bad
+    print(f"k={k} (batch chunk {chunk})  three callers: {rk['three_callers']} proofs/s", flush=True)
+    for P in cli.ps:
+        sub = items[:P]
+        assert crs.prove_batch(sub) == expect[:P]
+        stats = zkg.prove_batch_stats()
+        seq = rates(lambda: [crs.prove_sparse(*it) for it in sub], P, cli.reps)
+        bat = rates(lambda: crs.prove_batch(sub), P, cli.reps)
+        rk["P"][P] = {"sequential": seq, "batch": bat, "batch_stats": stats, "batch_min_over_sequential_max": round(bat["min"] / seq["max"], 3),
+                      "batch_median_over_three_callers_median": round(bat["median"] / rk["three_callers"]["median"], 3)}
+        print(f"k={k} P={P:3d}  sequential {seq}  batch {bat}  batch min / sequential max = {bat['min'] / seq['max']:.2f}", flush=True)
+    res["results"][k] = rk
+    crs.free()
+line = json.dumps(res)
+print(line)
+if cli.out:
+    with open(cli.out, "w") as f:
+        f.write(line + "\n")
+zkg.shutdown()

@@ -24,6 +24,7 @@ DECLARED_SYMBOLS = [
     "zkg_msm_g1_multi", "zkg_g1_add_quad29", "zkg_crs_shard_h", "zkg_msm_g1_bases_upload", "zkg_msm_g1_resident", "zkg_msm_g1_bases_free",
     "zkg_prover_peak_in_flight", "zkg_msm_g1_host_scalars", "zkg_multi_rccl_calls", "zkg_g1_add_pair29",
     "zkg_groth16_verify_batch", "zkg_pairing_product", "zkg_verify_batch_stats",
+    "zkg_groth16_prove_batch", "zkg_prove_batch_stats", "zkg_prove_batch_chunk",
 ]
 # the reference's own seam, exported with its original names (zklaim.h:257-259)
 COMPAT_SYMBOLS = ["libsnark_trusted_setup", "libsnark_prove", "libsnark_verify"]
@@ -369,6 +370,16 @@ class Crs:
             _check(rc, "zkg_groth16_prove_sparse")
         return rc, bytes(out[:ln.value])
 
+    def prove_batch(self, items, check_satisfied=True):
+        """zkg_groth16_prove_batch: items are (witness, r, s) or (tags, full_index, full_values, r, s); -> [(status, proof bytes or None)]"""
+        return groth16_prove_batch(self, items, check_satisfied)
+
+    def prove_batch_chunk(self):
+        """proofs per batched chunk for this key; 0: prove_batch takes the single-proof path"""
+        lib().zkg_prove_batch_chunk.restype = C.c_size_t
+        lib().zkg_prove_batch_chunk.argtypes = [C.c_void_p]
+        return int(lib().zkg_prove_batch_chunk(C.c_void_p(self._h)))
+
     def shard_h(self, devices):
         """zkg_crs_shard_h: the H query's tables sharded by points over `devices` (one GPU listed several times rehearses the path)"""
         d = (C.c_int * len(devices))(*devices)
@@ -611,6 +622,60 @@ def verify_batch_stats():
     """(combined checks, items decided by the single verifier's code, of those: B outside G2) of this thread's last groth16_verify_batch"""
     out = (C.c_size_t * 3)()
     lib().zkg_verify_batch_stats(out)
+    return tuple(int(v) for v in out)
+
+
+class ProveItem(C.Structure):
+    _fields_ = [("witness", C.c_void_p), ("tags", C.c_void_p), ("full_index", C.c_void_p), ("full_values", C.c_void_p), ("count", C.c_size_t),
+                ("r", C.c_void_p), ("s", C.c_void_p)]
+
+
+def groth16_prove_batch(crs, items, check_satisfied=True):
+    """Proves every item on one resident key in one call (Crs.prove_batch).  items: (witness, r, s) for a dense witness of n x 4 limbs, or
+    (tags, full_index, full_values, r, s) for the sparse form.  Returns [(status, proof bytes or None)]: status OK / UNSATISFIED / ERROR per
+    item, as Crs.prove / Crs.prove_sparse would give for it alone.  Raises ZkgError when an item is malformed or the call itself fails."""
+    L = lib()
+    L.zkg_groth16_prove_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
+    L.zkg_crs_num_variables.argtypes = [C.c_void_p]
+    L.zkg_crs_num_variables.restype = C.c_uint32
+    handle = crs._h if crs is not None else None
+    n = int(L.zkg_crs_num_variables(C.c_void_p(handle))) if handle else None
+    arr = (ProveItem * max(1, len(items)))()
+    keep = []
+
+    def fr(x, what, k):
+        a = _u64(x).reshape(-1)
+        if a.size != 4:
+            raise ZkgError(f"prove_batch: item {k}: {what} must be 4 limbs")
+        return a
+    for k, it in enumerate(items):
+        if len(it) == 3:
+            w = _u64(it[0]).reshape(-1, 4) if np.size(it[0]) % 4 == 0 else None
+            if w is None or (n is not None and w.shape[0] != n):
+                raise ZkgError(f"prove_batch: item {k}: the witness must be n x 4 limbs" + (f" (n = {n})" if n is not None else ""))
+            r, s = fr(it[1], "r", k), fr(it[2], "s", k)
+            keep += [w, r, s]
+            arr[k] = ProveItem(w.ctypes.data if w.size else None, None, None, None, 0, r.ctypes.data, s.ctypes.data)
+        elif len(it) == 5:
+            tags = np.ascontiguousarray(it[0], np.uint8).reshape(-1); idx = np.ascontiguousarray(it[1], np.uint32).reshape(-1); vals = _u64(it[2]).reshape(-1, 4)
+            if (n is not None and tags.size != n) or vals.shape[0] != idx.size:
+                raise ZkgError(f"prove_batch: item {k}: tags must have n entries and every listed index its value")
+            r, s = fr(it[3], "r", k), fr(it[4], "s", k)
+            keep += [tags, idx, vals, r, s]
+            arr[k] = ProveItem(None, tags.ctypes.data if tags.size else None, idx.ctypes.data if idx.size else None, vals.ctypes.data if vals.size else None,
+                               idx.size, r.ctypes.data, s.ctypes.data)
+        else:
+            raise ZkgError(f"prove_batch: item {k}: (witness, r, s) or (tags, full_index, full_values, r, s)")
+    proofs = np.zeros((max(1, len(items)), 134), np.uint8)
+    status = np.full(max(1, len(items)), -1, np.int32)
+    _check(L.zkg_groth16_prove_batch(C.c_void_p(handle), C.cast(arr, C.c_void_p), len(items), int(check_satisfied), _p(proofs), _p(status)), "zkg_groth16_prove_batch")
+    return [(int(status[k]), proofs[k].tobytes() if status[k] == OK else None) for k in range(len(items))]
+
+
+def prove_batch_stats():
+    """(items through batched launches, items through the single-proof path, batched chunks) of this thread's last prove_batch"""
+    out = (C.c_size_t * 3)()
+    lib().zkg_prove_batch_stats(out)
     return tuple(int(v) for v in out)
 
 

@@ -147,6 +147,11 @@ void msm_job_destroy(MsmJob *j);
 // d_gather (optional, n entries): scalar i is d_scalars[d_gather[i]] and stands for element d_gather[i] of every base set
 int msm_job_launch(MsmJob *job, const MsmBases *sets, int nsets, const uint32_t *d_scalars, size_t n, bool scalars_mont, const uint32_t *d_gather = nullptr);
 int msm_job_finish(MsmJob *job, G1 *out_g1, G2 *out_g2);   // out_g1[k]: k-th G1 set of the launch, out_g2[k]: k-th G2 set
+// the dual: `count` scalar vectors of n elements, scalar_stride 32-bit words apart, over the same table sets (all windows, no gather /
+// remap / index_sub), as one launch sequence; out_g1[p * (G1 sets) + k] = vector p over the k-th G1 set, out_g2 likewise
+bool msm_multi_supported(size_t n, int c, uint32_t count);
+int msm_job_launch_multi(MsmJob *job, const MsmBases *sets, int nsets, const uint32_t *d_scalars, size_t n, size_t scalar_stride, uint32_t count, bool scalars_mont);
+int msm_job_finish_multi(MsmJob *job, G1 *out_g1, G2 *out_g2);
 // the multi_exp_with_mixed_addition split of a witness z = [1 | w] (n1 elements, Montgomery): tags (0 zero, 1 one, 2 other), the
 // indices of the others and their count; and the flat sum of the bases tagged one (result lands in pinned host memory)
 // d_count: two words, [0] the number of listed elements, [1] set to 1 when a listed element has no entry in d_subset_pos (optional: position of
@@ -160,12 +165,14 @@ int gather_points_g2(const G2Affine *d_src, const uint32_t *d_idx, size_t count,
 int scatter_points_g1(const G1Affine *d_src, const uint32_t *d_idx, size_t count, G1Affine *d_out, hipStream_t s);
 int scatter_points_g2(const G2Affine *d_src, const uint32_t *d_idx, size_t count, G2Affine *d_out, hipStream_t s);
 struct OnesSum {                                            // results: nsets points (G1 or G2, XYZZ) back to back in pinned host memory
-    DevBuf partials; void *host = nullptr; bool g2 = false; int nsets = 0; void release();
+    DevBuf partials; void *host = nullptr; size_t host_bytes = 0; bool g2 = false; int nsets = 0; void release();
     const G1 &g1(int i) const { return reinterpret_cast<const G1 *>(host)[i]; }
     const G2 &g2pt(int i) const { return reinterpret_cast<const G2 *>(host)[i]; }
 };
 // level 0 of each set (its plain bases) and its index_sub are read; all sets of one field
 int ones_sum_launch(OnesSum &o, const MsmBases *sets, int nsets, const uint8_t *d_tags, size_t n1, hipStream_t s);
+// `count` witnesses' tag arrays, tag_stride bytes apart, in one launch pair (blockIdx.z = witness): result of witness p, set i at index p * nsets + i
+int ones_sum_launch_multi(OnesSum &o, const MsmBases *sets, int nsets, const uint8_t *d_tags, size_t tag_stride, size_t n1, uint32_t count, hipStream_t s);
 // scalars: n x 8 u32 (canonical, or Montgomery when scalars_mont).  Zero scalars are dropped and ones land in
 // one heavy bucket, which is what libff's multi_exp_with_mixed_addition prefilter achieves.
 int msm_g1(const G1Affine *d_bases, const uint32_t *d_scalars, size_t n, bool scalars_mont, G1 *out, hipStream_t s, bool mostly_bits = false);

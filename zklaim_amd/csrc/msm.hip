@@ -191,6 +191,70 @@ __global__ __launch_bounds__(256) void k_digits_c(const uint32_t *scalars, const
     }
 }
 
+// Several scalar vectors over ONE table (msm_job_launch_multi: the H queries of a batch of proofs), blockIdx.y = vector.  The digit array gets
+// a row per (window, vector), window-major: row (w / merge) * P * merge + p * merge + w % merge.  The rows of one window then lie side by side
+// as ONE window of P * B buckets — an entry finds its level as bucket / (P * B), the fold over the windows leaves P bucket sets back to back,
+// and every kernel behind this one runs unchanged on a geometry of W * P rows (with merged rows: a vector's `merge` consecutive windows stay adjacent).
+template <int C>
+__global__ __launch_bounds__(256) void k_digits_multi(const uint32_t *scalars, size_t scalar_stride /* words between vectors */, size_t n, int mont, uint32_t merge, uint32_t *digits, ZeroList zl) {
+    sort_wave_priority();
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t lanes = (size_t)gridDim.x * blockDim.x;
+    if (blockIdx.y == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) for (size_t z = i; z < zl.words[k]; z += lanes) zl.p[k][z] = 0;
+    }
+    if (i >= n) return;
+    const uint32_t p = blockIdx.y, P = gridDim.y;
+    Fr f;
+    const uint4 *src = reinterpret_cast<const uint4 *>(scalars + (size_t)p * scalar_stride + 8 * i);
+    uint4 a = src[0], b = src[1];
+    f.v[0] = a.x; f.v[1] = a.y; f.v[2] = a.z; f.v[3] = a.w; f.v[4] = b.x; f.v[5] = b.y; f.v[6] = b.z; f.v[7] = b.w;
+    if (mont) f = f.from_mont();
+    constexpr int WT = (SCALAR_BITS + C - 1) / C;
+    constexpr uint32_t B = 1u << (C - 1), MASK = (1u << C) - 1;
+    uint32_t carry = 0;
+#pragma unroll
+    for (int w = 0; w < WT; ++w) {
+        const int off = w * C, limb = off >> 5, sh = off & 31;
+        uint32_t v = limb < 8 ? f.v[limb < 8 ? limb : 7] >> sh : 0u;
+        if (sh + C > 32 && limb + 1 < 8) v |= f.v[limb + 1 < 8 ? limb + 1 : 7] << (32 - sh);
+        const uint32_t raw = (v & MASK) + carry;
+        const bool neg = raw > B;
+        const uint32_t d = neg ? (1u << C) - raw : raw;
+        carry = neg ? 1u : 0u;
+        const uint32_t code = d ? (d << 1) | (neg ? 1u : 0u) : 0u;
+        const size_t row = ((size_t)((uint32_t)w / merge) * P + p) * merge + (uint32_t)w % merge;
+        digits[row * n + i] = code;
+    }
+}
+
+// the same for any window size (the witness tables': 10 ... 14 bits), as k_digits
+__global__ __launch_bounds__(256) void k_digits_multi_any(const uint32_t *scalars, size_t scalar_stride, size_t n, int mont, MsmGeom g, uint32_t merge, uint32_t *digits, ZeroList zl) {
+    sort_wave_priority();
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t lanes = (size_t)gridDim.x * blockDim.x;
+    if (blockIdx.y == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) for (size_t z = i; z < zl.words[k]; z += lanes) zl.p[k][z] = 0;
+    }
+    if (i >= n) return;
+    const uint32_t p = blockIdx.y, P = gridDim.y;
+    Fr f;
+    const uint4 *src = reinterpret_cast<const uint4 *>(scalars + (size_t)p * scalar_stride + 8 * i);
+    uint4 a = src[0], b = src[1];
+    f.v[0] = a.x; f.v[1] = a.y; f.v[2] = a.z; f.v[3] = a.w; f.v[4] = b.x; f.v[5] = b.y; f.v[6] = b.z; f.v[7] = b.w;
+    if (mont) f = f.from_mont();
+    uint32_t carry = 0;
+    for (uint32_t w = 0; w < g.Wt; ++w) {
+        uint32_t raw = bits_at(f.v, w * g.c, g.c) + carry, code = 0;
+        if (raw > g.B) { uint32_t d = (1u << g.c) - raw; carry = 1; if (d) code = (d << 1) | 1u; }
+        else { carry = 0; if (raw) code = raw << 1; }
+        const size_t row = ((size_t)(w / merge) * P + p) * merge + w % merge;
+        digits[row * n + i] = code;
+    }
+}
+
 // ... and four consecutive scalars per thread (no gather list, n a multiple of 4, every window owned): a window's four digits leave as ONE 16-byte
 // store per lane — 1 KiB per wavefront instead of four 256-byte stores (the kernel is bound by its store instructions: 16.7 M four-byte stores at 2^20)
 template <int C>
@@ -1200,13 +1264,15 @@ __global__ __launch_bounds__(256) void k_scatter_points(const Affine<F> *src, co
 // addition is a real one.  (Round 2 strode over the tags themselves: with half the witness bits zero half of each wavefront's additions were
 // masked off, the kernel's time was twice its work.)
 template <class F>
-__global__ __launch_bounds__(256) void k_ones_sum(const ViewSet<F> views, const uint8_t *tags, size_t n1, uint32_t span, XYZZ<F> *partials) {
+__global__ __launch_bounds__(256) void k_ones_sum(const ViewSet<F> views, const uint8_t *tags, size_t n1, uint32_t span, XYZZ<F> *partials,
+                                                   size_t tag_stride, size_t vec_stride /* blockIdx.z = witness of a batch (ones_sum_launch_multi): its tags and its partials */) {
     extern __shared__ unsigned char red_smem[];
     LdsPoint<F> *sh = reinterpret_cast<LdsPoint<F> *>(red_smem);            // 256 points
     uint32_t *list = reinterpret_cast<uint32_t *>(red_smem + 256 * sizeof(LdsPoint<F>));        // span positions, span / 4 per wavefront
     __shared__ uint32_t seg_count[4];
     const Affine<F> *bases = views.v[blockIdx.y].p; const uint32_t index_sub = views.v[blockIdx.y].index_sub;
-    partials += (size_t)blockIdx.y * (gridDim.x + 1);
+    tags += (size_t)blockIdx.z * tag_stride;
+    partials += (size_t)blockIdx.z * vec_stride + (size_t)blockIdx.y * (gridDim.x + 1);
     const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, cap = span >> 2;
     const size_t first = (size_t)blockIdx.x * span + (size_t)wv * cap;
     uint32_t count = 0;                                                       // uniform across the wavefront
@@ -1231,10 +1297,10 @@ __global__ __launch_bounds__(256) void k_ones_sum(const ViewSet<F> views, const 
     if (tid == 0) partials[blockIdx.x] = sh[0].normalized();
 }
 template <class F>
-__global__ __launch_bounds__(256) void k_sum_partials(XYZZ<F> *partials_all, uint32_t count) {        // per set: partials[0..count) -> partials[count]
+__global__ __launch_bounds__(256) void k_sum_partials(XYZZ<F> *partials_all, uint32_t count, size_t vec_stride) {        // per set (and witness, blockIdx.y): partials[0..count) -> partials[count]
     extern __shared__ unsigned char red_smem[];
     LdsPoint<F> *sh = reinterpret_cast<LdsPoint<F> *>(red_smem);
-    XYZZ<F> *partials = partials_all + (size_t)blockIdx.x * (count + 1), *out = partials + count;
+    XYZZ<F> *partials = partials_all + (size_t)blockIdx.y * vec_stride + (size_t)blockIdx.x * (count + 1), *out = partials + count;
     XYZZ<F> acc = XYZZ<F>::inf();
     for (uint32_t i = threadIdx.x; i < count; i += 256) acc.add(partials[i]);
     sh[threadIdx.x] = acc;
@@ -1292,6 +1358,8 @@ struct MsmJob {
     hipStream_t sort_stream = nullptr; hipEvent_t ev_sorted = nullptr, ev_acc_done = nullptr;
     uint32_t w0 = 0, ws = 1;           // window subset of the next launches (window-sharded multi-GPU runs)
     bool empty = false;
+    // msm_job_launch_multi: `multi` scalar vectors, multi_stride words apart, over one table; the geometry then has W * multi rows (k_digits_multi)
+    uint32_t multi = 1; size_t multi_stride = 0;
     // bases resident, scalars in host memory (msm_g1_host_scalars): device copy of the scalars, the copy stream and one event per piece
     DevBuf hs_scalars; hipStream_t copy = nullptr; hipEvent_t ev_piece[8] = {nullptr};
     std::mutex mu;
@@ -1300,6 +1368,8 @@ struct MsmJob {
 template <class F>
 static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, const uint32_t *d_gather, bool time_it) {
     const MsmGeom g = job->g; const size_t n = job->n, total_buckets = (size_t)g.W * g.B; const unsigned ns = (unsigned)gr.nsets;
+    // a multi launch (msm_job_launch_multi): P vectors' rows side by side, a window is P * B buckets wide and the fold leaves P bucket sets
+    const uint32_t P = job->multi, BP = g.B * P, Wp = g.W / P;
     hipStream_t s = job->stream;
     size_t n_entries_max = n * g.W;
     // worst case of the device-side threshold: a heavy bucket holds more than 8 entries (G1; 4 for G2), so there are fewer than
@@ -1308,7 +1378,7 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
                  max_items = max_heavy + n_entries_max / HEAVY_S + 1;
     typedef RedGeom<F> RG;
     gr.table = sets[0].level_stride != 0;
-    gr.red_windows = gr.table ? 1 : g.W;                             // a table's windows are folded into one bucket set first
+    gr.red_windows = gr.table ? P : g.W;                             // a table's windows are folded into one bucket set (per vector) first
     const size_t red_buckets = (size_t)gr.red_windows * g.B;
     static const char *force_l = getenv("ZKG_RED_L_LOG");                                                  // tuning aid: 0, 2 or 4
     const int red_l_log = force_l ? atoi(force_l) : red_buckets >= RED_LARGE_BUCKETS ? RED_L_LOG_LARGE : red_buckets > RED_SMALL_BUCKETS ? RED_L_LOG_SMALL : RED_L_LOG_TINY;
@@ -1316,17 +1386,17 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
     gr.cpw = (g.B + (1u << gr.chunk_log) - 1) >> gr.chunk_log; gr.nred = (size_t)gr.red_windows * gr.cpw;
     DevBuf &bucket_buf = job->bucket_owner ? job->bucket_owner->group[sizeof(F) != sizeof(Fq) ? 1 : 0].buckets : gr.buckets;
     gr.red_slots = 2;
-    SetLayout L; L.buckets = total_buckets; L.items = max_items; L.heavy = max_heavy; L.partials = max_items; L.folded = g.B; L.red_out = gr.nred * 3;      // two results per chunk, three from k_bucket_reduce29l (gr.red_slots)
+    SetLayout L; L.buckets = total_buckets; L.items = max_items; L.heavy = max_heavy; L.partials = max_items; L.folded = BP; L.red_out = gr.nred * 3;      // two results per chunk, three from k_bucket_reduce29l (gr.red_slots)
     if (gr.heavy_items.reserve(ns * max_items * sizeof(HeavyItem)) || gr.heavy_buckets.reserve(ns * max_heavy * sizeof(HeavyBucket)) ||
         gr.heavy_counters.reserve(8 * MSM_MAX_SETS) || gr.heavy_partials.reserve(ns * max_items * sizeof(XYZZ<F>)) ||
         bucket_buf.reserve(ns * total_buckets * std::max(sizeof(XYZZ<F>), sizeof(Bucket29))) || gr.red_out.reserve(ns * L.red_out * sizeof(XYZZ<F>)) || ((gr.red_stride = L.red_out), false) ||
-        (gr.table && gr.folded.reserve(ns * (size_t)g.B * std::max(sizeof(XYZZ<F>), sizeof(Bucket29)))) || gr.host_reserve(ns * L.red_out * sizeof(XYZZ<F>))) return ZKG_ERROR;
+        (gr.table && gr.folded.reserve(ns * (size_t)BP * std::max(sizeof(XYZZ<F>), sizeof(Bucket29)))) || gr.host_reserve(ns * L.red_out * sizeof(XYZZ<F>))) return ZKG_ERROR;
     // (gr.heavy_counters: cleared by the job's k_digits)
     XYZZ<F> *buckets = bucket_buf.as<XYZZ<F>>();
     ViewSet<F> views;
     for (unsigned i = 0; i < (unsigned)MSM_MAX_SETS; ++i) {
         const MsmBases &b = sets[i < ns ? i : 0];
-        views.v[i] = BaseView<F>{reinterpret_cast<const Affine<F> *>(b.p), b.level_stride, d_gather, b.index_sub, g.B, b.remap};
+        views.v[i] = BaseView<F>{reinterpret_cast<const Affine<F> *>(b.p), b.level_stride, d_gather, b.index_sub, BP, b.remap};
     }
     // `order` lists the buckets by descending length, the empty ones last.  A table launch folds through the bucket lengths and never reads
     // an empty bucket, so its accumulation covers at most one lane per entry: a witness' ~10^5 entries over 2^19 buckets would otherwise
@@ -1359,7 +1429,7 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
     // ... and so do a lone table set's (the prover's H query: accumulate -> k_bucket_fold29 -> reduce, all on the records)
     // — where the rows are few (8 after the row merge of the large tables: a bucket's rows are added in sequence, 4 us each; a one-payload key's 22
     // rows of 2048 buckets keep the 32-bit fold, a tree over the rows: 0.75 against 0.83 ms per proof)
-    const bool out29 = use29 && !red32_env && (stride29 == 0 ? !gr.table : (gr.table && ns == 1 && g.W <= 8 && !fold32_env));
+    const bool out29 = use29 && !red32_env && (stride29 == 0 ? !gr.table : (gr.table && ns == 1 && Wp <= 8 && !fold32_env));
     const int resume = job->resume ? 1 : 0;
     MsmJob *owner = job->bucket_owner ? job->bucket_owner : job;                // (whose buckets these are)
     if (resume && !(out29 && owner->last_out29)) { set_error("msm: a piece can only continue 29-bit buckets"); return ZKG_ERROR; }
@@ -1414,7 +1484,7 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
         static const int waves_env = getenv("ZKG_ACC29_WAVES") ? atoi(getenv("ZKG_ACC29_WAVES")) : 0;               // tuning aid: 2 or 3 everywhere
         const int waves29 = waves_env ? waves_env : (job->sort_stream || gr.table || job->bucket_owner) ? 2 : 3;
         auto launch29 = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, rec29, stride29, g.B, job->sorted.as<uint32_t>(),
+            hipLaunchKernelGGL(kern, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, rec29, stride29, BP, job->sorted.as<uint32_t>(),
                                job->offsets.as<uint32_t>(), job->order.as<uint32_t>(), lanes, (void *)buckets, gr.heavy_items.as<HeavyItem>(),
                                gr.heavy_buckets.as<HeavyBucket>(), gr.heavy_counters.as<uint32_t>(), L, resume | (job->critical ? 2 : 0));
         };
@@ -1447,16 +1517,16 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
     bool folded29 = false;
     if constexpr (sizeof(F) == sizeof(Fq)) {
         if (gr.table && out29) {
-            hipLaunchKernelGGL(k_bucket_fold29, dim3((2 * g.B + 255) / 256), dim3(256), 0, s, reinterpret_cast<const Bucket29 *>(buckets), job->counts.as<uint32_t>(), g.W, g.B,
+            hipLaunchKernelGGL(k_bucket_fold29, dim3((2 * BP + 255) / 256), dim3(256), 0, s, reinterpret_cast<const Bucket29 *>(buckets), job->counts.as<uint32_t>(), Wp, BP,
                                gr.folded.as<Bucket29>(), job->critical ? 1 : 0);
             red_in = gr.folded.as<XYZZ<F>>(); in_stride = L.folded; folded29 = true;
         }
     }
     if (gr.table && !folded29) {
-        uint32_t slots = 1; while (slots < g.W && slots < 32) slots <<= 1;                // window slots per workgroup: W rounded up to a power of two (<= 32)
+        uint32_t slots = 1; while (slots < Wp && slots < 32) slots <<= 1;                // window slots per workgroup: W rounded up to a power of two (<= 32)
         uint32_t fold_b_log = 0; while ((FOLD_THREADS >> (fold_b_log + 1)) >= slots) ++fold_b_log;
-        hipLaunchKernelGGL(k_bucket_fold<F>, dim3((g.B + (1u << fold_b_log) - 1) >> fold_b_log, ns), dim3(FOLD_THREADS), FOLD_THREADS * sizeof(LdsPoint<F>), s,
-                           buckets, job->counts.as<uint32_t>(), g.W, g.B, fold_b_log, gr.folded.as<XYZZ<F>>(), L);
+        hipLaunchKernelGGL(k_bucket_fold<F>, dim3((BP + (1u << fold_b_log) - 1) >> fold_b_log, ns), dim3(FOLD_THREADS), FOLD_THREADS * sizeof(LdsPoint<F>), s,
+                           buckets, job->counts.as<uint32_t>(), Wp, BP, fold_b_log, gr.folded.as<XYZZ<F>>(), L);
         red_in = gr.folded.as<XYZZ<F>>(); in_stride = L.folded;
     }
     bool reduce29 = false;
@@ -1514,8 +1584,9 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
 // host: window value V_w = sum_b (b+1) X_b = U_w + P_w, with chunk ch contributing U_ch + (ch*RED_CHUNK) * P_ch to U_w
 // and P_ch to P_w; then Horner over windows (c doublings each).  A table set arrives as ONE window of weight 1: no doublings at all.
 template <class F>
-static XYZZ<F> host_combine(const MsmJob *job, const MsmGroup &gr, int set) {
+static XYZZ<F> host_combine(const MsmJob *job, const MsmGroup &gr, int set, int vec = 0 /* a multi launch: which scalar vector */) {
     const MsmGeom g = job->g; const uint32_t cpw = gr.cpw, W = gr.red_windows;
+    const bool multi = gr.table && job->multi > 1;                              // msm_job_launch_multi: vector `vec` is window `vec` of the reduction
     const XYZZ<F> *red = reinterpret_cast<const XYZZ<F> *>(gr.host_red) + (size_t)set * gr.red_stride;
     const size_t sl = (size_t)gr.red_slots;                                     // 2: (P, U) per chunk; 3: (P, T, A) with U = T + 8 A (k_bucket_reduce29l)
     std::vector<XYZZ<F>> V(W);
@@ -1533,6 +1604,7 @@ static XYZZ<F> host_combine(const MsmJob *job, const MsmGroup &gr, int set) {
         Usum.add(weighted); Usum.add(suffix);
         V[w] = Usum;
     };
+    if (multi) { window(vec); return V[vec]; }                                  // its folded bucket set: one window of weight 1
     if (gr.table) {                                                             // one window of weight 1; its chunks in segments on the host pool
         const int SEG = 16, nseg = ((int)cpw + SEG - 1) / SEG;
         if (nseg <= 1) { window(0); return V[0]; }
@@ -1571,6 +1643,7 @@ static XYZZ<F> host_combine(const MsmJob *job, const MsmGroup &gr, int set) {
 static int sort_digits(MsmJob *job, const uint32_t *d_scalars, bool mont, const uint32_t *d_gather) {
     const MsmGeom g0 = job->g; const size_t n0 = job->n;                        // as the scalars see them (k_digits)
     if (job->merge > 1) { job->g.W /= job->merge; job->g.Wt = job->g.W; job->n *= job->merge; }     // rows of the digit array read `merge` at a time from here on
+    if (job->multi > 1) { job->g.W *= job->multi; job->g.Wt = job->g.W; }                           // ... and a row per (window, vector)
     const MsmGeom g = job->g; const size_t n = job->n;
     hipStream_t s = job->sort_stream ? job->sort_stream : job->stream;
     const size_t total = (size_t)g.W * g.B;
@@ -1607,7 +1680,13 @@ static int sort_digits(MsmJob *job, const uint32_t *d_scalars, bool mont, const 
         const dim3 dg((unsigned)((n0 + 255) / 256));                                                     // n >= 1 (msm_job_launch)
         const bool four = !d_gather && (n0 & 3) == 0 && g0.w0 == 0 && g0.ws == 1 && g0.W == g0.Wt;      // every window stored, rows 16-byte aligned
         const dim3 dg4((unsigned)((n0 / 4 + 255) / 256));
-        if (!generic_digits && four && g0.c == 16) hipLaunchKernelGGL(k_digits_c4<16>, dg4, dim3(256), 0, s, d_scalars, n0, (int)mont, g0, digits, zl);
+        if (job->multi > 1) {
+            const dim3 dgm(dg.x, job->multi);
+            if (g0.c == 16) hipLaunchKernelGGL(k_digits_multi<16>, dgm, dim3(256), 0, s, d_scalars, job->multi_stride, n0, (int)mont, job->merge, digits, zl);
+            else if (g0.c == 12) hipLaunchKernelGGL(k_digits_multi<12>, dgm, dim3(256), 0, s, d_scalars, job->multi_stride, n0, (int)mont, job->merge, digits, zl);
+            else hipLaunchKernelGGL(k_digits_multi_any, dgm, dim3(256), 0, s, d_scalars, job->multi_stride, n0, (int)mont, g0, job->merge, digits, zl);
+        }
+        else if (!generic_digits && four && g0.c == 16) hipLaunchKernelGGL(k_digits_c4<16>, dg4, dim3(256), 0, s, d_scalars, n0, (int)mont, g0, digits, zl);
         else if (!generic_digits && four && g0.c == 12) hipLaunchKernelGGL(k_digits_c4<12>, dg4, dim3(256), 0, s, d_scalars, n0, (int)mont, g0, digits, zl);
         else if (!generic_digits && g0.c == 16) hipLaunchKernelGGL(k_digits_c<16>, dg, dim3(256), 0, s, d_scalars, d_gather, n0, (int)mont, g0, digits, zl);
         else if (!generic_digits && g0.c == 12) hipLaunchKernelGGL(k_digits_c<12>, dg, dim3(256), 0, s, d_scalars, d_gather, n0, (int)mont, g0, digits, zl);
@@ -1694,7 +1773,7 @@ int msm_job_launch(MsmJob *job, const MsmBases *sets, int nsets, const uint32_t 
     for (int i = 0; i < nsets; ++i) if ((sets[i].level_stride != 0) != any_table) { set_error("msm: table and plain base sets cannot share a launch"); return ZKG_ERROR; }
     if (any_table && (job->w0 != 0 || job->ws != 1 || job->window_hint <= 0)) { set_error("msm: a table launch covers all windows at the table's window size"); return ZKG_ERROR; }
     job->g = pick_geom(n, job->window_hint, job->w0, job->ws); job->n = n;
-    job->empty = false;
+    job->empty = false; job->multi = 1;
     MsmBases by_field[2][MSM_MAX_SETS];
     for (MsmGroup &gr : job->group) gr.nsets = 0;
     job->group[0].g2 = false; job->group[1].g2 = true;
@@ -1736,6 +1815,47 @@ int msm_job_launch(MsmJob *job, const MsmBases *sets, int nsets, const uint32_t 
     if (job->group[1].nsets && launch_accumulate<Fq2>(job, job->group[1], by_field[1], d_gather, job == &g_default_job && timed_field_g2)) return fail();   // G2 first: the longer chains
     if (job->group[0].nsets && launch_accumulate<Fq>(job, job->group[0], by_field[0], d_gather, job == &g_default_job || job == &g_piece_job)) return fail();
     lap("accum enqueued");
+    return ZKG_OK;
+}
+// The dual of a launch over several base sets: `count` scalar vectors of n elements, scalar_stride words apart, over the SAME table sets (all
+// windows, no gather / remap / index_sub).  One digit sort, one accumulation, one fold and one reduction per field for all of them; the fold
+// leaves a bucket set per (set, vector) and the reduction treats a set's as `count` windows (see k_digits_multi).
+bool msm_multi_supported(size_t n, int c, uint32_t count) {
+    const MsmGeom g = pick_geom(n, c);
+    return c > 0 && count >= 1 && n >= 1 && (uint64_t)n * g.W * count < ((uint64_t)1 << 31) &&
+           ((uint64_t)g.W * g.B * count + 1024 * SCAN_ITEMS - 1) / (1024 * SCAN_ITEMS) <= 1024;
+}
+int msm_job_launch_multi(MsmJob *job, const MsmBases *sets, int nsets, const uint32_t *d_scalars, size_t n, size_t scalar_stride, uint32_t count, bool scalars_mont) {
+    bool ok = job->w0 == 0 && job->ws == 1 && nsets >= 1 && nsets <= MSM_MAX_SETS && msm_multi_supported(n, job->window_hint, count);
+    for (int i = 0; i < nsets && ok; ++i) ok = sets[i].level_stride != 0 && !sets[i].remap && sets[i].index_sub == 0;
+    if (!ok) { set_error("msm: unsupported multi launch"); return ZKG_ERROR; }
+    job->g = pick_geom(n, job->window_hint); job->n = n;
+    job->empty = false; job->converted_aside = false;
+    MsmBases by_field[2][MSM_MAX_SETS];
+    for (MsmGroup &gr : job->group) gr.nsets = 0;
+    job->group[0].g2 = false; job->group[1].g2 = true;
+    for (int i = 0; i < nsets; ++i) { MsmGroup &gr = job->group[sets[i].g2 ? 1 : 0]; by_field[sets[i].g2 ? 1 : 0][gr.nsets] = sets[i]; gr.out_index[gr.nsets] = gr.nsets; ++gr.nsets; }
+    job->merge = 1;
+    if (job->merge_hint > 1 && job->g.W % job->merge_hint == 0) {                                       // as msm_job_launch
+        bool m = true;
+        for (int i = 0; i < nsets; ++i) m = m && sets[i].level_stride == n;
+        if (m) job->merge = job->merge_hint;
+    }
+    job->multi = count; job->multi_stride = scalar_stride;
+    if (sort_digits(job, d_scalars, scalars_mont, nullptr)) return ZKG_ERROR;
+    for (int k = 0; k < 2; ++k) for (int i = 0; i < job->group[k].nsets; ++i) by_field[k][i].level_stride *= job->merge;
+    if (job->group[1].nsets && launch_accumulate<Fq2>(job, job->group[1], by_field[1], nullptr, false)) return ZKG_ERROR;
+    if (job->group[0].nsets && launch_accumulate<Fq>(job, job->group[0], by_field[0], nullptr, false)) return ZKG_ERROR;
+    return ZKG_OK;
+}
+// out_g1[p * (G1 sets) + k]: vector p over the k-th G1 set of the launch; out_g2 likewise
+int msm_job_finish_multi(MsmJob *job, G1 *out_g1, G2 *out_g2) {
+    ZK_HIP(hipStreamSynchronize(job->stream));
+    const int n1 = job->group[0].nsets, n2 = job->group[1].nsets;
+    host_parallel_for((int)job->multi, [&](int p) {
+        for (int k = 0; k < n1; ++k) out_g1[p * n1 + k] = host_combine<Fq>(job, job->group[0], k, p);
+        for (int k = 0; k < n2; ++k) out_g2[p * n2 + k] = host_combine<Fq2>(job, job->group[1], k, p);
+    });
     return ZKG_OK;
 }
 // wait for the job's stream and finish on the host; outputs in launch order: out_g1[k] for the k-th G1 set, out_g2[k] for the k-th G2 set
@@ -1943,21 +2063,31 @@ template <class F> static int scatter_points_t(const Affine<F> *d_src, const uin
 int scatter_points_g1(const G1Affine *d_src, const uint32_t *d_idx, size_t count, G1Affine *d_out, hipStream_t s) { return scatter_points_t<Fq>(d_src, d_idx, count, d_out, s); }
 int scatter_points_g2(const G2Affine *d_src, const uint32_t *d_idx, size_t count, G2Affine *d_out, hipStream_t s) { return scatter_points_t<Fq2>(d_src, d_idx, count, d_out, s); }
 template <class F>
-static int ones_sum_launch_t(OnesSum &o, const MsmBases *sets, int nsets, const uint8_t *d_tags, size_t n1, hipStream_t s) {
+static int ones_sum_launch_t(OnesSum &o, const MsmBases *sets, int nsets, const uint8_t *d_tags, size_t n1, hipStream_t s, size_t tag_stride = 0, uint32_t vecs = 1) {
     // per workgroup: list the positions tagged 1, lanes stride over the list, an 8-level LDS tree; one more workgroup per set sums the partials
     if (nsets < 1 || nsets > MSM_MAX_SETS) { set_error("ones-sum: bad set count"); return ZKG_ERROR; }
     // tags per workgroup: a 256th of the vector, at least 1024 (a short list per lane leaves only the trees) and at most 8192 (32 KiB of LDS list)
     const uint32_t span = (uint32_t)std::min<size_t>(8192, std::max<size_t>(1024, ((n1 + 255) / 256 + 255) / 256 * 256));
     const unsigned blocks = (unsigned)std::max<size_t>(1, (n1 + span - 1) / span);
     o.g2 = sizeof(F) != sizeof(Fq); o.nsets = nsets;
-    if (o.partials.reserve((size_t)nsets * (blocks + 1) * sizeof(XYZZ<F>))) return ZKG_ERROR;
-    if (!o.host) { if (!hip_ok(hipHostMalloc(&o.host, MSM_MAX_SETS * sizeof(G2), hipHostMallocDefault), "hipHostMalloc", __FILE__, __LINE__)) return ZKG_ERROR; }
+    const size_t vec_stride = (size_t)nsets * (blocks + 1), host_bytes = std::max<size_t>(MSM_MAX_SETS, (size_t)vecs * nsets) * sizeof(G2);
+    if (o.partials.reserve(vecs * vec_stride * sizeof(XYZZ<F>))) return ZKG_ERROR;
+    if (o.host_bytes < host_bytes) {
+        if (o.host) (void)hipHostFree(o.host);
+        o.host = nullptr; o.host_bytes = 0;
+        if (!hip_ok(hipHostMalloc(&o.host, host_bytes, hipHostMallocDefault), "hipHostMalloc", __FILE__, __LINE__)) return ZKG_ERROR;
+        o.host_bytes = host_bytes;
+    }
     XYZZ<F> *part = o.partials.as<XYZZ<F>>();
     ViewSet<F> views;
     for (int i = 0; i < MSM_MAX_SETS; ++i) { const MsmBases &b = sets[i < nsets ? i : 0]; views.v[i] = BaseView<F>{reinterpret_cast<const Affine<F> *>(b.p), 0, nullptr, b.index_sub, 1, nullptr}; }
-    hipLaunchKernelGGL(k_ones_sum<F>, dim3(blocks, (unsigned)nsets), dim3(256), 256 * sizeof(LdsPoint<F>) + (size_t)span * 4, s, views, d_tags, n1, span, part);
-    hipLaunchKernelGGL(k_sum_partials<F>, dim3((unsigned)nsets), dim3(256), 256 * sizeof(LdsPoint<F>), s, part, blocks);
+    hipLaunchKernelGGL(k_ones_sum<F>, dim3(blocks, (unsigned)nsets, vecs), dim3(256), 256 * sizeof(LdsPoint<F>) + (size_t)span * 4, s, views, d_tags, n1, span, part, tag_stride, vec_stride);
+    hipLaunchKernelGGL(k_sum_partials<F>, dim3((unsigned)nsets, vecs), dim3(256), 256 * sizeof(LdsPoint<F>), s, part, blocks, vec_stride);
     if (hipGetLastError() != hipSuccess) { set_error("ones-sum launch failed"); return ZKG_ERROR; }
+    if (vecs > 1) {                                                             // vecs x nsets results, (blocks + 1) points apart, in one strided copy
+        ZK_HIP(hipMemcpy2DAsync(o.host, sizeof(XYZZ<F>), part + blocks, (blocks + 1) * sizeof(XYZZ<F>), sizeof(XYZZ<F>), (size_t)vecs * nsets, hipMemcpyDeviceToHost, s));
+        return ZKG_OK;
+    }
     for (int i = 0; i < nsets; ++i)
         ZK_HIP(hipMemcpyAsync((char *)o.host + (size_t)i * sizeof(XYZZ<F>), part + (size_t)i * (blocks + 1) + blocks, sizeof(XYZZ<F>), hipMemcpyDeviceToHost, s));
     return ZKG_OK;
@@ -1966,7 +2096,13 @@ int ones_sum_launch(OnesSum &o, const MsmBases *sets, int nsets, const uint8_t *
     for (int i = 1; i < nsets; ++i) if (sets[i].g2 != sets[0].g2) { set_error("ones-sum: one field per launch"); return ZKG_ERROR; }
     return sets[0].g2 ? ones_sum_launch_t<Fq2>(o, sets, nsets, d_tags, n1, s) : ones_sum_launch_t<Fq>(o, sets, nsets, d_tags, n1, s);
 }
-void OnesSum::release() { partials.release(); if (host) (void)hipHostFree(host); host = nullptr; }
+// the same for `count` witnesses' tag arrays, tag_stride bytes apart, as one launch pair: result of witness p, set i at index p * nsets + i
+int ones_sum_launch_multi(OnesSum &o, const MsmBases *sets, int nsets, const uint8_t *d_tags, size_t tag_stride, size_t n1, uint32_t count, hipStream_t s) {
+    for (int i = 1; i < nsets; ++i) if (sets[i].g2 != sets[0].g2) { set_error("ones-sum: one field per launch"); return ZKG_ERROR; }
+    if (count < 1 || count > 65535) { set_error("ones-sum: bad witness count"); return ZKG_ERROR; }
+    return sets[0].g2 ? ones_sum_launch_t<Fq2>(o, sets, nsets, d_tags, n1, s, tag_stride, count) : ones_sum_launch_t<Fq>(o, sets, nsets, d_tags, n1, s, tag_stride, count);
+}
+void OnesSum::release() { partials.release(); if (host) (void)hipHostFree(host); host = nullptr; host_bytes = 0; }
 
 // ---- fixed-base batch: out[i] = k_i * base (libff batch_exp with a window table; libsnark's generator, snark.cpp:91) --------------
 //      Table: entry [j][d-1] = d * 256^j * base (j < 32, d = 1..255), affine, 522 KB for G1: a scalar is 32 byte digits, i.e. at most

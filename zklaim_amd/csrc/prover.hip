@@ -86,6 +86,23 @@ struct ProverSlot {
     std::chrono::steady_clock::time_point t0;
 };
 
+// The workspace of zkg_groth16_prove_batch: one chunk of up to P proofs of the key in flight as ONE launch sequence.  Proof p's vectors lie
+// p strides apart in every buffer (z: n + 1 elements; aABC: aA | aB | aC, 3 m; the transform scratch the same shape), so that the kernels
+// take the proof as blockIdx.y and the transforms see a batch of 3 P (then P) vectors.  The multi-exponentiations are multi launches
+// (msm_job_launch_multi: P scalar vectors over one table): H over coefficients_for_H, the witness queries over wscal — every proof's values
+// at the elements the witness tables cover, zero where this witness has a bit there — one job for A / B_1 / L and one for B_2, on streams of
+// their own.  The flat sums over the ones take the proof as blockIdx.z (ones_sum_launch_multi), on two more streams.  Kept with the key, reused
+// by every call, freed with it.
+struct BatchWs {
+    uint32_t P = 0; bool ready = false;
+    zk::DevBuf z, aABC, scratch, wtags, wlisted, words, stage, wscal;
+    uint8_t *host_stage = nullptr; size_t host_cap = 0;      // pinned: the chunk's witnesses, packed (one upload)
+    uint32_t *host_words = nullptr;                          // pinned: P x BATCH_WORDS after the split, then P x BATCH_WORDS after the mat-vec
+    hipStream_t stream = nullptr, wst[4] = {nullptr, nullptr, nullptr, nullptr};
+    zk::MsmJob *job_h = nullptr, *job_w1 = nullptr, *job_w2 = nullptr; zk::OnesSum ones_g1, ones_g2;
+    hipEvent_t ev_split = nullptr, ev_flags = nullptr, ev_gathered = nullptr;      // the split's words landed; the mat-vec's flags landed; the witness jobs' scalars gathered
+};
+
 // Host-side fixed-base table of one key element P (alpha_1, beta_1, delta_1, delta_2): entry [j][d-1] = d * 16^j * P, affine.  k * P for a
 // 254-bit k is then 64 mixed additions and no doubling (~20 us for G1) instead of 254 doublings + ~127 additions (~130 us): the products
 // r*delta, s*delta, rs*delta, s*alpha, r*beta that every proof needs cost less than one variable-base multiplication together.
@@ -161,6 +178,8 @@ struct zkg_crs {
     float stage_ms[8] = {0};
     std::mutex mu; std::condition_variable cv;
     bool busy[MAX_SLOTS] = {false, false, false}; int leases = 0, waiting_ext = 0; bool extending = false;
+    // zkg_groth16_prove_batch: one chunk workspace per key; batch callers take turns on it (batch_mu, always taken BEFORE a slot lease)
+    BatchWs batch; std::mutex batch_mu;
 };
 
 namespace zk {
@@ -297,13 +316,13 @@ ZK_D bool claim_listed_tag(uint8_t *wtags, uint32_t pos, uint32_t tag) {
         old = prev;
     }
 }
-__global__ __launch_bounds__(256) void k_scatter_full(const uint32_t *idx, const Fr *vals, size_t cnt, size_t n, Fr *z, const uint8_t *tags, uint8_t *wtags,
-                                                      uint32_t *listed, uint32_t *count, uint32_t *words, const uint32_t *subset_pos, uint32_t *host_words) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+// entry i of one witness' listing (every lane of the wavefront takes part: the list positions come from a ballot); bad: the call's "bad listed entry" word
+ZK_D void scatter_full_entry(size_t i, const uint32_t *idx, const Fr *vals, size_t cnt, size_t n, Fr *z, const uint8_t *tags, uint8_t *wtags,
+                             uint32_t *listed, uint32_t *count, uint32_t *bad, const uint32_t *subset_pos) {
     uint32_t tag = 0, pos = 0;
     if (i < cnt) {
         const uint32_t v = idx[i];
-        if (v >= n || tags[v] != 2) or_and_wait(words + 3);                    // a listed index must be in range and tagged 2 (and listed once)
+        if (v >= n || tags[v] != 2) or_and_wait(bad);                          // a listed index must be in range and tagged 2 (and listed once)
         else {
             const Fr val = vals[i];
             uint32_t any = 0, diff = 0;
@@ -312,7 +331,7 @@ __global__ __launch_bounds__(256) void k_scatter_full(const uint32_t *idx, const
             tag = any == 0 ? 0u : (diff == 0 ? 1u : 2u);
             pos = v + 1;
             if (claim_listed_tag(wtags, pos, tag)) z[pos] = val;
-            else { or_and_wait(words + 3); tag = 0; }                           // listed twice: the call fails (words[3]), nothing is listed again
+            else { or_and_wait(bad); tag = 0; }                                 // listed twice: the call fails (words[3]), nothing is listed again
         }
     }
     const unsigned long long mask = __ballot(tag == 2);
@@ -326,6 +345,10 @@ __global__ __launch_bounds__(256) void k_scatter_full(const uint32_t *idx, const
             if (subset_pos && subset_pos[pos] == SUBSET_NONE) or_and_wait(count + 1);    // the witness tables do not cover this element (yet)
         }
     }
+}
+__global__ __launch_bounds__(256) void k_scatter_full(const uint32_t *idx, const Fr *vals, size_t cnt, size_t n, Fr *z, const uint8_t *tags, uint8_t *wtags,
+                                                      uint32_t *listed, uint32_t *count, uint32_t *words, const uint32_t *subset_pos, uint32_t *host_words) {
+    scatter_full_entry((size_t)blockIdx.x * blockDim.x + threadIdx.x, idx, vals, cnt, n, z, tags, wtags, listed, count, words + 3, subset_pos);
     __syncthreads();
     if (threadIdx.x == 0 && atomicAdd(words + 2, 1u) == gridDim.x - 1) {
         host_words[1] = atomicOr(count, 0u); host_words[2] = atomicOr(count + 1, 0u); host_words[3] = atomicOr(words + 3, 0u);
@@ -338,6 +361,79 @@ __global__ __launch_bounds__(256) void k_pointwise_h(Fr *aA, const Fr *aB, const
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
     aA[i] = ((aA[i] * aB[i] - aC[i]) * zinv).normalized();
+}
+
+// ---- the same steps for a chunk of proofs of one key (zkg_groth16_prove_batch): blockIdx.y = proof, proof p's vectors p strides apart.
+// Every witness arrives in the sparse form (the host rewrites a dense one), packed into one staging buffer: desc[p] = where its listing
+// starts among the chunk's (index, value) records and how long it is.  words: BATCH_WORDS per proof — [0] satisfiability flag, [3] bad listed
+// entry, [4] listed (non-bit) elements, [5] one of them misses the witness tables; the host reads all proofs' words in one copy.
+static constexpr uint32_t BATCH_WORDS = 8;
+struct BatchDesc { uint32_t off, cnt; };
+__global__ __launch_bounds__(256) void k_expand_tags_batch(const uint8_t *tags, size_t tag_stride, size_t n, Fr *z, uint8_t *wtags, size_t wtag_stride, uint32_t *words) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; const uint32_t p = blockIdx.y;
+    tags += p * tag_stride; z += p * (n + 1); wtags += p * wtag_stride; words += p * BATCH_WORDS;
+    if (i == 0) { z[0] = Fr::one(); wtags[0] = 1; for (uint32_t k = 0; k < BATCH_WORDS; ++k) words[k] = 0; }
+    if (i >= n) return;
+    const bool one = tags[i] == 1;
+    z[i + 1] = one ? Fr::one() : Fr::zero();
+    wtags[i + 1] = one ? 1 : (tags[i] == 2 ? TAG_UNCLAIMED : 0);
+}
+__global__ __launch_bounds__(256) void k_scatter_full_batch(const BatchDesc *desc, const uint32_t *idx, const Fr *vals, const uint8_t *tags, size_t tag_stride, size_t n, Fr *z,
+                                                            uint8_t *wtags, size_t wtag_stride, uint32_t *listed, uint32_t *words, const uint32_t *subset_pos) {
+    const uint32_t p = blockIdx.y; const BatchDesc d = desc[p];
+    if ((size_t)blockIdx.x * blockDim.x >= d.cnt) return;                       // (uniform per workgroup: the ballot below sees whole wavefronts)
+    uint32_t *w = words + p * BATCH_WORDS;
+    scatter_full_entry((size_t)blockIdx.x * blockDim.x + threadIdx.x, idx + d.off, vals + d.off, d.cnt, n, z + p * (n + 1), tags + p * tag_stride, wtags + p * wtag_stride,
+                       listed + p * (n + 1), w + 4, w + 3, subset_pos);
+}
+// proof p: aA | aB | aC at aABC + 3 p m.  The long rows are k_r1cs_long_batch's, their satisfiability k_r1cs_check_rows_batch's (as the single proof's default sequence)
+__global__ __launch_bounds__(256) void k_r1cs_eval_batch(const uint32_t *a_rp, const uint32_t *a_col, const Fr *a_val, const uint32_t *b_rp, const uint32_t *b_col, const Fr *b_val,
+                                                          const uint32_t *c_rp, const uint32_t *c_col, const Fr *c_val, const Fr *z, size_t z_stride, uint32_t C, uint32_t l, size_t m,
+                                                          Fr *aABC, uint32_t *words /* or null */) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; const uint32_t p = blockIdx.y;
+    if (i >= m) return;
+    z += p * z_stride;
+    Fr *aA = aABC + (size_t)3 * p * m, *aB = aA + m, *aC = aB + m;
+    Fr a = Fr::zero(), b = Fr::zero(), c = Fr::zero();
+    bool la = false, lb = false, lc = false;
+    if (i < C) {
+        a = row_dot_short(a_rp, a_col, a_val, z, i, la);
+        b = row_dot_short(b_rp, b_col, b_val, z, i, lb);
+        c = row_dot_short(c_rp, c_col, c_val, z, i, lc);
+        if (words && !(la | lb | lc) && a * b != c) or_and_wait(words + p * BATCH_WORDS);
+    } else if (i <= (size_t)C + l) {
+        a = z[i - C];
+    }
+    aA[i] = a.normalized(); aB[i] = b.normalized(); aC[i] = c.normalized();
+}
+__global__ __launch_bounds__(256) void k_r1cs_long_batch(const uint32_t *list, uint32_t n_long, const uint32_t *a_rp, const uint32_t *a_col, const Fr *a_val,
+                                                          const uint32_t *b_rp, const uint32_t *b_col, const Fr *b_val, const uint32_t *c_rp, const uint32_t *c_col, const Fr *c_val,
+                                                          const Fr *z, size_t z_stride, size_t m, Fr *aABC) {
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63, p = blockIdx.y;
+    if (wave >= n_long) return;
+    Fr *aA = aABC + (size_t)3 * p * m;
+    r1cs_long_entry(list[wave], lane, a_rp, a_col, a_val, b_rp, b_col, b_val, c_rp, c_col, c_val, z + p * z_stride, aA, aA + m, aA + 2 * m);
+}
+__global__ __launch_bounds__(256) void k_r1cs_check_rows_batch(const uint32_t *list, uint32_t n_long, const Fr *aABC, size_t m, uint32_t *words) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x, p = blockIdx.y;
+    if (j >= n_long) return;
+    const Fr *aA = aABC + (size_t)3 * p * m;
+    const uint32_t row = list[j] & 0x3fffffffu;
+    if (aA[row] * aA[m + row] != aA[2 * m + row]) or_and_wait(words + p * BATCH_WORDS);
+}
+// the witness jobs' scalars: out[p][j] = z_p[idx[j]] where witness p has a non-bit value at element idx[j] of the witness tables' subset, else 0
+// (its zeros contribute nothing and its ones belong to the flat sum)
+__global__ __launch_bounds__(256) void k_gather_nonbits_batch(const Fr *z, const uint8_t *wtags, size_t n1, size_t wtag_stride, const uint32_t *idx, size_t count, Fr *out) {
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; const uint32_t p = blockIdx.y;
+    if (j >= count) return;
+    const uint32_t e = idx[j];
+    out[p * count + j] = (e < n1 && wtags[p * wtag_stride + e] == 2) ? z[p * n1 + e] : Fr::zero();
+}
+__global__ __launch_bounds__(256) void k_pointwise_h_batch(Fr *aABC, size_t m, Fr zinv) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    Fr *aA = aABC + (size_t)3 * blockIdx.y * m;
+    aA[i] = ((aA[i] * aA[m + i] - aA[2 * m + i]) * zinv).normalized();
 }
 
 static int upload(DevBuf &d, const void *src, size_t bytes) {
@@ -467,6 +563,10 @@ int table_window_bits(size_t n) {                                    // window s
     //  the seam, whose witness pass dominates there: 17 windows x 2^14 buckets cost chip time that other proofs could use.  12 stays.)
     return lg >= 15 ? 16 : lg >= 9 ? 12 : 8;
 }
+static uint32_t h_row_merge(const zkg_crs *crs) {                             // (ZKG_H_ROW_MERGE: tuning aid)
+    static const int force = getenv("ZKG_H_ROW_MERGE") ? atoi(getenv("ZKG_H_ROW_MERGE")) : 0;
+    return force ? (uint32_t)force : (crs->H_query.n >= H_ROW_MERGE_MIN ? 2u : 1u);
+}
 static int slot_create(zkg_crs *crs, ProverSlot &S) {
     if (S.ready) return ZKG_OK;
     const size_t n = crs->n, m = crs->m;
@@ -498,7 +598,7 @@ static int slot_create(zkg_crs *crs, ProverSlot &S) {
             // H: sixteen windows in eight rows of buckets from 49152 points on — where the unmerged launch already takes the two-pass sort
             // (2 / 4 / 8 payloads: 0.78 -> 0.72, 0.93 -> 0.88, 1.22 -> 1.17 ms; four rows at 8 payloads: 1.26 — one round of lanes, the
             // longest chain sets the time; one payload, 2^15 points: 0.75 -> 0.89, the doubled rows leave the one-pass sort's range)
-            { static const int force = getenv("ZKG_H_ROW_MERGE") ? atoi(getenv("ZKG_H_ROW_MERGE")) : 0; msm_job_set_row_merge(S.job_h, force ? (uint32_t)force : (crs->H_query.n >= H_ROW_MERGE_MIN ? 2u : 1u)); }
+            msm_job_set_row_merge(S.job_h, h_row_merge(crs));
         }
     }
     if (ok) {
@@ -625,6 +725,7 @@ static void slot_release_h_runs(ProverSlot &S) {                              //
     }
     S.h_runs.clear();
 }
+static void batch_destroy(BatchWs &B);
 void zkg_crs_free(zkg_crs *crs) {
     if (!crs) return;
     for (DevBuf *b : {&crs->A.rowptr, &crs->A.col, &crs->A.val, &crs->B.rowptr, &crs->B.col, &crs->B.val, &crs->Cm.rowptr, &crs->Cm.col, &crs->Cm.val,
@@ -637,6 +738,7 @@ void zkg_crs_free(zkg_crs *crs) {
     for (auto &sh : crs->h_shards) { (void)hipSetDevice(sh.device); sh.table.release(); }
     (void)hipSetDevice(cur);
     for (ProverSlot &S : crs->slot) slot_destroy(S);
+    batch_destroy(crs->batch);
     delete crs;
 }
 
@@ -722,7 +824,7 @@ static MsmBases query_set(const DevBuf &q, bool g2, uint32_t index_sub) { MsmBas
 // The witness tables grow to cover `listed` more elements (the first proof on a key; later only when a witness has a non-bit value where
 // every earlier one had a bit).  Host: membership -> ascending element list and positions; device: level 0 gathered from the queries, then
 // the levels.  Runs on the helper thread with the ones-sum stream, which has nothing of this proof queued yet.
-static int subset_extend(zkg_crs *crs, ProverSlot &S, size_t listed) {
+static int subset_extend(zkg_crs *crs, ProverSlot &S, size_t listed, const std::vector<uint32_t> *listed_host = nullptr /* a batch: the union of its witnesses' lists */) {
     zkg_crs::SubsetTables &T = crs->sub;
     const size_t n1 = (size_t)crs->n + 1; hipStream_t s = S.stream_o;
     // From here until one of the two success exits the key has NO witness tables: pos / idx / the tables / the window size are rewritten
@@ -731,9 +833,13 @@ static int subset_extend(zkg_crs *crs, ProverSlot &S, size_t listed) {
     T.count = 0;
     const auto t_ext0 = std::chrono::steady_clock::now();
     auto ext_lap = [&](const char *w) { if (g_dbg_timing) fprintf(stderr, "[zkg]       subset_extend %-28s %8.3f ms\n", w, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_ext0).count()); };
-    std::vector<uint32_t> li(listed);
-    ZK_HIP(hipMemcpyAsync(li.data(), S.wlisted.p, listed * 4, hipMemcpyDeviceToHost, s));
-    ZK_HIP(hipStreamSynchronize(s));
+    std::vector<uint32_t> li;
+    if (listed_host) li = *listed_host;
+    else {
+        li.resize(listed);
+        ZK_HIP(hipMemcpyAsync(li.data(), S.wlisted.p, listed * 4, hipMemcpyDeviceToHost, s));
+        ZK_HIP(hipStreamSynchronize(s));
+    }
     if (T.member.empty()) T.member.assign(n1, 0);
     for (uint32_t i : li) { if (i >= n1) { set_error("prover: witness split out of range"); return ZKG_ERROR; } T.member[i] = 1; }
     std::vector<uint32_t> pos(n1, SUBSET_NONE), idx;
@@ -1090,6 +1196,263 @@ static int groth16_prove_sparse_impl(const zkg_crs *crs_, const uint8_t *tags, c
     return prove_finish(crs, S, proof_out, proof_len);
 }
 
+// ---- zkg_groth16_prove_batch: P proofs of one key per launch sequence -----------------------------------------------------------
+// Proofs per chunk, 0 = the key takes the single-proof path inside the call: radix-2 domains up to 2^17 without H shards run batched (up to
+// four payloads: a lone proof leaves most of the chip idle there); a step domain, a larger one (one proof fills the chip) or a sharded H
+// query do not.  16 proofs up to m = 2^15, 8 above: the H launch's P x W x B buckets stay within the block scan of the digit sort.
+static uint32_t batch_chunk_for(const zkg_crs *crs) {
+    if (!crs->dom || crs->m > ((size_t)1 << 17) || crs->m < 2 || !crs->n || !crs->h_shards.empty()) return 0;
+    const uint32_t P = (crs->m <= ((size_t)1 << 15) && crs->c_w_forced < 15) ? 16 : 8;               // (a forced 15- or 16-bit witness window: as the large H windows)
+    return msm_multi_supported(crs->m - 1, crs->H_query.c, P) ? P : 0;
+}
+static void batch_destroy(BatchWs &B) {
+    for (DevBuf *b : {&B.z, &B.aABC, &B.scratch, &B.wtags, &B.wlisted, &B.words, &B.stage, &B.wscal}) b->release();
+    msm_job_destroy(B.job_h); msm_job_destroy(B.job_w1); msm_job_destroy(B.job_w2); B.job_h = B.job_w1 = B.job_w2 = nullptr;
+    B.ones_g1.release(); B.ones_g2.release();
+    if (B.stream) (void)hipStreamDestroy(B.stream);
+    B.stream = nullptr;
+    for (hipStream_t &st : B.wst) { if (st) (void)hipStreamDestroy(st); st = nullptr; }
+    for (hipEvent_t *e : {&B.ev_split, &B.ev_flags, &B.ev_gathered}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
+    if (B.host_stage) (void)hipHostFree(B.host_stage);
+    if (B.host_words) (void)hipHostFree(B.host_words);
+    B.host_stage = nullptr; B.host_words = nullptr; B.host_cap = 0; B.ready = false; B.P = 0;
+}
+static size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+static int batch_create(zkg_crs *crs, BatchWs &B, uint32_t P) {
+    if (B.ready) return ZKG_OK;
+    const size_t n1 = (size_t)crs->n + 1, m = crs->m;
+    bool ok = B.z.reserve(P * n1 * 32) == 0 && B.aABC.reserve((size_t)P * 3 * m * 32) == 0 && B.scratch.reserve((size_t)P * 3 * m * NTT_SCRATCH_BYTES) == 0 &&
+              B.wtags.reserve(P * round_up(n1, 16)) == 0 && B.wlisted.reserve(P * n1 * 4) == 0 && B.words.reserve((size_t)P * BATCH_WORDS * 4) == 0 &&
+              hip_ok(hipHostMalloc((void **)&B.host_words, (size_t)2 * P * BATCH_WORDS * 4, hipHostMallocDefault), "hipHostMalloc", __FILE__, __LINE__);
+    if (ok) {
+        int prio_lo = 0, prio_hi = 0;
+        (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+        // the chunk's critical path (upload, split, mat-vec, transforms, H) on one stream, as a slot's; wst[0] the B_2 job, wst[1] the A / B_1 / L job, wst[2..3] the flat sums
+        ok = hip_ok(hipStreamCreateWithPriority(&B.stream, hipStreamNonBlocking, prio_hi), "hipStreamCreate", __FILE__, __LINE__);
+        for (hipStream_t &st : B.wst) ok = ok && hip_ok(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, prio_lo), "hipStreamCreate", __FILE__, __LINE__);
+        ok = ok && hip_ok(hipEventCreateWithFlags(&B.ev_split, hipEventDisableTiming), "hipEventCreate", __FILE__, __LINE__) &&
+             hip_ok(hipEventCreateWithFlags(&B.ev_flags, hipEventDisableTiming), "hipEventCreate", __FILE__, __LINE__) &&
+             hip_ok(hipEventCreateWithFlags(&B.ev_gathered, hipEventDisableTiming), "hipEventCreate", __FILE__, __LINE__);
+        B.job_h = ok ? msm_job_create(B.stream, false) : nullptr;
+        B.job_w2 = ok ? msm_job_create(B.wst[0], false) : nullptr; B.job_w1 = ok ? msm_job_create(B.wst[1], false) : nullptr;
+        ok = ok && B.job_h && B.job_w1 && B.job_w2;
+        if (ok) { msm_job_set_window(B.job_h, crs->H_query.c); msm_job_set_row_merge(B.job_h, h_row_merge(crs)); }
+    }
+    if (!ok) { batch_destroy(B); return ZKG_ERROR; }
+    B.P = P; B.ready = true;
+    return ZKG_OK;
+}
+static void batch_drain(BatchWs &B) {
+    (void)hipStreamSynchronize(B.stream);
+    for (hipStream_t st : B.wst) (void)hipStreamSynchronize(st);
+}
+// a dense witness in the sparse form: tag per variable, the variables that are neither 0 nor 1 listed (idx / vals null: count only)
+static size_t dense_to_sparse(const uint64_t *w, size_t n, uint8_t *tags, uint32_t *idx, uint64_t *vals) {
+    const Fr one_fr = Fr::one();
+    uint64_t one[4]; memcpy(one, one_fr.v, 32);
+    size_t cnt = 0;
+    for (size_t v = 0; v < n; ++v) {
+        const uint64_t *e = w + 4 * v;
+        uint8_t t = 2;
+        if ((e[0] | e[1] | e[2] | e[3]) == 0) t = 0;
+        else if (e[0] == one[0] && e[1] == one[1] && e[2] == one[2] && e[3] == one[3]) t = 1;
+        if (tags) tags[v] = t;
+        if (t == 2) { if (idx) { idx[cnt] = (uint32_t)v; memcpy(vals + 4 * cnt, e, 32); } ++cnt; }
+    }
+    return cnt;
+}
+// proof bytes from the four multi-exponentiations' results (W1: A, B_1, L over the whole witness; the same algebra as prove_finish)
+static void assemble_proof(const zkg_crs *crs, const Fr &r, const Fr &s, const G1 W1[3], const G2 &Wb2, const G1 &Ht, uint8_t *out) {
+    uint32_t rc[8], sc[8], rsc[8];
+    canonical_limbs(r, rc); canonical_limbs(s, sc); canonical_limbs(r * s, rsc);
+    G1 gA = G1::from_affine(crs->alpha_g1); gA.add(crs->delta1_comb.mul(rc)); gA.add(W1[0]);             // alpha + r delta + W_a
+    G2 gB2 = G2::from_affine(crs->beta_g2); gB2.add(crs->delta2_comb.mul(sc)); gB2.add(Wb2);             // beta + s delta + W_b
+    G1 gC = crs->alpha1_comb.mul(sc); gC.add(crs->beta1_comb.mul(rc)); gC.add(crs->delta1_comb.mul(rsc)); // s alpha + r beta_1 + rs delta
+    gC.add(W1[0].mul(sc, 8)); gC.add(W1[1].mul(rc, 8)); gC.add(W1[2]); gC.add(Ht);                       // + s W_a + r W_b + L + H
+    size_t off = ser_g1(out, gA);
+    off += ser_g2(out + off, gB2);
+    ser_g1(out + off, gC);
+}
+static thread_local size_t t_batch_stats[3] = {0, 0, 0};
+
+// one chunk: P <= B.P items, under the batch mutex and a slot lease (the lease is the chunk's place in the key's extension protocol; its
+// slot lends the streams of a table extension)
+static int prove_chunk(zkg_crs *crs, BatchWs &B, ProverSlot &S, const zkg_prove_item *items, uint32_t P, bool check, uint8_t *proofs_out, int *status) {
+    const size_t n = crs->n, n1 = n + 1, m = crs->m, l = crs->l, tag_stride = round_up(n, 16), wtag_stride = round_up(n1, 16);
+    hipStream_t s = B.stream;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto lap = [&](const char *what) { if (g_dbg_timing) fprintf(stderr, "[zkg batch] %-28s %8.3f ms\n", what, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count()); };
+    // ---- 1. pack the witnesses: [desc | values | indices | tags], one upload
+    std::vector<uint32_t> cnt(P, 0); std::vector<uint8_t> skip(P, 0);
+    host_parallel_for((int)P, [&](int p) {
+        const zkg_prove_item &it = items[p];
+        if (!it.r || !it.s) skip[p] = 1;
+        else if (it.witness) cnt[p] = (uint32_t)dense_to_sparse(it.witness, n, nullptr, nullptr, nullptr);
+        else if (!it.tags || (it.count && (!it.full_index || !it.full_values)) || it.count > n) skip[p] = 1;
+        else cnt[p] = (uint32_t)it.count;
+    });
+    std::vector<uint32_t> off(P + 1, 0);
+    for (uint32_t p = 0; p < P; ++p) off[p + 1] = off[p] + cnt[p];
+    const size_t total = off[P], o_vals = round_up((size_t)P * sizeof(BatchDesc), 64), o_idx = o_vals + total * 32, o_tags = round_up(o_idx + total * 4, 64),
+                 bytes = o_tags + P * tag_stride;
+    if (bytes > B.host_cap) {
+        if (B.host_stage) (void)hipHostFree(B.host_stage);
+        B.host_stage = nullptr; B.host_cap = 0;
+        ZK_HIP(hipHostMalloc((void **)&B.host_stage, bytes + bytes / 2, hipHostMallocDefault));
+        B.host_cap = bytes + bytes / 2;
+    }
+    if (B.stage.reserve(bytes)) return ZKG_ERROR;
+    uint8_t *hs = B.host_stage;
+    host_parallel_for((int)P, [&](int p) {
+        const zkg_prove_item &it = items[p];
+        BatchDesc *d = reinterpret_cast<BatchDesc *>(hs) + p; d->off = off[p]; d->cnt = cnt[p];
+        uint8_t *tags = hs + o_tags + (size_t)p * tag_stride; uint32_t *idx = reinterpret_cast<uint32_t *>(hs + o_idx) + off[p]; uint64_t *vals = reinterpret_cast<uint64_t *>(hs + o_vals) + 4 * (size_t)off[p];
+        if (skip[p]) memset(tags, 0, n);
+        else if (it.witness) (void)dense_to_sparse(it.witness, n, tags, idx, vals);
+        else { memcpy(tags, it.tags, n); if (cnt[p]) { memcpy(idx, it.full_index, (size_t)cnt[p] * 4); memcpy(vals, it.full_values, (size_t)cnt[p] * 32); } }
+    });
+    lap("witnesses packed");
+    ZK_HIP(hipMemcpyAsync(B.stage.p, hs, bytes, hipMemcpyHostToDevice, s));
+    const uint8_t *st = B.stage.as<uint8_t>();
+    const BatchDesc *d_desc = reinterpret_cast<const BatchDesc *>(st); const Fr *d_vals = reinterpret_cast<const Fr *>(st + o_vals);
+    const uint32_t *d_idx = reinterpret_cast<const uint32_t *>(st + o_idx); const uint8_t *d_tags = st + o_tags;
+    Fr *z = B.z.as<Fr>(), *aABC = B.aABC.as<Fr>(), *scr = B.scratch.as<Fr>();
+    uint8_t *wtags = B.wtags.as<uint8_t>(); uint32_t *wlisted = B.wlisted.as<uint32_t>(), *words = B.words.as<uint32_t>();
+    uint32_t *hw_split = B.host_words, *hw_flags = B.host_words + (size_t)B.P * BATCH_WORDS;
+    const uint32_t *subset_pos = crs->sub.count ? crs->sub.pos.as<uint32_t>() : nullptr;
+    // ---- 2. split, mat-vec, transforms, H: one launch sequence for the chunk
+    const uint32_t max_cnt = *std::max_element(cnt.begin(), cnt.end());
+    hipLaunchKernelGGL(k_expand_tags_batch, dim3((unsigned)((n + 255) / 256), P), dim3(256), 0, s, d_tags, tag_stride, n, z, wtags, wtag_stride, words);
+    if (max_cnt) hipLaunchKernelGGL(k_scatter_full_batch, dim3((max_cnt + 255) / 256, P), dim3(256), 0, s, d_desc, d_idx, d_vals, d_tags, tag_stride, n, z, wtags, wtag_stride, wlisted, words, subset_pos);
+    ZK_HIP(hipMemcpyAsync(hw_split, words, (size_t)P * BATCH_WORDS * 4, hipMemcpyDeviceToHost, s));
+    ZK_HIP(hipEventRecord(B.ev_split, s));
+    const unsigned grid_m = (unsigned)((m + 255) / 256);
+    hipLaunchKernelGGL(k_r1cs_eval_batch, dim3(grid_m, P), dim3(256), 0, s, crs->A.rowptr.as<uint32_t>(), crs->A.col.as<uint32_t>(), crs->A.val.as<Fr>(),
+                       crs->B.rowptr.as<uint32_t>(), crs->B.col.as<uint32_t>(), crs->B.val.as<Fr>(), crs->Cm.rowptr.as<uint32_t>(), crs->Cm.col.as<uint32_t>(), crs->Cm.val.as<Fr>(),
+                       z, n1, crs->C, crs->l, m, aABC, check ? words : nullptr);
+    if (crs->n_long) {
+        hipLaunchKernelGGL(k_r1cs_long_batch, dim3((crs->n_long + 3) / 4, P), dim3(256), 0, s, crs->long_rows.as<uint32_t>(), crs->n_long,
+                           crs->A.rowptr.as<uint32_t>(), crs->A.col.as<uint32_t>(), crs->A.val.as<Fr>(), crs->B.rowptr.as<uint32_t>(), crs->B.col.as<uint32_t>(), crs->B.val.as<Fr>(),
+                           crs->Cm.rowptr.as<uint32_t>(), crs->Cm.col.as<uint32_t>(), crs->Cm.val.as<Fr>(), z, n1, m, aABC);
+        if (check) hipLaunchKernelGGL(k_r1cs_check_rows_batch, dim3((crs->n_long + 255) / 256, P), dim3(256), 0, s, crs->long_rows.as<uint32_t>(), crs->n_long, aABC, m, words);
+    }
+    if (check) { ZK_HIP(hipMemcpyAsync(hw_flags, words, (size_t)P * BATCH_WORDS * 4, hipMemcpyDeviceToHost, s)); ZK_HIP(hipEventRecord(B.ev_flags, s)); }
+    // the transforms as batches of 3 P and P vectors (proof p's aA | aB | aC are vectors 3 p .. 3 p + 2; its aA alone 3 m apart)
+    if (ntt_run_ex(crs->dom, aABC, true, nullptr, crs->coset_over_m.as<Fr>(), nullptr, s, scr, 3 * P, 0, nullptr, crs->coset_over_m29.p)) return ZKG_ERROR;
+    if (ntt_run_ex(crs->dom, aABC, false, nullptr, nullptr, nullptr, s, scr, 3 * P)) return ZKG_ERROR;
+    hipLaunchKernelGGL(k_pointwise_h_batch, dim3(grid_m, P), dim3(256), 0, s, aABC, m, crs->z_inv_coset);
+    if (ntt_run_ex(crs->dom, aABC, true, nullptr, crs->dom->icoset_post.as<Fr>(), nullptr, s, scr, P, 3 * m)) return ZKG_ERROR;
+    if (hipGetLastError() != hipSuccess) { set_error("prover kernel launch failed"); return ZKG_ERROR; }
+    const MsmBases h = table_set(crs->H_query, false, 0);
+    if (msm_job_launch_multi(B.job_h, &h, 1, B.aABC.as<uint32_t>(), m - 1, 3 * m * 8, P, true)) return ZKG_ERROR;
+    lap("chunk stream enqueued");
+    // ---- 3. the split has landed: per-item verdicts, the witness tables, the witness jobs
+    ZK_HIP(hipEventSynchronize(B.ev_split));
+    lap("split landed");
+    std::vector<uint8_t> good(P, 0);
+    bool extend = false;
+    for (uint32_t p = 0; p < P; ++p) {
+        const uint32_t *w = hw_split + (size_t)p * BATCH_WORDS;
+        status[p] = ZKG_ERROR;
+        if (skip[p]) { set_error("zkg_groth16_prove_batch: bad item"); continue; }
+        if (w[3]) { set_error("prover: a listed witness index is out of range, not tagged 2 or listed twice"); continue; }
+        if (w[4] > n1) { set_error("prover: witness split out of range"); continue; }
+        good[p] = 1;
+        extend = extend || (w[4] && (w[5] || !crs->sub.count));
+    }
+    if (extend) {
+        // ONE extension for the union of the chunk's non-bit elements, under the key's protocol (see zkg_crs): no other proof in flight meanwhile
+        std::vector<uint32_t> li;
+        for (uint32_t p = 0; p < P; ++p) if (good[p]) {
+            const size_t k = hw_split[(size_t)p * BATCH_WORDS + 4], at = li.size();
+            li.resize(at + k);
+            if (k) ZK_HIP(hipMemcpy(li.data() + at, wlisted + (size_t)p * n1, k * 4, hipMemcpyDeviceToHost));
+        }
+        std::unique_lock<std::mutex> lk(crs->mu);
+        ++crs->waiting_ext; crs->cv.notify_all();
+        crs->cv.wait(lk, [&] { return !crs->extending && crs->leases - crs->waiting_ext == 0; });
+        --crs->waiting_ext; crs->extending = true;
+        lk.unlock();
+        int rc_ext = ZKG_ERROR;
+        try { rc_ext = subset_extend(crs, S, li.size(), &li); } catch (...) { set_error("prover: witness table extension failed"); }
+        lk.lock();
+        crs->extending = false; crs->cv.notify_all();
+        lk.unlock();
+        if (rc_ext) return ZKG_ERROR;
+    }
+    // bucket method: every proof's non-bit values over the subset tables, two multi launches; flat sums over the ones: the queries as uploaded, per proof
+    const size_t sub_n = crs->sub.count;
+    bool any_listed = false;
+    for (uint32_t p = 0; p < P; ++p) any_listed = any_listed || (good[p] && hw_split[(size_t)p * BATCH_WORDS + 4]);
+    const bool jobs = any_listed && sub_n;                                   // (no table yet and nothing listed: the witness queries are flat sums only)
+    if (jobs) {
+        if (!msm_multi_supported(sub_n, crs->c_w, P) || B.wscal.reserve((size_t)P * sub_n * 32)) { set_error("prover: witness tables too large for a batched launch"); return ZKG_ERROR; }
+        hipStream_t s2 = msm_job_stream(B.job_w2), s1 = msm_job_stream(B.job_w1);
+        hipLaunchKernelGGL(k_gather_nonbits_batch, dim3((unsigned)((sub_n + 255) / 256), P), dim3(256), 0, s2, z, wtags, n1, wtag_stride, crs->sub.idx.as<uint32_t>(), sub_n, B.wscal.as<Fr>());
+        ZK_HIP(hipEventRecord(B.ev_gathered, s2)); ZK_HIP(hipStreamWaitEvent(s1, B.ev_gathered, 0));
+        const MsmBases g1[3] = {table_set(crs->sub.A, false, 0), table_set(crs->sub.B1, false, 0), table_set(crs->sub.L, false, 0)}, b2 = table_set(crs->sub.B2, true, 0);
+        msm_job_set_window(B.job_w1, crs->c_w); msm_job_set_window(B.job_w2, crs->c_w);
+        if (msm_job_launch_multi(B.job_w2, &b2, 1, B.wscal.as<uint32_t>(), sub_n, sub_n * 8, P, true) ||
+            msm_job_launch_multi(B.job_w1, g1, 3, B.wscal.as<uint32_t>(), sub_n, sub_n * 8, P, true)) return ZKG_ERROR;
+    }
+    const MsmBases o1[3] = {query_set(crs->A_query, false, 0), query_set(crs->B_g1, false, 0), query_set(crs->L_query, false, (uint32_t)(l + 1))}, o2 = query_set(crs->B_g2, true, 0);
+    // (the split is complete: nothing to wait for on these streams)
+    if (ones_sum_launch_multi(B.ones_g2, &o2, 1, wtags, wtag_stride, n1, P, B.wst[2]) || ones_sum_launch_multi(B.ones_g1, o1, 3, wtags, wtag_stride, n1, P, B.wst[3])) return ZKG_ERROR;
+    lap("witness jobs enqueued");
+    // ---- 4. results: H for the whole chunk, then the proofs' host work side by side on the host pool
+    std::vector<G1> Ht(P), Wg1((size_t)3 * P, G1::inf()); std::vector<G2> Wg2(P, G2::inf());
+    if (msm_job_finish_multi(B.job_h, Ht.data(), nullptr)) return ZKG_ERROR;     // (waits for the chunk's stream: the flags have landed too)
+    lap("H landed");
+    for (hipStream_t w : B.wst) ZK_HIP(hipStreamSynchronize(w));
+    if (jobs && (msm_job_finish_multi(B.job_w1, Wg1.data(), nullptr) || msm_job_finish_multi(B.job_w2, nullptr, Wg2.data()))) return ZKG_ERROR;
+    lap("witness jobs landed");
+    host_parallel_for((int)P, [&](int p) {
+        if (!good[p]) return;
+        if (check && hw_flags[(size_t)p * BATCH_WORDS]) { status[p] = ZKG_UNSATISFIED; return; }
+        G1 W1[3] = {Wg1[3 * (size_t)p], Wg1[3 * (size_t)p + 1], Wg1[3 * (size_t)p + 2]}; G2 Wb2 = Wg2[p];
+        for (int i = 0; i < 3; ++i) W1[i].add(B.ones_g1.g1(3 * p + i));
+        Wb2.add(B.ones_g2.g2pt(p));
+        Fr r, sv; memcpy(r.v, items[p].r, 32); memcpy(sv.v, items[p].s, 32);
+        assemble_proof(crs, r, sv, W1, Wb2, Ht[p], proofs_out + (size_t)p * ZKG_PROOF_BYTES);
+        status[p] = ZKG_OK;
+    });
+    lap("proofs assembled");
+    for (uint32_t p = 0; p < P; ++p) if (status[p] == ZKG_UNSATISFIED) set_error("constraint system not satisfied; not creating proof");
+    return ZKG_OK;
+}
+static int groth16_prove_batch_impl(const zkg_crs *crs_, const zkg_prove_item *items, size_t count, int check_satisfied, uint8_t *proofs_out, int *status) {
+    t_batch_stats[0] = t_batch_stats[1] = t_batch_stats[2] = 0;
+    if (!count) return ZKG_OK;
+    zkg_crs *crs = const_cast<zkg_crs *>(crs_);
+    if (!crs || !items || !proofs_out || !status) { set_error("zkg_groth16_prove_batch: bad argument"); return ZKG_ERROR; }
+    const uint32_t chunk = batch_chunk_for(crs);
+    if (!chunk) {                                                            // this key's proofs do not batch: the single-proof path, item by item
+        for (size_t i = 0; i < count; ++i) {
+            const zkg_prove_item &it = items[i];
+            uint8_t buf[256]; size_t len = 0;
+            status[i] = it.witness ? groth16_prove_impl(crs, it.witness, it.r, it.s, check_satisfied, buf, &len)
+                                   : groth16_prove_sparse_impl(crs, it.tags, it.full_index, it.full_values, it.count, it.r, it.s, check_satisfied, buf, &len);
+            if (status[i] == ZKG_OK) memcpy(proofs_out + i * ZKG_PROOF_BYTES, buf, ZKG_PROOF_BYTES);
+            ++t_batch_stats[1];
+        }
+        return ZKG_OK;
+    }
+    std::lock_guard<std::mutex> batch_lock(crs->batch_mu);
+    if (batch_create(crs, crs->batch, chunk)) return ZKG_ERROR;
+    for (size_t first = 0; first < count; first += chunk) {
+        const uint32_t P = (uint32_t)std::min<size_t>(chunk, count - first);
+        SlotLease lease(crs);                                                // per chunk: between chunks other callers may extend the witness tables
+        if (!lease.ok()) return ZKG_ERROR;
+        int rc = ZKG_ERROR;
+        try { rc = prove_chunk(crs, crs->batch, lease.S(), items + first, P, check_satisfied != 0, proofs_out + first * ZKG_PROOF_BYTES, status + first); }
+        catch (const std::exception &e) { set_error(std::string("zkg_groth16_prove_batch: ") + e.what()); }
+        catch (...) { set_error("zkg_groth16_prove_batch: unexpected exception"); }
+        if (rc) { batch_drain(crs->batch); return ZKG_ERROR; }                  // nothing of the chunk may still be running when the workspace changes hands
+        t_batch_stats[0] += P; ++t_batch_stats[2];
+    }
+    return ZKG_OK;
+}
+
 // helper threads and host containers are used below these two: nothing may propagate through the C boundary
 int zkg_groth16_prove(const zkg_crs *crs, const uint64_t *witness, const uint64_t r[4], const uint64_t s[4], int check_satisfied,
                       uint8_t *proof_out, size_t *proof_len) {
@@ -1103,6 +1466,15 @@ int zkg_groth16_prove_sparse(const zkg_crs *crs, const uint8_t *tags, const uint
     catch (const std::exception &e) { set_error(std::string("zkg_groth16_prove_sparse: ") + e.what()); return ZKG_ERROR; }
     catch (...) { set_error("zkg_groth16_prove_sparse: unexpected exception"); return ZKG_ERROR; }
 }
+
+int zkg_groth16_prove_batch(const zkg_crs *crs, const zkg_prove_item *items, size_t count, int check_satisfied, uint8_t *proofs_out, int *status) {
+    try { return groth16_prove_batch_impl(crs, items, count, check_satisfied, proofs_out, status); }
+    catch (const std::exception &e) { set_error(std::string("zkg_groth16_prove_batch: ") + e.what()); }
+    catch (...) { set_error("zkg_groth16_prove_batch: unexpected exception"); }
+    return ZKG_ERROR;
+}
+void zkg_prove_batch_stats(size_t out[3]) { if (out) for (int i = 0; i < 3; ++i) out[i] = t_batch_stats[i]; }
+size_t zkg_prove_batch_chunk(const zkg_crs *crs) { return crs ? batch_chunk_for(crs) : 0; }
 
 // Shards the H query of a resident key over `ndev` devices (a device may be listed more than once: how a one-GPU box rehearses the
 // path).  No proof of this key may be in flight.  The key's own device keeps everything else (witness queries, transforms, assembly).
