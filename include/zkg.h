@@ -237,10 +237,10 @@ int zkg_groth16_prove_sparse(const zkg_crs *crs, const uint8_t *tags, const uint
  *      (witness == NULL) call with its own (r, s); status[i] and the ZKG_PROOF_BYTES at proofs_out + i * ZKG_PROOF_BYTES are exactly what that
  *      call returns and writes for item i alone — proof bytes are deterministic given (key, witness, r, s).  An unsatisfied witness (with
  *      check_satisfied) is ZKG_UNSATISFIED for that item only, a bad sparse listing or a null pointer inside an item ZKG_ERROR for that item
- *      only; the other items are still proved and nothing is written for a failed one.  Keys on a radix-2 domain up to 2^17 without H
- *      shards are proved in chunks of zkg_prove_batch_chunk items whose GPU work is ONE launch sequence (the kernels carry a proof
- *      dimension; the H multi-exponentiations of a chunk share one sort, accumulation, fold and reduction); other keys go through the
- *      single-proof path item by item.  Synchronous; host pointers; safe from several threads and beside zkg_groth16_prove* on the same key.
+ *      only; the other items are still proved and nothing is written for a failed one.  Keys on a domain below 2^18 (radix-2 up to 2^17
+ *      and every step_radix2 size under 2^18: one to seven zklaim payloads) without H shards are proved in chunks of zkg_prove_batch_chunk
+ *      items whose GPU work is ONE launch sequence (the kernels carry a proof dimension; the H multi-exponentiations of a chunk share one
+ *      sort, accumulation, fold and reduction); other keys go through the single-proof path item by item.  Synchronous; host pointers; safe from several threads and beside zkg_groth16_prove* on the same key.
  *      Returns ZKG_OK when every status was written (count == 0 included: nothing is touched), ZKG_ERROR for a null argument or a HIP failure. */
 typedef struct zkg_prove_item {
     const uint64_t *witness;                 /* dense form: n x 4 limbs as zkg_groth16_prove, or NULL for the sparse form */
@@ -332,6 +332,14 @@ int libsnark_trusted_setup(struct zklaim_ctx *ctx);
 int libsnark_prove(struct zklaim_ctx *ctx);
 int libsnark_verify(struct zklaim_ctx *ctx);
 void zkg_compat_reset(void);
+/* ---- many libsnark_prove calls in one (no counterpart in the reference, hence the prefix).
+ * rc[i] = what libsnark_prove(ctxs[i]) returns: 0 (ZKLAIM_OK) with ctxs[i]->proof / proof_size set (malloc'ed, ZKG_PROOF_BYTES), 1 for an
+ * unsatisfied credential or any other failure (the reference's two codes coincide).  A failed item leaves its ctx untouched and does
+ * not disturb the others; a null ctx or one without a key is rc 1, decided before any GPU call.  Contexts are grouped by their key, every
+ * group resolves its resident key once, the witnesses are generated side by side on the host pool and each group is one
+ * zkg_groth16_prove_batch with fresh (r, s) per item.  Returns ZKG_OK when every rc[i] was written (count == 0: nothing is touched),
+ * ZKG_ERROR for a null ctxs or rc.  Safe beside libsnark_prove on the same key from other threads. */
+int zkg_zklaim_prove_batch(struct zklaim_ctx *const *ctxs, size_t count, int *rc);
 
 /* ---- known-answer hook for the device arithmetic (libff Fp_model<4,...>::mul_reduce, Fp2_model —
  *      here the generated v_mad_u64_u32 streams of csrc/mont_asm.inc).  Element-wise ON THE GPU, host pointers:

@@ -6,9 +6,14 @@ P distinct credentials of one key, sparse witnesses, fresh (r, s):
   batch         one Crs.prove_batch of the P items                              (leg c)
 --reps timed repetitions each after one warm-up; min / median / max proofs/s.  The batch's bytes are compared with the sequential leg's.
 Prints a table and one JSON line; --out writes the JSON to a file.  --commit names the source state in the JSON.
+--seam measures the zklaim seam instead: P contexts of one key (libsnark_trusted_setup's) through a loop of libsnark_prove calls (sequential)
+against one zkg_zklaim_prove_batch (batch), witness generation included in both; same output shape, no three-callers leg.
 Usage: python tools/prove_batch_time.py [--ks 1 2 4] [--ps 1 2 4 8 16 32] [--reps 5] [--out profiles/prove_batch_time.json]
-       rocprofv3 --kernel-trace --stats -d DIR -- python tools/prove_batch_time.py --trace-only single|batch
-                                           (key setup, then 11 times one proof / one batch of 16 at k = 1: the runs to trace, no counters with them)
+       python tools/prove_batch_time.py --ks 3 5 6 7 --ps 1 4 8 16        (the step-domain keys below 2^18)
+       python tools/prove_batch_time.py --seam --ks 1 3 --ps 8 16
+       rocprofv3 --kernel-trace --stats -d DIR -- python tools/prove_batch_time.py --trace-only single|batch [--trace-k K]
+                                           (key setup, then 11 times one proof / one batch of the key's chunk at K payloads, default 1: the runs to
+                                            trace, no counters with them)
        python tools/prove_batch_time.py --merge-stats SINGLE_kernel_stats.csv BATCH_kernel_stats.csv profiles/prove_batch_kernel_stats.csv"""
 import argparse
 import json
@@ -31,7 +36,10 @@ ap.add_argument("--commit", default=None)
 ap.add_argument("--note", action="append", default=[], help="free text recorded in the JSON (e.g. the parent build's prove_throughput lines)")
 ap.add_argument("--out", default=None)
 ap.add_argument("--trace-only", choices=["single", "batch"], default=None)
+ap.add_argument("--trace-k", type=int, default=1, help="payload count of the --trace-only runs")
+ap.add_argument("--seam", action="store_true", help="libsnark_prove loop against zkg_zklaim_prove_batch")
 ap.add_argument("--merge-stats", nargs=3, metavar=("SINGLE_CSV", "BATCH_CSV", "OUT_CSV"), default=None)
+ap.add_argument("--merge-batch-size", type=int, default=16, help="proofs per traced batch, for the column names of --merge-stats")
 cli = ap.parse_args()
 TRACE_CALLS = 11
 
@@ -71,13 +79,15 @@ if cli.merge_stats:
             rows.setdefault(r["Name"], [[0, 0], [0, 0]])[col] = [int(r["Calls"]), int(r["TotalDurationNs"])]
     with open(out, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(["Name", "single_launches", "single_total_us", "batch16_launches", "batch16_total_us", "traced_calls_each"])
+        b_ = f"batch{cli.merge_batch_size}"
+        w.writerow(["Name", "single_launches", "single_total_us", b_ + "_launches", b_ + "_total_us", "traced_calls_each"])
         for name, (a, b) in sorted(rows.items(), key=lambda kv: -kv[1][1][1]):
             w.writerow([name, a[0], round(a[1] / 1e3, 1), b[0], round(b[1] / 1e3, 1), TRACE_CALLS])
     sys.exit(0)
 zkg.init(0)
 if cli.trace_only:
-    crs, items, keep = key_and_items(1, 16)
+    crs, items, keep = key_and_items(cli.trace_k, 16)
+    items = items[:crs.prove_batch_chunk() or 16]
     for _ in range(TRACE_CALLS):                                # (the first call is the warm-up: witness tables, workspaces)
         if cli.trace_only == "single":
             assert crs.prove_sparse(*items[0])[0] == 0
@@ -89,7 +99,54 @@ if cli.trace_only:
 
 res = {"tool": "prove_batch_time", "commit": cli.commit, "reps": cli.reps, "device": zkg.device_info() if hasattr(zkg, "device_info") else None,
        "notes": cli.note, "results": {}}
-for k in cli.ks:
+if cli.seam:
+    import ctypes as C
+    libc_free = C.CDLL(None).free
+    libc_free.argtypes = [C.c_void_p]
+    res["leg"] = "seam"
+    for k in cli.ks:
+        keep = []
+
+        def payloads(v):
+            return [dict(attrs=[1990 + i, 7 * i, 42, i, 5], refs=[2100, 7 * i, 41, 0, 5], ops=["less", "eq", "greater", "noop", "greater_or_eq"], salt=0x5A4B + i + 131 * v)
+                    for i in range(k)]
+        owner = zkg.make_ctx(payloads(0), keep)
+        assert zkg.libsnark_trusted_setup(owner) == 0
+        ctxs = []
+        for v in range(max(cli.ps)):
+            c = zkg.make_ctx(payloads(v), keep)
+            c.pk, c.pk_size, c.vk, c.vk_size = owner.pk, owner.pk_size, owner.vk, owner.vk_size
+            ctxs.append(c)
+
+        def drop_proofs(sub):                                   # ctx->proof is the caller's to free (zklaim_ctx_free)
+            for c in sub:
+                if c.proof:
+                    libc_free(c.proof)
+                c.proof = None; c.proof_size = 0
+
+        rk = {"P": {}}
+        for P in cli.ps:
+            sub = ctxs[:P]
+
+            def loop():
+                drop_proofs(sub)
+                assert [zkg.libsnark_prove(c) for c in sub] == [0] * P
+
+            def batch():
+                drop_proofs(sub)
+                assert zkg.zklaim_prove_batch(sub) == [0] * P
+
+            batch()
+            stats = zkg.prove_batch_stats()
+            assert all(zkg.libsnark_verify(c) == 0 for c in sub)
+            seq = rates(loop, P, cli.reps)
+            bat = rates(batch, P, cli.reps)
+            rk["P"][P] = {"sequential": seq, "batch": bat, "batch_stats": stats, "batch_min_over_sequential_max": round(bat["min"] / seq["max"], 3)}
+            print(f"seam k={k} P={P:3d}  libsnark_prove loop {seq}  zkg_zklaim_prove_batch {bat}  batch min / loop max = {bat['min'] / seq['max']:.2f}", flush=True)
+        drop_proofs(ctxs)
+        res["results"][k] = rk
+        zkg.lib().zkg_compat_reset()
+for k in ([] if cli.seam else cli.ks):
     crs, items, keep = key_and_items(k, max(cli.ps))
     chunk = crs.prove_batch_chunk()
     expect = [crs.prove_sparse(*it) for it in items]

@@ -24,7 +24,7 @@ DECLARED_SYMBOLS = [
     "zkg_msm_g1_multi", "zkg_g1_add_quad29", "zkg_crs_shard_h", "zkg_msm_g1_bases_upload", "zkg_msm_g1_resident", "zkg_msm_g1_bases_free",
     "zkg_prover_peak_in_flight", "zkg_msm_g1_host_scalars", "zkg_multi_rccl_calls", "zkg_g1_add_pair29",
     "zkg_groth16_verify_batch", "zkg_pairing_product", "zkg_verify_batch_stats",
-    "zkg_groth16_prove_batch", "zkg_prove_batch_stats", "zkg_prove_batch_chunk",
+    "zkg_groth16_prove_batch", "zkg_prove_batch_stats", "zkg_prove_batch_chunk", "zkg_zklaim_prove_batch",
 ]
 # the reference's own seam, exported with its original names (zklaim.h:257-259)
 COMPAT_SYMBOLS = ["libsnark_trusted_setup", "libsnark_prove", "libsnark_verify"]
@@ -701,6 +701,17 @@ def pairing_selfcheck(exponent):
 def libsnark_trusted_setup(ctx): return lib().libsnark_trusted_setup(C.byref(ctx))
 def libsnark_prove(ctx): return lib().libsnark_prove(C.byref(ctx))
 def libsnark_verify(ctx): return lib().libsnark_verify(C.byref(ctx))
+
+
+def zklaim_prove_batch(ctxs):
+    """zkg_zklaim_prove_batch: one libsnark_prove per ZklaimCtx (None: a null entry), grouped by key and batched -> [rc, ...]"""
+    L = lib()
+    L.zkg_zklaim_prove_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+    n = len(ctxs)
+    ptrs = (C.c_void_p * max(1, n))(*[None if c is None else C.addressof(c) for c in ctxs])
+    rc = (C.c_int * max(1, n))(*([-1] * max(1, n)))
+    _check(L.zkg_zklaim_prove_batch(ptrs, n, rc), "zkg_zklaim_prove_batch")
+    return [int(rc[i]) for i in range(n)]
 
 
 def ctx_blob(ctx, which):

@@ -87,7 +87,7 @@ int ntt_run_ex(NttDomain *d, Fr *d_a, bool inverse, const Fr *pre, const Fr *pos
 int ntt_table29(DevBuf &out, const Fr *d_in, size_t n, hipStream_t s);       // a table in libff's form -> its 29-bit records
 
 // libfqfft get_evaluation_domain(min_size) for min_size <= 2^28: basic_radix2_domain (m = 2^k) or step_radix2_domain (m = big + small,
-// big = 2^(ceil_log2(m)-1), small = 2^b < big).  zklaim's circuits land on a step domain for 10 of the 20 payload counts.
+// big = 2^(ceil_log2(m)-1), small = 2^b < big).  zklaim's circuits land on a step domain for 11 of the 20 payload counts.
 struct DomainShape { size_t m = 0, big = 0, small = 0; bool step = false; unsigned log_m = 0; /* ceil(log2 m) */ };
 bool evaluation_domain_shape(size_t min_size, DomainShape &d);
 bool domain_shape_of(size_t m, DomainShape &d);           // m must be a size the rule maps to itself

@@ -2,6 +2,7 @@
 //     int libsnark_trusted_setup(zklaim_ctx*), int libsnark_prove(zklaim_ctx*), int libsnark_verify(zklaim_ctx*)
 // (declared /root/reference/zklaim/zklaim.h:257-259, defined zklaim/libsnark_wrapper.cpp:195-276, called from
 // zklaim_trusted_setup / zklaim_proof_generate / zklaim_proof_verify at zklaim/zklaim.c:77-91).
+// and one entry the reference does not have: int zkg_zklaim_prove_batch(zklaim_ctx *const *, size_t, int *rc), many libsnark_prove calls in one.
 // Behaviour kept: 0 on success; prove returns 1 for an unsatisfied credential (libsnark_wrapper.cpp:233-240); verify returns
 // !valid (:269); ctx->pk / vk / proof are malloc'd here and freed by zklaim_ctx_free (zklaim.c:57-72).
 // Behaviour changed on purpose: file descriptor 1 is never closed (the reference closes stdout around every call,
@@ -281,6 +282,104 @@ int libsnark_prove(zklaim_ctx *ctx) {
     try { return libsnark_prove_impl(ctx); }                      // nothing propagates through the C boundary
     catch (const std::exception &e) { zk::set_error(std::string("libsnark_prove: ") + e.what()); return ZKLAIM_ERROR; }
     catch (...) { zk::set_error("libsnark_prove: unexpected exception"); return ZKLAIM_ERROR; }
+}
+
+
+// ---- zkg_zklaim_prove_batch: many libsnark_prove calls in one -----------------------------------------------------------------------
+// The contexts of one key (same blob: same pointer and size, or equal sampled and full digests) are one group: one resident-key lookup, the
+// witnesses side by side on the host pool, one zkg_groth16_prove_batch.
+namespace {
+struct SeamItem { zkg_circuit *ck = nullptr; const uint8_t *tags = nullptr; const uint32_t *fidx = nullptr; const uint64_t *fval = nullptr; size_t nfull = 0; uint64_t r[4], s[4]; bool ok = false; };
+struct SeamGroup {
+    const unsigned char *pk = nullptr; size_t size = 0; uint64_t key = 0; bool have_full = false; Digest128 full;
+    std::vector<size_t> at;                                      // indices into ctxs
+    const Digest128 &full_of() { if (!have_full) { full = full_digest(pk, size); have_full = true; } return full; }
+};
+}  // namespace
+static void prove_group(zklaim_ctx *const *ctxs, SeamGroup &g, int *rc) {
+    const size_t n = g.at.size();
+    const zklaim_ctx *first = ctxs[g.at[0]];
+    bool speculative = false;                                    // as libsnark_prove_impl: a hit by the sampled digest is confirmed by the full one
+    Digest128 recorded_full;
+    std::shared_ptr<zkg_crs> crs = resident_key(first, g.key, speculative, recorded_full);
+    if (!crs) return;
+    std::future<Digest128> confirm;
+    if (speculative && !g.have_full) confirm = std::async(std::launch::async, [&] { return full_digest(g.pk, g.size); });      // under the witness passes and the GPU's work
+    std::vector<SeamItem> items(n);
+    struct FreeAll { std::vector<SeamItem> &v; ~FreeAll() { for (SeamItem &it : v) if (it.ck) zkg_circuit_free(it.ck); } } free_all{items};
+    host_parallel_for((int)n, [&](int i) {
+        SeamItem &it = items[i];
+        try {
+            it.ck = zkg_zklaim_witness_new(ctxs[g.at[i]]);
+            it.ok = it.ck && zkg_circuit_sparse_witness(it.ck, &it.tags, &it.fidx, &it.fval, &it.nfull) == ZKG_OK;
+        } catch (...) { it.ok = false; }
+    });
+    for (SeamItem &it : items) { random_fr_mont(it.r); random_fr_mont(it.s); }
+    std::vector<uint8_t> proofs(n * ZKG_PROOF_BYTES);
+    std::vector<int> status(n, ZKG_ERROR);
+    // the items whose variable count is the key's (a key made for another payload count: that item fails alone), as one batch
+    auto prove = [&](zkg_crs *c) {
+        std::vector<zkg_prove_item> batch; std::vector<size_t> which;
+        for (size_t i = 0; i < n; ++i) {
+            status[i] = ZKG_ERROR;
+            if (!items[i].ok) continue;
+            if (zkg_circuit_num_variables(items[i].ck) != zkg_crs_num_variables(c)) { set_error("zkg_zklaim_prove_batch: ctx->pk was generated for a different circuit (variable count differs)"); continue; }
+            zkg_prove_item p{};
+            p.witness = nullptr; p.tags = items[i].tags; p.full_index = items[i].fidx; p.full_values = items[i].fval; p.count = items[i].nfull; p.r = items[i].r; p.s = items[i].s;
+            batch.push_back(p); which.push_back(i);
+        }
+        if (batch.empty()) return;
+        std::vector<uint8_t> out(batch.size() * ZKG_PROOF_BYTES); std::vector<int> st(batch.size(), ZKG_ERROR);
+        if (zkg_groth16_prove_batch(c, batch.data(), batch.size(), 1, out.data(), st.data()) != ZKG_OK) return;
+        for (size_t j = 0; j < which.size(); ++j) { status[which[j]] = st[j]; if (st[j] == ZKG_OK) memcpy(proofs.data() + which[j] * ZKG_PROOF_BYTES, out.data() + j * ZKG_PROOF_BYTES, ZKG_PROOF_BYTES); }
+    };
+    prove(crs.get());
+    if (speculative) {
+        const Digest128 full = g.have_full ? g.full : confirm.get();
+        if (!(full == recorded_full)) {                          // same size and samples, different bytes: not the resident key after all
+            std::fill(status.begin(), status.end(), ZKG_ERROR);
+            crs = replace_key(first, g.key, full);
+            if (crs) prove(crs.get());
+        }
+    }
+    for (size_t i = 0; i < n; ++i) {
+        if (status[i] != ZKG_OK) continue;                       // (unsatisfied and every other failure: 1, the ctx untouched)
+        unsigned char *proof = (unsigned char *)malloc(ZKG_PROOF_BYTES);
+        if (!proof) continue;
+        memcpy(proof, proofs.data() + i * ZKG_PROOF_BYTES, ZKG_PROOF_BYTES);
+        zklaim_ctx *ctx = ctxs[g.at[i]];
+        ctx->proof = proof; ctx->proof_size = ZKG_PROOF_BYTES; rc[g.at[i]] = ZKLAIM_OK;
+    }
+}
+static int zklaim_prove_batch_impl(zklaim_ctx *const *ctxs, size_t count, int *rc) {
+    if (!count) return ZKG_OK;
+    if (!ctxs || !rc) { set_error("zkg_zklaim_prove_batch: null argument"); return ZKG_ERROR; }
+    std::vector<SeamGroup> groups;
+    for (size_t i = 0; i < count; ++i) {
+        rc[i] = ZKLAIM_ERROR;
+        const zklaim_ctx *ctx = ctxs[i];
+        if (!ctx || !ctx->pk || !ctx->pk_size) continue;          // decided before any GPU call
+        SeamGroup *g = nullptr;
+        for (SeamGroup &o : groups) if (o.pk == ctx->pk && o.size == ctx->pk_size) { g = &o; break; }
+        if (!g) {                                                 // another copy of a blob already seen?  sampled digest first, every byte to confirm
+            SeamGroup fresh; fresh.pk = ctx->pk; fresh.size = ctx->pk_size; fresh.key = sampled_digest(ctx->pk, ctx->pk_size);
+            for (SeamGroup &o : groups) if (o.size == fresh.size && o.key == fresh.key && o.full_of() == fresh.full_of()) { g = &o; break; }
+            if (!g) { groups.push_back(fresh); g = &groups.back(); }
+        }
+        g->at.push_back(i);
+    }
+    for (SeamGroup &g : groups) {
+        try { prove_group(ctxs, g, rc); }                        // a group that fails leaves its items at 1 and the other groups alone
+        catch (const std::exception &e) { zk::set_error(std::string("zkg_zklaim_prove_batch: ") + e.what()); }
+        catch (...) { zk::set_error("zkg_zklaim_prove_batch: unexpected exception"); }
+    }
+    return ZKG_OK;
+}
+int zkg_zklaim_prove_batch(zklaim_ctx *const *ctxs, size_t count, int *rc) {
+    try { return zklaim_prove_batch_impl(ctxs, count, rc); }     // nothing propagates through the C boundary
+    catch (const std::exception &e) { zk::set_error(std::string("zkg_zklaim_prove_batch: ") + e.what()); }
+    catch (...) { zk::set_error("zkg_zklaim_prove_batch: unexpected exception"); }
+    return ZKG_ERROR;
 }
 
 

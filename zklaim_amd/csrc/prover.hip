@@ -436,6 +436,15 @@ __global__ __launch_bounds__(256) void k_pointwise_h_batch(Fr *aABC, size_t m, F
     aA[i] = ((aA[i] * aA[m + i] - aA[2 * m + i]) * zinv).normalized();
 }
 
+// the same on a step_radix2_domain (k_pointwise_h_step's arithmetic, the proof as blockIdx.y)
+__global__ __launch_bounds__(256) void k_pointwise_h_step_batch(Fr *aABC, size_t m, size_t big, const Fr *zinv, uint32_t period_mask, Fr zinv_small) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    Fr *aA = aABC + (size_t)3 * blockIdx.y * m;
+    const Fr zi = i < big ? zinv[i & period_mask] : zinv_small;
+    aA[i] = ((aA[i] * aA[m + i] - aA[2 * m + i]) * zi).normalized();
+}
+
 static int upload(DevBuf &d, const void *src, size_t bytes) {
     if (d.reserve(bytes ? bytes : 16)) return ZKG_ERROR;
     if (bytes && !hip_ok(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice), "H2D", __FILE__, __LINE__)) return ZKG_ERROR;
@@ -1197,11 +1206,11 @@ static int groth16_prove_sparse_impl(const zkg_crs *crs_, const uint8_t *tags, c
 }
 
 // ---- zkg_groth16_prove_batch: P proofs of one key per launch sequence -----------------------------------------------------------
-// Proofs per chunk, 0 = the key takes the single-proof path inside the call: radix-2 domains up to 2^17 without H shards run batched (up to
-// four payloads: a lone proof leaves most of the chip idle there); a step domain, a larger one (one proof fills the chip) or a sharded H
-// query do not.  16 proofs up to m = 2^15, 8 above: the H launch's P x W x B buckets stay within the block scan of the digit sort.
+// Proofs per chunk, 0 = the key takes the single-proof path inside the call: domains below 2^18 without H shards run batched (up to seven
+// payloads: a lone proof leaves most of the chip idle there), radix-2 and step_radix2 alike; a larger domain (one proof fills the chip) or a
+// sharded H query do not.  16 proofs up to m = 2^15, 8 above: the H launch's P x W x B buckets stay within the block scan of the digit sort.
 static uint32_t batch_chunk_for(const zkg_crs *crs) {
-    if (!crs->dom || crs->m > ((size_t)1 << 17) || crs->m < 2 || !crs->n || !crs->h_shards.empty()) return 0;
+    if ((!crs->dom && !crs->sdom) || crs->m >= ((size_t)1 << 18) || crs->m < 2 || !crs->n || !crs->h_shards.empty()) return 0;
     const uint32_t P = (crs->m <= ((size_t)1 << 15) && crs->c_w_forced < 15) ? 16 : 8;               // (a forced 15- or 16-bit witness window: as the large H windows)
     return msm_multi_supported(crs->m - 1, crs->H_query.c, P) ? P : 0;
 }
@@ -1338,10 +1347,22 @@ static int prove_chunk(zkg_crs *crs, BatchWs &B, ProverSlot &S, const zkg_prove_
     }
     if (check) { ZK_HIP(hipMemcpyAsync(hw_flags, words, (size_t)P * BATCH_WORDS * 4, hipMemcpyDeviceToHost, s)); ZK_HIP(hipEventRecord(B.ev_flags, s)); }
     // the transforms as batches of 3 P and P vectors (proof p's aA | aB | aC are vectors 3 p .. 3 p + 2; its aA alone 3 m apart)
-    if (ntt_run_ex(crs->dom, aABC, true, nullptr, crs->coset_over_m.as<Fr>(), nullptr, s, scr, 3 * P, 0, nullptr, crs->coset_over_m29.p)) return ZKG_ERROR;
-    if (ntt_run_ex(crs->dom, aABC, false, nullptr, nullptr, nullptr, s, scr, 3 * P)) return ZKG_ERROR;
-    hipLaunchKernelGGL(k_pointwise_h_batch, dim3(grid_m, P), dim3(256), 0, s, aABC, m, crs->z_inv_coset);
-    if (ntt_run_ex(crs->dom, aABC, true, nullptr, crs->dom->icoset_post.as<Fr>(), nullptr, s, scr, P, 3 * m)) return ZKG_ERROR;
+    if (crs->dom) {
+        if (ntt_run_ex(crs->dom, aABC, true, nullptr, crs->coset_over_m.as<Fr>(), nullptr, s, scr, 3 * P, 0, nullptr, crs->coset_over_m29.p)) return ZKG_ERROR;
+        if (ntt_run_ex(crs->dom, aABC, false, nullptr, nullptr, nullptr, s, scr, 3 * P)) return ZKG_ERROR;
+        hipLaunchKernelGGL(k_pointwise_h_batch, dim3(grid_m, P), dim3(256), 0, s, aABC, m, crs->z_inv_coset);
+        if (ntt_run_ex(crs->dom, aABC, true, nullptr, crs->dom->icoset_post.as<Fr>(), nullptr, s, scr, P, 3 * m)) return ZKG_ERROR;
+    } else {
+        // step_radix2_domain: compute_h_transforms' four steps with the proof dimension.  Every vector's partial sums (32-byte elements) and
+        // transform scratch (40-byte records, the small transform's behind the big one's) stay inside its own stride of the P x 3 m scratch:
+        // 32 big + 40 small <= 40 m bytes
+        StepDomain *sd = crs->sdom;
+        if (step_ntt_run(sd, aABC, true, false, s, scr, 3 * P, m)) return ZKG_ERROR;                 // iFFT x 3 P
+        if (step_ntt_run(sd, aABC, false, true, s, scr, 3 * P, m)) return ZKG_ERROR;                 // cosetFFT x 3 P
+        hipLaunchKernelGGL(k_pointwise_h_step_batch, dim3(grid_m, P), dim3(256), 0, s, aABC, m, sd->shape.big, sd->zinv.as<Fr>(),
+                           (uint32_t)(sd->shape.big / sd->shape.small - 1), sd->zinv_small);
+        if (step_ntt_run(sd, aABC, true, true, s, scr, P, 3 * m)) return ZKG_ERROR;                  // icosetFFT x P
+    }
     if (hipGetLastError() != hipSuccess) { set_error("prover kernel launch failed"); return ZKG_ERROR; }
     const MsmBases h = table_set(crs->H_query, false, 0);
     if (msm_job_launch_multi(B.job_h, &h, 1, B.aABC.as<uint32_t>(), m - 1, 3 * m * 8, P, true)) return ZKG_ERROR;
