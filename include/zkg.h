@@ -253,6 +253,33 @@ int zkg_groth16_prove_batch(const zkg_crs *crs, const zkg_prove_item *items, siz
  * that went through the single-proof path, out[2] batched chunks launched.  Counters, not clocks. */
 void zkg_prove_batch_stats(size_t out[3]);
 size_t zkg_prove_batch_chunk(const zkg_crs *crs);   /* proofs per batched chunk for this key; 0 = this key takes the single-proof path */
+/* ---- many zklaim credentials of ONE resident key, their witnesses generated on the GPU.  ctxs[i] is a zklaim_ctx (include/zklaim_abi.h) whose
+ *      payload count is the key's; rs holds (r, s) per item, 8 limbs: r | s, Montgomery Fr.  status[i] and the proof bytes are exactly those of
+ *      zkg_groth16_prove_sparse on the host witness of ctxs[i] (zkg_zklaim_witness_new + zkg_circuit_sparse_witness) with the same (r, s).
+ *      Per chunk, 128 bytes per payload go up (pre-image, hash, reference values, ops) and one kernel writes every variable's tag and the
+ *      listed values into the chunk's device stage; everything from the split on is zkg_groth16_prove_batch's.  A null context, a broken
+ *      payload list or a payload count other than the key's is ZKG_ERROR for that item only, an unsatisfied credential ZKG_UNSATISFIED for
+ *      that item only.  For a key that does not batch (zkg_prove_batch_chunk == 0) the witnesses are made on the host and the existing
+ *      paths are taken: same bytes.  The generator counts a payload's variables itself; if that count ever disagrees with the host pass's,
+ *      or with the key's variable count, the call keeps the host witnesses and zkg_last_error says so.  Returns as zkg_groth16_prove_batch. */
+struct zklaim_ctx;
+int zkg_groth16_prove_batch_zklaim(const zkg_crs *crs, const struct zklaim_ctx *const *ctxs, size_t count, const uint64_t *rs /* count x 8 limbs */,
+                                   int check_satisfied, uint8_t *proofs_out /* count x ZKG_PROOF_BYTES */, int *status /* count entries */);
+/* what the calling thread's last zkg_groth16_prove_batch_zklaim or zkg_zklaim_prove_batch did: out[0] items whose witness the GPU made,
+ * out[1] items whose witness the host made.  Counters, not clocks. */
+void zkg_zklaim_witness_stats(size_t out[2]);
+/* Variables of the credential circuit with `payloads` payloads (0: out of range), and optionally the most one witness can list, as the
+ * generator counts them.  No GPU, no zkg_init. */
+size_t zkg_zklaim_witness_size(size_t payloads, size_t *cap_listed);
+/* test hook: the generator alone.  Contexts of ONE payload count (that of the first non-null one), n = zkg_zklaim_witness_size of it:
+ * tags_out[i * n ..] the tag of every variable (0 zero, 1 one, 2 listed), index_out[i * cap_listed ..] / values_out[4 * i * cap_listed ..]
+ * the listed variables in ascending order with their Montgomery values, listed_counts[i] how many.  A null context, a broken payload list or
+ * another payload count fails alone: listed_counts[i] = (size_t)-1, its tags zero.  Needs zkg_init, no key. */
+int zkg_zklaim_witness_gpu(const struct zklaim_ctx *const *ctxs, size_t count, uint8_t *tags_out /* count x n */, uint32_t *index_out,
+                           uint64_t *values_out, size_t cap_listed /* per item */, size_t *listed_counts);
+/* the same outputs for one context from the generator's code compiled for the host.  No GPU, no zkg_init (as zkg_pk_blob_inspect). */
+int zkg_zklaim_witness_mirror(const struct zklaim_ctx *ctx, uint8_t *tags_out /* n */, uint32_t *index_out, uint64_t *values_out, size_t cap_listed,
+                              size_t *listed_count);
 /* coefficients_for_H (m+1 Fr, Montgomery) of r1cs_to_qap_witness_map, for parity tests */
 int zkg_qap_witness_h(const zkg_crs *crs, const uint64_t *witness, uint64_t *h_out);
 /* per-stage device milliseconds of the last zkg_groth16_prove on this crs (the stages run on their own streams, so the entries
@@ -336,8 +363,9 @@ void zkg_compat_reset(void);
  * rc[i] = what libsnark_prove(ctxs[i]) returns: 0 (ZKLAIM_OK) with ctxs[i]->proof / proof_size set (malloc'ed, ZKG_PROOF_BYTES), 1 for an
  * unsatisfied credential or any other failure (the reference's two codes coincide).  A failed item leaves its ctx untouched and does
  * not disturb the others; a null ctx or one without a key is rc 1, decided before any GPU call.  Contexts are grouped by their key, every
- * group resolves its resident key once, the witnesses are generated side by side on the host pool and each group is one
- * zkg_groth16_prove_batch with fresh (r, s) per item.  Returns ZKG_OK when every rc[i] was written (count == 0: nothing is touched),
+ * group resolves its resident key once and is one zkg_groth16_prove_batch_zklaim with fresh (r, s) per item when its key batches (the
+ * witnesses are generated on the GPU; ZKG_SEAM_GPU_WITNESS=0, read once, keeps the host passes), otherwise the witnesses are generated
+ * side by side on the host pool and the group is one zkg_groth16_prove_batch.  Returns ZKG_OK when every rc[i] was written (count == 0: nothing is touched),
  * ZKG_ERROR for a null ctxs or rc.  Safe beside libsnark_prove on the same key from other threads. */
 int zkg_zklaim_prove_batch(struct zklaim_ctx *const *ctxs, size_t count, int *rc);
 

@@ -7,10 +7,15 @@ P distinct credentials of one key, sparse witnesses, fresh (r, s):
 --reps timed repetitions each after one warm-up; min / median / max proofs/s.  The batch's bytes are compared with the sequential leg's.
 Prints a table and one JSON line; --out writes the JSON to a file.  --commit names the source state in the JSON.
 --seam measures the zklaim seam instead: P contexts of one key (libsnark_trusted_setup's) through a loop of libsnark_prove calls (sequential)
-against one zkg_zklaim_prove_batch (batch), witness generation included in both; same output shape, no three-callers leg.
+against one zkg_zklaim_prove_batch (batch), witness generation included in both; same output shape, no three-callers leg.  The batch is
+measured per witness source: "batch" as the process is configured (GPU witnesses unless ZKG_SEAM_GPU_WITNESS=0), and — the switch is read
+once per process — "batch_host_witness" from a child process of this tool with the switch off (--seam-child, not for direct use).  "core"
+is zkg_groth16_prove_batch on ready-made sparse witnesses of the same key and contexts: the ceiling a seam batch can reach.
 Usage: python tools/prove_batch_time.py [--ks 1 2 4] [--ps 1 2 4 8 16 32] [--reps 5] [--out profiles/prove_batch_time.json]
        python tools/prove_batch_time.py --ks 3 5 6 7 --ps 1 4 8 16        (the step-domain keys below 2^18)
        python tools/prove_batch_time.py --seam --ks 1 3 --ps 8 16
+       python tools/prove_batch_time.py --seam --ks 1 --ps 1 16 --out profiles/prove_batch_gpu_witness_time.json
+       rocprofv3 --kernel-trace --stats -d DIR -- python tools/prove_batch_time.py --trace-only seam [--trace-k K]
        rocprofv3 --kernel-trace --stats -d DIR -- python tools/prove_batch_time.py --trace-only single|batch [--trace-k K]
                                            (key setup, then 11 times one proof / one batch of the key's chunk at K payloads, default 1: the runs to
                                             trace, no counters with them)
@@ -35,9 +40,10 @@ ap.add_argument("--caller-proofs", type=int, default=40)
 ap.add_argument("--commit", default=None)
 ap.add_argument("--note", action="append", default=[], help="free text recorded in the JSON (e.g. the parent build's prove_throughput lines)")
 ap.add_argument("--out", default=None)
-ap.add_argument("--trace-only", choices=["single", "batch"], default=None)
+ap.add_argument("--trace-only", choices=["single", "batch", "seam"], default=None)
 ap.add_argument("--trace-k", type=int, default=1, help="payload count of the --trace-only runs")
 ap.add_argument("--seam", action="store_true", help="libsnark_prove loop against zkg_zklaim_prove_batch")
+ap.add_argument("--seam-child", action="store_true", help="(internal) the host-witness leg: batch figures only, as JSON")
 ap.add_argument("--merge-stats", nargs=3, metavar=("SINGLE_CSV", "BATCH_CSV", "OUT_CSV"), default=None)
 ap.add_argument("--merge-batch-size", type=int, default=16, help="proofs per traced batch, for the column names of --merge-stats")
 cli = ap.parse_args()
@@ -85,6 +91,31 @@ if cli.merge_stats:
             w.writerow([name, a[0], round(a[1] / 1e3, 1), b[0], round(b[1] / 1e3, 1), TRACE_CALLS])
     sys.exit(0)
 zkg.init(0)
+
+
+def seam_contexts(k, count, keep):
+    """a key from libsnark_trusted_setup and `count` contexts of their own on it"""
+    def payloads(v):
+        return [dict(attrs=[1990 + i, 7 * i, 42, i, 5], refs=[2100, 7 * i, 41, 0, 5], ops=["less", "eq", "greater", "noop", "greater_or_eq"], salt=0x5A4B + i + 131 * v)
+                for i in range(k)]
+    owner = zkg.make_ctx(payloads(0), keep)
+    assert zkg.libsnark_trusted_setup(owner) == 0
+    ctxs = []
+    for v in range(count):
+        c = zkg.make_ctx(payloads(v), keep)
+        c.pk, c.pk_size, c.vk, c.vk_size = owner.pk, owner.pk_size, owner.vk, owner.vk_size
+        ctxs.append(c)
+    return owner, ctxs
+
+
+if cli.trace_only == "seam":
+    keep = []
+    owner, ctxs = seam_contexts(cli.trace_k, 16, keep)
+    for _ in range(TRACE_CALLS):
+        assert zkg.zklaim_prove_batch(ctxs) == [0] * 16
+    zkg.lib().zkg_compat_reset()
+    zkg.shutdown()
+    sys.exit(0)
 if cli.trace_only:
     crs, items, keep = key_and_items(cli.trace_k, 16)
     items = items[:crs.prove_batch_chunk() or 16]
@@ -106,17 +137,8 @@ if cli.seam:
     res["leg"] = "seam"
     for k in cli.ks:
         keep = []
-
-        def payloads(v):
-            return [dict(attrs=[1990 + i, 7 * i, 42, i, 5], refs=[2100, 7 * i, 41, 0, 5], ops=["less", "eq", "greater", "noop", "greater_or_eq"], salt=0x5A4B + i + 131 * v)
-                    for i in range(k)]
-        owner = zkg.make_ctx(payloads(0), keep)
-        assert zkg.libsnark_trusted_setup(owner) == 0
-        ctxs = []
-        for v in range(max(cli.ps)):
-            c = zkg.make_ctx(payloads(v), keep)
-            c.pk, c.pk_size, c.vk, c.vk_size = owner.pk, owner.pk_size, owner.vk, owner.vk_size
-            ctxs.append(c)
+        owner, ctxs = seam_contexts(k, max(cli.ps), keep)
+        want_core = not cli.seam_child and hasattr(zkg, "zklaim_witness_stats")
 
         def drop_proofs(sub):                                   # ctx->proof is the caller's to free (zklaim_ctx_free)
             for c in sub:
@@ -138,14 +160,43 @@ if cli.seam:
 
             batch()
             stats = zkg.prove_batch_stats()
+            wstats = zkg.zklaim_witness_stats() if hasattr(zkg, "zklaim_witness_stats") else None
             assert all(zkg.libsnark_verify(c) == 0 for c in sub)
+            if cli.seam_child:
+                rk["P"][P] = {"batch": rates(batch, P, cli.reps), "batch_stats": stats, "witness_stats": wstats}
+                continue
             seq = rates(loop, P, cli.reps)
             bat = rates(batch, P, cli.reps)
-            rk["P"][P] = {"sequential": seq, "batch": bat, "batch_stats": stats, "batch_min_over_sequential_max": round(bat["min"] / seq["max"], 3)}
+            rk["P"][P] = {"sequential": seq, "batch": bat, "batch_stats": stats, "witness_stats": wstats, "batch_min_over_sequential_max": round(bat["min"] / seq["max"], 3)}
             print(f"seam k={k} P={P:3d}  libsnark_prove loop {seq}  zkg_zklaim_prove_batch {bat}  batch min / loop max = {bat['min'] / seq['max']:.2f}", flush=True)
+        # the ceiling last: its key (the same blob, resident a second time) is loaded only after the seam's legs have been measured
+        core = zkg.Crs(blob=zkg.ctx_blob(owner, "pk")) if want_core else None
+        for P in (cli.ps if core is not None else []):
+            items = []
+            for v, c in enumerate(ctxs[:P]):
+                ck = zkg.ZklaimCircuit(c, witness_only=True)
+                rs = bench.splitmix_fr(2, 9 + v)
+                items.append(ck.sparse_witness() + (rs[0], rs[1]))
+                ck.free()
+            assert all(g[0] == 0 for g in core.prove_batch(items))
+            rk["P"][P]["core"] = rates(lambda: core.prove_batch(items), P, cli.reps)
         drop_proofs(ctxs)
+        if core is not None:
+            core.free()
         res["results"][k] = rk
         zkg.lib().zkg_compat_reset()
+    if not cli.seam_child and hasattr(zkg, "zklaim_witness_stats") and os.environ.get("ZKG_SEAM_GPU_WITNESS", "1")[:1] != "0":
+        # the other witness source: the switch is read once per process, so a child of this tool measures it after this process has gone quiet
+        import subprocess
+        cmd = [sys.executable, os.path.abspath(__file__), "--seam", "--seam-child", "--reps", str(cli.reps), "--ks", *map(str, cli.ks), "--ps", *map(str, cli.ps)]
+        out = subprocess.run(cmd, env=dict(os.environ, ZKG_SEAM_GPU_WITNESS="0"), capture_output=True, text=True, check=True).stdout
+        child = json.loads(out.strip().splitlines()[-1])["results"]
+        for k in cli.ks:
+            for P in cli.ps:
+                here, there = res["results"][k]["P"][P], child[str(k)]["P"][str(P)]
+                assert there["witness_stats"][0] == 0, "the child did not keep the host witnesses"
+                here["batch_host_witness"] = there["batch"]
+                print(f"seam k={k} P={P:3d}  batch, host witnesses {there['batch']}  core {here.get('core')}", flush=True)
 for k in ([] if cli.seam else cli.ks):
     crs, items, keep = key_and_items(k, max(cli.ps))
     chunk = crs.prove_batch_chunk()

@@ -16,6 +16,7 @@ _SO = os.path.join(_HERE, "libzkg.so")
 DECLARED_SYMBOLS = [
     "zkg_init", "zkg_shutdown", "zkg_last_error", "zkg_device_info", "zkg_ntt", "zkg_ntt_dev", "zkg_evaluation_domain_size", "zkg_ntt_domain", "zkg_ntt_domain_dev", "zkg_msm_g1", "zkg_msm_g2",
     "zkg_msm_g1_dev", "zkg_msm_g2_dev", "zkg_msm_g1_windows_dev", "zkg_g1_sum", "zkg_g2_sum", "zkg_g1_fixed_base_dev", "zkg_g2_fixed_base_dev",
+    "zkg_groth16_prove_batch_zklaim", "zkg_zklaim_witness_stats", "zkg_zklaim_witness_size", "zkg_zklaim_witness_gpu", "zkg_zklaim_witness_mirror",
     "zkg_crs_upload", "zkg_crs_upload_blob", "zkg_pk_blob_inspect", "zkg_crs_free", "zkg_crs_num_variables", "zkg_groth16_prove", "zkg_groth16_prove_sparse", "zkg_circuit_sparse_witness", "zkg_qap_witness_h", "zkg_prove_stage_ms", "zkg_timing_reset",
     "zkg_timing_dominant_ms", "zkg_zklaim_circuit_new", "zkg_zklaim_witness_new", "zkg_circuit_num_variables", "zkg_circuit_free", "zkg_circuit_r1cs", "zkg_circuit_witness",
     "zkg_circuit_is_satisfied", "zkg_circuit_first_unsatisfied", "zkg_zklaim_input_map", "zkg_groth16_setup", "zkg_keypair_free",
@@ -374,6 +375,11 @@ class Crs:
         """zkg_groth16_prove_batch: items are (witness, r, s) or (tags, full_index, full_values, r, s); -> [(status, proof bytes or None)]"""
         return groth16_prove_batch(self, items, check_satisfied)
 
+    def prove_batch_zklaim(self, ctxs, rs, check_satisfied=True):
+        """zkg_groth16_prove_batch_zklaim: credentials (ZklaimCtx, None: a null entry) of this key, witnesses made on the GPU; rs: (r, s) pairs of
+        4 Montgomery limbs each -> [(status, proof bytes or None)]"""
+        return groth16_prove_batch_zklaim(self, ctxs, rs, check_satisfied)
+
     def prove_batch_chunk(self):
         """proofs per batched chunk for this key; 0: prove_batch takes the single-proof path"""
         lib().zkg_prove_batch_chunk.restype = C.c_size_t
@@ -670,6 +676,77 @@ def groth16_prove_batch(crs, items, check_satisfied=True):
     status = np.full(max(1, len(items)), -1, np.int32)
     _check(L.zkg_groth16_prove_batch(C.c_void_p(handle), C.cast(arr, C.c_void_p), len(items), int(check_satisfied), _p(proofs), _p(status)), "zkg_groth16_prove_batch")
     return [(int(status[k]), proofs[k].tobytes() if status[k] == OK else None) for k in range(len(items))]
+
+
+def _ctx_ptrs(ctxs):
+    return (C.c_void_p * max(1, len(ctxs)))(*[None if c is None else C.addressof(c) for c in ctxs])
+
+
+def groth16_prove_batch_zklaim(crs, ctxs, rs, check_satisfied=True):
+    """Crs.prove_batch_zklaim.  Status per item as Crs.prove_sparse on the host witness of that context would give."""
+    L = lib()
+    L.zkg_groth16_prove_batch_zklaim.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    n = len(ctxs)
+    rs_a = np.zeros((max(1, n), 8), np.uint64)
+    if len(rs) != n:
+        raise ZkgError("prove_batch_zklaim: one (r, s) per context")
+    for k, (r, s) in enumerate(rs):
+        r = _u64(r).reshape(-1); s = _u64(s).reshape(-1)
+        if r.size != 4 or s.size != 4:
+            raise ZkgError(f"prove_batch_zklaim: item {k}: r and s must be 4 limbs")
+        rs_a[k, :4] = r; rs_a[k, 4:] = s
+    proofs = np.zeros((max(1, n), 134), np.uint8)
+    status = np.full(max(1, n), -1, np.int32)
+    ptrs = _ctx_ptrs(ctxs)
+    handle = crs._h if crs is not None else None
+    _check(L.zkg_groth16_prove_batch_zklaim(C.c_void_p(handle), ptrs, n, _p(rs_a), int(check_satisfied), _p(proofs), _p(status)), "zkg_groth16_prove_batch_zklaim")
+    return [(int(status[k]), proofs[k].tobytes() if status[k] == OK else None) for k in range(n)]
+
+
+def zklaim_witness_stats():
+    """(items whose witness the GPU made, items whose witness the host made) of this thread's last prove_batch_zklaim / zklaim_prove_batch"""
+    out = (C.c_size_t * 2)()
+    lib().zkg_zklaim_witness_stats(out)
+    return tuple(int(v) for v in out)
+
+
+def zklaim_witness_size(payloads):
+    """(variables, most listed per witness) of the credential circuit with that many payloads, as the generator counts them"""
+    L = lib()
+    L.zkg_zklaim_witness_size.restype = C.c_size_t
+    L.zkg_zklaim_witness_size.argtypes = [C.c_size_t, C.c_void_p]
+    cap = C.c_size_t(0)
+    n = int(L.zkg_zklaim_witness_size(payloads, C.byref(cap)))
+    if not n:
+        raise ZkgError("zklaim_witness_size: payload count out of range")
+    return n, int(cap.value)
+
+
+def zklaim_witness_mirror(ctx):
+    """zkg_zklaim_witness_mirror (no GPU): -> (tags uint8[n], full_index uint32[count], full_values uint64[count, 4]) as ZklaimCircuit.sparse_witness"""
+    L = lib()
+    L.zkg_zklaim_witness_mirror.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    n, cap = zklaim_witness_size(int(ctx.num_of_payloads))
+    tags = np.zeros(n, np.uint8); idx = np.zeros(cap, np.uint32); vals = np.zeros((cap, 4), np.uint64); cnt = C.c_size_t(0)
+    _check(L.zkg_zklaim_witness_mirror(C.addressof(ctx), _p(tags), _p(idx), _p(vals), cap, C.byref(cnt)), "zkg_zklaim_witness_mirror")
+    return tags, idx[:cnt.value].copy(), vals[:cnt.value].copy()
+
+
+def zklaim_witness_gpu(ctxs):
+    """zkg_zklaim_witness_gpu: the generator alone for contexts of one payload count (None: a null entry) -> one (tags, full_index, full_values)
+    per context, or None where the context failed alone"""
+    L = lib()
+    L.zkg_zklaim_witness_gpu.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    k = next((int(c.num_of_payloads) for c in ctxs if c is not None), 0)
+    if not k:
+        raise ZkgError("zklaim_witness_gpu: no context")
+    n, cap = zklaim_witness_size(k)
+    cnt = len(ctxs)
+    tags = np.zeros((cnt, n), np.uint8); idx = np.zeros((cnt, cap), np.uint32); vals = np.zeros((cnt, cap, 4), np.uint64)
+    counts = (C.c_size_t * cnt)()
+    _check(L.zkg_zklaim_witness_gpu(_ctx_ptrs(ctxs), cnt, _p(tags), _p(idx), _p(vals), cap, counts), "zkg_zklaim_witness_gpu")
+    bad = C.c_size_t(-1).value
+    return [None if counts[i] == bad else (tags[i].copy(), idx[i, :counts[i]].copy(), vals[i, :counts[i]].copy()) for i in range(cnt)]
 
 
 def prove_batch_stats():

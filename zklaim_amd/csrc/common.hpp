@@ -10,6 +10,8 @@
 #include <mutex>
 #include "curve.hip.hpp"
 
+struct zklaim_ctx;                       // include/zklaim_abi.h
+
 namespace zk {
 
 void set_error(const std::string &msg);
@@ -208,6 +210,22 @@ VerifyWorkspace *verify_workspace_acquire();             // a free one or a new 
 void verify_workspace_release(VerifyWorkspace *w);       // back to the free list (null: nothing)
 void verify_workspace_destroy(VerifyWorkspace *w);
 void verify_release_all();                               // zkg_shutdown: the free workspaces' buffers, streams and events
+
+// ---------------- zklaim witnesses on the device (zklaim_witness.hip) ----------------
+// The generator derives the sparse witness of every context of a chunk (tags, listed indices and values) from a 128-byte record per
+// payload and writes it in the packed form the batched prover's split reads: [descriptors | values | indices | tags].
+struct ZwPlan { uint32_t k = 0, per = 0, n = 0, cap = 0; };          // payloads, variables per payload sub-circuit, variables, listed slots per item
+uint32_t zklaim_payload_vars_host();                               // zklaim_circuit.hip: what the host pass measures per payload
+// the plan for k payloads, or for the key with n variables; false (message set) when the generator's own count of a payload's variables
+// disagrees with the host pass's, or no payload count gives n: the caller then keeps the host witnesses
+bool zklaim_witness_plan(uint32_t k, ZwPlan &pl);
+bool zklaim_witness_plan_for_n(size_t n, ZwPlan &pl);
+size_t zklaim_witness_input_bytes(const ZwPlan &pl, uint32_t P);  // [error word | table of 1/1 .. 1/64 | P x k records], one upload
+// fills the input block; ok[p] = 0 for a null context, a payload count other than k or a broken payload list (nothing is written for it)
+void zklaim_witness_pack(const ZwPlan &pl, const struct ::zklaim_ctx *const *ctxs, uint32_t P, uint8_t *host_in, uint8_t *ok);
+// desc: P (offset, count) pairs; item p's listed slots are pl.cap entries from p * pl.cap.  d_in[0] is non-zero afterwards if a cursor went astray.
+extern thread_local size_t t_zklaim_witness_stats[2];          // prover.hip; the seam adds its groups up in it
+int zklaim_witness_launch(const ZwPlan &pl, uint32_t P, uint8_t *d_in, uint32_t *d_desc, Fr *d_vals, uint32_t *d_idx, uint8_t *d_tags, size_t tag_stride, hipStream_t s);
 
 // ---------------- ABI encodings (capi.cpp) ----------------
 void store_norm(uint64_t *out, const G1 &p);   // normalised jac, 12 limbs

@@ -11,6 +11,7 @@
 #include "common.hpp"
 #include <cstdio>
 #include <chrono>
+#include <sys/random.h>
 #include "../../include/zkg.h"
 #include "../../include/zklaim_abi.h"
 #include <cstdlib>
@@ -111,6 +112,31 @@ void random_fr_mont(uint64_t out[4]) {
         bool lt = false;
         for (int i = 7; i >= 0; --i) if (v[i] != FrParams::P[i]) { lt = v[i] < FrParams::P[i]; break; }
         if (lt) { memcpy(out, v, 32); return; }
+    }
+}
+// `count` scalars for a batch, from ONE read of the kernel's generator (getrandom(2)) instead of a std::random_device call per 32-bit
+// word: 16 calls per proof at ~20 us each on the measured hosts, 5 ms for a group of 16 credentials — more than the group's GPU work.
+// Same rejection sampling of 254-bit candidates (three of four are accepted: twice the words are read); whatever the read leaves
+// short is drawn by random_fr_mont.
+void random_fr_mont_many(uint64_t *out, size_t count) {
+    std::vector<uint32_t> pool(count * 16);
+    size_t got = 0; const size_t want = pool.size() * 4;
+    while (got < want) {
+        const ssize_t r = getrandom(reinterpret_cast<unsigned char *>(pool.data()) + got, want - got, 0);
+        if (r <= 0) break;
+        got += (size_t)r;
+    }
+    size_t at = 0; const size_t words = got / 4;
+    for (size_t i = 0; i < count; ++i) {
+        bool done = false;
+        while (!done && at + 8 <= words) {
+            uint32_t v[8]; memcpy(v, pool.data() + at, 32); at += 8;
+            v[7] &= 0x3fffffffu;
+            bool lt = false;
+            for (int j = 7; j >= 0; --j) if (v[j] != FrParams::P[j]) { lt = v[j] < FrParams::P[j]; break; }
+            if (lt) { memcpy(out + 4 * i, v, 32); done = true; }
+        }
+        if (!done) random_fr_mont(out + 4 * i);
     }
 }
 
@@ -296,8 +322,14 @@ struct SeamGroup {
     const Digest128 &full_of() { if (!have_full) { full = full_digest(pk, size); have_full = true; } return full; }
 };
 }  // namespace
-static void prove_group(zklaim_ctx *const *ctxs, SeamGroup &g, int *rc) {
+// ZKG_SEAM_GPU_WITNESS=0 keeps the host witness passes for every key (read once; the timing tool's second leg)
+static bool seam_gpu_witness() { static const bool on = [] { const char *e = getenv("ZKG_SEAM_GPU_WITNESS"); return !(e && e[0] == '0'); }(); return on; }
+static void prove_group(zklaim_ctx *const *ctxs, SeamGroup &g, int *rc, size_t made[2] /* out: witnesses the GPU / the host made */) {
     const size_t n = g.at.size();
+    made[0] = made[1] = 0;
+    static const bool dbg = getenv("ZKG_DEBUG_TIMING") != nullptr;
+    const auto t_begin = std::chrono::steady_clock::now();
+    auto lap = [&](const char *what) { if (dbg) fprintf(stderr, "[zkg seam batch] %-28s %8.3f ms\n", what, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count()); };
     const zklaim_ctx *first = ctxs[g.at[0]];
     bool speculative = false;                                    // as libsnark_prove_impl: a hit by the sampled digest is confirmed by the full one
     Digest128 recorded_full;
@@ -307,18 +339,41 @@ static void prove_group(zklaim_ctx *const *ctxs, SeamGroup &g, int *rc) {
     if (speculative && !g.have_full) confirm = std::async(std::launch::async, [&] { return full_digest(g.pk, g.size); });      // under the witness passes and the GPU's work
     std::vector<SeamItem> items(n);
     struct FreeAll { std::vector<SeamItem> &v; ~FreeAll() { for (SeamItem &it : v) if (it.ck) zkg_circuit_free(it.ck); } } free_all{items};
-    host_parallel_for((int)n, [&](int i) {
-        SeamItem &it = items[i];
-        try {
-            it.ck = zkg_zklaim_witness_new(ctxs[g.at[i]]);
-            it.ok = it.ck && zkg_circuit_sparse_witness(it.ck, &it.tags, &it.fidx, &it.fval, &it.nfull) == ZKG_OK;
-        } catch (...) { it.ok = false; }
-    });
-    for (SeamItem &it : items) { random_fr_mont(it.r); random_fr_mont(it.s); }
+    bool host_witnesses = false;
+    auto make_host_witnesses = [&] {                             // (once per group, and only for a key whose witnesses the GPU does not make)
+        if (host_witnesses) return;
+        host_witnesses = true;
+        host_parallel_for((int)n, [&](int i) {
+            SeamItem &it = items[i];
+            try {
+                it.ck = zkg_zklaim_witness_new(ctxs[g.at[i]]);
+                it.ok = it.ck && zkg_circuit_sparse_witness(it.ck, &it.tags, &it.fidx, &it.fval, &it.nfull) == ZKG_OK;
+            } catch (...) { it.ok = false; }
+        });
+    };
+    {
+        std::vector<uint64_t> rs(8 * n);
+        random_fr_mont_many(rs.data(), 2 * n);
+        for (size_t i = 0; i < n; ++i) { memcpy(items[i].r, &rs[8 * i], 32); memcpy(items[i].s, &rs[8 * i + 4], 32); }
+    }
     std::vector<uint8_t> proofs(n * ZKG_PROOF_BYTES);
     std::vector<int> status(n, ZKG_ERROR);
     // the items whose variable count is the key's (a key made for another payload count: that item fails alone), as one batch
     auto prove = [&](zkg_crs *c) {
+        if (seam_gpu_witness() && zkg_prove_batch_chunk(c)) {
+            // a key that batches: the contexts go to the device as they are (a payload count other than the key's fails alone there)
+            std::vector<const zklaim_ctx *> cs(n); std::vector<uint64_t> rs(8 * n);
+            for (size_t i = 0; i < n; ++i) { cs[i] = ctxs[g.at[i]]; memcpy(&rs[8 * i], items[i].r, 32); memcpy(&rs[8 * i + 4], items[i].s, 32); status[i] = ZKG_ERROR; }
+            std::vector<int> st(n, ZKG_ERROR);
+            if (zkg_groth16_prove_batch_zklaim(c, cs.data(), n, rs.data(), 1, proofs.data(), st.data()) != ZKG_OK) return;
+            size_t ws[2]; zkg_zklaim_witness_stats(ws);
+            made[0] = ws[0]; made[1] = ws[1];
+            for (size_t i = 0; i < n; ++i) status[i] = st[i];
+            return;
+        }
+        make_host_witnesses();
+        made[0] = 0; made[1] = 0;
+        for (size_t i = 0; i < n; ++i) made[1] += items[i].ok;
         std::vector<zkg_prove_item> batch; std::vector<size_t> which;
         for (size_t i = 0; i < n; ++i) {
             status[i] = ZKG_ERROR;
@@ -333,9 +388,12 @@ static void prove_group(zklaim_ctx *const *ctxs, SeamGroup &g, int *rc) {
         if (zkg_groth16_prove_batch(c, batch.data(), batch.size(), 1, out.data(), st.data()) != ZKG_OK) return;
         for (size_t j = 0; j < which.size(); ++j) { status[which[j]] = st[j]; if (st[j] == ZKG_OK) memcpy(proofs.data() + which[j] * ZKG_PROOF_BYTES, out.data() + j * ZKG_PROOF_BYTES, ZKG_PROOF_BYTES); }
     };
+    lap("key resolved, (r, s) drawn");
     prove(crs.get());
+    lap("group proved");
     if (speculative) {
         const Digest128 full = g.have_full ? g.full : confirm.get();
+        lap("full digest confirmed");
         if (!(full == recorded_full)) {                          // same size and samples, different bytes: not the resident key after all
             std::fill(status.begin(), status.end(), ZKG_ERROR);
             crs = replace_key(first, g.key, full);
@@ -368,8 +426,12 @@ static int zklaim_prove_batch_impl(zklaim_ctx *const *ctxs, size_t count, int *r
         }
         g->at.push_back(i);
     }
+    size_t made_all[2] = {0, 0};
+    struct Report { size_t *m; ~Report() { zk::t_zklaim_witness_stats[0] = m[0]; zk::t_zklaim_witness_stats[1] = m[1]; } } report{made_all};
     for (SeamGroup &g : groups) {
-        try { prove_group(ctxs, g, rc); }                        // a group that fails leaves its items at 1 and the other groups alone
+        size_t made[2] = {0, 0};
+        struct Add { size_t *all, *one; ~Add() { all[0] += one[0]; all[1] += one[1]; } } add{made_all, made};
+        try { prove_group(ctxs, g, rc, made); }                        // a group that fails leaves its items at 1 and the other groups alone
         catch (const std::exception &e) { zk::set_error(std::string("zkg_zklaim_prove_batch: ") + e.what()); }
         catch (...) { zk::set_error("zkg_zklaim_prove_batch: unexpected exception"); }
     }

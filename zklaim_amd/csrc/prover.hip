@@ -14,6 +14,7 @@
 // sharing one digit sort); the prover randomness (r, s) is an explicit input.
 #include "common.hpp"
 #include "../../include/zkg.h"
+#include "../../include/zklaim_abi.h"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -29,6 +30,7 @@
 namespace zk {
 
 struct DevCsr { DevBuf rowptr, col, val; size_t nnz = 0; };
+thread_local size_t t_zklaim_witness_stats[2] = {0, 0};      // zkg_zklaim_witness_stats: items whose witness the GPU made, the host made
 
 }  // namespace zk
 
@@ -97,7 +99,7 @@ struct BatchWs {
     uint32_t P = 0; bool ready = false;
     zk::DevBuf z, aABC, scratch, wtags, wlisted, words, stage, wscal;
     uint8_t *host_stage = nullptr; size_t host_cap = 0;      // pinned: the chunk's witnesses, packed (one upload)
-    uint32_t *host_words = nullptr;                          // pinned: P x BATCH_WORDS after the split, then P x BATCH_WORDS after the mat-vec
+    uint32_t *host_words = nullptr;                          // pinned: P x BATCH_WORDS after the split, then P x BATCH_WORDS after the mat-vec, then the witness generator's error word
     hipStream_t stream = nullptr, wst[4] = {nullptr, nullptr, nullptr, nullptr};
     zk::MsmJob *job_h = nullptr, *job_w1 = nullptr, *job_w2 = nullptr; zk::OnesSum ones_g1, ones_g2;
     hipEvent_t ev_split = nullptr, ev_flags = nullptr, ev_gathered = nullptr;      // the split's words landed; the mat-vec's flags landed; the witness jobs' scalars gathered
@@ -1232,7 +1234,7 @@ static int batch_create(zkg_crs *crs, BatchWs &B, uint32_t P) {
     const size_t n1 = (size_t)crs->n + 1, m = crs->m;
     bool ok = B.z.reserve(P * n1 * 32) == 0 && B.aABC.reserve((size_t)P * 3 * m * 32) == 0 && B.scratch.reserve((size_t)P * 3 * m * NTT_SCRATCH_BYTES) == 0 &&
               B.wtags.reserve(P * round_up(n1, 16)) == 0 && B.wlisted.reserve(P * n1 * 4) == 0 && B.words.reserve((size_t)P * BATCH_WORDS * 4) == 0 &&
-              hip_ok(hipHostMalloc((void **)&B.host_words, (size_t)2 * P * BATCH_WORDS * 4, hipHostMallocDefault), "hipHostMalloc", __FILE__, __LINE__);
+              hip_ok(hipHostMalloc((void **)&B.host_words, ((size_t)2 * P * BATCH_WORDS + 16) * 4, hipHostMallocDefault), "hipHostMalloc", __FILE__, __LINE__);
     if (ok) {
         int prio_lo = 0, prio_hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
@@ -1284,44 +1286,69 @@ static void assemble_proof(const zkg_crs *crs, const Fr &r, const Fr &s, const G
 }
 static thread_local size_t t_batch_stats[3] = {0, 0, 0};
 
+// where a chunk's witnesses come from when they are not items: zklaim contexts of the key's payload count, generated on the device
+struct ZklaimChunk { const zklaim_ctx *const *ctxs; const uint64_t *rs; /* 8 limbs per item: r | s */ const ZwPlan *plan; bool cursor_error; };
+
 // one chunk: P <= B.P items, under the batch mutex and a slot lease (the lease is the chunk's place in the key's extension protocol; its
-// slot lends the streams of a table extension)
-static int prove_chunk(zkg_crs *crs, BatchWs &B, ProverSlot &S, const zkg_prove_item *items, uint32_t P, bool check, uint8_t *proofs_out, int *status) {
+// slot lends the streams of a table extension).  Two ways in: `items` (the witnesses are packed on the host and uploaded), or `zc` (a
+// few bytes per credential go up and k_zklaim_witness writes the same packed form into the device stage); from the split on they are one.
+static int prove_chunk(zkg_crs *crs, BatchWs &B, ProverSlot &S, const zkg_prove_item *items, ZklaimChunk *zc, uint32_t P, bool check, uint8_t *proofs_out, int *status) {
     const size_t n = crs->n, n1 = n + 1, m = crs->m, l = crs->l, tag_stride = round_up(n, 16), wtag_stride = round_up(n1, 16);
     hipStream_t s = B.stream;
     const auto t0 = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) { if (g_dbg_timing) fprintf(stderr, "[zkg batch] %-28s %8.3f ms\n", what, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count()); };
-    // ---- 1. pack the witnesses: [desc | values | indices | tags], one upload
-    std::vector<uint32_t> cnt(P, 0); std::vector<uint8_t> skip(P, 0);
-    host_parallel_for((int)P, [&](int p) {
-        const zkg_prove_item &it = items[p];
-        if (!it.r || !it.s) skip[p] = 1;
-        else if (it.witness) cnt[p] = (uint32_t)dense_to_sparse(it.witness, n, nullptr, nullptr, nullptr);
-        else if (!it.tags || (it.count && (!it.full_index || !it.full_values)) || it.count > n) skip[p] = 1;
-        else cnt[p] = (uint32_t)it.count;
-    });
-    std::vector<uint32_t> off(P + 1, 0);
-    for (uint32_t p = 0; p < P; ++p) off[p + 1] = off[p] + cnt[p];
-    const size_t total = off[P], o_vals = round_up((size_t)P * sizeof(BatchDesc), 64), o_idx = o_vals + total * 32, o_tags = round_up(o_idx + total * 4, 64),
-                 bytes = o_tags + P * tag_stride;
-    if (bytes > B.host_cap) {
+    auto host_stage_for = [&](size_t bytes) {
+        if (bytes <= B.host_cap) return ZKG_OK;
         if (B.host_stage) (void)hipHostFree(B.host_stage);
         B.host_stage = nullptr; B.host_cap = 0;
         ZK_HIP(hipHostMalloc((void **)&B.host_stage, bytes + bytes / 2, hipHostMallocDefault));
         B.host_cap = bytes + bytes / 2;
+        return ZKG_OK;
+    };
+    // ---- 1. the chunk's witnesses in the device stage: [desc | values | indices | tags]
+    std::vector<uint32_t> cnt(P, 0); std::vector<uint8_t> skip(P, 0);
+    std::vector<uint32_t> off(P + 1, 0);
+    size_t o_vals = round_up((size_t)P * sizeof(BatchDesc), 64), o_idx = 0, o_tags = 0, o_gen = 0;
+    uint32_t max_cnt = 0;
+    if (!zc) {                                                                   // packed on the host, one upload
+        host_parallel_for((int)P, [&](int p) {
+            const zkg_prove_item &it = items[p];
+            if (!it.r || !it.s) skip[p] = 1;
+            else if (it.witness) cnt[p] = (uint32_t)dense_to_sparse(it.witness, n, nullptr, nullptr, nullptr);
+            else if (!it.tags || (it.count && (!it.full_index || !it.full_values)) || it.count > n) skip[p] = 1;
+            else cnt[p] = (uint32_t)it.count;
+        });
+        for (uint32_t p = 0; p < P; ++p) off[p + 1] = off[p] + cnt[p];
+        const size_t total = off[P];
+        o_idx = o_vals + total * 32; o_tags = round_up(o_idx + total * 4, 64);
+        const size_t bytes = o_tags + P * tag_stride;
+        if (host_stage_for(bytes) || B.stage.reserve(bytes)) return ZKG_ERROR;
+        uint8_t *hs = B.host_stage;
+        host_parallel_for((int)P, [&](int p) {
+            const zkg_prove_item &it = items[p];
+            BatchDesc *d = reinterpret_cast<BatchDesc *>(hs) + p; d->off = off[p]; d->cnt = cnt[p];
+            uint8_t *tags = hs + o_tags + (size_t)p * tag_stride; uint32_t *idx = reinterpret_cast<uint32_t *>(hs + o_idx) + off[p]; uint64_t *vals = reinterpret_cast<uint64_t *>(hs + o_vals) + 4 * (size_t)off[p];
+            if (skip[p]) memset(tags, 0, n);
+            else if (it.witness) (void)dense_to_sparse(it.witness, n, tags, idx, vals);
+            else { memcpy(tags, it.tags, n); if (cnt[p]) { memcpy(idx, it.full_index, (size_t)cnt[p] * 4); memcpy(vals, it.full_values, (size_t)cnt[p] * 32); } }
+        });
+        lap("witnesses packed");
+        ZK_HIP(hipMemcpyAsync(B.stage.p, hs, bytes, hipMemcpyHostToDevice, s));
+        max_cnt = *std::max_element(cnt.begin(), cnt.end());
+    } else {                                                                     // generated in place: fixed-capacity listed slots per item, counts made on the device
+        const ZwPlan &pl = *zc->plan;
+        if (pl.n != n) { set_error("zkg_groth16_prove_batch_zklaim: plan does not fit the key"); return ZKG_ERROR; }
+        const size_t total = (size_t)P * pl.cap, in_bytes = zklaim_witness_input_bytes(pl, P);
+        o_idx = o_vals + total * 32; o_tags = round_up(o_idx + total * 4, 64); o_gen = round_up(o_tags + P * tag_stride, 64);
+        if (host_stage_for(in_bytes) || B.stage.reserve(o_gen + in_bytes)) return ZKG_ERROR;
+        zklaim_witness_pack(pl, zc->ctxs, P, B.host_stage, skip.data());
+        for (uint32_t p = 0; p < P; ++p) skip[p] = !skip[p];                      // (pack reports the good ones)
+        lap("credentials packed");
+        uint8_t *st = B.stage.as<uint8_t>();
+        ZK_HIP(hipMemcpyAsync(st + o_gen, B.host_stage, in_bytes, hipMemcpyHostToDevice, s));
+        if (zklaim_witness_launch(pl, P, st + o_gen, reinterpret_cast<uint32_t *>(st), reinterpret_cast<Fr *>(st + o_vals), reinterpret_cast<uint32_t *>(st + o_idx), st + o_tags, tag_stride, s)) return ZKG_ERROR;
+        max_cnt = pl.cap;
     }
-    if (B.stage.reserve(bytes)) return ZKG_ERROR;
-    uint8_t *hs = B.host_stage;
-    host_parallel_for((int)P, [&](int p) {
-        const zkg_prove_item &it = items[p];
-        BatchDesc *d = reinterpret_cast<BatchDesc *>(hs) + p; d->off = off[p]; d->cnt = cnt[p];
-        uint8_t *tags = hs + o_tags + (size_t)p * tag_stride; uint32_t *idx = reinterpret_cast<uint32_t *>(hs + o_idx) + off[p]; uint64_t *vals = reinterpret_cast<uint64_t *>(hs + o_vals) + 4 * (size_t)off[p];
-        if (skip[p]) memset(tags, 0, n);
-        else if (it.witness) (void)dense_to_sparse(it.witness, n, tags, idx, vals);
-        else { memcpy(tags, it.tags, n); if (cnt[p]) { memcpy(idx, it.full_index, (size_t)cnt[p] * 4); memcpy(vals, it.full_values, (size_t)cnt[p] * 32); } }
-    });
-    lap("witnesses packed");
-    ZK_HIP(hipMemcpyAsync(B.stage.p, hs, bytes, hipMemcpyHostToDevice, s));
     const uint8_t *st = B.stage.as<uint8_t>();
     const BatchDesc *d_desc = reinterpret_cast<const BatchDesc *>(st); const Fr *d_vals = reinterpret_cast<const Fr *>(st + o_vals);
     const uint32_t *d_idx = reinterpret_cast<const uint32_t *>(st + o_idx); const uint8_t *d_tags = st + o_tags;
@@ -1329,11 +1356,12 @@ static int prove_chunk(zkg_crs *crs, BatchWs &B, ProverSlot &S, const zkg_prove_
     uint8_t *wtags = B.wtags.as<uint8_t>(); uint32_t *wlisted = B.wlisted.as<uint32_t>(), *words = B.words.as<uint32_t>();
     uint32_t *hw_split = B.host_words, *hw_flags = B.host_words + (size_t)B.P * BATCH_WORDS;
     const uint32_t *subset_pos = crs->sub.count ? crs->sub.pos.as<uint32_t>() : nullptr;
+    uint32_t *hw_gen = B.host_words + (size_t)2 * B.P * BATCH_WORDS;
     // ---- 2. split, mat-vec, transforms, H: one launch sequence for the chunk
-    const uint32_t max_cnt = *std::max_element(cnt.begin(), cnt.end());
     hipLaunchKernelGGL(k_expand_tags_batch, dim3((unsigned)((n + 255) / 256), P), dim3(256), 0, s, d_tags, tag_stride, n, z, wtags, wtag_stride, words);
     if (max_cnt) hipLaunchKernelGGL(k_scatter_full_batch, dim3((max_cnt + 255) / 256, P), dim3(256), 0, s, d_desc, d_idx, d_vals, d_tags, tag_stride, n, z, wtags, wtag_stride, wlisted, words, subset_pos);
     ZK_HIP(hipMemcpyAsync(hw_split, words, (size_t)P * BATCH_WORDS * 4, hipMemcpyDeviceToHost, s));
+    if (zc) ZK_HIP(hipMemcpyAsync(hw_gen, st + o_gen, 4, hipMemcpyDeviceToHost, s));
     ZK_HIP(hipEventRecord(B.ev_split, s));
     const unsigned grid_m = (unsigned)((m + 255) / 256);
     hipLaunchKernelGGL(k_r1cs_eval_batch, dim3(grid_m, P), dim3(256), 0, s, crs->A.rowptr.as<uint32_t>(), crs->A.col.as<uint32_t>(), crs->A.val.as<Fr>(),
@@ -1370,6 +1398,7 @@ static int prove_chunk(zkg_crs *crs, BatchWs &B, ProverSlot &S, const zkg_prove_
     // ---- 3. the split has landed: per-item verdicts, the witness tables, the witness jobs
     ZK_HIP(hipEventSynchronize(B.ev_split));
     lap("split landed");
+    if (zc && *hw_gen) { zc->cursor_error = true; set_error("zklaim witness generator: a cursor left its range (host witnesses are used)"); return ZKG_ERROR; }
     std::vector<uint8_t> good(P, 0);
     bool extend = false;
     for (uint32_t p = 0; p < P; ++p) {
@@ -1433,7 +1462,7 @@ static int prove_chunk(zkg_crs *crs, BatchWs &B, ProverSlot &S, const zkg_prove_
         G1 W1[3] = {Wg1[3 * (size_t)p], Wg1[3 * (size_t)p + 1], Wg1[3 * (size_t)p + 2]}; G2 Wb2 = Wg2[p];
         for (int i = 0; i < 3; ++i) W1[i].add(B.ones_g1.g1(3 * p + i));
         Wb2.add(B.ones_g2.g2pt(p));
-        Fr r, sv; memcpy(r.v, items[p].r, 32); memcpy(sv.v, items[p].s, 32);
+        Fr r, sv; memcpy(r.v, zc ? zc->rs + 8 * (size_t)p : items[p].r, 32); memcpy(sv.v, zc ? zc->rs + 8 * (size_t)p + 4 : items[p].s, 32);
         assemble_proof(crs, r, sv, W1, Wb2, Ht[p], proofs_out + (size_t)p * ZKG_PROOF_BYTES);
         status[p] = ZKG_OK;
     });
@@ -1465,7 +1494,7 @@ static int groth16_prove_batch_impl(const zkg_crs *crs_, const zkg_prove_item *i
         SlotLease lease(crs);                                                // per chunk: between chunks other callers may extend the witness tables
         if (!lease.ok()) return ZKG_ERROR;
         int rc = ZKG_ERROR;
-        try { rc = prove_chunk(crs, crs->batch, lease.S(), items + first, P, check_satisfied != 0, proofs_out + first * ZKG_PROOF_BYTES, status + first); }
+        try { rc = prove_chunk(crs, crs->batch, lease.S(), items + first, nullptr, P, check_satisfied != 0, proofs_out + first * ZKG_PROOF_BYTES, status + first); }
         catch (const std::exception &e) { set_error(std::string("zkg_groth16_prove_batch: ") + e.what()); }
         catch (...) { set_error("zkg_groth16_prove_batch: unexpected exception"); }
         if (rc) { batch_drain(crs->batch); return ZKG_ERROR; }                  // nothing of the chunk may still be running when the workspace changes hands
@@ -1494,6 +1523,78 @@ int zkg_groth16_prove_batch(const zkg_crs *crs, const zkg_prove_item *items, siz
     catch (...) { set_error("zkg_groth16_prove_batch: unexpected exception"); }
     return ZKG_ERROR;
 }
+// ---- zkg_groth16_prove_batch_zklaim: the same chunks, their witnesses generated on the device from the contexts
+// host witnesses for ctxs[0 .. count) through zkg_groth16_prove_batch (which takes the single-proof path for keys that do not batch)
+static int prove_zklaim_host_witnesses(const zkg_crs *crs, const zklaim_ctx *const *ctxs, size_t count, const uint64_t *rs, int check_satisfied, uint8_t *proofs_out, int *status) {
+    std::vector<zkg_circuit *> cks(count, nullptr);
+    struct FreeAll { std::vector<zkg_circuit *> &v; ~FreeAll() { for (zkg_circuit *c : v) if (c) zkg_circuit_free(c); } } free_all{cks};
+    std::vector<zkg_prove_item> items(count); std::vector<uint8_t> ok(count, 0);
+    host_parallel_for((int)count, [&](int i) {
+        try {
+            zkg_prove_item &it = items[i]; it = zkg_prove_item{};
+            if (!ctxs[i]) return;
+            cks[i] = zkg_zklaim_witness_new(ctxs[i]);
+            ok[i] = cks[i] && zkg_circuit_num_variables(cks[i]) == crs->n && zkg_circuit_sparse_witness(cks[i], &it.tags, &it.full_index, &it.full_values, &it.count) == ZKG_OK;
+            it.r = rs + 8 * (size_t)i; it.s = it.r + 4;
+        } catch (...) { ok[i] = 0; }
+    });
+    std::vector<zkg_prove_item> batch; std::vector<size_t> which;
+    for (size_t i = 0; i < count; ++i) {
+        status[i] = ZKG_ERROR;
+        if (ok[i]) { batch.push_back(items[i]); which.push_back(i); }
+        else set_error("zkg_groth16_prove_batch_zklaim: null context, broken payload list or a payload count other than the key's");
+    }
+    zk::t_zklaim_witness_stats[1] += which.size();
+    const size_t before[3] = {t_batch_stats[0], t_batch_stats[1], t_batch_stats[2]};
+    std::vector<uint8_t> out(batch.size() * ZKG_PROOF_BYTES); std::vector<int> st(batch.size(), ZKG_ERROR);
+    const int rc = groth16_prove_batch_impl(crs, batch.data(), batch.size(), check_satisfied, out.data(), st.data());
+    for (int j = 0; j < 3; ++j) t_batch_stats[j] += before[j];
+    if (rc != ZKG_OK) return rc;
+    for (size_t j = 0; j < which.size(); ++j) { status[which[j]] = st[j]; if (st[j] == ZKG_OK) memcpy(proofs_out + which[j] * ZKG_PROOF_BYTES, out.data() + j * ZKG_PROOF_BYTES, ZKG_PROOF_BYTES); }
+    return ZKG_OK;
+}
+static int groth16_prove_batch_zklaim_impl(const zkg_crs *crs_, const zklaim_ctx *const *ctxs, size_t count, const uint64_t *rs, int check_satisfied, uint8_t *proofs_out, int *status) {
+    t_batch_stats[0] = t_batch_stats[1] = t_batch_stats[2] = 0; zk::t_zklaim_witness_stats[0] = zk::t_zklaim_witness_stats[1] = 0;
+    if (!count) return ZKG_OK;
+    zkg_crs *crs = const_cast<zkg_crs *>(crs_);
+    if (!crs || !ctxs || !rs || !proofs_out || !status) { set_error("zkg_groth16_prove_batch_zklaim: bad argument"); return ZKG_ERROR; }
+    const uint32_t chunk = batch_chunk_for(crs);
+    ZwPlan pl;
+    // a key that does not batch, or a generator that disagrees with the host pass about the circuit: host witnesses, the existing paths
+    if (!chunk || !zklaim_witness_plan_for_n(crs->n, pl)) return prove_zklaim_host_witnesses(crs, ctxs, count, rs, check_satisfied, proofs_out, status);
+    std::vector<std::pair<size_t, uint32_t>> redo;                            // chunks whose generator reported a stray cursor
+    {
+        std::lock_guard<std::mutex> batch_lock(crs->batch_mu);
+        if (batch_create(crs, crs->batch, chunk)) return ZKG_ERROR;
+        for (size_t first = 0; first < count; first += chunk) {
+            const uint32_t P = (uint32_t)std::min<size_t>(chunk, count - first);
+            SlotLease lease(crs);
+            if (!lease.ok()) return ZKG_ERROR;
+            ZklaimChunk zc{ctxs + first, rs + 8 * first, &pl, false};
+            int rc = ZKG_ERROR;
+            try { rc = prove_chunk(crs, crs->batch, lease.S(), nullptr, &zc, P, check_satisfied != 0, proofs_out + first * ZKG_PROOF_BYTES, status + first); }
+            catch (const std::exception &e) { set_error(std::string("zkg_groth16_prove_batch_zklaim: ") + e.what()); }
+            catch (...) { set_error("zkg_groth16_prove_batch_zklaim: unexpected exception"); }
+            if (rc) {
+                batch_drain(crs->batch);
+                if (!zc.cursor_error) return ZKG_ERROR;
+                redo.push_back({first, P});
+                continue;
+            }
+            t_batch_stats[0] += P; ++t_batch_stats[2]; zk::t_zklaim_witness_stats[0] += P;
+        }
+    }
+    for (auto &c : redo)
+        if (prove_zklaim_host_witnesses(crs, ctxs + c.first, c.second, rs + 8 * c.first, check_satisfied, proofs_out + c.first * ZKG_PROOF_BYTES, status + c.first)) return ZKG_ERROR;
+    return ZKG_OK;
+}
+int zkg_groth16_prove_batch_zklaim(const zkg_crs *crs, const struct zklaim_ctx *const *ctxs, size_t count, const uint64_t *rs, int check_satisfied, uint8_t *proofs_out, int *status) {
+    try { return groth16_prove_batch_zklaim_impl(crs, ctxs, count, rs, check_satisfied, proofs_out, status); }
+    catch (const std::exception &e) { set_error(std::string("zkg_groth16_prove_batch_zklaim: ") + e.what()); }
+    catch (...) { set_error("zkg_groth16_prove_batch_zklaim: unexpected exception"); }
+    return ZKG_ERROR;
+}
+void zkg_zklaim_witness_stats(size_t out[2]) { if (out) { out[0] = zk::t_zklaim_witness_stats[0]; out[1] = zk::t_zklaim_witness_stats[1]; } }
 void zkg_prove_batch_stats(size_t out[3]) { if (out) for (int i = 0; i < 3; ++i) out[i] = t_batch_stats[i]; }
 size_t zkg_prove_batch_chunk(const zkg_crs *crs) { return crs ? batch_chunk_for(crs) : 0; }
 

@@ -79,6 +79,9 @@ void give_storage(Builder &pb) {
 }
 }  // namespace
 
+// variables of one payload's sub-circuit, as a pass over the gadgets measured it (0: no pass has run yet)
+static std::atomic<uint32_t> g_known_vars{0};
+
 static zkg_circuit *build_zklaim(const zklaim_ctx *ctx, bool with_witness, bool witness_only = false, bool reference_quirk = false) {
     zkg_circuit *ck = new zkg_circuit();
     Builder &pb = ck->pb;
@@ -191,7 +194,8 @@ static zkg_circuit *build_zklaim(const zklaim_ctx *ctx, bool with_witness, bool 
         // through views of the pre-sized storage; constraints recorded by the views are appended in payload order, which makes the
         // system identical to the one a serial pass records.  The per-payload sizes are a property of the circuit, measured once per
         // process (payload 0 on this thread, the rest in parallel) and remembered, so that later passes start all k at once.
-        static std::atomic<uint32_t> known_vars{0}, known_cons{0}, known_terms{0};
+        static std::atomic<uint32_t> known_cons{0}, known_terms{0};
+        std::atomic<uint32_t> &known_vars = g_known_vars;
         uint32_t per = known_vars.load();
         size_t cons_per = known_cons.load(), terms_per = known_terms.load();
         size_t first_parallel = 0;
@@ -221,7 +225,9 @@ static zkg_circuit *build_zklaim(const zklaim_ctx *ctx, bool with_witness, bool 
         known_vars = per;
         if (pb.recording && cons_per) { known_cons = (uint32_t)cons_per; known_terms = (uint32_t)terms_per; }
     } else {
+        const uint32_t before = pb.num_variables();
         for (size_t i = 0; i < k; ++i) payload_gadgets(pb, i);
+        if (k == 1) g_known_vars = pb.num_variables() - before;
     }
     lap("payload sub-circuits");
     if (pb.recording) {
@@ -310,6 +316,19 @@ size_t zkg_zklaim_input_map(const zklaim_ctx *ctx, uint64_t *out, size_t cap_ele
 }
 
 }  // extern "C"
+
+// The per-payload variable count the host pass measures (what the device generator's own cursor must agree with): a witness-only pass
+// over one all-zero payload the first time nobody has measured it yet.
+uint32_t zk::zklaim_payload_vars_host() {
+    if (!g_known_vars.load()) {
+        zklaim_wrap_payload_ctx pl; memset(&pl, 0, sizeof(pl));
+        zklaim_ctx ctx; memset(&ctx, 0, sizeof(ctx));
+        ctx.num_of_payloads = 1; ctx.pl_ctx_head = &pl;
+        zkg_circuit *ck = build_zklaim(&ctx, true, true);
+        if (ck) zkg_circuit_free(ck);
+    }
+    return g_known_vars.load();
+}
 
 // the circuit gives up its CSR matrices (the seam's key generation: no copy of 100 MB); zkg_circuit_r1cs is empty afterwards
 void circuit_release_csr(zkg_circuit *c, zk::OwnedCsr &out) {
