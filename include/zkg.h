@@ -280,6 +280,24 @@ int zkg_zklaim_witness_gpu(const struct zklaim_ctx *const *ctxs, size_t count, u
 /* the same outputs for one context from the generator's code compiled for the host.  No GPU, no zkg_init (as zkg_pk_blob_inspect). */
 int zkg_zklaim_witness_mirror(const struct zklaim_ctx *ctx, uint8_t *tags_out /* n */, uint32_t *index_out, uint64_t *values_out, size_t cap_listed,
                               size_t *listed_count);
+/* ---- ONE zklaim credential of a resident key, its witness generated on the GPU: status and proof bytes are exactly those of
+ *      zkg_groth16_prove_sparse on the host witness of ctx (zkg_zklaim_witness_new + zkg_circuit_sparse_witness) with the same (r, s).
+ *      Every key the single-proof path serves: radix-2 and step domains, m >= 2^18, H shards.  128 bytes per payload go up in one copy and
+ *      k_zklaim_witness_par — a plain SHA-256 per payload, then one thread per slice of the circuit's trace — writes tags and listed values in
+ *      front of the split, on the proof's own stream; nothing waits on the host for it.  A null context, a broken payload list or a payload
+ *      count other than the key's: ZKG_ERROR; an unsatisfied credential: ZKG_UNSATISFIED; nothing is written in either case.  If the
+ *      generator's plan does not fit the key, disagrees with the host pass about a payload's variables, or the kernel raises its error word,
+ *      the witness is made on the host and zkg_groth16_prove_sparse's path is taken: same bytes, zkg_last_error says why. */
+int zkg_groth16_prove_zklaim(const zkg_crs *crs, const struct zklaim_ctx *ctx, const uint64_t r[4], const uint64_t s[4],
+                             int check_satisfied, uint8_t *proof_out, size_t *proof_len);
+/* the calling thread's last zkg_groth16_prove_zklaim / libsnark_prove: out[0] = 1 if the GPU made the witness, out[1] = 1 if the host did */
+void zkg_prove_zklaim_stats(size_t out[2]);
+/* test hooks: zkg_zklaim_witness_gpu's contract on k_zklaim_witness_par; and zkg_zklaim_witness_mirror's on that kernel's device code
+ * compiled for the host — the value pass, then every slice on its own, last one first (no GPU, no zkg_init) */
+int zkg_zklaim_witness_gpu_parallel(const struct zklaim_ctx *const *ctxs, size_t count, uint8_t *tags_out /* count x n */, uint32_t *index_out,
+                                    uint64_t *values_out, size_t cap_listed /* per item */, size_t *listed_counts);
+int zkg_zklaim_witness_mirror_parallel(const struct zklaim_ctx *ctx, uint8_t *tags_out /* n */, uint32_t *index_out, uint64_t *values_out,
+                                       size_t cap_listed, size_t *listed_count);
 /* coefficients_for_H (m+1 Fr, Montgomery) of r1cs_to_qap_witness_map, for parity tests */
 int zkg_qap_witness_h(const zkg_crs *crs, const uint64_t *witness, uint64_t *h_out);
 /* per-stage device milliseconds of the last zkg_groth16_prove on this crs (the stages run on their own streams, so the entries

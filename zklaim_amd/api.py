@@ -26,6 +26,7 @@ DECLARED_SYMBOLS = [
     "zkg_prover_peak_in_flight", "zkg_msm_g1_host_scalars", "zkg_multi_rccl_calls", "zkg_g1_add_pair29",
     "zkg_groth16_verify_batch", "zkg_pairing_product", "zkg_verify_batch_stats",
     "zkg_groth16_prove_batch", "zkg_prove_batch_stats", "zkg_prove_batch_chunk", "zkg_zklaim_prove_batch",
+    "zkg_groth16_prove_zklaim", "zkg_prove_zklaim_stats", "zkg_zklaim_witness_gpu_parallel", "zkg_zklaim_witness_mirror_parallel",
 ]
 # the reference's own seam, exported with its original names (zklaim.h:257-259)
 COMPAT_SYMBOLS = ["libsnark_trusted_setup", "libsnark_prove", "libsnark_verify"]
@@ -380,6 +381,15 @@ class Crs:
         4 Montgomery limbs each -> [(status, proof bytes or None)]"""
         return groth16_prove_batch_zklaim(self, ctxs, rs, check_satisfied)
 
+    def prove_zklaim(self, ctx, r, s, check_satisfied=True):
+        """zkg_groth16_prove_zklaim: one credential (ZklaimCtx, None: a null context) of this key, its witness made on the GPU -> (rc, proof
+        bytes or None): what prove_sparse gives on the host witness of ctx, ERROR included (no exception: the failures are the contract)"""
+        L = lib()
+        L.zkg_groth16_prove_zklaim.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        out = np.zeros(256, np.uint8); ln = C.c_size_t(0)
+        rc = L.zkg_groth16_prove_zklaim(C.c_void_p(self._h), None if ctx is None else C.addressof(ctx), _p(_u64(r)), _p(_u64(s)), int(check_satisfied), _p(out), C.byref(ln))
+        return rc, (bytes(out[:ln.value]) if rc == OK else None)
+
     def prove_batch_chunk(self):
         """proofs per batched chunk for this key; 0: prove_batch takes the single-proof path"""
         lib().zkg_prove_batch_chunk.restype = C.c_size_t
@@ -722,21 +732,43 @@ def zklaim_witness_size(payloads):
     return n, int(cap.value)
 
 
-def zklaim_witness_mirror(ctx):
-    """zkg_zklaim_witness_mirror (no GPU): -> (tags uint8[n], full_index uint32[count], full_values uint64[count, 4]) as ZklaimCircuit.sparse_witness"""
-    L = lib()
-    L.zkg_zklaim_witness_mirror.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+def _witness_mirror(ctx, name):
+    fn = getattr(lib(), name)
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     n, cap = zklaim_witness_size(int(ctx.num_of_payloads))
     tags = np.zeros(n, np.uint8); idx = np.zeros(cap, np.uint32); vals = np.zeros((cap, 4), np.uint64); cnt = C.c_size_t(0)
-    _check(L.zkg_zklaim_witness_mirror(C.addressof(ctx), _p(tags), _p(idx), _p(vals), cap, C.byref(cnt)), "zkg_zklaim_witness_mirror")
+    _check(fn(C.addressof(ctx), _p(tags), _p(idx), _p(vals), cap, C.byref(cnt)), name)
     return tags, idx[:cnt.value].copy(), vals[:cnt.value].copy()
 
 
-def zklaim_witness_gpu(ctxs):
+def zklaim_witness_mirror(ctx):
+    """zkg_zklaim_witness_mirror (no GPU): -> (tags uint8[n], full_index uint32[count], full_values uint64[count, 4]) as ZklaimCircuit.sparse_witness"""
+    return _witness_mirror(ctx, "zkg_zklaim_witness_mirror")
+
+
+def zklaim_witness_mirror_parallel(ctx):
+    """zkg_zklaim_witness_mirror_parallel (no GPU): the same from k_zklaim_witness_par's code on the host, its slices run last one first"""
+    return _witness_mirror(ctx, "zkg_zklaim_witness_mirror_parallel")
+
+
+def prove_zklaim_stats():
+    """(1 if the GPU made the witness, 1 if the host did) of this thread's last Crs.prove_zklaim / libsnark_prove"""
+    out = (C.c_size_t * 2)()
+    lib().zkg_prove_zklaim_stats(out)
+    return tuple(int(v) for v in out)
+
+
+def zklaim_witness_gpu_parallel(ctxs):
+    """zkg_zklaim_witness_gpu_parallel: zklaim_witness_gpu on k_zklaim_witness_par"""
+    return zklaim_witness_gpu(ctxs, "zkg_zklaim_witness_gpu_parallel")
+
+
+def zklaim_witness_gpu(ctxs, name="zkg_zklaim_witness_gpu"):
     """zkg_zklaim_witness_gpu: the generator alone for contexts of one payload count (None: a null entry) -> one (tags, full_index, full_values)
     per context, or None where the context failed alone"""
     L = lib()
-    L.zkg_zklaim_witness_gpu.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    fn = getattr(L, name)
+    fn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     k = next((int(c.num_of_payloads) for c in ctxs if c is not None), 0)
     if not k:
         raise ZkgError("zklaim_witness_gpu: no context")
@@ -744,8 +776,10 @@ def zklaim_witness_gpu(ctxs):
     cnt = len(ctxs)
     tags = np.zeros((cnt, n), np.uint8); idx = np.zeros((cnt, cap), np.uint32); vals = np.zeros((cnt, cap, 4), np.uint64)
     counts = (C.c_size_t * cnt)()
-    _check(L.zkg_zklaim_witness_gpu(_ctx_ptrs(ctxs), cnt, _p(tags), _p(idx), _p(vals), cap, counts), "zkg_zklaim_witness_gpu")
+    _check(fn(_ctx_ptrs(ctxs), cnt, _p(tags), _p(idx), _p(vals), cap, counts), name)
     bad = C.c_size_t(-1).value
+    if any(counts[i] == bad and tags[i].any() for i in range(cnt)):
+        raise ZkgError(name + ": tags written for a context that failed")
     return [None if counts[i] == bad else (tags[i].copy(), idx[i, :counts[i]].copy(), vals[i, :counts[i]].copy()) for i in range(cnt)]
 
 

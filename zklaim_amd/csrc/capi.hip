@@ -310,6 +310,7 @@ void zkg_shutdown(void) {
     ntt_release_all();
     msm_release_all();
     verify_release_all();
+    zklaim_witness_release_all();
     g_device = -1;
 }
 const char *zkg_last_error(void) { std::lock_guard<std::mutex> lk(g_err_mu); static std::string copy; copy = g_error; return copy.c_str(); }

@@ -225,7 +225,16 @@ size_t zklaim_witness_input_bytes(const ZwPlan &pl, uint32_t P);  // [error word
 void zklaim_witness_pack(const ZwPlan &pl, const struct ::zklaim_ctx *const *ctxs, uint32_t P, uint8_t *host_in, uint8_t *ok);
 // desc: P (offset, count) pairs; item p's listed slots are pl.cap entries from p * pl.cap.  d_in[0] is non-zero afterwards if a cursor went astray.
 extern thread_local size_t t_zklaim_witness_stats[2];          // prover.hip; the seam adds its groups up in it
+extern thread_local size_t t_prove_zklaim_stats[2];            // prover.hip: zkg_prove_zklaim_stats; libsnark_prove's host pass reports itself here
 int zklaim_witness_launch(const ZwPlan &pl, uint32_t P, uint8_t *d_in, uint32_t *d_desc, Fr *d_vals, uint32_t *d_idx, uint8_t *d_tags, size_t tag_stride, hipStream_t s);
+// The same contract on k_zklaim_witness_par, the generator shaped for one proof's latency: its input block is [error word | P x k records]
+// only — the 1 / c table and the slices' plan are resident on the device, uploaded by the first launch there.  _ready: the slices' plan
+// (derived from the mirror's trace) ends where the payload's does; false (message set): the caller keeps the host witness.
+bool zklaim_witness_par_ready(const ZwPlan &pl);
+size_t zklaim_witness_par_input_bytes(const ZwPlan &pl, uint32_t P);
+void zklaim_witness_par_pack(const ZwPlan &pl, const struct ::zklaim_ctx *const *ctxs, uint32_t P, uint8_t *host_in, uint8_t *ok);
+int zklaim_witness_par_launch(const ZwPlan &pl, uint32_t P, uint8_t *d_in, uint32_t *d_desc, Fr *d_vals, uint32_t *d_idx, uint8_t *d_tags, size_t tag_stride, hipStream_t s);
+void zklaim_witness_release_all();                              // zkg_shutdown: the resident tables
 
 // ---------------- ABI encodings (capi.cpp) ----------------
 void store_norm(uint64_t *out, const G1 &p);   // normalised jac, 12 limbs

@@ -266,6 +266,8 @@ static std::shared_ptr<zkg_crs> replace_key(const zklaim_ctx *ctx, uint64_t key,
     return crs;
 }
 
+// ZKG_SEAM_GPU_WITNESS=0 keeps the host witness passes for every key (read once; the timing tool's second leg)
+static bool seam_gpu_witness() { static const bool on = [] { const char *e = getenv("ZKG_SEAM_GPU_WITNESS"); return !(e && e[0] == '0'); }(); return on; }
 static int libsnark_prove_impl(zklaim_ctx *ctx) {
     if (!ctx || !ctx->pk || !ctx->pk_size) return ZKLAIM_ERROR;
     const uint64_t key = sampled_digest(ctx->pk, ctx->pk_size);
@@ -274,34 +276,46 @@ static int libsnark_prove_impl(zklaim_ctx *ctx) {
     std::shared_ptr<zkg_crs> crs = resident_key(ctx, key, speculative, recorded_full);
     if (!crs) return ZKLAIM_ERROR;
     // the witness only: the constraint system already sits on the GPU inside the resident key, and pb.is_satisfied()
-    // (snark.cpp:121-124) is evaluated there, fused with the R1CS mat-vec of the prover (check_satisfied = 1)
-    zkg_circuit *ck = zkg_zklaim_witness_new(ctx);
-    if (!ck) return ZKLAIM_ERROR;
+    // (snark.cpp:121-124) is evaluated there, fused with the R1CS mat-vec of the prover (check_satisfied = 1).  By default the witness is
+    // made there too (zkg_groth16_prove_zklaim: 128 bytes per payload go up); ZKG_SEAM_GPU_WITNESS=0, or a generator that disagrees with
+    // the host pass about the circuit, keeps the host pass and the sparse upload (tags + the few non-bit values).
+    t_prove_zklaim_stats[0] = t_prove_zklaim_stats[1] = 0;
+    ZwPlan pl;
+    const bool gpu = seam_gpu_witness() && ctx->num_of_payloads >= 1 && ctx->num_of_payloads <= 64 && zklaim_witness_plan((uint32_t)ctx->num_of_payloads, pl);
+    zkg_circuit *ck = gpu ? nullptr : zkg_zklaim_witness_new(ctx);
+    if (!gpu && !ck) return ZKLAIM_ERROR;
     int rc = ZKLAIM_ERROR;
-    uint64_t r[4], s[4];
-    random_fr_mont(r); random_fr_mont(s);
+    uint64_t rs[8];
+    random_fr_mont_many(rs, 2);                                  // (r, s) from one read of the kernel's generator
+    const uint64_t *r = rs, *s = rs + 4;
     unsigned char *proof = (unsigned char *)malloc(ZKG_PROOF_BYTES);
     size_t len = 0;
     const uint8_t *tags = nullptr; const uint32_t *fidx = nullptr; const uint64_t *fval = nullptr; size_t nfull = 0;
-    int prc = ZKG_ERROR;                                         // the witness goes up as tags + the few non-bit values (30x less PCIe traffic)
-    if (proof && zkg_circuit_sparse_witness(ck, &tags, &fidx, &fval, &nfull) == ZKG_OK) {
+    int prc = ZKG_ERROR;
+    if (proof && (gpu || zkg_circuit_sparse_witness(ck, &tags, &fidx, &fval, &nfull) == ZKG_OK)) {
+        const size_t n_ctx = gpu ? pl.n : zkg_circuit_num_variables(ck);
+        auto prove_on = [&](zkg_crs *key) -> int {
+            // a key made for another payload count has another variable count: refuse instead of reading past the witness
+            if (n_ctx != zkg_crs_num_variables(key)) { set_error("libsnark_prove: ctx->pk was generated for a different circuit (variable count differs)"); return ZKG_ERROR; }
+            if (gpu) return zkg_groth16_prove_zklaim(key, ctx, r, s, 1, proof, &len);
+            t_prove_zklaim_stats[0] = 0; t_prove_zklaim_stats[1] = 1;
+            return zkg_groth16_prove_sparse(key, tags, fidx, fval, nfull, r, s, 1, proof, &len);
+        };
         std::future<Digest128> confirm;
         if (speculative) confirm = std::async(std::launch::async, [&] { return full_digest(ctx->pk, ctx->pk_size); });     // under the GPU's work
-        // a key made for another payload count has another variable count: refuse instead of reading past the witness
-        if (zkg_circuit_num_variables(ck) != zkg_crs_num_variables(crs.get())) set_error("libsnark_prove: ctx->pk was generated for a different circuit (variable count differs)");
-        else prc = zkg_groth16_prove_sparse(crs.get(), tags, fidx, fval, nfull, r, s, 1, proof, &len);
+        prc = prove_on(crs.get());
         if (speculative) {
             const Digest128 full = confirm.get();
             if (!(full == recorded_full)) {                      // same size and samples, different bytes: not the resident key after all
                 prc = ZKG_ERROR;
                 crs = replace_key(ctx, key, full);
-                if (crs && zkg_circuit_num_variables(ck) == zkg_crs_num_variables(crs.get())) prc = zkg_groth16_prove_sparse(crs.get(), tags, fidx, fval, nfull, r, s, 1, proof, &len);
+                if (crs) prc = prove_on(crs.get());
             }
         }
     }
     if (prc == ZKG_OK) { ctx->proof = proof; ctx->proof_size = len; rc = ZKLAIM_OK; }          // libsnark_wrapper.cpp:242
     else { free(proof); if (prc == ZKG_UNSATISFIED) rc = 1; }                                  // "system not satisfied!! not creating proof." -> 1
-    zkg_circuit_free(ck);
+    if (ck) zkg_circuit_free(ck);
     return rc;
 }
 int libsnark_prove(zklaim_ctx *ctx) {
@@ -322,8 +336,6 @@ struct SeamGroup {
     const Digest128 &full_of() { if (!have_full) { full = full_digest(pk, size); have_full = true; } return full; }
 };
 }  // namespace
-// ZKG_SEAM_GPU_WITNESS=0 keeps the host witness passes for every key (read once; the timing tool's second leg)
-static bool seam_gpu_witness() { static const bool on = [] { const char *e = getenv("ZKG_SEAM_GPU_WITNESS"); return !(e && e[0] == '0'); }(); return on; }
 static void prove_group(zklaim_ctx *const *ctxs, SeamGroup &g, int *rc, size_t made[2] /* out: witnesses the GPU / the host made */) {
     const size_t n = g.at.size();
     made[0] = made[1] = 0;

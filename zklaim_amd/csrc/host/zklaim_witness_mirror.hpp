@@ -6,7 +6,8 @@
 // (base cursor, up to two value words with their allocation masks, emitted most significant bit first, word 0's bit before word 1's).
 // Nothing here knows an offset: the layout is the allocation order of build_zklaim restated as arithmetic on the payload count, and the
 // size of a payload's sub-circuit is whatever cursor the trace ends at (the callers compare it with what the host pass measures).
-// The same code runs on the host (zkg_zklaim_witness_mirror, the tests' reference point without a GPU) and inside k_zklaim_witness.
+// The same code runs on the host (zkg_zklaim_witness_mirror, the tests' reference point without a GPU) and inside k_zklaim_witness; the
+// trace is cut into slices that k_zklaim_witness_par (and zkg_zklaim_witness_mirror_parallel on the host) run independently of each other.
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
@@ -165,41 +166,116 @@ ZW_HD Alpha alpha_of(uint64_t attr, uint64_t ref) {
 }
 
 // ---- the sub-circuit of one payload (payload_gadgets of build_zklaim): five comparisons, then sha256_compress_from_iv of the padded
-// block with the digest written into h_bits (which carry the context's hash already: only the carries are new).  W: storage for the 64
-// message words (the schedule is allocated in full before the rounds, so all of them live at once).  Returns the cursor behind the last
-// variable; base: tag index of the sub-circuit's first variable.
-template <class Sink> ZW_HD uint32_t payload_trace(const Rec &r, uint32_t base, Wd *W, Sink &s) {
+// block with the digest written into h_bits (which carry the context's hash already: only the carries are new) — as ZW_SLICES slices that
+// each take their operands as words and advance the cursor: comparison j, schedule step t = 16 .. 63, round t = 0 .. 63, final addition j.
+// What a slice allocates depends on its operands' masks only; its values on the plain SHA-256 words of the step it stands for.
+static constexpr uint32_t ZW_SL_SCHED = 5, ZW_SL_ROUND = ZW_SL_SCHED + 48, ZW_SL_FINAL = ZW_SL_ROUND + 64, ZW_SLICES = ZW_SL_FINAL + 8;
+static constexpr int ZW_SLICE_OPERANDS = 9;                                     // a round's: the eight state words and W[t]
+
+// 64 alpha bits (least significant first), alpha_packed, not_all_zeros, inv
+template <class Sink> ZW_HD void slice_compare(const Rec &r, int j, uint32_t &cur, Sink &s) {
+    const Alpha a = alpha_of(le64(r.pre + 8 * j), r.ref[j]);
+    s.put(cur, __builtin_bitreverse32((uint32_t)a.lo), 0xffffffffu, 0, 0);
+    s.put(cur + 32, __builtin_bitreverse32((uint32_t)(a.lo >> 32)), 0xffffffffu, 0, 0);
+    s.put(cur + 65, a.cnt ? 0x80000000u : 0u, 0x80000000u, 0, 0);
+    cur += 67;
+}
+// in: W[t - 16], W[t - 15], W[t - 7], W[t - 2] -> W[t]
+template <class Sink> ZW_HD Wd slice_schedule(const Wd *in, uint32_t &cur, Sink &s) {
+    const Wd s0 = xor3(s, cur, rotr(in[1], 7), rotr(in[1], 18), shr(in[1], 3));
+    const Wd s1 = xor3(s, cur, rotr(in[3], 17), rotr(in[3], 19), shr(in[3], 10));
+    const Wd terms[4] = {in[0], s0, in[2], s1};
+    return add(s, cur, terms, 4, 0, false);
+}
+// st: a .. h at the round's entry, replaced by the state at its exit
+template <class Sink> ZW_HD void slice_round(Wd *st, Wd w, int t, uint32_t &cur, Sink &s) {
+    const Wd a = st[0], b = st[1], c = st[2], d = st[3], e = st[4], f = st[5], g = st[6], h = st[7];
+    const Wd S1 = xor3(s, cur, rotr(e, 6), rotr(e, 11), rotr(e, 25));
+    const Wd ch = choice(s, cur, e, f, g);
+    const Wd S0 = xor3(s, cur, rotr(a, 2), rotr(a, 13), rotr(a, 22));
+    const Wd mj = majority(s, cur, a, b, c);
+    const Wd te[5] = {d, h, S1, ch, w};
+    const Wd new_e = add(s, cur, te, 5, sha_k(t), false);
+    const Wd ta[6] = {h, S1, ch, w, S0, mj};
+    const Wd new_a = add(s, cur, ta, 6, sha_k(t), false);
+    st[7] = g; st[6] = f; st[5] = e; st[4] = new_e; st[3] = c; st[2] = b; st[1] = a; st[0] = new_a;
+}
+// word j of the state after the last round + IV[j] = the digest word that h_bits hold already: the carries only
+template <class Sink> ZW_HD void slice_final(Wd x, int j, uint32_t &cur, Sink &s) { (void)add(s, cur, &x, 1, sha_iv(j), true); }
+
+// The serial composition.  W: storage for the 64 message words (the schedule is allocated in full before the rounds, so all of them live
+// at once).  Returns the cursor behind the last variable; base: tag index of the sub-circuit's first variable.  The observer is shown
+// every slice as it is entered: its cursor relative to base and its operands (slice_plan_derive keeps them; payload_trace looks away).
+struct NoObserver { ZW_HD void slice(uint32_t, uint32_t, const Wd *, int) {} };
+template <class Sink, class Obs> ZW_HD uint32_t payload_trace_observed(const Rec &r, uint32_t base, Wd *W, Sink &s, Obs &o) {
     uint32_t cur = base;
-    for (int j = 0; j < 5; ++j) {                                               // 64 alpha bits (least significant first), alpha_packed, not_all_zeros, inv
-        const Alpha a = alpha_of(le64(r.pre + 8 * j), r.ref[j]);
-        s.put(cur, __builtin_bitreverse32((uint32_t)a.lo), 0xffffffffu, 0, 0);
-        s.put(cur + 32, __builtin_bitreverse32((uint32_t)(a.lo >> 32)), 0xffffffffu, 0, 0);
-        s.put(cur + 65, a.cnt ? 0x80000000u : 0u, 0x80000000u, 0, 0);
-        cur += 67;
-    }
+    for (int j = 0; j < 5; ++j) { o.slice((uint32_t)j, cur - base, nullptr, 0); slice_compare(r, j, cur, s); }
     for (int t = 0; t < 12; ++t) { W[t].v = be32(r.pre + 4 * t); W[t].m = 0xffffffffu; }
     W[12] = konst(0x80000000u); W[13] = konst(0); W[14] = konst(0); W[15] = konst(0x180u);     // the padding of a 48-byte message
     for (int t = 16; t < 64; ++t) {
-        const Wd s0 = xor3(s, cur, rotr(W[t - 15], 7), rotr(W[t - 15], 18), shr(W[t - 15], 3));
-        const Wd s1 = xor3(s, cur, rotr(W[t - 2], 17), rotr(W[t - 2], 19), shr(W[t - 2], 10));
-        const Wd terms[4] = {W[t - 16], s0, W[t - 7], s1};
-        W[t] = add(s, cur, terms, 4, 0, false);
+        const Wd in[4] = {W[t - 16], W[t - 15], W[t - 7], W[t - 2]};
+        o.slice(ZW_SL_SCHED + (uint32_t)(t - 16), cur - base, in, 4);
+        W[t] = slice_schedule(in, cur, s);
     }
-    Wd a = konst(sha_iv(0)), b = konst(sha_iv(1)), c = konst(sha_iv(2)), d = konst(sha_iv(3)), e = konst(sha_iv(4)), f = konst(sha_iv(5)), g = konst(sha_iv(6)), h = konst(sha_iv(7));
+    Wd st[ZW_SLICE_OPERANDS];
+    for (int j = 0; j < 8; ++j) st[j] = konst(sha_iv(j));
     for (int t = 0; t < 64; ++t) {
-        const Wd S1 = xor3(s, cur, rotr(e, 6), rotr(e, 11), rotr(e, 25));
-        const Wd ch = choice(s, cur, e, f, g);
-        const Wd S0 = xor3(s, cur, rotr(a, 2), rotr(a, 13), rotr(a, 22));
-        const Wd mj = majority(s, cur, a, b, c);
-        const Wd te[5] = {d, h, S1, ch, W[t]};
-        const Wd new_e = add(s, cur, te, 5, sha_k(t), false);
-        const Wd ta[6] = {h, S1, ch, W[t], S0, mj};
-        const Wd new_a = add(s, cur, ta, 6, sha_k(t), false);
-        h = g; g = f; f = e; e = new_e; d = c; c = b; b = a; a = new_a;
+        st[8] = W[t];
+        o.slice(ZW_SL_ROUND + (uint32_t)t, cur - base, st, 9);
+        slice_round(st, W[t], t, cur, s);
     }
-    const Wd out[8] = {a, b, c, d, e, f, g, h};
-    for (int j = 0; j < 8; ++j) (void)add(s, cur, &out[j], 1, sha_iv(j), true);
+    for (int j = 0; j < 8; ++j) { o.slice(ZW_SL_FINAL + (uint32_t)j, cur - base, &st[j], 1); slice_final(st[j], j, cur, s); }
     return cur;
+}
+template <class Sink> ZW_HD uint32_t payload_trace(const Rec &r, uint32_t base, Wd *W, Sink &s) { NoObserver o; return payload_trace_observed(r, base, W, s, o); }
+
+// ---- the slices on their own (k_zklaim_witness_par, zkg_zklaim_witness_mirror_parallel).  The plan: for every slice the cursor it is
+// entered at (relative to the payload's segment), the index of its first record and its operands' masks; entry ZW_SLICES closes the
+// list with the segment's size and the record count.  Derived by running the serial trace on a zero record, never written down.
+struct SliceEntry { uint32_t cur, rec, m[ZW_SLICE_OPERANDS]; };
+struct SlicePlan { SliceEntry e[ZW_SLICES + 1]; };
+// the plain SHA-256 compression of the padded 48-byte pre-image: W[0 .. 63] and the state at the entry of round t in st[8 t .. 8 t + 7]
+// (t = 64: after the last round, before the IV is added) — the values of every slice's operands
+static constexpr uint32_t ZW_SHA_STATE_WORDS = 65 * 8;
+ZW_HD void sha_values(const Rec &r, uint32_t *W, uint32_t *st) {
+    for (int t = 0; t < 12; ++t) W[t] = be32(r.pre + 4 * t);
+    W[12] = 0x80000000u; W[13] = 0; W[14] = 0; W[15] = 0x180u;
+    for (int t = 16; t < 64; ++t) {
+        const uint32_t x = W[t - 15], y = W[t - 2];
+        W[t] = W[t - 16] + (rr(x, 7) ^ rr(x, 18) ^ (x >> 3)) + W[t - 7] + (rr(y, 17) ^ rr(y, 19) ^ (y >> 10));
+    }
+    uint32_t a = sha_iv(0), b = sha_iv(1), c = sha_iv(2), d = sha_iv(3), e = sha_iv(4), f = sha_iv(5), g = sha_iv(6), h = sha_iv(7);
+    for (int t = 0; t <= 64; ++t) {
+        uint32_t *o = st + 8 * t;
+        o[0] = a; o[1] = b; o[2] = c; o[3] = d; o[4] = e; o[5] = f; o[6] = g; o[7] = h;
+        if (t == 64) break;
+        const uint32_t t1 = h + (rr(e, 6) ^ rr(e, 11) ^ rr(e, 25)) + ((e & f) | (~e & g)) + sha_k(t) + W[t];
+        const uint32_t t2 = (rr(a, 2) ^ rr(a, 13) ^ rr(a, 22)) + ((a & b) | (c & (a ^ b)));
+        h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
+    }
+}
+// slice q of a payload whose plain SHA-256 words are (W, st): its records go to the sink, the cursor it ends at (relative to base) comes back
+template <class Sink> ZW_HD uint32_t slice_run(const Rec &r, const SliceEntry &e, uint32_t q, const uint32_t *W, const uint32_t *st, uint32_t base, Sink &s) {
+    uint32_t cur = base + e.cur;
+    if (q < ZW_SL_SCHED) slice_compare(r, (int)q, cur, s);
+    else if (q < ZW_SL_ROUND) {
+        const int t = 16 + (int)(q - ZW_SL_SCHED);
+        Wd in[4];
+        in[0].v = W[t - 16]; in[1].v = W[t - 15]; in[2].v = W[t - 7]; in[3].v = W[t - 2];
+        for (int j = 0; j < 4; ++j) in[j].m = e.m[j];
+        (void)slice_schedule(in, cur, s);
+    } else if (q < ZW_SL_FINAL) {
+        const int t = (int)(q - ZW_SL_ROUND);
+        Wd x[8], w;
+        for (int j = 0; j < 8; ++j) { x[j].v = st[8 * t + j]; x[j].m = e.m[j]; }
+        w.v = W[t]; w.m = e.m[8];
+        slice_round(x, w, t, cur, s);
+    } else if (q < ZW_SLICES) {
+        const int j = (int)(q - ZW_SL_FINAL);
+        Wd x; x.v = st[8 * 64 + j]; x.m = e.m[0];
+        slice_final(x, j, cur, s);
+    }
+    return cur - base;
 }
 
 // ---- the payload's bits outside its sub-circuit, as records at their places: record q of ZW_PUBLIC_RECORDS
@@ -275,5 +351,32 @@ ZW_HD uint8_t candidate_value(const uint32_t raw[8], bool is_inv, const Fr *inv_
 // sinks: count only (the cursor is the result), and straight into a tag array
 struct CountSink { uint32_t records = 0; ZW_HD void put(uint32_t, uint32_t, uint32_t, uint32_t, uint32_t) { ++records; } };
 struct TagSink { uint8_t *tags; uint32_t limit; ZW_HD void put(uint32_t base, uint32_t v0, uint32_t m0, uint32_t v1, uint32_t m1) { expand(tags, limit, base, v0, m0, v1, m1); } };
+// one record per put, as the expansion reads them; a slice's records lie at [at, end) of the payload's list, `at` counts on past `end`
+struct SliceRec { uint32_t base, v0, m0, v1, m1; };
+struct SliceSink {
+    SliceRec *r; uint32_t at, end;
+    ZW_HD void put(uint32_t base, uint32_t v0, uint32_t m0, uint32_t v1, uint32_t m1) {
+        if (at < end) { SliceRec x; x.base = base; x.v0 = v0; x.m0 = m0; x.v1 = v1; x.m1 = m1; r[at] = x; }
+        ++at;
+    }
+};
+
+// the plan: the serial trace of a zero record, watched (host, once per process)
+struct PlanObserver {
+    SlicePlan *p; const CountSink *s;
+    ZW_HD void slice(uint32_t q, uint32_t cur, const Wd *ops, int n) {
+        SliceEntry &e = p->e[q];
+        e.cur = cur; e.rec = s->records;
+        for (int j = 0; j < ZW_SLICE_OPERANDS; ++j) e.m[j] = j < n ? ops[j].m : 0;
+    }
+};
+inline void slice_plan_derive(SlicePlan &p) {
+    Rec r;
+    for (size_t i = 0; i < sizeof(Rec); ++i) reinterpret_cast<uint8_t *>(&r)[i] = 0;
+    Wd W[64]; CountSink s; PlanObserver o; o.p = &p; o.s = &s;
+    SliceEntry &last = p.e[ZW_SLICES];
+    last.cur = payload_trace_observed(r, 0, W, s, o); last.rec = s.records;
+    for (int j = 0; j < ZW_SLICE_OPERANDS; ++j) last.m[j] = 0;
+}
 
 }}  // namespace zk::zwm

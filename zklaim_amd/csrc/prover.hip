@@ -31,6 +31,7 @@ namespace zk {
 
 struct DevCsr { DevBuf rowptr, col, val; size_t nnz = 0; };
 thread_local size_t t_zklaim_witness_stats[2] = {0, 0};      // zkg_zklaim_witness_stats: items whose witness the GPU made, the host made
+thread_local size_t t_prove_zklaim_stats[2] = {0, 0};        // zkg_prove_zklaim_stats: the last single credential's witness came from the GPU, from the host
 
 }  // namespace zk
 
@@ -70,6 +71,9 @@ struct ProverSlot {
     zk::DevBuf z, aABC, flag, up_tags, up_idx, up_vals;    // up_*: staging of a sparse witness                   // [1 | w] and aA | aB | aC back to back (batched NTTs)
     zk::DevBuf ntt_scratch;                     // inter-pass scratch, 3 m elements
     zk::DevBuf wtags, wlisted, wcount;          // the witness split: tag per element of z, indices of the non-bit elements, their count
+    // a zklaim credential whose witness the device generates (zkg_groth16_prove_zklaim): its records packed in pinned memory, their place on
+    // the device ([error word | records | descriptor]), and what became of it (ZW_*: prove_enqueue's error is the context's, or the generator's)
+    uint8_t *zw_stage = nullptr; size_t zw_stage_cap = 0; zk::DevBuf zw_in; int zw_state = 0;
     hipStream_t stream = nullptr;               // upload + split + mat-vec + NTT stream
     // witness multi-exponentiations: one job for the three G1 queries (A, B_g1, L share the digit sort), one for B_g2; H on its own
     zk::MsmJob *job_w1 = nullptr, *job_w2 = nullptr, *job_h = nullptr;
@@ -83,7 +87,7 @@ struct ProverSlot {
     hipEvent_t ev[20]; bool ev_ok = false, ready = false;
     float stage_ms[8] = {0};
     // the proof in flight between prove_enqueue and prove_finish
-    uint32_t *flag_host = nullptr;              // pinned: [0] lands the satisfiability flag, [1] the count of non-bit witness elements
+    uint32_t *flag_host = nullptr;              // pinned: [0] lands the satisfiability flag, [1] the count of non-bit witness elements, [4] the witness generator's error word
     bool check = false; zk::Fr r, s;
     std::chrono::steady_clock::time_point t0;
 };
@@ -357,6 +361,18 @@ __global__ __launch_bounds__(256) void k_scatter_full(const uint32_t *idx, const
     }
 }
 
+// the same for a listing made on the device (k_zklaim_witness_par): its length is desc[1], known there only, so the launch covers the
+// listing's capacity; the last workgroup also hands the generator's error word to the host
+__global__ __launch_bounds__(256) void k_scatter_full_counted(const uint32_t *desc, const uint32_t *idx, const Fr *vals, size_t cap, size_t n, Fr *z, const uint8_t *tags, uint8_t *wtags,
+                                                              uint32_t *listed, uint32_t *count, uint32_t *words, const uint32_t *subset_pos, uint32_t *host_words, const uint32_t *gen_err) {
+    const size_t cnt = desc[1] < cap ? desc[1] : cap;
+    scatter_full_entry((size_t)blockIdx.x * blockDim.x + threadIdx.x, idx + desc[0], vals + desc[0], cnt, n, z, tags, wtags, listed, count, words + 3, subset_pos);
+    __syncthreads();
+    if (threadIdx.x == 0 && atomicAdd(words + 2, 1u) == gridDim.x - 1) {
+        host_words[1] = atomicOr(count, 0u); host_words[2] = atomicOr(count + 1, 0u); host_words[3] = atomicOr(words + 3, 0u); host_words[4] = *gen_err;
+    }
+}
+
 // H_tmp = (aA . aB - aC) * Zinv  (divide_by_Z_on_coset fused with the pointwise product)
 __global__ __launch_bounds__(256) void k_pointwise_h(Fr *aA, const Fr *aB, const Fr *aC, size_t m, Fr zinv, int critical) {
     crit_wave_priority(critical);
@@ -475,10 +491,12 @@ static size_t ser_g2(uint8_t *out, const G2 &p) {
     return 66;
 }
 
-struct WitnessSrc {                           // dense: n x 4 limbs; or sparse: tags[n] + (idx[count], vals[count x 4 limbs])
+struct WitnessSrc {                           // dense: n x 4 limbs; or sparse: tags[n] + (idx[count], vals[count x 4 limbs]); or a zklaim context and its plan
     const uint64_t *dense = nullptr;
     const uint8_t *tags = nullptr; const uint32_t *idx = nullptr; const uint64_t *vals = nullptr; size_t count = 0;
+    const zklaim_ctx *ctx = nullptr; const ZwPlan *plan = nullptr;
 };
+enum { ZW_NONE = 0, ZW_BAD_CONTEXT = 1, ZW_GENERATOR_ERROR = 2 };
 // phase 1 of r1cs_to_qap_witness_map: z = [1 | w] resident and split, the three mat-vecs, the satisfiability flag
 static unsigned floor_log2(size_t x) { unsigned r = 0; while (x >>= 1) ++r; return r; }
 static int compute_h_matvec(zkg_crs *crs, ProverSlot &S, const WitnessSrc &W, bool want_flag) {
@@ -489,7 +507,28 @@ static int compute_h_matvec(zkg_crs *crs, ProverSlot &S, const WitnessSrc &W, bo
     Fr *z = S.z.as<Fr>(), *aA = S.aABC.as<Fr>(), *aB = aA + m, *aC = aA + 2 * m;
     uint32_t *words = S.flag.as<uint32_t>(), *count = S.wcount.as<uint32_t>();
     const uint32_t *subset_pos = crs->sub.count ? crs->sub.pos.as<uint32_t>() : nullptr;
-    if (W.dense || !crs->n) {
+    if (W.plan) {
+        // the credential goes up as 128 bytes per payload in ONE copy; k_zklaim_witness_par writes the sparse form into the slot's staging, the split follows
+        // in stream order.  The listing's length stays on the device (the descriptor), nothing here waits for anything.
+        const ZwPlan &pl = *W.plan; const size_t n = crs->n, in_bytes = zklaim_witness_par_input_bytes(pl, 1), o_desc = (in_bytes + 63) / 64 * 64;
+        if (pl.n != n) { set_error("zkg_groth16_prove_zklaim: plan does not fit the key"); return ZKG_ERROR; }
+        if (S.zw_stage_cap < in_bytes) {
+            if (S.zw_stage) (void)hipHostFree(S.zw_stage);
+            S.zw_stage = nullptr; S.zw_stage_cap = 0;
+            ZK_HIP(hipHostMalloc((void **)&S.zw_stage, in_bytes, hipHostMallocDefault));
+            S.zw_stage_cap = in_bytes;
+        }
+        if (S.zw_in.reserve(o_desc + 64) || S.up_tags.reserve(n) || S.up_idx.reserve((size_t)pl.cap * 4 + 16) || S.up_vals.reserve((size_t)pl.cap * 32 + 16)) return ZKG_ERROR;
+        uint8_t ok = 0;
+        zklaim_witness_par_pack(pl, &W.ctx, 1, S.zw_stage, &ok);
+        if (!ok) { S.zw_state = ZW_BAD_CONTEXT; set_error("zkg_groth16_prove_zklaim: broken payload list or a payload count other than the key's"); return ZKG_ERROR; }
+        uint8_t *d_in = S.zw_in.as<uint8_t>(); uint32_t *desc = reinterpret_cast<uint32_t *>(d_in + o_desc);
+        ZK_HIP(hipMemcpyAsync(d_in, S.zw_stage, in_bytes, hipMemcpyHostToDevice, s));
+        if (zklaim_witness_par_launch(pl, 1, d_in, desc, S.up_vals.as<Fr>(), S.up_idx.as<uint32_t>(), S.up_tags.as<uint8_t>(), n, s)) return ZKG_ERROR;
+        hipLaunchKernelGGL(k_expand_tags, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, S.up_tags.as<uint8_t>(), n, z, S.wtags.as<uint8_t>(), words, count);
+        hipLaunchKernelGGL(k_scatter_full_counted, dim3((unsigned)((pl.cap + 255) / 256)), dim3(256), 0, s, desc, S.up_idx.as<uint32_t>(), S.up_vals.as<Fr>(), (size_t)pl.cap, n, z,
+                           S.up_tags.as<uint8_t>(), S.wtags.as<uint8_t>(), S.wlisted.as<uint32_t>(), count, words, subset_pos, S.flag_host, reinterpret_cast<const uint32_t *>(d_in));
+    } else if (W.dense || !crs->n) {
         hipLaunchKernelGGL(k_set_one, dim3(1), dim3(64), 0, s, z);
         if (crs->n) ZK_HIP(hipMemcpyAsync(z + 1, W.dense, (size_t)crs->n * 32, hipMemcpyHostToDevice, s));
         ZK_HIP(hipMemsetAsync(words, 0, 16, s));
@@ -623,7 +662,9 @@ static int slot_create(zkg_crs *crs, ProverSlot &S) {
 }
 static void slot_destroy(ProverSlot &S) {
     S.helper.shutdown();
-    for (DevBuf *b : {&S.z, &S.aABC, &S.flag, &S.ntt_scratch, &S.up_tags, &S.up_idx, &S.up_vals, &S.wtags, &S.wlisted, &S.wcount}) b->release();
+    for (DevBuf *b : {&S.z, &S.aABC, &S.flag, &S.ntt_scratch, &S.up_tags, &S.up_idx, &S.up_vals, &S.wtags, &S.wlisted, &S.wcount, &S.zw_in}) b->release();
+    if (S.zw_stage) (void)hipHostFree(S.zw_stage);
+    S.zw_stage = nullptr; S.zw_stage_cap = 0;
     msm_job_destroy(S.job_w1); msm_job_destroy(S.job_w2); msm_job_destroy(S.job_h);
     S.job_w1 = S.job_w2 = S.job_h = nullptr;
     for (OnesSum *o : {&S.ones_g1, &S.ones_g2}) o->release();
@@ -992,7 +1033,7 @@ static int h_shards_finish(zkg_crs *crs, ProverSlot &S, G1 &out) {
 static int prove_enqueue(zkg_crs *crs, ProverSlot &S, const WitnessSrc &witness, const uint64_t r_[4], const uint64_t s_[4], bool check) {
     S.t0 = std::chrono::steady_clock::now();
     S.check = check; memcpy(S.r.v, r_, 32); memcpy(S.s.v, s_, 32);
-    S.flag_host[0] = 0; S.flag_host[1] = 0; S.flag_host[2] = 0; S.flag_host[3] = 0;
+    S.flag_host[0] = 0; S.flag_host[1] = 0; S.flag_host[2] = 0; S.flag_host[3] = 0; S.flag_host[4] = 0; S.zw_state = ZW_NONE;
     if (compute_h_matvec(crs, S, witness, check)) return ZKG_ERROR;
     lap(S, "upload + mat-vec enqueued");
     const size_t n = crs->n, l = crs->l, m = crs->m;
@@ -1003,6 +1044,7 @@ static int prove_enqueue(zkg_crs *crs, ProverSlot &S, const WitnessSrc &witness,
         ZK_HIP(hipEventSynchronize(S.ev[0]));
         lap(S, "  (helper) split landed");
         const size_t listed = S.flag_host[1];
+        if (witness.plan && S.flag_host[4]) { S.zw_state = ZW_GENERATOR_ERROR; set_error("zklaim witness generator: a cursor left its range (the host witness is used)"); return ZKG_ERROR; }
         if (S.flag_host[3]) { set_error("prover: a listed witness index is out of range, not tagged 2 or listed twice"); return ZKG_ERROR; }
         if (listed > n + 1) { set_error("prover: witness split out of range"); return ZKG_ERROR; }
         const uint8_t *tags = S.wtags.as<uint8_t>(); const uint32_t *gather = S.wlisted.as<uint32_t>(), *z = S.z.as<uint32_t>();
@@ -1205,6 +1247,44 @@ static int groth16_prove_sparse_impl(const zkg_crs *crs_, const uint8_t *tags, c
     WitnessSrc W; W.tags = tags; W.idx = full_index; W.vals = full_values; W.count = count;
     if (prove_enqueue(crs, S, W, r_, s_, check_satisfied != 0)) { slot_drain(crs, S); return ZKG_ERROR; }
     return prove_finish(crs, S, proof_out, proof_len);
+}
+
+// ---- zkg_groth16_prove_zklaim: one credential of a resident key, its witness generated on the device (k_zklaim_witness_par, launched by
+// compute_h_matvec in front of the split).  Every key the single path serves.  A key the generator's plan does not fit, a plan that
+// disagrees with the host pass, or a generator that raised its error word: the host witness and groth16_prove_sparse_impl.
+static int prove_zklaim_host_witness(zkg_crs *crs, const zklaim_ctx *ctx, const uint64_t r_[4], const uint64_t s_[4], int check_satisfied, uint8_t *proof_out, size_t *proof_len) {
+    zkg_circuit *ck = zkg_zklaim_witness_new(ctx);
+    if (!ck) return ZKG_ERROR;
+    struct Free { zkg_circuit *c; ~Free() { zkg_circuit_free(c); } } free_ck{ck};
+    const uint8_t *tags = nullptr; const uint32_t *fidx = nullptr; const uint64_t *fval = nullptr; size_t nfull = 0;
+    if (zkg_circuit_num_variables(ck) != crs->n) { set_error("zkg_groth16_prove_zklaim: broken payload list or a payload count other than the key's"); return ZKG_ERROR; }
+    if (zkg_circuit_sparse_witness(ck, &tags, &fidx, &fval, &nfull) != ZKG_OK) { set_error("zkg_groth16_prove_zklaim: no witness"); return ZKG_ERROR; }
+    t_prove_zklaim_stats[1] = 1;
+    return groth16_prove_sparse_impl(crs, tags, fidx, fval, nfull, r_, s_, check_satisfied, proof_out, proof_len);   // (zkg_last_error keeps what sent the call here)
+}
+static int groth16_prove_zklaim_impl(const zkg_crs *crs_, const zklaim_ctx *ctx, const uint64_t r_[4], const uint64_t s_[4], int check_satisfied, uint8_t *proof_out, size_t *proof_len) {
+    t_prove_zklaim_stats[0] = t_prove_zklaim_stats[1] = 0;
+    zkg_crs *crs = const_cast<zkg_crs *>(crs_);
+    if (initialised_device() < 0) { set_error("zkg_groth16_prove_zklaim: zkg_init has not been called"); return ZKG_ERROR; }
+    if (!crs || !ctx || !r_ || !s_ || !proof_out || !proof_len) { set_error("zkg_groth16_prove_zklaim: bad argument"); return ZKG_ERROR; }
+    ZwPlan pl;
+    if (zklaim_witness_plan_for_n(crs->n, pl) && zklaim_witness_par_ready(pl)) {
+        SlotLease lease(crs);
+        if (!lease.ok()) return ZKG_ERROR;
+        ProverSlot &S = lease.S();
+        WitnessSrc W; W.ctx = ctx; W.plan = &pl;
+        uint8_t buf[256]; size_t len = 0;                                       // nothing is written unless the proof is made
+        if (prove_enqueue(crs, S, W, r_, s_, check_satisfied != 0)) {
+            slot_drain(crs, S);
+            if (S.zw_state != ZW_GENERATOR_ERROR) return ZKG_ERROR;
+        } else {
+            const int rc = prove_finish(crs, S, buf, &len);
+            if (rc == ZKG_OK) { memcpy(proof_out, buf, len); *proof_len = len; }
+            if (rc == ZKG_OK || rc == ZKG_UNSATISFIED) t_prove_zklaim_stats[0] = 1;
+            return rc;
+        }
+    }
+    return prove_zklaim_host_witness(crs, ctx, r_, s_, check_satisfied, proof_out, proof_len);
 }
 
 // ---- zkg_groth16_prove_batch: P proofs of one key per launch sequence -----------------------------------------------------------
@@ -1516,6 +1596,13 @@ int zkg_groth16_prove_sparse(const zkg_crs *crs, const uint8_t *tags, const uint
     catch (const std::exception &e) { set_error(std::string("zkg_groth16_prove_sparse: ") + e.what()); return ZKG_ERROR; }
     catch (...) { set_error("zkg_groth16_prove_sparse: unexpected exception"); return ZKG_ERROR; }
 }
+
+int zkg_groth16_prove_zklaim(const zkg_crs *crs, const struct zklaim_ctx *ctx, const uint64_t r[4], const uint64_t s[4], int check_satisfied, uint8_t *proof_out, size_t *proof_len) {
+    try { return groth16_prove_zklaim_impl(crs, ctx, r, s, check_satisfied, proof_out, proof_len); }
+    catch (const std::exception &e) { set_error(std::string("zkg_groth16_prove_zklaim: ") + e.what()); return ZKG_ERROR; }
+    catch (...) { set_error("zkg_groth16_prove_zklaim: unexpected exception"); return ZKG_ERROR; }
+}
+void zkg_prove_zklaim_stats(size_t out[2]) { if (out) { out[0] = zk::t_prove_zklaim_stats[0]; out[1] = zk::t_prove_zklaim_stats[1]; } }
 
 int zkg_groth16_prove_batch(const zkg_crs *crs, const zkg_prove_item *items, size_t count, int check_satisfied, uint8_t *proofs_out, int *status) {
     try { return groth16_prove_batch_impl(crs, items, count, check_satisfied, proofs_out, status); }
