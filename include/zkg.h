@@ -398,6 +398,21 @@ int zkg_zklaim_prove_batch(struct zklaim_ctx *const *ctxs, size_t count, int *rc
  *      (safegcd divsteps on 30-bit limbs, f29::inverse: what the batched-affine accumulation shares across a workgroup; 0 -> 0).     */
 int zkg_field_op(int field, int op, const uint64_t *a, const uint64_t *b, size_t n, uint64_t *out);
 
+/* known-answer hook for the NTT's 29-bit Fr arithmetic (csrc/fr29.hip.hpp: Fr as nine 29-bit limbs, R' = 2^261, lazy limb-wise sums).
+ * Element-wise ON THE GPU, one lane per element, host pointers, RAW limbs: element i reads k vectors of nine 32-bit limbs at
+ * in + 9 k i and writes m vectors at out + 9 m i, so a caller can place limbs at the lazy bounds.  No input is range-checked.
+ *   op  0  mul(a, b)                      k 2, m 1     the single product stream (a: data side, b: table side)
+ *       1  mul2(a, b, c, d)               k 4, m 2     the interleaved pair: a b and c d
+ *       2  norm(a)                        k 1, m 1     carry propagation
+ *       3  add_norm(a, b)   4  sub_norm(a, b)   5  add_lazy(a, b)   6  sub_lazy(a, b)          k 2, m 1     (subtractions: a + 2r - b)
+ *       7  slice(x)                       k 1, m 1     x: eight 32-bit words of libff's form in the first eight slots (the ninth is ignored)
+ *       8  unslice_reduce(a)              k 1, m 1     out: eight 32-bit words, the ninth slot zero
+ *       9  the radix-4 step of k_ntt_pass29_r4, a stage with a product: in x0 x1 x2 x3 wa wb wc, out the four stored rows       k 7, m 4
+ *      10  the same at stage 0 (wa unused)     11  op 9 with the carry propagations on the stores (ZKG_NTT_NORM_STORES)     12  op 10 likewise
+ *      13  the radix-2 step that ends an odd R: in u v w, out the two stored rows       k 3, m 2          14  the same at stage 0 (w unused)
+ * Ops 9-14 run a copy of the kernel's step bodies (csrc/capi.hip, marked at both places): the kernel keeps its own text.  n at most 2^24. */
+int zkg_fr29_op(int op, const uint32_t *in, size_t n, uint32_t *out);
+
 /* known-answer hook for the 29-bit group law of the bucket-reduction kernels (csrc/fq29.hip.hpp, xyzz29_add_quad): on the GPU,
  * out[i] = a[i] + b[i], then `chain` rounds of x <- 2x + b[i]; points as normalised Jacobian (12 limbs), host pointers.          */
 int zkg_g1_add_quad29(const uint64_t *a_jac, const uint64_t *b_jac, size_t n, int chain, uint64_t *out_jac);

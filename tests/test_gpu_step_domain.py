@@ -30,13 +30,29 @@ def test_step_ntt_golden(zkg):
                 assert ints(out, R) == [h(x) for x in c[f"out_inv{inv}_coset{coset}"]], (c["m"], inv, coset)
 
 
-@pytest.mark.parametrize("a_log,b_log", [(10, 3), (11, 10), (12, 0), (13, 12), (16, 12), (17, 13)])
+# (9, 4): big / small = 32, the first chunked fold, two chunks; (6, 3): big / small = 8; (18, 12) and (19, 11): the big half takes the radix-4
+# geometry — (19, 11) is zklaim's 19-payload domain
+@pytest.mark.parametrize("a_log,b_log", [(6, 3), (9, 4), (10, 3), (11, 10), (12, 0), (13, 12), (16, 12), (17, 13), (18, 12), (19, 11)])
 def test_step_ntt_vs_oracle(zkg, oracle, a_log, b_log):
     m = (1 << a_log) + (1 << b_log)
     a = random_fr_canonical(m, 0x57E9 + m)          # any 4-limb values < r serve as Montgomery representations
     for inv in (0, 1):
         for coset in (0, 1):
             assert np.array_equal(zkg.ntt(a, inverse=inv, coset=coset), oracle.fft(a, inverse=inv, coset=coset)), (m, inv, coset)
+
+
+@pytest.mark.parametrize("a_log,b_log", [(11, 10), (16, 12)])
+def test_step_ntt_structured_inputs(zkg, oracle, a_log, b_log):
+    """the prover's kind of input on a step domain: zeros (canonical zeros out), all r - 1 and 0/1 bits, all four modes"""
+    from ntt_vectors import MODES, bits, fill, oracle_many
+    m = (1 << a_log) + (1 << b_log)
+    vecs = {"all r-1": fill(m, R - 1), "bits": bits(m, 0x57E9 + m)}
+    jobs = [(name, v, inv, coset) for name, v in vecs.items() for inv, coset in MODES]
+    exp = oracle_many(oracle, [(v, inv, coset) for _, v, inv, coset in jobs])
+    for (name, v, inv, coset), e in zip(jobs, exp):
+        assert np.array_equal(zkg.ntt(v, inverse=inv, coset=coset), e), (m, name, inv, coset)
+    for inv, coset in MODES:
+        assert not zkg.ntt(fill(m, 0), inverse=inv, coset=coset).any(), (m, inv, coset)
 
 
 def test_step_ntt_roundtrip_large(zkg):

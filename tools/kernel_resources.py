@@ -5,7 +5,7 @@ src = sys.argv[1]
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
        "-c", src, "-o", "/tmp/_kres.o"]
 txt = subprocess.run(cmd, capture_output=True, text=True).stderr
-keys = [("VGPRs", "VGPR"), ("AGPRs", "AGPR"), (r"ScratchSize \[bytes/lane\]", "scratch"), (r"Occupancy \[waves/SIMD\]", "occ"), (r"LDS Size \[bytes/block\]", "LDS")]
+keys = [("SGPRs", "SGPR"), ("VGPRs", "VGPR"), ("AGPRs", "AGPR"), (r"ScratchSize \[bytes/lane\]", "scratch"), (r"Occupancy \[waves/SIMD\]", "occ"), (r"LDS Size \[bytes/block\]", "LDS")]
 for b in re.split(r"remark: [^\n]*Function Name: ", txt)[1:]:
     name = b.split("\n")[0]
     vals = []

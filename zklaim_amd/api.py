@@ -27,6 +27,7 @@ DECLARED_SYMBOLS = [
     "zkg_groth16_verify_batch", "zkg_pairing_product", "zkg_verify_batch_stats",
     "zkg_groth16_prove_batch", "zkg_prove_batch_stats", "zkg_prove_batch_chunk", "zkg_zklaim_prove_batch",
     "zkg_groth16_prove_zklaim", "zkg_prove_zklaim_stats", "zkg_zklaim_witness_gpu_parallel", "zkg_zklaim_witness_mirror_parallel",
+    "zkg_fr29_op",
 ]
 # the reference's own seam, exported with its original names (zklaim.h:257-259)
 COMPAT_SYMBOLS = ["libsnark_trusted_setup", "libsnark_prove", "libsnark_verify"]
@@ -123,6 +124,22 @@ def field_op(field, op, a, b=None):
     out = np.zeros_like(a)
     bb = None if b is None else _u64(b)
     _check(lib().zkg_field_op(int(field), int(op), _p(a), _p(bb), C.c_size_t(a.size // limbs), _p(out)), "zkg_field_op")
+    return out
+
+
+FR29_OPS = {"mul": (0, 2, 1), "mul2": (1, 4, 2), "norm": (2, 1, 1), "add_norm": (3, 2, 1), "sub_norm": (4, 2, 1), "add_lazy": (5, 2, 1), "sub_lazy": (6, 2, 1),
+            "slice": (7, 1, 1), "unslice_reduce": (8, 1, 1), "r4": (9, 7, 4), "r4_stage0": (10, 7, 4), "r4_norm_stores": (11, 7, 4),
+            "r4_stage0_norm_stores": (12, 7, 4), "r2_tail": (13, 3, 2), "r2_tail_stage0": (14, 3, 2)}          # name -> (op, k, m) of zkg_fr29_op
+
+
+def fr29_op(name, x):
+    """the NTT's 29-bit Fr arithmetic on raw limbs (zkg_fr29_op): x is (n, k, 9) uint32, the result (n, m, 9) uint32"""
+    op, k, m = FR29_OPS[name]
+    x = np.ascontiguousarray(x, dtype=np.uint32)
+    if x.ndim != 3 or x.shape[1:] != (k, 9):
+        raise ZkgError(f"fr29_op {name}: input must be (n, {k}, 9), got {x.shape}")
+    out = np.zeros((x.shape[0], m, 9), np.uint32)
+    _check(lib().zkg_fr29_op(int(op), _p(x), C.c_size_t(x.shape[0]), _p(out)), "zkg_fr29_op")
     return out
 
 

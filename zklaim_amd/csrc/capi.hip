@@ -5,6 +5,7 @@
 // There is no CPU fallback: every entry point fails with ZKG_ERROR when no HIP device is usable.
 #include "common.hpp"
 #include "fq29.hip.hpp"
+#include "fr29.hip.hpp"
 #include "../../include/zkg.h"
 #include <atomic>
 #include <condition_variable>
@@ -262,6 +263,82 @@ template <class F> static int field_op_run(int op, const uint64_t *a, const uint
         if (hipGetLastError() == hipSuccess && hip_ok(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost), "D2H", __FILE__, __LINE__)) rc = ZKG_OK;
     }
     da.release(); db.release(); dout.release();
+    return rc;
+}
+
+// ---- the NTT's 29-bit Fr arithmetic on raw limbs (the known-answer hook behind zkg_fr29_op): one lane per element, k vectors of nine
+//      limbs in, m out.
+// COPIES of the radix-4 step and of the odd-R tail step of k_ntt_pass29_r4 (csrc/ntt.hip), from the loaded records to the stored ones — the
+// kernel keeps its own text (moving the body into a shared function changed its register allocation): keep the two alike, line by line.
+ZK_D void fr29_r4_step_copy(Fr29 &r0, Fr29 &r1, Fr29 &r2, Fr29 &r3, const Fr29 &wa, const Fr29 &wb, const Fr29 &wc, bool product, bool norm_stores) {
+    Fr29 x0 = r0, x2 = r2;
+    if (!norm_stores) { x0 = fr29::norm(x0); x2 = fr29::norm(x2); }
+    Fr29 t1 = r1, t3 = r3;
+    if (product) { fr29::mul2(t1, t3, t1, wa, t3, wa); }
+    else if (!norm_stores) { t1 = fr29::norm(t1); t3 = fr29::norm(t3); }      // (stage 0 has no product to bring them back to digits)
+    const Fr29 y0 = fr29::add_lazy(x0, t1), y1 = fr29::sub_lazy(x0, t1), y2 = fr29::add_lazy(x2, t3), y3 = fr29::sub_lazy(x2, t3);
+    Fr29 u2, u3;
+    fr29::mul2(u2, u3, y2, wb, y3, wc);
+    if (norm_stores) {
+        r0 = fr29::norm(fr29::add_lazy(y0, u2));
+        r2 = fr29::norm(fr29::sub_lazy(y0, u2));
+        r1 = fr29::norm(fr29::add_lazy(y1, u3));
+        r3 = fr29::norm(fr29::sub_lazy(y1, u3));
+    } else {
+        r0 = fr29::add_lazy(y0, u2);
+        r2 = fr29::sub_lazy(y0, u2);
+        r1 = fr29::add_lazy(y1, u3);
+        r3 = fr29::sub_lazy(y1, u3);
+    }
+}
+ZK_D void fr29_r2_tail_copy(Fr29 &r0, Fr29 &r1, const Fr29 &w, bool product) {
+    const Fr29 u = fr29::norm(r0);
+    Fr29 v = r1;
+    if (product) v = fr29::mul(v, w);
+    else v = fr29::norm(v);
+    r0 = fr29::add_norm(u, v);
+    r1 = fr29::sub_norm(u, v);
+}
+static constexpr int FR29_OPS = 15;
+static const int FR29_K[FR29_OPS] = {2, 4, 1, 2, 2, 2, 2, 1, 1, 7, 7, 7, 7, 3, 3};
+static const int FR29_M[FR29_OPS] = {1, 2, 1, 1, 1, 1, 1, 1, 1, 4, 4, 4, 4, 2, 2};
+__global__ __launch_bounds__(64) void k_fr29_op(int op, int k, int m, const uint32_t *in, size_t n, uint32_t *out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Fr29 x[7], y[4];
+    for (int j = 0; j < 7; ++j) for (int l = 0; l < 9; ++l) x[j].v[l] = j < k ? in[(i * k + j) * 9 + l] : 0u;
+    for (int j = 0; j < 4; ++j) for (int l = 0; l < 9; ++l) y[j].v[l] = 0u;
+    switch (op) {
+    case 0: y[0] = fr29::mul(x[0], x[1]); break;
+    case 1: fr29::mul2(y[0], y[1], x[0], x[1], x[2], x[3]); break;
+    case 2: y[0] = fr29::norm(x[0]); break;
+    case 3: y[0] = fr29::add_norm(x[0], x[1]); break;
+    case 4: y[0] = fr29::sub_norm(x[0], x[1]); break;
+    case 5: y[0] = fr29::add_lazy(x[0], x[1]); break;
+    case 6: y[0] = fr29::sub_lazy(x[0], x[1]); break;
+    case 7: { Fr f; for (int l = 0; l < 8; ++l) f.v[l] = x[0].v[l]; y[0] = fr29::slice(f); break; }
+    case 8: { const Fr f = fr29::unslice_reduce(x[0]); for (int l = 0; l < 8; ++l) y[0].v[l] = f.v[l]; break; }
+    case 9: case 10: case 11: case 12:
+        fr29_r4_step_copy(x[0], x[1], x[2], x[3], x[4], x[5], x[6], op == 9 || op == 11, op >= 11);
+        y[0] = x[0]; y[1] = x[1]; y[2] = x[2]; y[3] = x[3];
+        break;
+    default:
+        fr29_r2_tail_copy(x[0], x[1], x[2], op == 13);
+        y[0] = x[0]; y[1] = x[1];
+        break;
+    }
+    for (int j = 0; j < m; ++j) for (int l = 0; l < 9; ++l) out[(i * m + j) * 9 + l] = y[j].v[l];
+}
+static int fr29_op_run(int op, const uint32_t *in, size_t n, uint32_t *out) {
+    DevBuf din, dout;
+    const int k = FR29_K[op], m = FR29_M[op];
+    const size_t in_bytes = n * k * 9 * sizeof(uint32_t), out_bytes = n * m * 9 * sizeof(uint32_t);
+    int rc = ZKG_ERROR;
+    if (!din.reserve(in_bytes) && !dout.reserve(out_bytes) && hip_ok(hipMemcpy(din.p, in, in_bytes, hipMemcpyHostToDevice), "H2D", __FILE__, __LINE__)) {
+        hipLaunchKernelGGL(k_fr29_op, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, nullptr, op, k, m, din.as<uint32_t>(), n, dout.as<uint32_t>());
+        if (hipGetLastError() == hipSuccess && hip_ok(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost), "D2H", __FILE__, __LINE__)) rc = ZKG_OK;
+    }
+    din.release(); dout.release();
     return rc;
 }
 
@@ -569,6 +646,13 @@ int zkg_field_op(int field, int op, const uint64_t *a, const uint64_t *b, size_t
     if (field == 0) return field_op_run<Fq>(op, a, binary ? b : nullptr, n, out);
     if (field == 1) return field_op_run<Fr>(op, a, binary ? b : nullptr, n, out);
     return field_op_run<Fq2>(op, a, binary ? b : nullptr, n, out);
+}
+
+int zkg_fr29_op(int op, const uint32_t *in, size_t n, uint32_t *out) {
+    REQUIRE_INIT();
+    if (op < 0 || op >= FR29_OPS || !in || !out || n > ((size_t)1 << 24)) { set_error("zkg_fr29_op: bad argument"); return ZKG_ERROR; }
+    if (!n) return ZKG_OK;
+    return fr29_op_run(op, in, n, out);
 }
 
 // ---- one process, several GPUs: the G1 multi-exponentiation sharded by points.  Every shard is a resident slice of

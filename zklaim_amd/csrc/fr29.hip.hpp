@@ -50,7 +50,7 @@ ZK_D void mul2(Fr29 &r0, Fr29 &r1, const Fr29 &a, const Fr29 &b, const Fr29 &c, 
 // of a value below 60 r with a twiddle below r), so its top limb stays below S2_1's; the results' limbs grow by 2^29 resp. 2^30.
 ZK_D Fr29 add_lazy(const Fr29 &a, const Fr29 &b) { Fr29 r; for (int i = 0; i < 9; ++i) r.v[i] = a.v[i] + b.v[i]; return r; }
 ZK_D Fr29 sub_lazy(const Fr29 &a, const Fr29 &b) { Fr29 r; for (int i = 0; i < 9; ++i) r.v[i] = a.v[i] + S2_1[i] - b.v[i]; return r; }
-ZK_D Fr29 norm(const Fr29 &a) {                               // carry propagation: limbs below 2^32 in, digits out
+ZK_D Fr29 norm(const Fr29 &a) {                               // carry propagation: limbs up to 2^32 - 8 in (a limb plus the carry into it, at most 7, must not wrap), digits out
     Fr29 r; uint32_t c = 0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) { uint32_t t = a.v[i] + c; r.v[i] = t & Fr29::M; c = t >> 29; }

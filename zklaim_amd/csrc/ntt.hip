@@ -200,6 +200,7 @@ __global__ __launch_bounds__(256) void k_ntt_pass29_r4(NttPassArgs29 A) {
             const uint32_t lo = A.first ? 0u : ((tile * CW + c) & lo_mask);
             const size_t eb = ((size_t)((j << A.s0) + lo)) << (A.n_log - 2 - s);              // stage s + 1, row bits j
             const Fr29 wb = fr29::load_rec(A.tw + eb), wc = fr29::load_rec(A.tw + eb + ((size_t)1 << (A.n_log - 2)));   // ... and row bits j + h: (h << s0) << (n - 2 - s) = N / 4 further
+            // (The step from here to the four stores has a COPY in csrc/capi.hip, fr29_r4_step_copy, for the known-answer hook zkg_fr29_op: keep the two alike.)
             // Records in LDS and between passes hold LAZY limbs (below 2.5 x 2^30, see the bounds above): the two rows that only get added to
             // (x0, x2) are carried here, on load; the two that get multiplied (x1, x3) go into the product as they are — two carry
             // propagations per butterfly instead of four on the stores (ZKG_NTT_NORM_STORES=1: the old placement, for A/B).
@@ -230,6 +231,7 @@ __global__ __launch_bounds__(256) void k_ntt_pass29_r4(NttPassArgs29 A) {
         for (uint32_t bf = tid; bf < (rows >> 1) * CW; bf += nthr) {
             uint32_t c = bf & (CW - 1), k = bf >> A.cw_log;
             uint32_t j = k & (half - 1), r0 = ((k >> q) << (q + 1)) | j, r1 = r0 + half;
+            // (This step, from the loads to the two stores, has a COPY in csrc/capi.hip, fr29_r2_tail_copy, for the same hook: keep the two alike.)
             const Fr29 u = fr29::norm(fr29::load_rec(lds + r0 * stride + c));                 // (lazy limbs in: see the radix-4 steps)
             Fr29 v = fr29::load_rec(lds + r1 * stride + c);
             if (s != 0) {
