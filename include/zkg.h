@@ -386,6 +386,38 @@ void zkg_compat_reset(void);
  * side by side on the host pool and the group is one zkg_groth16_prove_batch.  Returns ZKG_OK when every rc[i] was written (count == 0: nothing is touched),
  * ZKG_ERROR for a null ctxs or rc.  Safe beside libsnark_prove on the same key from other threads. */
 int zkg_zklaim_prove_batch(struct zklaim_ctx *const *ctxs, size_t count, int *rc);
+/* ---- many libsnark_verify calls in one (no counterpart in the reference, hence the prefix).
+ * rc[i] = what libsnark_verify(ctxs[i]) returns: 0 valid, 1 otherwise — except with probability at most (combined checks) * 2^-128, as
+ * zkg_groth16_verify_batch documents.  A null ctx, or one without vk / vk_size or without proof, is rc 1, decided before any GPU call.
+ * count == 0 touches nothing and returns ZKG_OK; a null ctxs or rc with count > 0 is ZKG_ERROR and nothing is written.  The same context may
+ * appear more than once: verification writes nothing into a ctx.  Synchronous; host pointers; safe from several threads at once and beside
+ * libsnark_verify, libsnark_prove and zkg_zklaim_prove_batch; the calling thread is bound to the seam's device (ZKG_DEVICE) as the prove
+ * entries bind it; a HIP failure returns ZKG_ERROR.
+ * Contexts are grouped by the bytes of ctx->vk and every group is one random linear combination on the GPU, as in zkg_groth16_verify_batch.
+ * An item enters its key's combination only if proof_size == ZKG_PROOF_BYTES and its payload list (walked as zkg_zklaim_input_map walks it;
+ * num_of_payloads is not trusted) yields as many inputs as the key takes; everything else — malformed or unusual keys, wrong sizes, points
+ * that do not decode, non-canonical limbs, B outside G2 — goes through the single verifier's own code on the host pool, with that item's
+ * input map computed on the host.  The device can do the front end too: per call, 134 bytes per proof and 80 bytes per payload go up,
+ * k_proof_decode takes the square roots and k_zklaim_input_sums forms the combination's input sums from the payloads' public bytes, so no
+ * public input exists on the host.  That is the default for a key's group of at least 512 payload records (entering items x payloads),
+ * where it was measured no slower than hand-built items; smaller groups, and a call whose device staging would exceed 64 MiB, take the
+ * host front end: zkg_zklaim_input_map per item on the host pool, then zkg_groth16_verify_batch's path.  ZKG_SEAM_GPU_VERIFY (read once
+ * per process) = 0 keeps the host front end for every group, = 1 the device's.  ZKG_VERIFY_BATCH_LAPS=1 prints that entry's lap line. */
+int zkg_zklaim_verify_batch(struct zklaim_ctx *const *ctxs, size_t count, int *rc);
+/* what the calling thread's last zkg_zklaim_verify_batch did: out[0] combined checks, out[1] items decided by the single verifier's code,
+ * out[2] items whose B failed the G2 test, out[3] items whose points and inputs the device front end produced.  Counters, not clocks. */
+void zkg_zklaim_verify_batch_stats(size_t out[4]);
+/* test hooks of the device front end.
+ * proofs: count x 134 bytes.  A / C: count x 8 limbs, B: count x 16 limbs (affine Montgomery, all-zero = infinity), ok: count bytes
+ * (bit 0 A, bit 1 B, bit 2 C decoded).  On the GPU; host pointers; needs zkg_init, no key. */
+int zkg_proof_decode_gpu(const uint8_t *proofs, size_t count, uint64_t *A, uint64_t *B, uint64_t *C, uint8_t *ok);
+/* contexts of ONE payload count; weights: count x 4 u32 (128-bit, as the verifier draws them); mask: count bytes or NULL (all ones);
+ * sums_out: l x 4 limbs Montgomery Fr = sum over positions lo <= p < hi with mask[p] of weight_p * x_p; returns l through *n_elems.
+ * On the GPU (k_zklaim_input_sums); a null context or another payload count is ZKG_ERROR. */
+int zkg_zklaim_input_sums_gpu(const struct zklaim_ctx *const *ctxs, size_t count, const uint32_t *weights, const uint8_t *mask,
+                              size_t lo, size_t hi, uint64_t *sums_out, size_t cap_elems, size_t *n_elems);
+/* the kernel's bit rule compiled for the host: same outputs as zkg_zklaim_input_map.  No GPU, no zkg_init. */
+size_t zkg_zklaim_input_map_mirror(const struct zklaim_ctx *ctx, uint64_t *out, size_t cap_elems);
 
 /* ---- known-answer hook for the device arithmetic (libff Fp_model<4,...>::mul_reduce, Fp2_model —
  *      here the generated v_mad_u64_u32 streams of csrc/mont_asm.inc).  Element-wise ON THE GPU, host pointers:

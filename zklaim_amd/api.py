@@ -28,6 +28,7 @@ DECLARED_SYMBOLS = [
     "zkg_groth16_prove_batch", "zkg_prove_batch_stats", "zkg_prove_batch_chunk", "zkg_zklaim_prove_batch",
     "zkg_groth16_prove_zklaim", "zkg_prove_zklaim_stats", "zkg_zklaim_witness_gpu_parallel", "zkg_zklaim_witness_mirror_parallel",
     "zkg_fr29_op",
+    "zkg_zklaim_verify_batch", "zkg_zklaim_verify_batch_stats", "zkg_proof_decode_gpu", "zkg_zklaim_input_sums_gpu", "zkg_zklaim_input_map_mirror",
 ]
 # the reference's own seam, exported with its original names (zklaim.h:257-259)
 COMPAT_SYMBOLS = ["libsnark_trusted_setup", "libsnark_prove", "libsnark_verify"]
@@ -840,6 +841,69 @@ def zklaim_prove_batch(ctxs):
     rc = (C.c_int * max(1, n))(*([-1] * max(1, n)))
     _check(L.zkg_zklaim_prove_batch(ptrs, n, rc), "zkg_zklaim_prove_batch")
     return [int(rc[i]) for i in range(n)]
+
+
+def zklaim_verify_batch(ctxs):
+    """zkg_zklaim_verify_batch: one libsnark_verify per ZklaimCtx (None: a null entry), grouped by key and combined on the GPU -> [rc, ...]"""
+    L = lib()
+    L.zkg_zklaim_verify_batch.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+    n = len(ctxs)
+    ptrs = _ctx_ptrs(ctxs)
+    rc = (C.c_int * max(1, n))(*([-1] * max(1, n)))
+    _check(L.zkg_zklaim_verify_batch(ptrs, n, rc), "zkg_zklaim_verify_batch")
+    return [int(rc[i]) for i in range(n)]
+
+
+def zklaim_verify_batch_stats():
+    """(combined checks, items decided by the single verifier's code, items whose B is outside G2, items whose points and inputs the device
+    front end produced) of this thread's last zklaim_verify_batch"""
+    out = (C.c_size_t * 4)()
+    lib().zkg_zklaim_verify_batch_stats(out)
+    return tuple(int(v) for v in out)
+
+
+def proof_decode_gpu(proofs):
+    """zkg_proof_decode_gpu: proofs (n, 134) uint8 -> A (n, 8), B (n, 16), C (n, 8) affine Montgomery limbs and ok (n,) flag bytes
+    (bit 0 A, bit 1 B, bit 2 C decoded)"""
+    pr = np.ascontiguousarray(proofs, np.uint8).reshape(-1, 134)
+    n = pr.shape[0]
+    A = np.zeros((n, 8), np.uint64); B = np.zeros((n, 16), np.uint64); Cc = np.zeros((n, 8), np.uint64); ok = np.zeros(n, np.uint8)
+    L = lib()
+    L.zkg_proof_decode_gpu.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    _check(L.zkg_proof_decode_gpu(_p(pr), n, _p(A), _p(B), _p(Cc), _p(ok)), "zkg_proof_decode_gpu")
+    return A, B, Cc, ok
+
+
+def zklaim_input_sums_gpu(ctxs, weights, mask=None, lo=0, hi=None):
+    """zkg_zklaim_input_sums_gpu: contexts of one payload count, weights (n, 4) uint32, mask (n,) uint8 or None -> (l, 4) Montgomery Fr sums"""
+    n = len(ctxs)
+    hi = n if hi is None else hi
+    w = np.ascontiguousarray(weights, np.uint32).reshape(-1, 4)
+    if w.shape[0] != n:
+        raise ZkgError("zklaim_input_sums_gpu: one weight per context")
+    m = None if mask is None else np.ascontiguousarray(mask, np.uint8).reshape(-1)
+    if m is not None and m.size != n:
+        raise ZkgError("zklaim_input_sums_gpu: one mask byte per context")
+    k = next((int(c.num_of_payloads) for c in ctxs if c is not None), 1)
+    cap = (1280 * max(k, 1) + 252) // 253 + 8
+    out = np.zeros((cap, 4), np.uint64); cnt = C.c_size_t(0)
+    L = lib()
+    L.zkg_zklaim_input_sums_gpu.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+    _check(L.zkg_zklaim_input_sums_gpu(_ctx_ptrs(ctxs), n, _p(w), _p(m), lo, hi, _p(out), cap, C.byref(cnt)), "zkg_zklaim_input_sums_gpu")
+    return out[:cnt.value].copy()
+
+
+def zklaim_input_map_mirror(ctx, count_only=False):
+    """zkg_zklaim_input_map_mirror (no GPU): the device's bit rule on the host -> (l, 4) Montgomery Fr as zklaim_input_map; count_only: l"""
+    L = lib()
+    L.zkg_zklaim_input_map_mirror.restype = C.c_size_t
+    L.zkg_zklaim_input_map_mirror.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    n = int(L.zkg_zklaim_input_map_mirror(C.addressof(ctx), None, 0))
+    if count_only:
+        return n
+    out = np.zeros((n, 4), np.uint64)
+    assert L.zkg_zklaim_input_map_mirror(C.addressof(ctx), _p(out), n) == n
+    return out
 
 
 def ctx_blob(ctx, which):

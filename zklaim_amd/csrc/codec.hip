@@ -17,6 +17,7 @@
 //   r1cs_constraint_system         : primary '\n' auxiliary '\n' #constraints '\n' , per constraint a, b, c
 //   linear_combination             : #terms '\n' , (index '\n' coeff(32 B))*
 #include "common.hpp"
+#include "sqrt.hip.hpp"
 #include "../../include/zkg.h"
 #include <chrono>
 #include <cstdio>
@@ -29,39 +30,7 @@
 
 namespace zk {
 
-// ---- square roots -------------------------------------------------------------------------------------------------
-// q = 3 mod 4: sqrt(a) = a^((q+1)/4) when a is a square
-ZK_D Fq fq_sqrt_candidate(const Fq &a) {
-    // (q + 1) / 4
-    const uint32_t e[8] = {0xb61f3f52u, 0x4f082305u, 0x5a1c72a3u, 0x65e05aa4u, 0xa0605617u, 0x6e14116du, 0xb84c680au, 0x0c19139cu};
-    return a.pow(e, 8);
-}
-// complex method in Fq2 = Fq[u]/(u^2+1): returns false when a is not a square
-ZK_D bool fq2_sqrt(const Fq2 &a, Fq2 &out) {
-    if (a.c1.is_zero()) {                               // a in Fq: sqrt is either in Fq or purely imaginary
-        Fq s = fq_sqrt_candidate(a.c0);
-        if (s.sqr() == a.c0) { out = {s, Fq::zero()}; return true; }
-        Fq t = fq_sqrt_candidate(a.c0.neg());
-        if (t.sqr() == a.c0.neg()) { out = {Fq::zero(), t}; return true; }
-        return false;
-    }
-    Fq norm = a.c0.sqr() + a.c1.sqr();
-    Fq s = fq_sqrt_candidate(norm);
-    if (s.sqr() != norm) return false;
-    Fq two_inv = Fq::from_u64(2).inverse();
-    Fq d = (a.c0 + s) * two_inv;
-    Fq c0 = fq_sqrt_candidate(d);
-    if (c0.sqr() != d) { d = (a.c0 - s) * two_inv; c0 = fq_sqrt_candidate(d); if (c0.sqr() != d) return false; }
-    Fq c1 = a.c1 * (c0.dbl()).inverse();
-    out = {c0, c1};
-    return true;
-}
-
-ZK_D Fq load_fq_bytes(const uint8_t *p) {
-    Fq r;
-    for (int i = 0; i < 8; ++i) r.v[i] = (uint32_t)p[4 * i] | ((uint32_t)p[4 * i + 1] << 8) | ((uint32_t)p[4 * i + 2] << 16) | ((uint32_t)p[4 * i + 3] << 24);
-    return r;
-}
+// (square roots and the limb loader of the decompression kernels: sqrt.hip.hpp, shared with verify.hip's k_proof_decode)
 
 // records of `stride` bytes starting at rec: G1 at offset off (34 B).  flag |= 1 on a malformed point.
 __global__ __launch_bounds__(256) void k_decompress_g1(const uint8_t *rec, size_t stride, size_t off, size_t n, G1Affine *out, uint32_t *flag) {

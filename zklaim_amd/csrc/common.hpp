@@ -203,6 +203,17 @@ int verify_g2_subgroup(const G2Affine *d_B, size_t n, uint8_t *d_ok, hipStream_t
 int verify_g1_mul128(const G1Affine *d_in, const uint32_t *d_w, size_t nw, size_t n, G1Affine *d_out, hipStream_t s);   // lane i: weight i mod nw
 int verify_miller(const G1Affine *d_P, const G2Affine *d_Q, const uint8_t *d_use, size_t n, void *d_out, hipStream_t s);
 int verify_fq12_product(const void *d_in, size_t lo, size_t hi, void *d_partial, void *d_out, hipStream_t s);   // d_out[0] = prod d_in[lo, hi)
+// the seam's device front end.  Proof records of ZKG_PROOF_BYTES -> B (n lanes), A and C back to back in d_AC (2 n lanes): affine Montgomery
+// points as ser::get_g1 / ser::get_g2 give them, infinity where the record is infinity or does not decode; d_dec: a byte per lane, 1 = decoded
+// by the single verifier's rule with canonical limbs.  use[i] = in_g2[i] && dec_b[i] && dec_ac[i] && dec_ac[n + i].
+int verify_proof_decode_b(const uint8_t *d_rec, size_t n, G2Affine *d_B, uint8_t *d_dec, hipStream_t s);
+int verify_proof_decode_ac(const uint8_t *d_rec, size_t n, G1Affine *d_AC, uint8_t *d_dec, hipStream_t s);
+int verify_use_mask(size_t n, const uint8_t *d_in_g2, const uint8_t *d_dec_b, const uint8_t *d_dec_ac, uint8_t *d_use, hipStream_t s);
+// d_out[k] = sum over positions lo <= p < hi with d_mask[p] (optional) of weight_p * x_pk, Montgomery Fr, k < zv_input_count(npl); position p
+// has its npl public records (zklaim_public.hip.hpp) at d_pub + (p - base) * npl * 80 and its weight at d_w + 4 p; d_part: ZV_SUM_SLICES x l Fr
+static constexpr size_t ZV_SUM_SLICES = 16;
+int verify_zklaim_input_sums(const uint8_t *d_pub, uint32_t npl, size_t base, const uint32_t *d_w, const uint8_t *d_mask, size_t lo, size_t hi,
+                             void *d_part, void *d_out, hipStream_t s);
 int initialised_device();                                // the device zkg_init selected, -1 before (capi.hip)
 // a batch call's device workspace: grow-only buffer, two streams (the subgroup check runs beside the scalar multiplications), two events
 struct VerifyWorkspace { DevBuf buf; hipStream_t s = nullptr, s2 = nullptr; hipEvent_t ev = nullptr, ev2 = nullptr; };

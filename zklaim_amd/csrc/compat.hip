@@ -2,7 +2,8 @@
 //     int libsnark_trusted_setup(zklaim_ctx*), int libsnark_prove(zklaim_ctx*), int libsnark_verify(zklaim_ctx*)
 // (declared /root/reference/zklaim/zklaim.h:257-259, defined zklaim/libsnark_wrapper.cpp:195-276, called from
 // zklaim_trusted_setup / zklaim_proof_generate / zklaim_proof_verify at zklaim/zklaim.c:77-91).
-// and one entry the reference does not have: int zkg_zklaim_prove_batch(zklaim_ctx *const *, size_t, int *rc), many libsnark_prove calls in one.
+// and two entries the reference does not have: int zkg_zklaim_prove_batch(zklaim_ctx *const *, size_t, int *rc), many libsnark_prove calls in
+// one, and int zkg_zklaim_verify_batch(zklaim_ctx *const *, size_t, int *rc), many libsnark_verify calls in one.
 // Behaviour kept: 0 on success; prove returns 1 for an unsatisfied credential (libsnark_wrapper.cpp:233-240); verify returns
 // !valid (:269); ctx->pk / vk / proof are malloc'd here and freed by zklaim_ctx_free (zklaim.c:57-72).
 // Behaviour changed on purpose: file descriptor 1 is never closed (the reference closes stdout around every call,
@@ -40,6 +41,8 @@ int seam_keygen(const zkg_r1cs *cs, zk::OwnedCsr *owned, const std::function<voi
                 unsigned char **vk_out, size_t *vk_len, zkg_crs **crs_out, const std::function<void(const unsigned char *, size_t)> &on_blob);    // setup_verify.hip
 void seam_keygen_quiesce();                                                                                              // setup_verify.hip
 void circuit_release_csr(zkg_circuit *c, zk::OwnedCsr &out);                                                            // zklaim_circuit.hip
+int seam_verify_batch(const zklaim_ctx *const *ctxs, size_t count, int *rc, int front_end);                              // setup_verify.hip
+void seam_verify_batch_stats_clear();                                                                                    // setup_verify.hip
 
 namespace {
 
@@ -468,6 +471,28 @@ int libsnark_verify(zklaim_ctx *ctx) {
     try { return libsnark_verify_impl(ctx); }                      // nothing propagates through the C boundary
     catch (const std::exception &e) { zk::set_error(std::string("libsnark_verify: ") + e.what()); return 1; }
     catch (...) { zk::set_error("libsnark_verify: unexpected exception"); return 1; }
+}
+
+
+// ---- zkg_zklaim_verify_batch: many libsnark_verify calls in one (the batch itself: setup_verify.hip, seam_verify_batch) -----------------
+// ZKG_SEAM_GPU_VERIFY=0 keeps the host front end — zkg_zklaim_input_map per context, the proofs decoded on the host pool — for every key
+// (read once; the timing tool's second leg), =1 the device front end for every key; unset: the default per group (setup_verify.hip)
+static int seam_gpu_verify() { static const int m = [] { const char *e = getenv("ZKG_SEAM_GPU_VERIFY"); return !e ? -1 : e[0] == '0' ? 0 : 1; }(); return m; }
+static int zklaim_verify_batch_impl(zklaim_ctx *const *ctxs, size_t count, int *rc) {
+    if (!count) return ZKG_OK;
+    if (!ctxs || !rc) { set_error("zkg_zklaim_verify_batch: null argument"); return ZKG_ERROR; }
+    seam_verify_batch_stats_clear();
+    bool any = false;
+    for (size_t i = 0; i < count && !any; ++i) any = ctxs[i] && ctxs[i]->vk && ctxs[i]->vk_size && ctxs[i]->proof;
+    if (!any) { for (size_t i = 0; i < count; ++i) rc[i] = 1; return ZKG_OK; }      // decided before any GPU call
+    { std::lock_guard<std::mutex> lk(g_mu); if (ensure_init()) return ZKG_ERROR; }
+    return seam_verify_batch(ctxs, count, rc, seam_gpu_verify());
+}
+int zkg_zklaim_verify_batch(zklaim_ctx *const *ctxs, size_t count, int *rc) {
+    try { return zklaim_verify_batch_impl(ctxs, count, rc); }    // nothing propagates through the C boundary
+    catch (const std::exception &e) { zk::set_error(std::string("zkg_zklaim_verify_batch: ") + e.what()); }
+    catch (...) { zk::set_error("zkg_zklaim_verify_batch: unexpected exception"); }
+    return ZKG_ERROR;
 }
 
 

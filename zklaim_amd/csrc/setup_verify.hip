@@ -19,6 +19,8 @@
 #include <thread>
 #include <chrono>
 #include "../../include/zkg.h"
+#include "../../include/zklaim_abi.h"
+#include "zklaim_public.hip.hpp"
 #include "host/serialize.hpp"
 #include <cstdio>
 #include <cstdlib>
@@ -491,8 +493,9 @@ static void draw_weights(uint32_t *w, size_t n) {
         while (!(w[4 * i] | w[4 * i + 1] | w[4 * i + 2] | w[4 * i + 3])) { std::random_device rd; for (int j = 0; j < 4; ++j) w[4 * i + j] = rd(); }
 }
 
-// what the last zkg_groth16_verify_batch call of this thread did (zkg_verify_batch_stats)
+// what the last zkg_groth16_verify_batch / zkg_zklaim_verify_batch call of this thread did (zkg_verify_batch_stats, zkg_zklaim_verify_batch_stats)
 static thread_local size_t t_batch_stats[3] = {0, 0, 0};
+static thread_local size_t t_seam_batch_stats[4] = {0, 0, 0, 0};
 
 namespace {
 struct BatchGroup {
@@ -500,43 +503,65 @@ struct BatchGroup {
     std::shared_ptr<const PreparedVk> vk; bool batchable = false;
     std::vector<size_t> items;                                              // item indices, then the positions [lo, hi) of those that enter
     size_t lo = 0, hi = 0;
+    uint32_t npl = 0; size_t pub_at = 0;                                    // the seam's device front end: payloads per item, where its records start
 };
 struct WorkspaceLease {                       // returned to the free list on every way out (after the call's streams are idle)
     VerifyWorkspace *w = nullptr;
     ~WorkspaceLease() { if (w) { (void)hipStreamSynchronize(w->s); (void)hipStreamSynchronize(w->s2); verify_workspace_release(w); } }
 };
+// ZKG_VERIFY_BATCH_LAPS=1: the host clock at the end of each stage, on stderr (where a batch's time goes)
+struct BatchLaps {
+    const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    std::string line; size_t n;
+    explicit BatchLaps(size_t count) : n(count) {}
+    void operator()(const char *what) {
+        static const bool laps = getenv("ZKG_VERIFY_BATCH_LAPS") && atoi(getenv("ZKG_VERIFY_BATCH_LAPS")) != 0;
+        if (laps) line += std::string(" ") + what + "=" + std::to_string(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    }
+    ~BatchLaps() { if (!line.empty()) fprintf(stderr, "[verify_batch] n=%zu ms:%s\n", n, line.c_str()); }
+};
+struct BatchCounts { size_t combined = 0, alone = 0, outside_g2 = 0, from_device = 0; };
+// where the core's arrays lie in a call's device workspace: N positions; o_flags: N bytes each of [B in G2 | B decoded | A decoded | C decoded
+// | enters]; o_fe: the front end's own staging, directly behind the weights (o_w)
+struct BatchLayout { uint8_t *d = nullptr; size_t N = 0, o_A = 0, o_C = 0, o_B = 0, o_w = 0, o_flags = 0, o_sums = 0, o_fe = 0; hipStream_t s = nullptr, s2 = nullptr; };
+
+// What the batch core (verify_batch_core) asks of its caller: (a) the proofs' points, (b) the input sums, (c) the single verifier's arguments.
+struct BatchFrontEnd {
+    virtual ~BatchFrontEnd() = default;
+    virtual bool on_device() const { return false; }                       // the points are decoded on the device, with a flag byte per position
+    virtual size_t stage_bytes(size_t) const { return 0; }                 // device bytes behind the weights
+    virtual size_t sum_elems() const { return 0; }                         // the most elements a key's sums have (device sums only)
+    // (a) B of every position at d + o_B on s; then A, C and the weights (A and C back to back).  item_at[p]: the item at position p.
+    virtual int stage_B(const BatchLayout &L, const std::vector<BatchGroup> &groups, const std::vector<size_t> &item_at, const uint32_t *w) = 0;
+    virtual int stage_AC(const BatchLayout &L, const uint32_t *w) = 0;
+    // (b) s_k = sum over positions p of [lo, hi) with in[p] of wm[p] * x_pk: sums_begin may start device work (in_dev: the mask on the device),
+    // sums_ready waits for it, scalar_of(k) then gives the sum for the key's k-th gamma_ABC entry (called from the host pool)
+    virtual int sums_begin(const BatchLayout &, const BatchGroup &, size_t, size_t) { return ZKG_OK; }
+    virtual int sums_ready(const BatchLayout &) { return ZKG_OK; }
+    virtual void scalar_of(const BatchGroup &G, const std::vector<size_t> &in, const std::vector<size_t> &item_at, const Fr *wm, size_t k, Fr &x) = 0;
+    // (c) zkg_groth16_verify's own code on item i: 0 valid, 1 invalid, 2 malformed
+    virtual int alone(size_t i) = 0;
+};
 }  // namespace
 
-static int verify_batch_impl(const zkg_verify_item *items, size_t count, uint8_t *verdicts) {
-    if (initialised_device() < 0) { set_error("zkg_groth16_verify_batch: zkg_init not called (no GPU: there is no CPU path)"); return ZKG_ERROR; }
-    if (count && (!items || !verdicts)) { set_error("zkg_groth16_verify_batch: null argument"); return ZKG_ERROR; }
-    size_t n_combined = 0, n_outside_g2 = 0;
-    t_batch_stats[0] = t_batch_stats[1] = t_batch_stats[2] = 0;
-    if (!count) return ZKG_OK;
-    // ZKG_VERIFY_BATCH_LAPS=1: the host clock at the end of each stage, on stderr (where a batch's time goes)
-    static const bool laps = getenv("ZKG_VERIFY_BATCH_LAPS") && atoi(getenv("ZKG_VERIFY_BATCH_LAPS")) != 0;
-    const auto t0 = std::chrono::steady_clock::now();
-    std::string lap_line;
-    auto lap = [&](const char *what) {
-        if (laps) lap_line += std::string(" ") + what + "=" + std::to_string(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-    };
-    struct PrintLaps { const std::string &l; size_t n; ~PrintLaps() { if (!l.empty()) fprintf(stderr, "[verify_batch] n=%zu ms:%s\n", n, l.c_str()); } } print_laps{lap_line, count};
-    std::vector<char> own(count, 0);                                        // decided by the single verifier's code
-    // 1. group by the key's bytes
-    std::vector<BatchGroup> groups; std::multimap<uint64_t, size_t> by_digest;
+// steps 1 and 2 of a batch: group by the key's bytes; per key the prepared form (shared with zkg_groth16_verify's cache) and the checks
+// the weights rely on, once per key.  blob_of(i, len): item i's key (null: the single verifier decides it).
+static void batch_group_keys(size_t count, const std::function<const uint8_t *(size_t, size_t &)> &blob_of, std::vector<BatchGroup> &groups, std::vector<char> &own) {
+    std::multimap<uint64_t, size_t> by_digest;
     for (size_t i = 0; i < count; ++i) {
-        const zkg_verify_item &it = items[i];
-        if (!it.vk_blob) { own[i] = 1; continue; }
-        const uint64_t d = vk_digest(it.vk_blob, it.vk_len);
+        if (own[i]) continue;
+        size_t len = 0;
+        const uint8_t *blob = blob_of(i, len);
+        if (!blob) { own[i] = 1; continue; }
+        const uint64_t d = vk_digest(blob, len);
         size_t g = groups.size();
         for (auto r = by_digest.equal_range(d); r.first != r.second; ++r.first) {
             const BatchGroup &c = groups[r.first->second];
-            if (c.len == it.vk_len && memcmp(c.blob, it.vk_blob, it.vk_len) == 0) { g = r.first->second; break; }
+            if (c.len == len && memcmp(c.blob, blob, len) == 0) { g = r.first->second; break; }
         }
-        if (g == groups.size()) { groups.push_back(BatchGroup{it.vk_blob, it.vk_len, d}); by_digest.emplace(d, g); }
+        if (g == groups.size()) { groups.push_back(BatchGroup{blob, len, d}); by_digest.emplace(d, g); }
         groups[g].items.push_back(i);
     }
-    // 2. per key: prepared form (shared with zkg_groth16_verify's cache) and the checks the weights rely on, once per key
     host_parallel_for((int)groups.size(), [&](int g) {
         BatchGroup &G = groups[g];
         try {
@@ -546,6 +571,160 @@ static int verify_batch_impl(const zkg_verify_item *items, size_t count, uint8_t
         } catch (...) { G.vk = nullptr; G.batchable = false; }              // the single verifier decides these items (and meets the same failure)
     });
     for (const BatchGroup &G : groups) if (!G.batchable) for (size_t i : G.items) own[i] = 1;
+}
+
+// Steps 4 to 7 of a batch, shared by zkg_groth16_verify_batch (host front end) and zkg_zklaim_verify_batch (device front end): layout and
+// weights, the GPU part, the combined check with bisection down to VERIFY_LEAF, the single verifier for whatever is left (own[i] != 0).
+static int verify_batch_core(std::vector<BatchGroup> &groups, std::vector<char> &own, size_t count, BatchFrontEnd &fe, uint8_t *verdicts, BatchLaps &lap, BatchCounts &cnt) {
+    // 4. layout: the entering proofs of each key at contiguous positions, a weight per position
+    std::vector<size_t> item_at;
+    for (BatchGroup &G : groups) {
+        G.lo = item_at.size();
+        for (size_t i : G.items) if (!own[i]) item_at.push_back(i);
+        G.hi = item_at.size();
+    }
+    const size_t N = item_at.size();
+    const bool dev = fe.on_device();
+    std::vector<G1Affine> rC(N); std::vector<uint32_t> w(4 * N); std::vector<Fr> wm(N);
+    draw_weights(w.data(), N);                                              // fresh on every call; no seed crosses the ABI
+    for (size_t p = 0; p < N; ++p) { Fr x = Fr::zero(); memcpy(x.v, &w[4 * p], 16); wm[p] = x.to_mont(); }
+    lap("weights");
+    std::vector<uint8_t> flags((dev ? 4 : 1) * N, 1);                       // [B in G2 | B decoded | A decoded | C decoded]
+    std::vector<uint8_t> in(N, 1);                                          // the position enters the sums
+    std::vector<size_t> decide_alone;
+    if (N) {
+        // 5. the GPU part: B in G2 (second stream) beside r_i A_i and r_i C_i (one launch), then the Miller values
+        const size_t ns = fe.sum_elems();
+        const size_t o_A = 0, o_C = o_A + 64 * N, o_B = o_C + 64 * N, o_rA = o_B + 128 * N, o_rC = o_rA + 64 * N, o_M = o_rC + 64 * N,
+                     o_part = o_M + 384 * N, o_out = o_part + 384 * VERIFY_PROD_BLOCKS, o_sums = o_out + 384, o_flags = o_sums + 32 * ns * (ZV_SUM_SLICES + 1),
+                     o_w = (o_flags + 5 * N + 15) & ~(size_t)15, o_fe = o_w + 16 * N, total = o_fe + fe.stage_bytes(N) + 16;
+        const size_t o_ok = o_flags, o_use = o_flags + 4 * N;
+        WorkspaceLease lease;
+        if (!(lease.w = verify_workspace_acquire()) || lease.w->buf.reserve(total)) return ZKG_ERROR;
+        uint8_t *d = lease.w->buf.as<uint8_t>(); hipStream_t s = lease.w->s, s2 = lease.w->s2;
+        BatchLayout L; L.d = d; L.N = N; L.o_A = o_A; L.o_C = o_C; L.o_B = o_B; L.o_w = o_w; L.o_flags = o_flags; L.o_sums = o_sums; L.o_fe = o_fe; L.s = s; L.s2 = s2;
+        if (fe.stage_B(L, groups, item_at, w.data())) return ZKG_ERROR;
+        ZK_HIP(hipEventRecord(lease.w->ev, s));
+        ZK_HIP(hipStreamWaitEvent(s2, lease.w->ev, 0));
+        if (verify_g2_subgroup((const G2Affine *)(d + o_B), N, d + o_ok, s2)) return ZKG_ERROR;
+        ZK_HIP(hipEventRecord(lease.w->ev2, s2));
+        if (fe.stage_AC(L, w.data())) return ZKG_ERROR;                     // A and C back to back: one launch for both
+        if (verify_g1_mul128((const G1Affine *)(d + o_A), (const uint32_t *)(d + o_w), N, 2 * N, (G1Affine *)(d + o_rA), s)) return ZKG_ERROR;
+        ZK_HIP(hipStreamWaitEvent(s, lease.w->ev2, 0));
+        // a position whose points did not decode keeps its place with the Miller value 1, as one whose B is outside G2 does
+        if (dev && verify_use_mask(N, d + o_ok, d + o_ok + N, d + o_ok + 2 * N, d + o_use, s)) return ZKG_ERROR;
+        if (verify_miller((const G1Affine *)(d + o_rA), (const G2Affine *)(d + o_B), d + (dev ? o_use : o_ok), N, d + o_M, s)) return ZKG_ERROR;
+        ZK_HIP(hipMemcpyAsync(flags.data(), d + o_ok, flags.size(), hipMemcpyDeviceToHost, s));
+        ZK_HIP(hipMemcpyAsync(rC.data(), d + o_rC, 64 * N, hipMemcpyDeviceToHost, s));
+        lap("upload_launch");
+        ZK_HIP(hipStreamSynchronize(s));
+        lap("gpu");
+        for (size_t p = 0; p < N; ++p) {                                    // its Miller value is 1: the ranges stay contiguous
+            if (!flags[p]) ++cnt.outside_g2;
+            in[p] = flags[p] && (!dev || (flags[N + p] && flags[2 * N + p] && flags[3 * N + p]));
+            if (!in[p]) own[item_at[p]] = 1;
+        }
+        if (dev) cnt.from_device += N;
+        // 6. one combined check per range; a failed range is halved
+        auto combined = [&](const BatchGroup &G, size_t lo, size_t hi, bool &pass) -> int {
+            Fq12 prod;
+            if (verify_fq12_product(d + o_M, lo, hi, d + o_part, d + o_out, s)) return ZKG_ERROR;
+            ZK_HIP(hipMemcpyAsync(&prod, d + o_out, 384, hipMemcpyDeviceToHost, s));
+            if (fe.sums_begin(L, G, lo, hi)) return ZKG_ERROR;              // (beside the product, on the second stream)
+            std::vector<size_t> inp;                                        // (the host work below runs while the product is computed)
+            for (size_t p = lo; p < hi; ++p) if (in[p]) inp.push_back(p);
+            Fr rsum = Fr::zero();
+            for (size_t p : inp) rsum += wm[p];
+            const int chunks = (int)std::min<size_t>(16, inp.size());
+            std::vector<G1> part(std::max(chunks, 1), G1::inf());
+            host_parallel_for(chunks, [&](int c) {
+                G1 a = G1::inf();
+                for (size_t t = inp.size() * c / chunks; t < inp.size() * (c + 1) / chunks; ++t) a.madd(rC[inp[t]]);
+                part[c] = a;
+            });
+            G1 csum = G1::inf();
+            for (const G1 &q : part) csum.add(q);
+            const PreparedVk &vk = *G.vk;
+            G1 acc = G1::from_affine(vk.ic0);
+            { uint32_t e[8]; fr_limbs(rsum, e); acc = acc.mul(e, 8); }
+            if (fe.sums_ready(L)) return ZKG_ERROR;
+            acc.add(ic_combination(vk, [&](size_t k, Fr &x) { fe.scalar_of(G, inp, item_at, wm.data(), k, x); }));      // s_k = sum_i r_i x_ik
+            std::vector<G1Affine> Ps; std::vector<G2Affine> Qs; std::vector<const std::vector<pairing::LineCoeff> *> prep;
+            auto ml = [&](const G1Affine &P, const G2Affine &Q, const std::vector<pairing::LineCoeff> *lines) { if (!P.is_inf() && !Q.is_inf()) { Ps.push_back(P); Qs.push_back(Q); prep.push_back(lines); } };
+            ml(acc.to_affine().neg(), vk.gamma_g2, &vk.gamma_lines); ml(csum.to_affine().neg(), vk.delta_g2, &vk.delta_lines);
+            Fq12 f = Ps.empty() ? Fq12::one() : pairing::multi_miller_loop(Ps.data(), Qs.data(), (int)Ps.size(), prep.data());
+            uint32_t e[8]; fr_limbs(rsum, e);
+            const Fq12 rhs = vk.alpha_beta.cyclotomic_pow(e, 8);
+            ZK_HIP(hipStreamSynchronize(s));
+            pass = pairing::final_exponentiation(prod * f) == rhs;
+            return ZKG_OK;
+        };
+        std::function<int(const BatchGroup &, size_t, size_t)> decide = [&](const BatchGroup &G, size_t lo, size_t hi) -> int {
+            size_t n_in = 0;
+            for (size_t p = lo; p < hi; ++p) n_in += in[p];
+            if (!n_in) return ZKG_OK;
+            bool pass = false;
+            ++cnt.combined;
+            if (int rc = combined(G, lo, hi, pass)) return rc;
+            if (pass) { for (size_t p = lo; p < hi; ++p) if (in[p]) verdicts[item_at[p]] = 0; return ZKG_OK; }
+            if (n_in <= VERIFY_LEAF) { for (size_t p = lo; p < hi; ++p) if (in[p]) own[item_at[p]] = 1; return ZKG_OK; }
+            const size_t mid = lo + (hi - lo) / 2;
+            if (int rc = decide(G, lo, mid)) return rc;
+            return decide(G, mid, hi);
+        };
+        for (const BatchGroup &G : groups)
+            if (G.hi > G.lo) if (int rc = decide(G, G.lo, G.hi)) return rc;
+        lap("checks");
+    }
+    // 7. everything the combination did not decide: the single verifier's code, on the host pool
+    for (size_t i = 0; i < count; ++i) if (own[i]) decide_alone.push_back(i);
+    host_parallel_for((int)decide_alone.size(), [&](int t) {
+        int v;
+        try { v = fe.alone(decide_alone[t]); } catch (...) { v = 2; }
+        verdicts[decide_alone[t]] = (uint8_t)v;
+    });
+    lap("alone");
+    cnt.alone += decide_alone.size();
+    return ZKG_OK;
+}
+
+namespace {
+// the host front end: the caller's items, their points decoded on the host pool (step 3), the sums formed inside ic_combination's chunks
+struct ItemFrontEnd : BatchFrontEnd {
+    const zkg_verify_item *items; const G1Affine *hA, *hC; const G2Affine *hB;
+    std::vector<G1Affine> pAC; std::vector<G2Affine> pB;
+    ItemFrontEnd(const zkg_verify_item *it, const G1Affine *a, const G2Affine *b, const G1Affine *c) : items(it), hA(a), hC(c), hB(b) {}
+    int stage_B(const BatchLayout &L, const std::vector<BatchGroup> &, const std::vector<size_t> &item_at, const uint32_t *) override {
+        pAC.resize(2 * L.N); pB.resize(L.N);
+        for (size_t p = 0; p < L.N; ++p) { pAC[p] = hA[item_at[p]]; pB[p] = hB[item_at[p]]; pAC[L.N + p] = hC[item_at[p]]; }
+        ZK_HIP(hipMemcpyAsync(L.d + L.o_B, pB.data(), 128 * L.N, hipMemcpyHostToDevice, L.s));
+        return ZKG_OK;
+    }
+    int stage_AC(const BatchLayout &L, const uint32_t *w) override {
+        ZK_HIP(hipMemcpyAsync(L.d + L.o_A, pAC.data(), 64 * L.N, hipMemcpyHostToDevice, L.s));
+        ZK_HIP(hipMemcpyAsync(L.d + L.o_C, pAC.data() + L.N, 64 * L.N, hipMemcpyHostToDevice, L.s));
+        ZK_HIP(hipMemcpyAsync(L.d + L.o_w, w, 16 * L.N, hipMemcpyHostToDevice, L.s));
+        return ZKG_OK;
+    }
+    void scalar_of(const BatchGroup &G, const std::vector<size_t> &in, const std::vector<size_t> &item_at, const Fr *wm, size_t k, Fr &x) override {
+        Fr sk = Fr::zero();
+        for (size_t p : in) { Fr xi; memcpy(xi.v, items[item_at[p]].primary_input + 4 * G.vk->idx[k], 32); sk += wm[p] * xi; }
+        x = sk;
+    }
+    int alone(size_t i) override {
+        const zkg_verify_item &it = items[i];
+        return groth16_verify_impl(it.vk_blob, it.vk_len, it.primary_input, it.n_inputs, it.proof, it.proof_len);
+    }
+};
+}  // namespace
+
+// zkg_groth16_verify_batch without its thread's counters: what the entry and the seam's host leg share
+static int verify_batch_items(const zkg_verify_item *items, size_t count, uint8_t *verdicts, BatchCounts &cnt) {
+    BatchLaps lap(count);
+    std::vector<char> own(count, 0);                                        // decided by the single verifier's code
+    // 1, 2. group by the key's bytes; per key the prepared form and the checks the weights rely on
+    std::vector<BatchGroup> groups;
+    batch_group_keys(count, [&](size_t i, size_t &len) { len = items[i].vk_len; return items[i].vk_blob; }, groups, own);
     lap("keys");
     // 3. per proof: sizes, encodings and inputs as the single verifier reads them; the proof's points decoded on the host pool
     std::vector<G1Affine> hA(count), hC(count); std::vector<G2Affine> hB(count);
@@ -567,110 +746,18 @@ static int verify_batch_impl(const zkg_verify_item *items, size_t count, uint8_t
         }
     });
     lap("decode");
-    // 4. layout: the entering proofs of each key at contiguous positions, a weight per position
-    std::vector<size_t> item_at;
-    for (BatchGroup &G : groups) {
-        G.lo = item_at.size();
-        for (size_t i : G.items) if (!own[i]) item_at.push_back(i);
-        G.hi = item_at.size();
-    }
-    const size_t N = item_at.size();
-    std::vector<G1Affine> pA(N), pC(N), rC(N); std::vector<G2Affine> pB(N); std::vector<uint32_t> w(4 * N); std::vector<Fr> wm(N);
-    draw_weights(w.data(), N);                                              // fresh on every call; no seed crosses the ABI
-    for (size_t p = 0; p < N; ++p) {
-        Fr x = Fr::zero(); memcpy(x.v, &w[4 * p], 16); wm[p] = x.to_mont();
-        pA[p] = hA[item_at[p]]; pB[p] = hB[item_at[p]]; pC[p] = hC[item_at[p]];
-    }
-    lap("weights");
-    std::vector<uint8_t> in_g2(N, 1);
-    std::vector<size_t> decide_alone;
-    if (N) {
-        // 5. the GPU part: B in G2 (second stream) beside r_i A_i and r_i C_i (one launch), then the Miller values
-        const size_t o_A = 0, o_C = o_A + 64 * N, o_B = o_C + 64 * N, o_rA = o_B + 128 * N, o_rC = o_rA + 64 * N, o_M = o_rC + 64 * N,
-                     o_part = o_M + 384 * N, o_out = o_part + 384 * VERIFY_PROD_BLOCKS, o_w = o_out + 384, o_ok = o_w + 16 * N, total = o_ok + N + 16;
-        WorkspaceLease lease;
-        if (!(lease.w = verify_workspace_acquire()) || lease.w->buf.reserve(total)) return ZKG_ERROR;
-        uint8_t *d = lease.w->buf.as<uint8_t>(); hipStream_t s = lease.w->s, s2 = lease.w->s2;
-        ZK_HIP(hipMemcpyAsync(d + o_B, pB.data(), 128 * N, hipMemcpyHostToDevice, s));
-        ZK_HIP(hipEventRecord(lease.w->ev, s));
-        ZK_HIP(hipStreamWaitEvent(s2, lease.w->ev, 0));
-        if (verify_g2_subgroup((const G2Affine *)(d + o_B), N, d + o_ok, s2)) return ZKG_ERROR;
-        ZK_HIP(hipEventRecord(lease.w->ev2, s2));
-        ZK_HIP(hipMemcpyAsync(d + o_A, pA.data(), 64 * N, hipMemcpyHostToDevice, s));      // A and C back to back: one launch for both
-        ZK_HIP(hipMemcpyAsync(d + o_C, pC.data(), 64 * N, hipMemcpyHostToDevice, s));
-        ZK_HIP(hipMemcpyAsync(d + o_w, w.data(), 16 * N, hipMemcpyHostToDevice, s));
-        if (verify_g1_mul128((const G1Affine *)(d + o_A), (const uint32_t *)(d + o_w), N, 2 * N, (G1Affine *)(d + o_rA), s)) return ZKG_ERROR;
-        ZK_HIP(hipStreamWaitEvent(s, lease.w->ev2, 0));
-        if (verify_miller((const G1Affine *)(d + o_rA), (const G2Affine *)(d + o_B), d + o_ok, N, d + o_M, s)) return ZKG_ERROR;
-        ZK_HIP(hipMemcpyAsync(in_g2.data(), d + o_ok, N, hipMemcpyDeviceToHost, s));
-        ZK_HIP(hipMemcpyAsync(rC.data(), d + o_rC, 64 * N, hipMemcpyDeviceToHost, s));
-        lap("upload_launch");
-        ZK_HIP(hipStreamSynchronize(s));
-        lap("gpu");
-        for (size_t p = 0; p < N; ++p) if (!in_g2[p]) { own[item_at[p]] = 1; ++n_outside_g2; }     // its Miller value is 1: the ranges stay contiguous
-        // 6. one combined check per range; a failed range is halved
-        auto combined = [&](const BatchGroup &G, size_t lo, size_t hi, bool &pass) -> int {
-            Fq12 prod;
-            if (verify_fq12_product(d + o_M, lo, hi, d + o_part, d + o_out, s)) return ZKG_ERROR;
-            ZK_HIP(hipMemcpyAsync(&prod, d + o_out, 384, hipMemcpyDeviceToHost, s));
-            std::vector<size_t> in;                                         // (the host work below runs while the product is computed)
-            for (size_t p = lo; p < hi; ++p) if (in_g2[p]) in.push_back(p);
-            Fr rsum = Fr::zero();
-            for (size_t p : in) rsum += wm[p];
-            const int chunks = (int)std::min<size_t>(16, in.size());
-            std::vector<G1> part(std::max(chunks, 1), G1::inf());
-            host_parallel_for(chunks, [&](int c) {
-                G1 a = G1::inf();
-                for (size_t t = in.size() * c / chunks; t < in.size() * (c + 1) / chunks; ++t) a.madd(rC[in[t]]);
-                part[c] = a;
-            });
-            G1 csum = G1::inf();
-            for (const G1 &q : part) csum.add(q);
-            const PreparedVk &vk = *G.vk;
-            G1 acc = G1::from_affine(vk.ic0);
-            { uint32_t e[8]; fr_limbs(rsum, e); acc = acc.mul(e, 8); }
-            acc.add(ic_combination(vk, [&](size_t k, Fr &x) {              // s_k = sum_i r_i x_ik
-                Fr sk = Fr::zero();
-                for (size_t p : in) { Fr xi; memcpy(xi.v, items[item_at[p]].primary_input + 4 * vk.idx[k], 32); sk += wm[p] * xi; }
-                x = sk;
-            }));
-            std::vector<G1Affine> Ps; std::vector<G2Affine> Qs; std::vector<const std::vector<pairing::LineCoeff> *> prep;
-            auto ml = [&](const G1Affine &P, const G2Affine &Q, const std::vector<pairing::LineCoeff> *lines) { if (!P.is_inf() && !Q.is_inf()) { Ps.push_back(P); Qs.push_back(Q); prep.push_back(lines); } };
-            ml(acc.to_affine().neg(), vk.gamma_g2, &vk.gamma_lines); ml(csum.to_affine().neg(), vk.delta_g2, &vk.delta_lines);
-            Fq12 f = Ps.empty() ? Fq12::one() : pairing::multi_miller_loop(Ps.data(), Qs.data(), (int)Ps.size(), prep.data());
-            uint32_t e[8]; fr_limbs(rsum, e);
-            const Fq12 rhs = vk.alpha_beta.cyclotomic_pow(e, 8);
-            ZK_HIP(hipStreamSynchronize(s));
-            pass = pairing::final_exponentiation(prod * f) == rhs;
-            return ZKG_OK;
-        };
-        std::function<int(const BatchGroup &, size_t, size_t)> decide = [&](const BatchGroup &G, size_t lo, size_t hi) -> int {
-            size_t n_in = 0;
-            for (size_t p = lo; p < hi; ++p) n_in += in_g2[p];
-            if (!n_in) return ZKG_OK;
-            bool pass = false;
-            ++n_combined;
-            if (int rc = combined(G, lo, hi, pass)) return rc;
-            if (pass) { for (size_t p = lo; p < hi; ++p) if (in_g2[p]) verdicts[item_at[p]] = 0; return ZKG_OK; }
-            if (n_in <= VERIFY_LEAF) { for (size_t p = lo; p < hi; ++p) if (in_g2[p]) own[item_at[p]] = 1; return ZKG_OK; }
-            const size_t mid = lo + (hi - lo) / 2;
-            if (int rc = decide(G, lo, mid)) return rc;
-            return decide(G, mid, hi);
-        };
-        for (const BatchGroup &G : groups)
-            if (G.hi > G.lo) if (int rc = decide(G, G.lo, G.hi)) return rc;
-        lap("checks");
-    }
-    // 7. everything the combination did not decide: the single verifier's code, on the host pool
-    for (size_t i = 0; i < count; ++i) if (own[i]) decide_alone.push_back(i);
-    host_parallel_for((int)decide_alone.size(), [&](int t) {
-        const zkg_verify_item &it = items[decide_alone[t]];
-        int v;
-        try { v = groth16_verify_impl(it.vk_blob, it.vk_len, it.primary_input, it.n_inputs, it.proof, it.proof_len); } catch (...) { v = 2; }
-        verdicts[decide_alone[t]] = (uint8_t)v;
-    });
-    lap("alone");
-    t_batch_stats[0] = n_combined; t_batch_stats[1] = decide_alone.size(); t_batch_stats[2] = n_outside_g2;
+    ItemFrontEnd fe(items, hA.data(), hB.data(), hC.data());
+    return verify_batch_core(groups, own, count, fe, verdicts, lap, cnt);
+}
+
+static int verify_batch_impl(const zkg_verify_item *items, size_t count, uint8_t *verdicts) {
+    if (initialised_device() < 0) { set_error("zkg_groth16_verify_batch: zkg_init not called (no GPU: there is no CPU path)"); return ZKG_ERROR; }
+    if (count && (!items || !verdicts)) { set_error("zkg_groth16_verify_batch: null argument"); return ZKG_ERROR; }
+    t_batch_stats[0] = t_batch_stats[1] = t_batch_stats[2] = 0;
+    if (!count) return ZKG_OK;
+    BatchCounts cnt;
+    if (int rc = verify_batch_items(items, count, verdicts, cnt)) return rc;
+    t_batch_stats[0] = cnt.combined; t_batch_stats[1] = cnt.alone; t_batch_stats[2] = cnt.outside_g2;
     return ZKG_OK;
 }
 
@@ -680,6 +767,254 @@ int zkg_groth16_verify_batch(const zkg_verify_item *items, size_t count, uint8_t
     try { return verify_batch_impl(items, count, verdicts); }
     catch (const std::exception &e) { set_error(std::string("zkg_groth16_verify_batch: ") + e.what()); return ZKG_ERROR; }
     catch (...) { set_error("zkg_groth16_verify_batch: unexpected exception"); return ZKG_ERROR; }
+}
+
+// ---- zkg_zklaim_verify_batch: many libsnark_verify calls in one.  The contexts of one key are one group of the batch above; by default its
+// front end is the device's (ZKG_SEAM_GPU_VERIFY=0: the host's, zkg_zklaim_input_map per item and then zkg_groth16_verify_batch's path; a
+// call that holds keys of both kinds runs the batch core once per front end).
+// One upload per call, directly behind the core's weights:
+//     [ weights 16 B x N | proof records 134 B x N | per group, per position: its payloads' public records, 80 B each (zklaim_public.hip.hpp) ]
+// k_proof_decode turns the records into the points (B on the first stream in front of the event that releases the G2 test, A and C in one
+// launch in front of k_g1_mul128), k_zklaim_input_sums forms the s_k of a range from the public records beside the range's Fq12 product.
+// Neither the proofs' square roots nor a single public input exist on the host.
+namespace {
+static constexpr size_t SEAM_VERIFY_STAGE_MAX = (size_t)64 << 20;           // device staging of one call's device groups; beyond: the host front end
+
+// payloads of a context as zkg_zklaim_input_map walks them, counted up to cap + 1
+uint32_t payloads_walked(const zklaim_ctx *ctx, uint32_t cap) {
+    uint32_t n = 0;
+    for (const zklaim_wrap_payload_ctx *cur = ctx->pl_ctx_head; cur && n <= cap; cur = cur->next) ++n;
+    return n;
+}
+void pack_public_records(const zklaim_ctx *ctx, uint32_t npl, uint8_t *out) {     // npl records (the list is at least that long)
+    const zklaim_wrap_payload_ctx *cur = ctx->pl_ctx_head;
+    for (uint32_t j = 0; j < npl; ++j, cur = cur->next, out += ZV_REC) {
+        memcpy(out, cur->pl.hash, 32); memcpy(out + 32, cur->pl.data_ref, 40); memset(out + 72, 0, 8);
+        for (int a = 0; a < 5; ++a) {
+            uint8_t code = 0;
+            switch ((int)cur->pl.data_op[a]) {                              // set_ops: which byte of the slot is set
+            case zklaim_less: code = 1; break;          case zklaim_less_or_eq: code = 2; break;
+            case zklaim_eq: code = 3; break;            case zklaim_greater_or_eq: code = 4; break;
+            case zklaim_greater: code = 5; break;       case zklaim_not_eq: code = 6; break;
+            case zklaim_noop: code = 7; break;          default: break;
+            }
+            out[72 + a] = code;
+        }
+    }
+}
+int verify_ctx_alone(const zklaim_ctx *c) {                                 // libsnark_verify's body
+    const size_t n = zkg_zklaim_input_map(c, nullptr, 0);
+    std::vector<uint64_t> input(4 * n + 4);
+    zkg_zklaim_input_map(c, input.data(), n);
+    return groth16_verify_impl(c->vk, c->vk_size, input.data(), n, c->proof, c->proof_size);
+}
+
+struct CtxFrontEnd : BatchFrontEnd {
+    const zklaim_ctx *const *ctxs;
+    std::vector<uint8_t> host;                                              // the upload
+    size_t pub_bytes = 0, max_elems = 0;
+    std::vector<Fr> sums;
+    BatchLaps *lap = nullptr;
+    explicit CtxFrontEnd(const zklaim_ctx *const *c) : ctxs(c) {}
+    bool on_device() const override { return true; }
+    size_t stage_bytes(size_t N) const override { return ((ZKG_PROOF_BYTES * N + 15) & ~(size_t)15) + pub_bytes; }
+    size_t sum_elems() const override { return max_elems; }
+    static size_t pub_at(size_t N) { return 16 * N + ((ZKG_PROOF_BYTES * N + 15) & ~(size_t)15); }
+    int stage_B(const BatchLayout &L, const std::vector<BatchGroup> &groups, const std::vector<size_t> &item_at, const uint32_t *w) override {
+        const size_t N = L.N;
+        host.resize(16 * N + stage_bytes(N));
+        memcpy(host.data(), w, 16 * N);
+        std::vector<const BatchGroup *> group_at(N);
+        for (const BatchGroup &G : groups) for (size_t p = G.lo; p < G.hi; ++p) group_at[p] = &G;
+        const int chunks = (int)std::min<size_t>(64, N);
+        host_parallel_for(chunks, [&](int c) {
+            for (size_t p = N * (size_t)c / chunks; p < N * (size_t)(c + 1) / chunks; ++p) {
+                const zklaim_ctx *ctx = ctxs[item_at[p]];
+                const BatchGroup &G = *group_at[p];
+                memcpy(host.data() + 16 * N + ZKG_PROOF_BYTES * p, ctx->proof, ZKG_PROOF_BYTES);
+                pack_public_records(ctx, G.npl, host.data() + pub_at(N) + G.pub_at + (p - G.lo) * G.npl * ZV_REC);
+            }
+        });
+        if (lap) (*lap)("decode");                                          // (the host's share of it: the records packed)
+        ZK_HIP(hipMemcpyAsync(L.d + L.o_w, host.data(), host.size(), hipMemcpyHostToDevice, L.s));
+        return verify_proof_decode_b(L.d + L.o_fe, N, (G2Affine *)(L.d + L.o_B), L.d + L.o_flags + N, L.s);
+    }
+    int stage_AC(const BatchLayout &L, const uint32_t *) override {
+        return verify_proof_decode_ac(L.d + L.o_fe, L.N, (G1Affine *)(L.d + L.o_A), L.d + L.o_flags + 2 * L.N, L.s);
+    }
+    int sums_begin(const BatchLayout &L, const BatchGroup &G, size_t lo, size_t hi) override {
+        const size_t l = zv_input_count(G.npl);
+        sums.resize(l);
+        uint8_t *d_out = L.d + L.o_sums, *d_part = d_out + 32 * max_elems;
+        if (verify_zklaim_input_sums(L.d + L.o_w + pub_at(L.N) + G.pub_at, G.npl, G.lo, (const uint32_t *)(L.d + L.o_w), L.d + L.o_flags + 4 * L.N,
+                                     lo, hi, d_part, d_out, L.s2)) return ZKG_ERROR;
+        ZK_HIP(hipMemcpyAsync(sums.data(), d_out, 32 * l, hipMemcpyDeviceToHost, L.s2));
+        return ZKG_OK;
+    }
+    int sums_ready(const BatchLayout &L) override { ZK_HIP(hipStreamSynchronize(L.s2)); return ZKG_OK; }
+    void scalar_of(const BatchGroup &G, const std::vector<size_t> &, const std::vector<size_t> &, const Fr *, size_t k, Fr &x) override { x = sums[G.vk->idx[k]]; }
+    int alone(size_t i) override { return verify_ctx_alone(ctxs[i]); }
+};
+}  // namespace
+
+// which front end a key's group takes when ZKG_SEAM_GPU_VERIFY is not set: the device's wherever tools/seam_verify_batch_time.py found it
+// no slower than hand-built items — every measured shape from 512 payload records (entering items x payloads) on; 64 one-payload items,
+// the one shape below, lose 0.7 ms to the decode chains in front of the G2 test ("Seam entry and device front end")
+static constexpr size_t SEAM_VERIFY_DEVICE_MIN_RECORDS = 512;
+static bool seam_verify_device_default(uint32_t npl, size_t n_in) { return n_in * npl >= SEAM_VERIFY_DEVICE_MIN_RECORDS; }
+
+// front_end: 0 the host's for every key, 1 the device's, anything else the default per group
+static int seam_verify_batch_impl(const zklaim_ctx *const *ctxs, size_t count, int *rc, int front_end) {
+    if (initialised_device() < 0) { set_error("zkg_zklaim_verify_batch: zkg_init not called (no GPU: there is no CPU path)"); return ZKG_ERROR; }
+    BatchCounts cnt;
+    std::vector<uint8_t> verdicts(count, 1);
+    std::vector<char> own(count, 0), host_leg(count, 0);
+    for (size_t i = 0; i < count; ++i) if (!ctxs[i] || !ctxs[i]->vk || !ctxs[i]->vk_size || !ctxs[i]->proof) own[i] = 2;       // rc 1, nothing to verify
+    if (front_end == 0) { for (size_t i = 0; i < count; ++i) if (!own[i]) host_leg[i] = 1; }
+    else {
+        BatchLaps lap(count);
+        std::vector<BatchGroup> groups;
+        batch_group_keys(count, [&](size_t i, size_t &len) { len = ctxs[i]->vk_size; return (const uint8_t *)ctxs[i]->vk; }, groups, own);
+        lap("keys");
+        // a key's input count names its payload count (1280 bits per payload, 253 per input: the counts grow strictly); an item enters if
+        // its proof has the size and its payload list, walked as zkg_zklaim_input_map walks it, has that many payloads
+        CtxFrontEnd fe(ctxs);
+        fe.lap = &lap;
+        size_t entering = 0;
+        for (BatchGroup &G : groups) {
+            if (!G.batchable) continue;
+            const size_t domain = G.vk->domain;
+            const uint32_t npl = (uint32_t)std::min<size_t>(domain * ZV_FR_CAPACITY / (ZV_STRING_BYTES * 8), (size_t)1 << 20);
+            G.npl = npl && zv_input_count(npl) == domain ? npl : 0;
+            size_t n_in = 0;
+            for (size_t i : G.items) if (G.npl && ctxs[i]->proof_size == ZKG_PROOF_BYTES && payloads_walked(ctxs[i], G.npl) == G.npl) ++n_in;
+            const size_t grown = entering + n_in, staged = 16 * grown + ((ZKG_PROOF_BYTES * grown + 15) & ~(size_t)15) + fe.pub_bytes + n_in * G.npl * ZV_REC;
+            if ((front_end != 1 && !seam_verify_device_default(G.npl, n_in)) || staged > SEAM_VERIFY_STAGE_MAX) {      // this key takes the host front end
+                for (size_t i : G.items) host_leg[i] = 1;
+                G.items.clear();
+                continue;
+            }
+            for (size_t i : G.items) if (!(G.npl && ctxs[i]->proof_size == ZKG_PROOF_BYTES && payloads_walked(ctxs[i], G.npl) == G.npl)) own[i] = 1;
+            G.pub_at = fe.pub_bytes;
+            fe.pub_bytes += n_in * G.npl * ZV_REC;
+            if (n_in) fe.max_elems = std::max(fe.max_elems, domain);
+            entering += n_in;
+        }
+        for (size_t i = 0; i < count; ++i) if (own[i] == 2 || host_leg[i]) own[i] = 0;       // decided already, or the other leg's: not this core's
+        if (int r = verify_batch_core(groups, own, count, fe, verdicts.data(), lap, cnt)) return r;
+    }
+    // the host front end: the input map of every context on the host pool, then zkg_groth16_verify_batch's own path
+    std::vector<size_t> live;
+    for (size_t i = 0; i < count; ++i) if (host_leg[i]) live.push_back(i);
+    if (!live.empty()) {
+        std::vector<std::vector<uint64_t>> inputs(live.size());
+        std::vector<zkg_verify_item> items(live.size());
+        const int chunks = (int)std::min<size_t>(64, live.size());
+        host_parallel_for(chunks, [&](int c) {
+            for (size_t t = live.size() * (size_t)c / chunks; t < live.size() * (size_t)(c + 1) / chunks; ++t) {
+                const zklaim_ctx *x = ctxs[live[t]];
+                const size_t n = zkg_zklaim_input_map(x, nullptr, 0);
+                inputs[t].resize(4 * n + 4);
+                zkg_zklaim_input_map(x, inputs[t].data(), n);
+                items[t] = zkg_verify_item{x->vk, x->vk_size, inputs[t].data(), n, x->proof, x->proof_size};
+            }
+        });
+        std::vector<uint8_t> v(live.size(), 1);
+        BatchCounts host_cnt;
+        if (int r = verify_batch_items(items.data(), live.size(), v.data(), host_cnt)) return r;
+        for (size_t t = 0; t < live.size(); ++t) verdicts[live[t]] = v[t];
+        cnt.combined += host_cnt.combined; cnt.alone += host_cnt.alone; cnt.outside_g2 += host_cnt.outside_g2;
+    }
+    for (size_t i = 0; i < count; ++i) rc[i] = verdicts[i] == 0 ? 0 : 1;
+    t_seam_batch_stats[0] = cnt.combined; t_seam_batch_stats[1] = cnt.alone; t_seam_batch_stats[2] = cnt.outside_g2; t_seam_batch_stats[3] = cnt.from_device;
+    return ZKG_OK;
+}
+}  // extern "C"
+// compat.hip's entry: arguments checked, the seam's device bound; rc[i] is written for every i
+int seam_verify_batch(const zklaim_ctx *const *ctxs, size_t count, int *rc, int front_end) {
+    for (size_t i = 0; i < 4; ++i) t_seam_batch_stats[i] = 0;
+    return seam_verify_batch_impl(ctxs, count, rc, front_end);
+}
+void seam_verify_batch_stats_clear() { for (size_t i = 0; i < 4; ++i) t_seam_batch_stats[i] = 0; }
+extern "C" {
+
+void zkg_zklaim_verify_batch_stats(size_t out[4]) { if (out) for (int i = 0; i < 4; ++i) out[i] = t_seam_batch_stats[i]; }
+
+// ---- test hooks of the device front end
+static int proof_decode_gpu_impl(const uint8_t *proofs, size_t count, uint64_t *A, uint64_t *B, uint64_t *C, uint8_t *ok) {
+    if (initialised_device() < 0) { set_error("zkg_proof_decode_gpu: zkg_init not called (no GPU: there is no CPU path)"); return ZKG_ERROR; }
+    if (count && (!proofs || !A || !B || !C || !ok)) { set_error("zkg_proof_decode_gpu: null argument"); return ZKG_ERROR; }
+    if (!count) return ZKG_OK;
+    if (count > ((size_t)1 << 24)) { set_error("zkg_proof_decode_gpu: at most 2^24 proofs"); return ZKG_ERROR; }
+    const size_t N = count, o_A = 0, o_C = 64 * N, o_B = 128 * N, o_dec = 256 * N, o_rec = (o_dec + 3 * N + 15) & ~(size_t)15, total = o_rec + ZKG_PROOF_BYTES * N + 16;
+    WorkspaceLease lease;
+    if (!(lease.w = verify_workspace_acquire()) || lease.w->buf.reserve(total)) return ZKG_ERROR;
+    uint8_t *d = lease.w->buf.as<uint8_t>(); hipStream_t s = lease.w->s;
+    std::vector<uint8_t> dec(3 * N);
+    ZK_HIP(hipMemcpyAsync(d + o_rec, proofs, ZKG_PROOF_BYTES * N, hipMemcpyHostToDevice, s));
+    if (verify_proof_decode_b(d + o_rec, N, (G2Affine *)(d + o_B), d + o_dec, s) ||
+        verify_proof_decode_ac(d + o_rec, N, (G1Affine *)(d + o_A), d + o_dec + N, s)) return ZKG_ERROR;
+    ZK_HIP(hipMemcpyAsync(A, d + o_A, 64 * N, hipMemcpyDeviceToHost, s));
+    ZK_HIP(hipMemcpyAsync(C, d + o_C, 64 * N, hipMemcpyDeviceToHost, s));
+    ZK_HIP(hipMemcpyAsync(B, d + o_B, 128 * N, hipMemcpyDeviceToHost, s));
+    ZK_HIP(hipMemcpyAsync(dec.data(), d + o_dec, 3 * N, hipMemcpyDeviceToHost, s));
+    ZK_HIP(hipStreamSynchronize(s));
+    for (size_t i = 0; i < N; ++i) ok[i] = (uint8_t)((dec[N + i] ? 1 : 0) | (dec[i] ? 2 : 0) | (dec[2 * N + i] ? 4 : 0));
+    return ZKG_OK;
+}
+int zkg_proof_decode_gpu(const uint8_t *proofs, size_t count, uint64_t *A, uint64_t *B, uint64_t *C, uint8_t *ok) {
+    try { return proof_decode_gpu_impl(proofs, count, A, B, C, ok); }
+    catch (const std::exception &e) { set_error(std::string("zkg_proof_decode_gpu: ") + e.what()); return ZKG_ERROR; }
+    catch (...) { set_error("zkg_proof_decode_gpu: unexpected exception"); return ZKG_ERROR; }
+}
+
+static int input_sums_gpu_impl(const zklaim_ctx *const *ctxs, size_t count, const uint32_t *weights, const uint8_t *mask, size_t lo, size_t hi,
+                               uint64_t *sums_out, size_t cap_elems, size_t *n_elems) {
+    if (initialised_device() < 0) { set_error("zkg_zklaim_input_sums_gpu: zkg_init not called (no GPU: there is no CPU path)"); return ZKG_ERROR; }
+    if (!ctxs || !count || !weights || !n_elems || lo > hi || hi > count) { set_error("zkg_zklaim_input_sums_gpu: bad argument"); return ZKG_ERROR; }
+    if (!ctxs[0]) { set_error("zkg_zklaim_input_sums_gpu: null context"); return ZKG_ERROR; }
+    const uint32_t npl = payloads_walked(ctxs[0], 4096);
+    if (!npl || npl > 4096 || count > ((size_t)1 << 24)) { set_error("zkg_zklaim_input_sums_gpu: payload or context count out of range"); return ZKG_ERROR; }
+    for (size_t i = 0; i < count; ++i)
+        if (!ctxs[i] || payloads_walked(ctxs[i], npl) != npl) { set_error("zkg_zklaim_input_sums_gpu: a null context or another payload count"); return ZKG_ERROR; }
+    const size_t l = zv_input_count(npl);
+    *n_elems = l;
+    if (!sums_out || cap_elems < l) { set_error("zkg_zklaim_input_sums_gpu: sums_out too small"); return ZKG_ERROR; }
+    const size_t N = count, pub = N * npl * ZV_REC, o_w = 0, o_mask = 16 * N, o_pub = (o_mask + N + 15) & ~(size_t)15, o_out = (o_pub + pub + 31) & ~(size_t)31,
+                 o_part = o_out + 32 * l, total = o_part + 32 * l * ZV_SUM_SLICES + 16;
+    std::vector<uint8_t> host(o_pub + pub);
+    memcpy(host.data() + o_w, weights, 16 * N);
+    if (mask) memcpy(host.data() + o_mask, mask, N);
+    for (size_t i = 0; i < N; ++i) pack_public_records(ctxs[i], npl, host.data() + o_pub + i * npl * ZV_REC);
+    WorkspaceLease lease;
+    if (!(lease.w = verify_workspace_acquire()) || lease.w->buf.reserve(total)) return ZKG_ERROR;
+    uint8_t *d = lease.w->buf.as<uint8_t>(); hipStream_t s = lease.w->s;
+    ZK_HIP(hipMemcpyAsync(d, host.data(), host.size(), hipMemcpyHostToDevice, s));
+    if (verify_zklaim_input_sums(d + o_pub, npl, 0, (const uint32_t *)(d + o_w), mask ? d + o_mask : nullptr, lo, hi, d + o_part, d + o_out, s)) return ZKG_ERROR;
+    ZK_HIP(hipMemcpyAsync(sums_out, d + o_out, 32 * l, hipMemcpyDeviceToHost, s));
+    ZK_HIP(hipStreamSynchronize(s));
+    return ZKG_OK;
+}
+int zkg_zklaim_input_sums_gpu(const zklaim_ctx *const *ctxs, size_t count, const uint32_t *weights, const uint8_t *mask, size_t lo, size_t hi,
+                              uint64_t *sums_out, size_t cap_elems, size_t *n_elems) {
+    try { return input_sums_gpu_impl(ctxs, count, weights, mask, lo, hi, sums_out, cap_elems, n_elems); }
+    catch (const std::exception &e) { set_error(std::string("zkg_zklaim_input_sums_gpu: ") + e.what()); return ZKG_ERROR; }
+    catch (...) { set_error("zkg_zklaim_input_sums_gpu: unexpected exception"); return ZKG_ERROR; }
+}
+
+// the kernel's bit rule (zv_input_element) on the host: same outputs as zkg_zklaim_input_map
+size_t zkg_zklaim_input_map_mirror(const zklaim_ctx *ctx, uint64_t *out, size_t cap_elems) {
+    if (!ctx) return 0;
+    try {
+        uint32_t npl = 0;
+        for (const zklaim_wrap_payload_ctx *cur = ctx->pl_ctx_head; cur; cur = cur->next) ++npl;
+        const size_t n = zv_input_count(npl);
+        if (!out || cap_elems < n) return n;
+        std::vector<uint8_t> rec((size_t)npl * ZV_REC + 1);
+        pack_public_records(ctx, npl, rec.data());
+        for (size_t k = 0; k < n; ++k) { Fr x; zv_input_element(rec.data(), npl, (uint32_t)k, x.v); x = x.to_mont(); memcpy(out + 4 * k, x.v, 32); }
+        return n;
+    } catch (...) { return 0; }
 }
 
 static int pairing_product_impl(const uint64_t *g1_affine, const uint64_t *g2_affine, size_t n, uint8_t out[384]) {

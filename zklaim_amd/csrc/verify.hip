@@ -7,8 +7,15 @@
 //   k_miller        ML(P_i, Q_i) (pairing.hip.hpp), 1 for a pair with a point at infinity or flagged out
 //   k_fq12_prod     the product of the Miller values of an index range [lo, hi): per block a strided product and an LDS tree; a second
 //                   launch of one block folds the block results
+// and the device front end of the seam's batch entry (zkg_zklaim_verify_batch), which leaves the host neither square roots nor input sums:
+//   k_proof_decode        a compressed point of a 134-byte proof record per lane -> the affine Montgomery point ser::get_g1 / ser::get_g2
+//                         produce and a flag byte per item (the single verifier's acceptance rule and coords_canonical, bit for bit)
+//   k_zklaim_input_sums   s_k = sum over the entering positions of a range of weight_p * x_pk, the public inputs x_pk assembled from the
+//                         payloads' public bytes (zklaim_public.hip.hpp); a block per (element, slice), k_fr_fold adds the slices
 #include "common.hpp"
 #include "pairing.hip.hpp"
+#include "sqrt.hip.hpp"
+#include "zklaim_public.hip.hpp"
 #include "host/pairing.hpp"
 #include "../../include/zkg.h"
 
@@ -72,6 +79,100 @@ __global__ __launch_bounds__(VB) void k_fq12_prod(const dev::Fq12 *in, size_t lo
     if (threadIdx.x == 0) out[blockIdx.x] = sh[0].normalized();
 }
 
+// ---- the device front end
+ZK_D bool limbs_below_q(const Fq &x) {                  // coords_canonical: the stored limbs are a canonical value
+    for (int i = 7; i >= 0; --i) if (x.v[i] != FqParams::P[i]) return x.v[i] < FqParams::P[i];
+    return false;
+}
+ZK_D bool decode_g1(const uint8_t *p, G1Affine &out) {   // ser::get_g1 && coords_canonical
+    out = G1Affine::inf();
+    if (p[0] == '1') return true;                       // infinity: nothing else is read
+    if (p[0] != '0' || (p[33] != '0' && p[33] != '1')) return false;
+    const Fq x = load_fq_bytes(p + 1);
+    if (!limbs_below_q(x)) return false;
+    const Fq rhs = x.sqr() * x + Fq::from_u64(3);
+    Fq y = fq_sqrt_candidate(rhs);
+    if (y.sqr() != rhs) return false;
+    if (((y.from_mont().v[0] & 1u) != 0) != (p[33] == '1')) y = y.neg();
+    out = G1Affine{x, y}.normalized();
+    return true;
+}
+ZK_D bool decode_g2(const uint8_t *p, G2Affine &out) {   // ser::get_g2 && coords_canonical
+    out = G2Affine::inf();
+    if (p[0] == '1') return true;
+    if (p[0] != '0' || (p[65] != '0' && p[65] != '1')) return false;
+    const Fq2 x = {load_fq_bytes(p + 1), load_fq_bytes(p + 33)};
+    if (!limbs_below_q(x.c0) || !limbs_below_q(x.c1)) return false;
+    Fq2 b;                                              // the twist's coefficient 3 / (9 + u), Montgomery limbs
+    { const uint32_t b0[8] = {0x77b802a8u, 0x3bf938e3u, 0x3633535du, 0x020b1b27u, 0x49755260u, 0x26b7edf0u, 0x4384a86du, 0x2514c632u};
+      const uint32_t b1[8] = {0xd1dcff67u, 0x38e7ecccu, 0x93ce0d3eu, 0x65f0b37du, 0x22ac00aau, 0xd749d0ddu, 0x4a688d4du, 0x0141b9ceu};
+      for (int k = 0; k < 8; ++k) { b.c0.v[k] = b0[k]; b.c1.v[k] = b1[k]; } }
+    const Fq2 rhs = x.sqr() * x + b;
+    Fq2 y;
+    if (!fq2_sqrt(rhs, y)) return false;
+    if (((y.c0.from_mont().v[0] & 1u) != 0) != (p[65] == '1')) y = y.neg();
+    out = G2Affine{x, y}.normalized();
+    return true;
+}
+// records of ZKG_PROOF_BYTES: A at 0, B at 34, C at 100.  g2 != 0: lane i decodes B of record i into out2[i].  g2 == 0: 2 n lanes, lane i < n
+// decodes A of record i, lane n + i its C, into out1[lane] (A and C back to back, as k_g1_mul128 reads them).  dec[lane] = 1 iff the point
+// decoded; a point that did not is stored as infinity (all-zero).
+__global__ __launch_bounds__(VB) void k_proof_decode(const uint8_t *rec, size_t n, int g2, G1Affine *out1, G2Affine *out2, uint8_t *dec) {
+    const size_t i = (size_t)blockIdx.x * VB + threadIdx.x;
+    if (g2) {
+        if (i >= n) return;
+        G2Affine q;
+        dec[i] = decode_g2(rec + i * ZKG_PROOF_BYTES + 34, q) ? 1 : 0;
+        out2[i] = q;
+    } else {
+        if (i >= 2 * n) return;
+        G1Affine p;
+        dec[i] = decode_g1(i < n ? rec + i * ZKG_PROOF_BYTES : rec + (i - n) * ZKG_PROOF_BYTES + 100, p) ? 1 : 0;
+        out1[i] = p;
+    }
+}
+// use[i] = the item enters the combination: B in G2 and A, B, C decoded (dec_ac: n flags of A, then n of C)
+__global__ __launch_bounds__(VB) void k_use_mask(size_t n, const uint8_t *in_g2, const uint8_t *dec_b, const uint8_t *dec_ac, uint8_t *use) {
+    const size_t i = (size_t)blockIdx.x * VB + threadIdx.x;
+    if (i < n) use[i] = in_g2[i] && dec_b[i] && dec_ac[i] && dec_ac[n + i] ? 1 : 0;
+}
+
+// block (k, slice): the slice's share of positions [lo, hi); position p reads its npl records at pub + (p - base) * npl * ZV_REC, its
+// 128-bit weight at w + 4 p and mask[p] (optional).  The product of the two raw values is r x / R; R^2 twice on the block's sum makes it
+// the Montgomery form of sum r x.  out[slice * l + k].
+__global__ __launch_bounds__(VB) void k_zklaim_input_sums(const uint8_t *pub, uint32_t npl, size_t base, const uint32_t *w, const uint8_t *mask,
+                                                          size_t lo, size_t hi, uint32_t l, Fr *out) {
+    __shared__ Fr sh[VB];
+    const uint32_t k = blockIdx.x;
+    const size_t n = hi - lo, b0 = lo + n * blockIdx.y / gridDim.y, b1 = lo + n * (blockIdx.y + 1) / gridDim.y;
+    Fr acc = Fr::zero();
+#pragma unroll 1
+    for (size_t p = b0 + threadIdx.x; p < b1; p += VB) {
+        if (mask && !mask[p]) continue;
+        Fr x, r = Fr::zero();
+        zv_input_element(pub + (p - base) * npl * ZV_REC, npl, k, x.v);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) r.v[j] = w[4 * p + j];
+        acc += r * x;
+    }
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+#pragma unroll 1
+    for (int s = VB / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[(size_t)blockIdx.y * l + k] = (sh[0] * Fr::r2() * Fr::r2()).normalized();
+}
+__global__ __launch_bounds__(VB) void k_fr_fold(const Fr *part, uint32_t l, uint32_t slices, Fr *out) {
+    const uint32_t k = blockIdx.x * VB + threadIdx.x;
+    if (k >= l) return;
+    Fr acc = part[k];
+#pragma unroll 1
+    for (uint32_t s = 1; s < slices; ++s) acc += part[(size_t)s * l + k];
+    out[k] = acc.normalized();
+}
+
 unsigned blocks_for(size_t n) { return (unsigned)((n + VB - 1) / VB); }
 
 }  // namespace
@@ -115,6 +216,39 @@ int verify_fq12_product(const void *d_in, size_t lo, size_t hi, void *d_partial,
         hipLaunchKernelGGL(k_fq12_prod, dim3(1), dim3(VB), 0, s, (const dev::Fq12 *)d_partial, (size_t)0, (size_t)g, (dev::Fq12 *)d_out);
     }
     ZK_HIP(hipGetLastError());
+    return ZKG_OK;
+}
+
+int verify_proof_decode_b(const uint8_t *d_rec, size_t n, G2Affine *d_B, uint8_t *d_dec, hipStream_t s) {
+    if (!n) return ZKG_OK;
+    hipLaunchKernelGGL(k_proof_decode, dim3(blocks_for(n)), dim3(VB), 0, s, d_rec, n, 1, (G1Affine *)nullptr, d_B, d_dec);
+    ZK_HIP(hipGetLastError());
+    return ZKG_OK;
+}
+int verify_proof_decode_ac(const uint8_t *d_rec, size_t n, G1Affine *d_AC, uint8_t *d_dec, hipStream_t s) {
+    if (!n) return ZKG_OK;
+    hipLaunchKernelGGL(k_proof_decode, dim3(blocks_for(2 * n)), dim3(VB), 0, s, d_rec, n, 0, d_AC, (G2Affine *)nullptr, d_dec);
+    ZK_HIP(hipGetLastError());
+    return ZKG_OK;
+}
+int verify_use_mask(size_t n, const uint8_t *d_in_g2, const uint8_t *d_dec_b, const uint8_t *d_dec_ac, uint8_t *d_use, hipStream_t s) {
+    if (!n) return ZKG_OK;
+    hipLaunchKernelGGL(k_use_mask, dim3(blocks_for(n)), dim3(VB), 0, s, n, d_in_g2, d_dec_b, d_dec_ac, d_use);
+    ZK_HIP(hipGetLastError());
+    return ZKG_OK;
+}
+unsigned zklaim_input_sums_slices(size_t n) { return (unsigned)std::min<size_t>(ZV_SUM_SLICES, std::max<size_t>(1, (n + 2 * VB - 1) / (2 * VB))); }
+// d_part: ZV_SUM_SLICES x l Fr; the l sums land in d_out (lo == hi: zeros)
+int verify_zklaim_input_sums(const uint8_t *d_pub, uint32_t npl, size_t base, const uint32_t *d_w, const uint8_t *d_mask, size_t lo, size_t hi,
+                             void *d_part, void *d_out, hipStream_t s) {
+    const uint32_t l = zv_input_count(npl);
+    const unsigned g = zklaim_input_sums_slices(hi - lo);
+    hipLaunchKernelGGL(k_zklaim_input_sums, dim3(l, g), dim3(VB), 0, s, d_pub, npl, base, d_w, d_mask, lo, hi, l, (Fr *)(g == 1 ? d_out : d_part));
+    ZK_HIP(hipGetLastError());
+    if (g > 1) {
+        hipLaunchKernelGGL(k_fr_fold, dim3(blocks_for(l)), dim3(VB), 0, s, (const Fr *)d_part, l, g, (Fr *)d_out);
+        ZK_HIP(hipGetLastError());
+    }
     return ZKG_OK;
 }
 
