@@ -253,6 +253,34 @@ int zkg_groth16_prove_batch(const zkg_crs *crs, const zkg_prove_item *items, siz
  * that went through the single-proof path, out[2] batched chunks launched.  Counters, not clocks. */
 void zkg_prove_batch_stats(size_t out[3]);
 size_t zkg_prove_batch_chunk(const zkg_crs *crs);   /* proofs per batched chunk for this key; 0 = this key takes the single-proof path */
+/* ---- proofs from witnesses that are ALREADY in device memory (a torch computation's output, the caller's own witness kernel): the *_dev form of
+ *      zkg_groth16_prove and zkg_groth16_prove_batch.  d_witness: n x 4 limbs Montgomery Fr in DEVICE memory, the layout zkg_groth16_prove takes
+ *      on the host, aligned to 16 bytes; item i of d_witnesses starts `stride` Fr elements (32 bytes each) after item i - 1, stride >= n, and what
+ *      lies between n and the stride is never read.  rs, proofs_out and status are HOST pointers: (r, s) per item as 8 limbs r | s.  Status
+ *      and proof bytes are exactly those of zkg_groth16_prove on a host copy of the same vector with the same (r, s), ZKG_UNSATISFIED
+ *      included; for the batch the per-item rules of zkg_groth16_prove_batch hold (a failed item fails alone, nothing is written for it;
+ *      count == 0 is ZKG_OK and touches nothing).  One kernel (k_split_dev, the proof as its second grid dimension) reads the caller's
+ *      buffer in place and writes [1 | w], the tags, the non-bit listing and its counts where the mat-vec and the witness jobs read them: no
+ *      staging buffer, no scan on the host, no host-to-device copy of witness data.
+ *      Ordering (zkg_msm_g1_resident's contract): the work runs on the library's own streams, behind everything queued on `stream` (NULL: the
+ *      null stream) at the time of the call — the work that wrote the witness — and the call returns when the proofs are in host memory,
+ *      so the caller may overwrite the buffer as soon as it returns.
+ *      Refused with ZKG_ERROR before any launch, nothing written: a null argument; stride < n; a calling thread whose current device is not
+ *      the key's; a pointer that hipPointerGetAttributes does not report as device memory of the key's device (pinned, managed and
+ *      unregistered host memory are all refused); a range that runs past the end of its allocation where hipMemGetAddressRange knows it
+ *      (best effort: a sub-range of a caching allocator's block is checked against that block).
+ *      zkg_groth16_prove_dev serves every key the single-proof path serves (radix-2 and step domains, m >= 2^18, H shards);
+ *      zkg_groth16_prove_batch_dev cuts the items into zkg_prove_batch_chunk chunks and sets zkg_prove_batch_stats exactly as
+ *      zkg_groth16_prove_batch does, and goes item by item through the single _dev path for a key whose chunk is 0.  Safe from several
+ *      threads and beside every other prove entry on the same key. */
+int zkg_groth16_prove_dev(const zkg_crs *crs, const void *d_witness, const uint64_t r[4], const uint64_t s[4], int check_satisfied,
+                          uint8_t *proof_out, size_t *proof_len, void *stream);
+int zkg_groth16_prove_batch_dev(const zkg_crs *crs, const void *d_witnesses, size_t stride /* Fr elements between items, >= n */, size_t count,
+                                const uint64_t *rs /* count x 8 limbs: r | s, host */, int check_satisfied,
+                                uint8_t *proofs_out /* count x ZKG_PROOF_BYTES, host */, int *status /* count entries, host */, void *stream);
+/* the calling thread's last zkg_groth16_prove_dev / zkg_groth16_prove_batch_dev: out[0] witnesses split on the device from the caller's buffer,
+ * out[1] witnesses staged through host memory (0 on every path).  Counters, not clocks. */
+void zkg_prove_dev_stats(size_t out[2]);
 /* ---- many zklaim credentials of ONE resident key, their witnesses generated on the GPU.  ctxs[i] is a zklaim_ctx (include/zklaim_abi.h) whose
  *      payload count is the key's; rs holds (r, s) per item, 8 limbs: r | s, Montgomery Fr.  status[i] and the proof bytes are exactly those of
  *      zkg_groth16_prove_sparse on the host witness of ctxs[i] (zkg_zklaim_witness_new + zkg_circuit_sparse_witness) with the same (r, s).

@@ -29,6 +29,7 @@ DECLARED_SYMBOLS = [
     "zkg_groth16_prove_zklaim", "zkg_prove_zklaim_stats", "zkg_zklaim_witness_gpu_parallel", "zkg_zklaim_witness_mirror_parallel",
     "zkg_fr29_op",
     "zkg_zklaim_verify_batch", "zkg_zklaim_verify_batch_stats", "zkg_proof_decode_gpu", "zkg_zklaim_input_sums_gpu", "zkg_zklaim_input_map_mirror",
+    "zkg_groth16_prove_dev", "zkg_groth16_prove_batch_dev", "zkg_prove_dev_stats",
 ]
 # the reference's own seam, exported with its original names (zklaim.h:257-259)
 COMPAT_SYMBOLS = ["libsnark_trusted_setup", "libsnark_prove", "libsnark_verify"]
@@ -408,6 +409,21 @@ class Crs:
         rc = L.zkg_groth16_prove_zklaim(C.c_void_p(self._h), None if ctx is None else C.addressof(ctx), _p(_u64(r)), _p(_u64(s)), int(check_satisfied), _p(out), C.byref(ln))
         return rc, (bytes(out[:ln.value]) if rc == OK else None)
 
+    def prove_dev(self, d_ptr, r, s, check_satisfied=True, stream=0):
+        """zkg_groth16_prove_dev: the witness (n x 4 Montgomery limbs) at the raw DEVICE pointer d_ptr, proved behind what is queued on `stream`
+        (a HIP stream handle, 0: the null stream) -> (rc, proof bytes or None): what prove gives on a host copy, ERROR included (no exception:
+        the refusals are the contract)"""
+        L = lib()
+        L.zkg_groth16_prove_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        out = np.zeros(256, np.uint8); ln = C.c_size_t(0)
+        rc = L.zkg_groth16_prove_dev(C.c_void_p(self._h), _vp(d_ptr), _p(_u64(r)), _p(_u64(s)), int(check_satisfied), _p(out), C.byref(ln), _vp(stream))
+        return rc, (bytes(out[:ln.value]) if rc == OK else None)
+
+    def prove_batch_dev(self, d_ptr, stride, count, rs, check_satisfied=True, stream=0):
+        """zkg_groth16_prove_batch_dev: `count` witnesses at the raw DEVICE pointer d_ptr, `stride` Fr elements apart; rs: (r, s) pairs of 4
+        Montgomery limbs each -> (rc, [(status, proof bytes or None)]): rc ERROR is a refused call (nothing was written)"""
+        return groth16_prove_batch_dev(self, d_ptr, stride, count, rs, check_satisfied, stream)
+
     def prove_batch_chunk(self):
         """proofs per batched chunk for this key; 0: prove_batch takes the single-proof path"""
         lib().zkg_prove_batch_chunk.restype = C.c_size_t
@@ -729,6 +745,35 @@ def groth16_prove_batch_zklaim(crs, ctxs, rs, check_satisfied=True):
     handle = crs._h if crs is not None else None
     _check(L.zkg_groth16_prove_batch_zklaim(C.c_void_p(handle), ptrs, n, _p(rs_a), int(check_satisfied), _p(proofs), _p(status)), "zkg_groth16_prove_batch_zklaim")
     return [(int(status[k]), proofs[k].tobytes() if status[k] == OK else None) for k in range(n)]
+
+
+def groth16_prove_batch_dev(crs, d_ptr, stride, count, rs, check_satisfied=True, stream=0):
+    """Crs.prove_batch_dev.  Pointer level: d_ptr is a device address (e.g. ``torch.Tensor.data_ptr()``), stream a HIP stream handle.  Status per
+    item as Crs.prove on a host copy of that item would give."""
+    L = lib()
+    L.zkg_groth16_prove_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    count = int(count)
+    if len(rs) != count:
+        raise ZkgError("prove_batch_dev: one (r, s) per item")
+    rs_a = np.zeros((max(1, count), 8), np.uint64)
+    for k, (r, s) in enumerate(rs):
+        r = _u64(r).reshape(-1); s = _u64(s).reshape(-1)
+        if r.size != 4 or s.size != 4:
+            raise ZkgError(f"prove_batch_dev: item {k}: r and s must be 4 limbs")
+        rs_a[k, :4] = r; rs_a[k, 4:] = s
+    proofs = np.zeros((max(1, count), 134), np.uint8)
+    status = np.full(max(1, count), -1, np.int32)
+    handle = crs._h if crs is not None else None
+    rc = L.zkg_groth16_prove_batch_dev(C.c_void_p(handle), _vp(d_ptr), int(stride), count, _p(rs_a), int(check_satisfied), _p(proofs), _p(status), _vp(stream))
+    return rc, [(int(status[k]), proofs[k].tobytes() if status[k] == OK else None) for k in range(count)]
+
+
+def prove_dev_stats():
+    """(witnesses split on the device from the caller's buffer, witnesses staged through host memory: always 0) of this thread's last
+    Crs.prove_dev / Crs.prove_batch_dev"""
+    out = (C.c_size_t * 2)()
+    lib().zkg_prove_dev_stats(out)
+    return tuple(int(v) for v in out)
 
 
 def zklaim_witness_stats():

@@ -32,6 +32,7 @@ namespace zk {
 struct DevCsr { DevBuf rowptr, col, val; size_t nnz = 0; };
 thread_local size_t t_zklaim_witness_stats[2] = {0, 0};      // zkg_zklaim_witness_stats: items whose witness the GPU made, the host made
 thread_local size_t t_prove_zklaim_stats[2] = {0, 0};        // zkg_prove_zklaim_stats: the last single credential's witness came from the GPU, from the host
+thread_local size_t t_prove_dev_stats[2] = {0, 0};           // zkg_prove_dev_stats: witnesses split on the device from the caller's buffer, staged through host memory
 
 }  // namespace zk
 
@@ -105,6 +106,7 @@ struct BatchWs {
     uint8_t *host_stage = nullptr; size_t host_cap = 0;      // pinned: the chunk's witnesses, packed (one upload)
     uint32_t *host_words = nullptr;                          // pinned: P x BATCH_WORDS after the split, then P x BATCH_WORDS after the mat-vec, then the witness generator's error word
     hipStream_t stream = nullptr, wst[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev_in = nullptr;                              // zkg_groth16_prove_batch_dev: the caller's stream at the time of the call; `stream` waits for it
     zk::MsmJob *job_h = nullptr, *job_w1 = nullptr, *job_w2 = nullptr; zk::OnesSum ones_g1, ones_g2;
     hipEvent_t ev_split = nullptr, ev_flags = nullptr, ev_gathered = nullptr;      // the split's words landed; the mat-vec's flags landed; the witness jobs' scalars gathered
 };
@@ -186,6 +188,7 @@ struct zkg_crs {
     bool busy[MAX_SLOTS] = {false, false, false}; int leases = 0, waiting_ext = 0; bool extending = false;
     // zkg_groth16_prove_batch: one chunk workspace per key; batch callers take turns on it (batch_mu, always taken BEFORE a slot lease)
     BatchWs batch; std::mutex batch_mu;
+    int device = 0;                             // the device the key was uploaded on (the *_dev prove entries refuse a caller on another one)
 };
 
 namespace zk {
@@ -373,6 +376,43 @@ __global__ __launch_bounds__(256) void k_scatter_full_counted(const uint32_t *de
     }
 }
 
+// Witnesses ALREADY on the device (zkg_groth16_prove_dev, zkg_groth16_prove_batch_dev): this kernel is the whole way in — no staging, no tags
+// from the host, no upload.  blockIdx.y = proof; proof p reads the caller's vector at src + p * src_stride (n elements; what lies between n and
+// the stride is never read) and writes z_p = [1 | w], the tag of every element by its VALUE (k_classify's rule), the listing of the non-bit
+// positions (ballot + one atomic per wavefront, unordered like k_scatter_full's), their count in count[0] and "one of them misses the witness
+// tables" in count[1] — each where the next stage reads it: a slot's z / wtags / wlisted / wcount (P = 1, the strides unused) or proof p's
+// strides of the batch workspace, count = the proof's words + 4.  count[0..1] and the ticket words[2] are zero when the launch starts (a memset in
+// front of it: one launch cannot both clear a counter and count into it).  host_words (single proof): the last workgroup to finish writes the two
+// counts into the pinned words, as k_scatter_full does; null (batch): the chunk's one copy of its words carries them.
+__global__ __launch_bounds__(256) void k_split_dev(const Fr *src, size_t src_stride, size_t n, Fr *z, uint8_t *wtags, size_t wtag_stride, uint32_t *listed,
+                                                   uint32_t *words, uint32_t *count, uint32_t word_stride, const uint32_t *subset_pos, uint32_t *host_words /* or null */) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, n1 = n + 1; const uint32_t p = blockIdx.y;
+    src += p * src_stride; z += p * n1; wtags += p * wtag_stride; listed += p * n1; words += (size_t)p * word_stride; count += (size_t)p * word_stride;
+    uint32_t tag = 0;
+    if (i < n1) {
+        const Fr v = i ? src[i - 1] : Fr::one();
+        uint32_t any = 0, diff = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { any |= v.v[j]; diff |= v.v[j] ^ FrParams::ONE[j]; }
+        tag = any == 0 ? 0u : (diff == 0 ? 1u : 2u);
+        z[i] = v; wtags[i] = (uint8_t)tag;
+    }
+    const unsigned long long mask = __ballot(tag == 2);                         // (every lane of the wavefront arrives here)
+    if (mask) {
+        const uint32_t lane = threadIdx.x & 63, leader = (uint32_t)__ffsll((long long)mask) - 1;
+        uint32_t base = 0;
+        if (lane == leader) base = atomicAdd(count, (uint32_t)__popcll(mask));
+        base = __shfl(base, leader, 64);
+        if (tag == 2) {
+            listed[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1))] = (uint32_t)i;
+            if (subset_pos && subset_pos[i] == SUBSET_NONE) or_and_wait(count + 1);     // the witness tables do not cover this element (yet)
+        }
+    }
+    if (!host_words) return;
+    __syncthreads();
+    if (threadIdx.x == 0 && atomicAdd(words + 2, 1u) == gridDim.x - 1) { host_words[1] = atomicOr(count, 0u); host_words[2] = atomicOr(count + 1, 0u); }
+}
+
 // H_tmp = (aA . aB - aC) * Zinv  (divide_by_Z_on_coset fused with the pointwise product)
 __global__ __launch_bounds__(256) void k_pointwise_h(Fr *aA, const Fr *aB, const Fr *aC, size_t m, Fr zinv, int critical) {
     crit_wave_priority(critical);
@@ -491,8 +531,9 @@ static size_t ser_g2(uint8_t *out, const G2 &p) {
     return 66;
 }
 
-struct WitnessSrc {                           // dense: n x 4 limbs; or sparse: tags[n] + (idx[count], vals[count x 4 limbs]); or a zklaim context and its plan
+struct WitnessSrc {                           // dense: n x 4 limbs; or sparse: tags[n] + (idx[count], vals[count x 4 limbs]); or a zklaim context and its plan; or n elements on the device
     const uint64_t *dense = nullptr;
+    const Fr *dev = nullptr;
     const uint8_t *tags = nullptr; const uint32_t *idx = nullptr; const uint64_t *vals = nullptr; size_t count = 0;
     const zklaim_ctx *ctx = nullptr; const ZwPlan *plan = nullptr;
 };
@@ -528,6 +569,13 @@ static int compute_h_matvec(zkg_crs *crs, ProverSlot &S, const WitnessSrc &W, bo
         hipLaunchKernelGGL(k_expand_tags, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, S.up_tags.as<uint8_t>(), n, z, S.wtags.as<uint8_t>(), words, count);
         hipLaunchKernelGGL(k_scatter_full_counted, dim3((unsigned)((pl.cap + 255) / 256)), dim3(256), 0, s, desc, S.up_idx.as<uint32_t>(), S.up_vals.as<Fr>(), (size_t)pl.cap, n, z,
                            S.up_tags.as<uint8_t>(), S.wtags.as<uint8_t>(), S.wlisted.as<uint32_t>(), count, words, subset_pos, S.flag_host, reinterpret_cast<const uint32_t *>(d_in));
+    } else if (W.dev) {
+        // the caller's device buffer (zkg_groth16_prove_dev; the slot's stream already waits for the caller's): k_split_dev reads it in place, and its
+        // last workgroup hands the counts to the pinned words.  The two memsets are the host-dense branch's.
+        ZK_HIP(hipMemsetAsync(words, 0, 16, s));
+        ZK_HIP(hipMemsetAsync(count, 0, 8, s));
+        hipLaunchKernelGGL(k_split_dev, dim3((unsigned)(((size_t)crs->n + 256) / 256), 1), dim3(256), 0, s, W.dev, (size_t)0, (size_t)crs->n, z, S.wtags.as<uint8_t>(), (size_t)0,
+                           S.wlisted.as<uint32_t>(), words, count, 0u, subset_pos, S.flag_host);
     } else if (W.dense || !crs->n) {
         hipLaunchKernelGGL(k_set_one, dim3(1), dim3(64), 0, s, z);
         if (crs->n) ZK_HIP(hipMemcpyAsync(z + 1, W.dense, (size_t)crs->n * 32, hipMemcpyHostToDevice, s));
@@ -695,6 +743,7 @@ static zkg_crs *zkg_crs_upload_impl(const zkg_pk *pk, bool queries_on_device = f
     static const bool dbg_timing = getenv("ZKG_DEBUG_TIMING") != nullptr;
     auto lap = [&](const char *what) { if (dbg_timing) fprintf(stderr, "[zkg key upload] %-24s %8.3f ms\n", what, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count()); };
     zkg_crs *crs = new zkg_crs();
+    crs->device = dev;
     crs->n = cs.num_variables; crs->l = cs.num_inputs; crs->C = cs.num_constraints; crs->log_m = pk->log_m; crs->m = shape.m;
     const size_t n = crs->n, l = crs->l, m = crs->m;
     bool ok = true;
@@ -1029,7 +1078,7 @@ static int h_shards_finish(zkg_crs *crs, ProverSlot &S, G1 &out) {
 }
 
 // event slots: 0 witness resident + split done, 1 mat-vec done, 2 H coefficients done, 3 satisfiability flag landed,
-//              4-5 G1 witness job, 6-7 G2 witness job, 8-9 H job
+//              4-5 G1 witness job, 6-7 G2 witness job, 8-9 H job, 10 G2 ones-sum landed, 11 table extension, 12 the caller's stream (zkg_groth16_prove_dev)
 static int prove_enqueue(zkg_crs *crs, ProverSlot &S, const WitnessSrc &witness, const uint64_t r_[4], const uint64_t s_[4], bool check) {
     S.t0 = std::chrono::steady_clock::now();
     S.check = check; memcpy(S.r.v, r_, 32); memcpy(S.s.v, s_, 32);
@@ -1303,7 +1352,7 @@ static void batch_destroy(BatchWs &B) {
     if (B.stream) (void)hipStreamDestroy(B.stream);
     B.stream = nullptr;
     for (hipStream_t &st : B.wst) { if (st) (void)hipStreamDestroy(st); st = nullptr; }
-    for (hipEvent_t *e : {&B.ev_split, &B.ev_flags, &B.ev_gathered}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
+    for (hipEvent_t *e : {&B.ev_split, &B.ev_flags, &B.ev_gathered, &B.ev_in}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
     if (B.host_stage) (void)hipHostFree(B.host_stage);
     if (B.host_words) (void)hipHostFree(B.host_words);
     B.host_stage = nullptr; B.host_words = nullptr; B.host_cap = 0; B.ready = false; B.P = 0;
@@ -1323,7 +1372,8 @@ static int batch_create(zkg_crs *crs, BatchWs &B, uint32_t P) {
         for (hipStream_t &st : B.wst) ok = ok && hip_ok(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, prio_lo), "hipStreamCreate", __FILE__, __LINE__);
         ok = ok && hip_ok(hipEventCreateWithFlags(&B.ev_split, hipEventDisableTiming), "hipEventCreate", __FILE__, __LINE__) &&
              hip_ok(hipEventCreateWithFlags(&B.ev_flags, hipEventDisableTiming), "hipEventCreate", __FILE__, __LINE__) &&
-             hip_ok(hipEventCreateWithFlags(&B.ev_gathered, hipEventDisableTiming), "hipEventCreate", __FILE__, __LINE__);
+             hip_ok(hipEventCreateWithFlags(&B.ev_gathered, hipEventDisableTiming), "hipEventCreate", __FILE__, __LINE__) &&
+             hip_ok(hipEventCreateWithFlags(&B.ev_in, hipEventDisableTiming), "hipEventCreate", __FILE__, __LINE__);
         B.job_h = ok ? msm_job_create(B.stream, false) : nullptr;
         B.job_w2 = ok ? msm_job_create(B.wst[0], false) : nullptr; B.job_w1 = ok ? msm_job_create(B.wst[1], false) : nullptr;
         ok = ok && B.job_h && B.job_w1 && B.job_w2;
@@ -1368,11 +1418,15 @@ static thread_local size_t t_batch_stats[3] = {0, 0, 0};
 
 // where a chunk's witnesses come from when they are not items: zklaim contexts of the key's payload count, generated on the device
 struct ZklaimChunk { const zklaim_ctx *const *ctxs; const uint64_t *rs; /* 8 limbs per item: r | s */ const ZwPlan *plan; bool cursor_error; };
+// or dense witnesses already on the device (zkg_groth16_prove_batch_dev): item p at src + p * stride
+struct DevChunk { const Fr *src; size_t stride; const uint64_t *rs; /* 8 limbs per item: r | s */ };
 
 // one chunk: P <= B.P items, under the batch mutex and a slot lease (the lease is the chunk's place in the key's extension protocol; its
-// slot lends the streams of a table extension).  Two ways in: `items` (the witnesses are packed on the host and uploaded), or `zc` (a
-// few bytes per credential go up and k_zklaim_witness writes the same packed form into the device stage); from the split on they are one.
-static int prove_chunk(zkg_crs *crs, BatchWs &B, ProverSlot &S, const zkg_prove_item *items, ZklaimChunk *zc, uint32_t P, bool check, uint8_t *proofs_out, int *status) {
+// slot lends the streams of a table extension).  Three ways in: `items` (the witnesses are packed on the host and uploaded), `zc` (a
+// few bytes per credential go up and k_zklaim_witness writes the same packed form into the device stage), or `dc` (the caller's device buffer,
+// split in place by k_split_dev: nothing is packed, staged or uploaded); from the split on they are one.
+static int prove_chunk(zkg_crs *crs, BatchWs &B, ProverSlot &S, const zkg_prove_item *items, ZklaimChunk *zc, uint32_t P, bool check, uint8_t *proofs_out, int *status,
+                       const DevChunk *dc = nullptr) {
     const size_t n = crs->n, n1 = n + 1, m = crs->m, l = crs->l, tag_stride = round_up(n, 16), wtag_stride = round_up(n1, 16);
     hipStream_t s = B.stream;
     const auto t0 = std::chrono::steady_clock::now();
@@ -1390,7 +1444,8 @@ static int prove_chunk(zkg_crs *crs, BatchWs &B, ProverSlot &S, const zkg_prove_
     std::vector<uint32_t> off(P + 1, 0);
     size_t o_vals = round_up((size_t)P * sizeof(BatchDesc), 64), o_idx = 0, o_tags = 0, o_gen = 0;
     uint32_t max_cnt = 0;
-    if (!zc) {                                                                   // packed on the host, one upload
+    if (dc) o_vals = 0;                                                          // resident already: no stage (the offsets below stay 0)
+    else if (!zc) {                                                              // packed on the host, one upload
         host_parallel_for((int)P, [&](int p) {
             const zkg_prove_item &it = items[p];
             if (!it.r || !it.s) skip[p] = 1;
@@ -1438,8 +1493,14 @@ static int prove_chunk(zkg_crs *crs, BatchWs &B, ProverSlot &S, const zkg_prove_
     const uint32_t *subset_pos = crs->sub.count ? crs->sub.pos.as<uint32_t>() : nullptr;
     uint32_t *hw_gen = B.host_words + (size_t)2 * B.P * BATCH_WORDS;
     // ---- 2. split, mat-vec, transforms, H: one launch sequence for the chunk
+    if (dc) {
+        ZK_HIP(hipMemsetAsync(words, 0, (size_t)P * BATCH_WORDS * 4, s));
+        hipLaunchKernelGGL(k_split_dev, dim3((unsigned)((n1 + 255) / 256), P), dim3(256), 0, s, dc->src, dc->stride, n, z, wtags, wtag_stride, wlisted, words, words + 4, BATCH_WORDS,
+                           subset_pos, (uint32_t *)nullptr);
+    } else {
     hipLaunchKernelGGL(k_expand_tags_batch, dim3((unsigned)((n + 255) / 256), P), dim3(256), 0, s, d_tags, tag_stride, n, z, wtags, wtag_stride, words);
     if (max_cnt) hipLaunchKernelGGL(k_scatter_full_batch, dim3((max_cnt + 255) / 256, P), dim3(256), 0, s, d_desc, d_idx, d_vals, d_tags, tag_stride, n, z, wtags, wtag_stride, wlisted, words, subset_pos);
+    }
     ZK_HIP(hipMemcpyAsync(hw_split, words, (size_t)P * BATCH_WORDS * 4, hipMemcpyDeviceToHost, s));
     if (zc) ZK_HIP(hipMemcpyAsync(hw_gen, st + o_gen, 4, hipMemcpyDeviceToHost, s));
     ZK_HIP(hipEventRecord(B.ev_split, s));
@@ -1542,7 +1603,8 @@ static int prove_chunk(zkg_crs *crs, BatchWs &B, ProverSlot &S, const zkg_prove_
         G1 W1[3] = {Wg1[3 * (size_t)p], Wg1[3 * (size_t)p + 1], Wg1[3 * (size_t)p + 2]}; G2 Wb2 = Wg2[p];
         for (int i = 0; i < 3; ++i) W1[i].add(B.ones_g1.g1(3 * p + i));
         Wb2.add(B.ones_g2.g2pt(p));
-        Fr r, sv; memcpy(r.v, zc ? zc->rs + 8 * (size_t)p : items[p].r, 32); memcpy(sv.v, zc ? zc->rs + 8 * (size_t)p + 4 : items[p].s, 32);
+        const uint64_t *rs_p = zc ? zc->rs + 8 * (size_t)p : dc ? dc->rs + 8 * (size_t)p : nullptr;
+        Fr r, sv; memcpy(r.v, rs_p ? rs_p : items[p].r, 32); memcpy(sv.v, rs_p ? rs_p + 4 : items[p].s, 32);
         assemble_proof(crs, r, sv, W1, Wb2, Ht[p], proofs_out + (size_t)p * ZKG_PROOF_BYTES);
         status[p] = ZKG_OK;
     });
@@ -1583,6 +1645,92 @@ static int groth16_prove_batch_impl(const zkg_crs *crs_, const zkg_prove_item *i
     return ZKG_OK;
 }
 
+
+// ---- zkg_groth16_prove_dev / zkg_groth16_prove_batch_dev: witnesses that are already in device memory.  The refusals come first, before any
+// launch: the calling thread on another device than the key's, a pointer that is not device memory of that device (pinned, managed and
+// unregistered host memory included), a range that runs past the end of its allocation (best effort: where the runtime knows the allocation).
+static int dev_witness_refused(const zkg_crs *crs, const void *d, size_t elems, const char *who) {
+    auto refuse = [&](const char *why) { set_error(std::string(who) + ": " + why); return ZKG_ERROR; };
+    if (initialised_device() < 0) return refuse("zkg_init has not been called");
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != crs->device) { (void)hipGetLastError(); return refuse("the calling thread's device is not the key's"); }
+    if (!elems) return ZKG_OK;                                                  // (a key without variables: nothing is read)
+    if (reinterpret_cast<uintptr_t>(d) % alignof(Fr)) return refuse("the witness must be aligned to 16 bytes");
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof at);
+    if (hipPointerGetAttributes(&at, d) != hipSuccess) { (void)hipGetLastError(); return refuse("the witness is not device memory"); }
+    if (at.type != hipMemoryTypeDevice || at.isManaged || at.device != crs->device) return refuse("the witness is not device memory of the key's device");
+    hipDeviceptr_t base = nullptr; size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)d) != hipSuccess) { (void)hipGetLastError(); return ZKG_OK; }
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(base), at_d = reinterpret_cast<uintptr_t>(d);
+    if (at_d < lo || at_d - lo > size || elems > (size - (at_d - lo)) / 32) return refuse("the witness runs past the end of its allocation");
+    return ZKG_OK;
+}
+// one proof from n elements at d_w, behind `stream`; counts into t_prove_dev_stats (the entries reset it)
+static int prove_dev_one(zkg_crs *crs, const Fr *d_w, const uint64_t r_[4], const uint64_t s_[4], int check_satisfied, uint8_t *proof_out, size_t *proof_len, hipStream_t stream) {
+    SlotLease lease(crs);
+    if (!lease.ok()) return ZKG_ERROR;
+    ProverSlot &S = lease.S();
+    // the proof runs on the slot's own (non-blocking) streams: order it behind whatever the caller queued on `stream` — the work that wrote the
+    // witness.  The call returns after the proof has landed, so nothing of it is left running for the caller to order after.
+    ZK_HIP(hipEventRecord(S.ev[12], stream));
+    ZK_HIP(hipStreamWaitEvent(S.stream, S.ev[12], 0));
+    WitnessSrc W; W.dev = d_w;
+    uint8_t buf[256]; size_t len = 0;                                           // nothing is written unless the proof is made
+    if (prove_enqueue(crs, S, W, r_, s_, check_satisfied != 0)) { slot_drain(crs, S); return ZKG_ERROR; }
+    ++t_prove_dev_stats[0];
+    const int rc = prove_finish(crs, S, buf, &len);
+    if (rc == ZKG_OK) { memcpy(proof_out, buf, len); *proof_len = len; }
+    return rc;
+}
+static int groth16_prove_dev_impl(const zkg_crs *crs_, const void *d_witness, const uint64_t r_[4], const uint64_t s_[4], int check_satisfied,
+                                  uint8_t *proof_out, size_t *proof_len, void *stream) {
+    t_prove_dev_stats[0] = t_prove_dev_stats[1] = 0;
+    zkg_crs *crs = const_cast<zkg_crs *>(crs_);
+    if (!crs || !d_witness || !r_ || !s_ || !proof_out || !proof_len) { set_error("zkg_groth16_prove_dev: bad argument"); return ZKG_ERROR; }
+    if (dev_witness_refused(crs, d_witness, crs->n, "zkg_groth16_prove_dev")) return ZKG_ERROR;
+    return prove_dev_one(crs, static_cast<const Fr *>(d_witness), r_, s_, check_satisfied, proof_out, proof_len, (hipStream_t)stream);
+}
+static int groth16_prove_batch_dev_impl(const zkg_crs *crs_, const void *d_witnesses, size_t stride, size_t count, const uint64_t *rs, int check_satisfied,
+                                        uint8_t *proofs_out, int *status, void *stream) {
+    t_batch_stats[0] = t_batch_stats[1] = t_batch_stats[2] = 0; t_prove_dev_stats[0] = t_prove_dev_stats[1] = 0;
+    if (!count) return ZKG_OK;
+    zkg_crs *crs = const_cast<zkg_crs *>(crs_);
+    if (!crs || !d_witnesses || !rs || !proofs_out || !status) { set_error("zkg_groth16_prove_batch_dev: bad argument"); return ZKG_ERROR; }
+    if (stride < crs->n) { set_error("zkg_groth16_prove_batch_dev: stride is shorter than the witness"); return ZKG_ERROR; }
+    if (stride && count - 1 > (SIZE_MAX / 64 - crs->n) / stride) { set_error("zkg_groth16_prove_batch_dev: count x stride out of range"); return ZKG_ERROR; }
+    if (dev_witness_refused(crs, d_witnesses, crs->n ? (count - 1) * stride + crs->n : 0, "zkg_groth16_prove_batch_dev")) return ZKG_ERROR;
+    const Fr *src = static_cast<const Fr *>(d_witnesses);
+    const uint32_t chunk = batch_chunk_for(crs);
+    if (!chunk) {                                                            // this key's proofs do not batch: the single-proof path from the same buffer, item by item
+        for (size_t i = 0; i < count; ++i) {
+            uint8_t buf[256]; size_t len = 0;
+            status[i] = prove_dev_one(crs, src + i * stride, rs + 8 * i, rs + 8 * i + 4, check_satisfied, buf, &len, (hipStream_t)stream);
+            if (status[i] == ZKG_OK) memcpy(proofs_out + i * ZKG_PROOF_BYTES, buf, ZKG_PROOF_BYTES);
+            ++t_batch_stats[1];
+        }
+        return ZKG_OK;
+    }
+    std::lock_guard<std::mutex> batch_lock(crs->batch_mu);
+    if (batch_create(crs, crs->batch, chunk)) return ZKG_ERROR;
+    // every chunk runs on the workspace's stream, in order: ONE wait puts the whole call behind the caller's stream
+    ZK_HIP(hipEventRecord(crs->batch.ev_in, (hipStream_t)stream));
+    ZK_HIP(hipStreamWaitEvent(crs->batch.stream, crs->batch.ev_in, 0));
+    for (size_t first = 0; first < count; first += chunk) {
+        const uint32_t P = (uint32_t)std::min<size_t>(chunk, count - first);
+        SlotLease lease(crs);                                                // per chunk, as zkg_groth16_prove_batch
+        if (!lease.ok()) return ZKG_ERROR;
+        const DevChunk dc{src + first * stride, stride, rs + 8 * first};
+        int rc = ZKG_ERROR;
+        try { rc = prove_chunk(crs, crs->batch, lease.S(), nullptr, nullptr, P, check_satisfied != 0, proofs_out + first * ZKG_PROOF_BYTES, status + first, &dc); }
+        catch (const std::exception &e) { set_error(std::string("zkg_groth16_prove_batch_dev: ") + e.what()); }
+        catch (...) { set_error("zkg_groth16_prove_batch_dev: unexpected exception"); }
+        if (rc) { batch_drain(crs->batch); return ZKG_ERROR; }
+        t_batch_stats[0] += P; ++t_batch_stats[2]; t_prove_dev_stats[0] += P;
+    }
+    return ZKG_OK;
+}
+
 // helper threads and host containers are used below these two: nothing may propagate through the C boundary
 int zkg_groth16_prove(const zkg_crs *crs, const uint64_t *witness, const uint64_t r[4], const uint64_t s[4], int check_satisfied,
                       uint8_t *proof_out, size_t *proof_len) {
@@ -1610,6 +1758,18 @@ int zkg_groth16_prove_batch(const zkg_crs *crs, const zkg_prove_item *items, siz
     catch (...) { set_error("zkg_groth16_prove_batch: unexpected exception"); }
     return ZKG_ERROR;
 }
+int zkg_groth16_prove_dev(const zkg_crs *crs, const void *d_witness, const uint64_t r[4], const uint64_t s[4], int check_satisfied, uint8_t *proof_out, size_t *proof_len, void *stream) {
+    try { return groth16_prove_dev_impl(crs, d_witness, r, s, check_satisfied, proof_out, proof_len, stream); }
+    catch (const std::exception &e) { set_error(std::string("zkg_groth16_prove_dev: ") + e.what()); return ZKG_ERROR; }
+    catch (...) { set_error("zkg_groth16_prove_dev: unexpected exception"); return ZKG_ERROR; }
+}
+int zkg_groth16_prove_batch_dev(const zkg_crs *crs, const void *d_witnesses, size_t stride, size_t count, const uint64_t *rs, int check_satisfied, uint8_t *proofs_out, int *status, void *stream) {
+    try { return groth16_prove_batch_dev_impl(crs, d_witnesses, stride, count, rs, check_satisfied, proofs_out, status, stream); }
+    catch (const std::exception &e) { set_error(std::string("zkg_groth16_prove_batch_dev: ") + e.what()); }
+    catch (...) { set_error("zkg_groth16_prove_batch_dev: unexpected exception"); }
+    return ZKG_ERROR;
+}
+void zkg_prove_dev_stats(size_t out[2]) { if (out) { out[0] = zk::t_prove_dev_stats[0]; out[1] = zk::t_prove_dev_stats[1]; } }
 // ---- zkg_groth16_prove_batch_zklaim: the same chunks, their witnesses generated on the device from the contexts
 // host witnesses for ctxs[0 .. count) through zkg_groth16_prove_batch (which takes the single-proof path for keys that do not batch)
 static int prove_zklaim_host_witnesses(const zkg_crs *crs, const zklaim_ctx *const *ctxs, size_t count, const uint64_t *rs, int check_satisfied, uint8_t *proofs_out, int *status) {
