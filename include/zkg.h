@@ -473,6 +473,30 @@ int zkg_field_op(int field, int op, const uint64_t *a, const uint64_t *b, size_t
  * Ops 9-14 run a copy of the kernel's step bodies (csrc/capi.hip, marked at both places): the kernel keeps its own text.  n at most 2^24. */
 int zkg_fr29_op(int op, const uint32_t *in, size_t n, uint32_t *out);
 
+/* known-answer hook for the multi-exponentiation's 29-bit Fq arithmetic (csrc/fq29.hip.hpp: Fq as nine 29-bit limbs, R' = 2^261, values kept
+ * lazily above q, subtractions through spread multiples of q): the functions of that file themselves, ON THE GPU, host pointers, RAW limbs
+ * (no to29 on the way in, no from29 on the way out), so a caller can place limbs and values at the bounds the file's comments state.
+ * Element i reads k vectors of nine 32-bit limbs at in + 9 k i and writes m vectors at out + 9 m i.  No input is range-checked.
+ *   op  0  mul(a, b)         k 2, m 1         1  mul2(a, b, c, d): a b and c d   k 4, m 2
+ *       2  sqr(a)            k 1, m 1         3  sqr2(a, c): a^2 and c^2         k 2, m 2
+ *       4  norm(a)   6  dbl(a)   11  S2_1 - a                                    k 1, m 1
+ *       5  add(a, b)   7 - 10  a + S - b for S = S2_1, S4_1, S6_1, S4_3, unnormalised, as f29::sub returns it          k 2, m 1
+ *      12  is_zero_mod_p(a): limb 0 of the result is 0 or 1                     k 1, m 1
+ *      13  unpack   14  to29: eight 32-bit words of libff's form in the first eight slots (the ninth is ignored)       k 1, m 1
+ *      15  from29: out eight 32-bit words, the ninth slot zero                  k 1, m 1
+ *      16  x, y, flag (limb 0: infinity) -> store_rec64 -> load_rec64 -> x, y, flag                                    k 3, m 3
+ *      17  x, y, zz, zzz, flag -> store_bucket29 -> load_bucket29_raw -> x, y, zz, zzz                                 k 5, m 4
+ *      18  inverse(a) (a launch's tail lanes invert 1: the early exit is a wavefront vote)                             k 1, m 1
+ *      19  XYZZ29::madd: in x, y, zz, zzz, bx, by, flag (limb 0: the accumulator is infinity); out x, y, zz, zzz (all zero for infinity),
+ *          flag (limb 0: infinity, limb 1: what madd returned).  A false return continues as k_bucket_accum29 does (from29, the 32-bit
+ *          madd, to29 — a copy of the kernel's lines, csrc/capi.hip, marked at both places).                           k 7, m 5
+ *      20  xyzz29_add_lane   21  xyzz29_add_pair (2 lanes per element)   22  xyzz29_add_quad (4 lanes per element): in two points of four
+ *          coordinates, infinity all zero; out the sum's four coordinates                                              k 8, m 4
+ * zkg_fq29_op_chain: ops 19-22 with 0 <= chain <= 64.  19: 1 + chain times acc <- acc + b (the flag is the last step's);  20-22: a + b, then
+ * `chain` rounds of x <- 2x + b, so stored invariants are re-entered without leaving the device.  Other ops take chain 0.  n at most 2^24. */
+int zkg_fq29_op(int op, const uint32_t *in, size_t n, uint32_t *out);
+int zkg_fq29_op_chain(int op, int chain, const uint32_t *in, size_t n, uint32_t *out);
+
 /* known-answer hook for the 29-bit group law of the bucket-reduction kernels (csrc/fq29.hip.hpp, xyzz29_add_quad): on the GPU,
  * out[i] = a[i] + b[i], then `chain` rounds of x <- 2x + b[i]; points as normalised Jacobian (12 limbs), host pointers.          */
 int zkg_g1_add_quad29(const uint64_t *a_jac, const uint64_t *b_jac, size_t n, int chain, uint64_t *out_jac);

@@ -27,7 +27,7 @@ DECLARED_SYMBOLS = [
     "zkg_groth16_verify_batch", "zkg_pairing_product", "zkg_verify_batch_stats",
     "zkg_groth16_prove_batch", "zkg_prove_batch_stats", "zkg_prove_batch_chunk", "zkg_zklaim_prove_batch",
     "zkg_groth16_prove_zklaim", "zkg_prove_zklaim_stats", "zkg_zklaim_witness_gpu_parallel", "zkg_zklaim_witness_mirror_parallel",
-    "zkg_fr29_op",
+    "zkg_fr29_op", "zkg_fq29_op", "zkg_fq29_op_chain",
     "zkg_zklaim_verify_batch", "zkg_zklaim_verify_batch_stats", "zkg_proof_decode_gpu", "zkg_zklaim_input_sums_gpu", "zkg_zklaim_input_map_mirror",
     "zkg_groth16_prove_dev", "zkg_groth16_prove_batch_dev", "zkg_prove_dev_stats",
 ]
@@ -121,7 +121,9 @@ def device_info():
 
 def field_op(field, op, a, b=None):
     """element-wise device arithmetic (zkg_field_op): field 0 Fq, 1 Fr, 2 Fq2; op 0 mul 1 add 2 sub 3 inv 4 to_mont 5 from_mont 6 neg 7 sqr;
-    Fq only: 10-14 the 29-bit representation of the accumulation kernel (mul, add, sub, zero test, composite)"""
+    Fq only: 10-15 the 29-bit representation of the accumulation kernel (mul, add, sub, zero test, composite, inverse of 3a) entered through
+    to29 on canonical values: a smoke of that code on digits below 1.01 q.  Its lazy bounds are tested on raw limbs through fq29_op
+    (tests/test_gpu_fq29.py)."""
     a = _u64(a); limbs = 8 if field == 2 else 4
     out = np.zeros_like(a)
     bb = None if b is None else _u64(b)
@@ -142,6 +144,24 @@ def fr29_op(name, x):
         raise ZkgError(f"fr29_op {name}: input must be (n, {k}, 9), got {x.shape}")
     out = np.zeros((x.shape[0], m, 9), np.uint32)
     _check(lib().zkg_fr29_op(int(op), _p(x), C.c_size_t(x.shape[0]), _p(out)), "zkg_fr29_op")
+    return out
+
+
+FQ29_OPS = {"mul": (0, 2, 1), "mul2": (1, 4, 2), "sqr": (2, 1, 1), "sqr2": (3, 2, 2), "norm": (4, 1, 1), "add": (5, 2, 1), "dbl": (6, 1, 1),
+            "sub_S2_1": (7, 2, 1), "sub_S4_1": (8, 2, 1), "sub_S6_1": (9, 2, 1), "sub_S4_3": (10, 2, 1), "neg_S2_1": (11, 1, 1), "is_zero": (12, 1, 1),
+            "unpack": (13, 1, 1), "to29": (14, 1, 1), "from29": (15, 1, 1), "rec64": (16, 3, 3), "bucket29": (17, 5, 4), "inverse": (18, 1, 1),
+            "madd": (19, 7, 5), "add_lane": (20, 8, 4), "add_pair": (21, 8, 4), "add_quad": (22, 8, 4)}           # name -> (op, k, m) of zkg_fq29_op
+
+
+def fq29_op(name, x, chain=0):
+    """the multi-exponentiation's 29-bit Fq arithmetic on raw limbs (zkg_fq29_op, zkg_fq29_op_chain): x is (n, k, 9) uint32, the result
+    (n, m, 9) uint32; chain (madd and the three additions only): that many further steps on the device"""
+    op, k, m = FQ29_OPS[name]
+    x = np.ascontiguousarray(x, dtype=np.uint32)
+    if x.ndim != 3 or x.shape[1:] != (k, 9):
+        raise ZkgError(f"fq29_op {name}: input must be (n, {k}, 9), got {x.shape}")
+    out = np.zeros((x.shape[0], m, 9), np.uint32)
+    _check(lib().zkg_fq29_op_chain(int(op), int(chain), _p(x), C.c_size_t(x.shape[0]), _p(out)), "zkg_fq29_op")
     return out
 
 

@@ -356,6 +356,126 @@ __global__ __launch_bounds__(64) void k_add_quad29(const XYZZ<Fq> *a, const XYZZ
     if (q == 0) out[i] = x.is_inf() ? XYZZ<Fq>::inf().normalized() : XYZZ<Fq>{f29::from29(x.x), f29::from29(x.y), f29::from29(x.zz), f29::from29(x.zzz)};
 }
 
+// ---- the multi-exponentiation's 29-bit Fq arithmetic on raw limbs (the known-answer hook behind zkg_fq29_op): k vectors of nine limbs
+//      in, m out, no to29 on the way in and no from29 on the way out, so that a caller can place limbs and values AT the lazy bounds the
+//      comments of fq29.hip.hpp state.  One lane per element; the pair and quad additions take 2 and 4 lanes per element.
+// COPY of the exceptional path of k_bucket_accum29 (csrc/msm.hip), from the false return of XYZZ29::madd to the accumulator's new value —
+// the kernel keeps its own text (its register allocation is tuned: ACC29_VGPRS): keep the two alike, line by line.
+ZK_D void fq29_madd_fallback_copy(XYZZ29 &acc, const Fq29 &bx, const Fq29 &by, bool &inf) {
+    XYZZ<Fq> a32 = {f29::from29(acc.x), f29::from29(acc.y), f29::from29(acc.zz), f29::from29(acc.zzz)};
+    a32.madd(Affine<Fq>{f29::from29(bx), f29::from29(f29::norm(by))});
+    if (a32.is_inf()) inf = true;
+    else { acc.x = f29::to29(a32.x.normalized()); acc.y = f29::to29(a32.y.normalized()); acc.zz = f29::to29(a32.zz.normalized()); acc.zzz = f29::to29(a32.zzz.normalized()); }
+}
+enum { FQ29_MUL, FQ29_MUL2, FQ29_SQR, FQ29_SQR2, FQ29_NORM, FQ29_ADD, FQ29_DBL, FQ29_SUB_S2_1, FQ29_SUB_S4_1, FQ29_SUB_S6_1, FQ29_SUB_S4_3, FQ29_NEG_S2_1, FQ29_IS_ZERO,
+       FQ29_UNPACK, FQ29_TO29, FQ29_FROM29, FQ29_REC64, FQ29_BUCKET29, FQ29_INVERSE, FQ29_MADD, FQ29_ADD_LANE, FQ29_ADD_PAIR, FQ29_ADD_QUAD, FQ29_OPS };
+static const int FQ29_K[FQ29_OPS] = {2, 4, 1, 2, 1, 2, 1, 2, 2, 2, 2, 1, 1, 1, 1, 1, 3, 5, 1, 7, 8, 8, 8};
+static const int FQ29_M[FQ29_OPS] = {1, 2, 1, 2, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 3, 4, 1, 5, 4, 4, 4};
+ZK_D Fq29 fq29_load(const uint32_t *p) { Fq29 r; for (int l = 0; l < 9; ++l) r.v[l] = p[l]; return r; }
+ZK_D void fq29_store(uint32_t *p, const Fq29 &a) { for (int l = 0; l < 9; ++l) p[l] = a.v[l]; }
+// `records`: room for n Bucket29 (ops rec64 and bucket29 store their record there, Rec64 or Bucket29, and load it back)
+__global__ __launch_bounds__(64) void k_fq29_op(int op, int k, int m, int chain, const uint32_t *in, size_t n, uint32_t *out, void *records) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = i < n;
+    if (!live && op != FQ29_INVERSE) return;             // (the inversion's early exit is a wavefront vote: a tail lane inverts the integer 1 and writes nothing)
+    Fq29 x[8], y[5];
+    for (int j = 0; j < 8; ++j) for (int l = 0; l < 9; ++l) x[j].v[l] = live ? (j < k ? in[(i * k + j) * 9 + l] : 0u) : (l == 0 ? 1u : 0u);
+    for (int j = 0; j < 5; ++j) y[j] = Fq29::zero();
+    switch (op) {
+    case FQ29_MUL: y[0] = f29::mul(x[0], x[1]); break;
+    case FQ29_MUL2: f29::mul2(y[0], y[1], x[0], x[1], x[2], x[3]); break;
+    case FQ29_SQR: y[0] = f29::sqr(x[0]); break;
+    case FQ29_SQR2: f29::sqr2(y[0], y[1], x[0], x[1]); break;
+    case FQ29_NORM: y[0] = f29::norm(x[0]); break;
+    case FQ29_ADD: y[0] = f29::add(x[0], x[1]); break;
+    case FQ29_DBL: y[0] = f29::dbl(x[0]); break;
+    case FQ29_SUB_S2_1: y[0] = f29::sub(x[0], f29::S2_1, x[1]); break;
+    case FQ29_SUB_S4_1: y[0] = f29::sub(x[0], f29::S4_1, x[1]); break;
+    case FQ29_SUB_S6_1: y[0] = f29::sub(x[0], f29::S6_1, x[1]); break;
+    case FQ29_SUB_S4_3: y[0] = f29::sub(x[0], f29::S4_3, x[1]); break;
+    case FQ29_NEG_S2_1: y[0] = f29::neg(f29::S2_1, x[0]); break;
+    case FQ29_IS_ZERO: y[0].v[0] = f29::is_zero_mod_p(x[0]) ? 1u : 0u; break;
+    case FQ29_UNPACK: { Fq f; for (int l = 0; l < 8; ++l) f.v[l] = x[0].v[l]; y[0] = f29::unpack(f); break; }
+    case FQ29_TO29: { Fq f; for (int l = 0; l < 8; ++l) f.v[l] = x[0].v[l]; y[0] = f29::to29(f); break; }
+    case FQ29_FROM29: { const Fq f = f29::from29(x[0]); for (int l = 0; l < 8; ++l) y[0].v[l] = f.v[l]; break; }
+    case FQ29_REC64: {
+        Rec64 *rec = reinterpret_cast<Rec64 *>(records) + i;
+        store_rec64(rec, x[0], x[1], (x[2].v[0] & 1u) != 0);
+        const Affine29 a = load_rec64(rec);
+        for (int l = 0; l < 9; ++l) { y[0].v[l] = a.x[l]; y[1].v[l] = a.y[l]; }
+        y[2].v[0] = a.inf;
+        break;
+    }
+    case FQ29_BUCKET29: {
+        XYZZ29 a; a.x = x[0]; a.y = x[1]; a.zz = x[2]; a.zzz = x[3];
+        Bucket29 *rec = reinterpret_cast<Bucket29 *>(records) + i;
+        store_bucket29(rec, a, (x[4].v[0] & 1u) != 0);
+        const Bucket29 b = load_bucket29_raw(rec);
+        for (int l = 0; l < 9; ++l) { y[0].v[l] = b.x[l]; y[1].v[l] = b.y[l]; y[2].v[l] = b.zz[l]; y[3].v[l] = b.zzz[l]; }
+        break;
+    }
+    case FQ29_INVERSE: y[0] = f29::inverse(x[0]); break;
+    case FQ29_MADD: {                                     // 1 + chain times acc <- acc + b, each as k_bucket_accum29 does it
+        XYZZ29 acc; acc.x = x[0]; acc.y = x[1]; acc.zz = x[2]; acc.zzz = x[3];
+        bool inf = (x[6].v[0] & 1u) != 0, ok = true;
+        for (int s = 0; s <= chain; ++s) {
+            ok = acc.madd(x[4], x[5], inf);
+            if (!ok) fq29_madd_fallback_copy(acc, x[4], x[5], inf);
+        }
+        if (!inf) { y[0] = acc.x; y[1] = acc.y; y[2] = acc.zz; y[3] = acc.zzz; }               // (infinity: all zero, as store_bucket29 writes it)
+        y[4].v[0] = inf ? 1u : 0u; y[4].v[1] = ok ? 1u : 0u;
+        break;
+    }
+    default: {                                            // FQ29_ADD_LANE: a + b, then `chain` rounds of x <- 2x + b
+        XYZZ29q a, b; a.x = x[0]; a.y = x[1]; a.zz = x[2]; a.zzz = x[3]; b.x = x[4]; b.y = x[5]; b.zz = x[6]; b.zzz = x[7];
+        xyzz29_add_lane(a, b);
+        for (int s = 0; s < chain; ++s) { const XYZZ29q z = a; xyzz29_add_lane(a, b); xyzz29_add_lane(a, z); }
+        y[0] = a.x; y[1] = a.y; y[2] = a.zz; y[3] = a.zzz;
+        break;
+    }
+    }
+    if (!live) return;
+    for (int j = 0; j < m; ++j) for (int l = 0; l < 9; ++l) out[(i * m + j) * 9 + l] = y[j].v[l];
+}
+// the pair form: lane r of a pair loads (X, ZZ) or (Y, ZZZ) of both points, as k_add_pair29 does, and writes its own two coordinates of the
+// sum — no exchange outside xyzz29_add_pair, inside which the whole pair is active (a pair leaves together: i is the pair's)
+__global__ __launch_bounds__(64) void k_fq29_add_pair(int chain, const uint32_t *in, size_t n, uint32_t *out) {
+    const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 1; const uint32_t r = threadIdx.x & 1;
+    if (i >= n) return;
+    const uint32_t *p = in + i * 72; uint32_t *o = out + i * 36;
+    Half29 a, b; a.c0 = fq29_load(p + 9 * r); a.c1 = fq29_load(p + 9 * (2 + r)); b.c0 = fq29_load(p + 9 * (4 + r)); b.c1 = fq29_load(p + 9 * (6 + r));
+    xyzz29_add_pair(a, b, r);
+    for (int s = 0; s < chain; ++s) { const Half29 z = a; xyzz29_add_pair(a, b, r); xyzz29_add_pair(a, z, r); }
+    fq29_store(o + 9 * r, a.c0); fq29_store(o + 9 * (2 + r), a.c1);
+}
+// the quad form: every lane of a quad holds both points whole; lane q writes coordinate q of ITS copy of the sum (the four copies must agree)
+__global__ __launch_bounds__(64) void k_fq29_add_quad(int chain, const uint32_t *in, size_t n, uint32_t *out) {
+    const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2; const uint32_t q = threadIdx.x & 3;
+    if (i >= n) return;
+    const uint32_t *p = in + i * 72;
+    XYZZ29q a, b; a.x = fq29_load(p); a.y = fq29_load(p + 9); a.zz = fq29_load(p + 18); a.zzz = fq29_load(p + 27);
+    b.x = fq29_load(p + 36); b.y = fq29_load(p + 45); b.zz = fq29_load(p + 54); b.zzz = fq29_load(p + 63);
+    xyzz29_add_quad(a, b, q);
+    for (int s = 0; s < chain; ++s) { const XYZZ29q z = a; xyzz29_add_quad(a, b, q); xyzz29_add_quad(a, z, q); }
+    fq29_store(out + i * 36 + 9 * q, quad_select29(q, a.x, a.y, a.zz, a.zzz));
+}
+static int fq29_op_run(int op, int chain, const uint32_t *in, size_t n, uint32_t *out) {
+    DevBuf din, dout, drec;
+    const int k = FQ29_K[op], m = FQ29_M[op];
+    const size_t in_bytes = n * k * 9 * sizeof(uint32_t), out_bytes = n * m * 9 * sizeof(uint32_t);
+    const bool records = op == FQ29_REC64 || op == FQ29_BUCKET29;
+    int rc = ZKG_ERROR;
+    if (!din.reserve(in_bytes) && !dout.reserve(out_bytes) && (!records || !drec.reserve(n * sizeof(Bucket29))) &&
+        hip_ok(hipMemcpy(din.p, in, in_bytes, hipMemcpyHostToDevice), "H2D", __FILE__, __LINE__)) {
+        if (op == FQ29_ADD_PAIR) hipLaunchKernelGGL(k_fq29_add_pair, dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, nullptr, chain, din.as<uint32_t>(), n, dout.as<uint32_t>());
+        else if (op == FQ29_ADD_QUAD) hipLaunchKernelGGL(k_fq29_add_quad, dim3((unsigned)((4 * n + 63) / 64)), dim3(64), 0, nullptr, chain, din.as<uint32_t>(), n, dout.as<uint32_t>());
+        else hipLaunchKernelGGL(k_fq29_op, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, nullptr, op, k, m, chain, din.as<uint32_t>(), n, dout.as<uint32_t>(), records ? drec.p : (void *)nullptr);
+        if (hipGetLastError() == hipSuccess && hip_ok(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost), "D2H", __FILE__, __LINE__)) rc = ZKG_OK;
+    }
+    din.release(); dout.release(); drec.release();
+    return rc;
+}
+
 static std::mutex g_init_mu;
 static std::atomic<int> g_device{-1};                     // written under g_init_mu, read by entry points on any thread
 int initialised_device() { return g_device.load(); }
@@ -654,6 +774,15 @@ int zkg_fr29_op(int op, const uint32_t *in, size_t n, uint32_t *out) {
     if (!n) return ZKG_OK;
     return fr29_op_run(op, in, n, out);
 }
+
+int zkg_fq29_op_chain(int op, int chain, const uint32_t *in, size_t n, uint32_t *out) {
+    REQUIRE_INIT();
+    const bool chained = op == FQ29_MADD || op == FQ29_ADD_LANE || op == FQ29_ADD_PAIR || op == FQ29_ADD_QUAD;
+    if (op < 0 || op >= FQ29_OPS || !in || !out || n > ((size_t)1 << 24) || chain < 0 || chain > 64 || (chain && !chained)) { set_error("zkg_fq29_op: bad argument"); return ZKG_ERROR; }
+    if (!n) return ZKG_OK;
+    return fq29_op_run(op, chain, in, n, out);
+}
+int zkg_fq29_op(int op, const uint32_t *in, size_t n, uint32_t *out) { return zkg_fq29_op_chain(op, 0, in, n, out); }
 
 // ---- one process, several GPUs: the G1 multi-exponentiation sharded by points.  Every shard is a resident slice of
 //      the bases on one device with its own stream and workspace; a call hands each shard its slice of the scalars on a host thread of

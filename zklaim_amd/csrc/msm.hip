@@ -749,6 +749,7 @@ __global__ __launch_bounds__(256, WAVES) ZK_VGPR_CAP(ACC29_VGPRS) void k_bucket_
                 if (ce & 1u) by = f29::neg(f29::S2_1, by);
                 if (__builtin_expect(!acc.madd(bx, by, inf), 0)) {
                     // b == +-accumulator (a duplicated base under equal digits): the doubling / cancellation cases on the 32-bit path
+                    // (These lines, down to the accumulator's new value, have a COPY in csrc/capi.hip, fq29_madd_fallback_copy, for the known-answer hook zkg_fq29_op: keep the two alike.)
                     XYZZ<Fq> a32 = {f29::from29(acc.x), f29::from29(acc.y), f29::from29(acc.zz), f29::from29(acc.zzz)};
                     a32.madd(Affine<Fq>{f29::from29(bx), f29::from29(f29::norm(by))});
                     if (a32.is_inf()) inf = true;
