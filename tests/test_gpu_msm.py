@@ -135,11 +135,11 @@ def test_size_limits_are_refused_not_truncated(zkg):
     # would need 1.6 GB of bases, so the positive side of the limit is covered by test_msm_full_size_properties
 
 
-@pytest.mark.parametrize("world", [2, 3, 8, 20])
-def test_window_sharded_partials_add_up(zkg, oracle, world):
+@pytest.mark.parametrize("n,world", [pytest.param(5000, w, id=str(w)) for w in (2, 3, 8, 20)] + [(40000, 3)])
+def test_window_sharded_partials_add_up(zkg, oracle, n, world):
     """the multi-GPU variant in which rank g owns the Pippenger windows g, g + G, ...: the G partials (each weighted by its windows'
-    2^(c w)) sum to the plain MSM, for window counts that divide, do not divide, and are smaller than G"""
-    n = 5000
+    2^(c w)) sum to the plain MSM, for window counts that divide, do not divide, and are smaller than G; at 40000 points a rank's 5 or 6
+    16-bit windows are the one plain launch between 2^16 and 2^18 buckets (the pair reduction at four buckets per lane on 29-bit records)"""
     d_b, bases, _ = dev_bases_g1(zkg, n, 77)
     sc = random_fr_canonical(n, 78)
     import torch
@@ -266,24 +266,15 @@ def _with_env(name, value, fn):
             os.environ[name] = old
 
 
-@pytest.mark.parametrize("levels", [1, 2, 3, 4])
-def test_batched_affine_levels_match_the_plain_accumulation(zkg, oracle, levels):
-    """ZKG_ACCUM_BA = levels (csrc/msm_ba.inc): the bucket lists summed as a pairwise tree of batched AFFINE additions (Montgomery's trick
-    shared by a workgroup, safegcd inversion) before the XYZZ accumulation — the same point as libff's multi_exp_inner<BDLO12> loop
-    (snark.cpp:126), bit for bit: uniform scalars against the oracle, and every exceptional pair inside the batch — equal points
-    (tangent), P + (-P), infinity as an operand, infinity as a result feeding the next level."""
+def test_exceptional_pairs_in_bucket_lists_match_the_oracle(zkg, oracle):
+    """every exceptional pair of the mixed addition as neighbours in a bucket's list — equal points (tangent), P + (-P), infinity as an
+    operand, infinity as a running sum — the same point as libff's multi_exp_inner<BDLO12> loop (snark.cpp:126), bit for bit"""
     from util import Q, from_limbs
-    n = 20000
-    _, bases, _ = dev_bases_g1(zkg, n, 0xBA0 + levels)
-    sc = random_fr_canonical(n, 0xBA1 + levels)
-    exp = oracle.msm_g1(bases, sc)
-    assert np.array_equal(_with_env("ZKG_ACCUM_BA", levels, lambda: zkg.msm_g1(bases, sc)), exp)
-    assert np.array_equal(_with_env("ZKG_BA_K", 6, lambda: _with_env("ZKG_ACCUM_BA", levels, lambda: zkg.msm_g1(bases, sc))), exp)
     # groups of four equal scalars land in one bucket; their bases are chosen so that neighbours in the bucket's list are equal, opposite
     # or at infinity (the order inside a bucket is the sort's, so several pairings of each group occur)
     n = 8192
     _, bases, _ = dev_bases_g1(zkg, n, 0xBA2)
-    sc = np.repeat(random_fr_canonical(n // 4, 0xBA3 + levels), 4, axis=0)
+    sc = np.repeat(random_fr_canonical(n // 4, 0xBA4), 4, axis=0)
 
     def negated(b):
         out = b.copy()
@@ -300,20 +291,7 @@ def test_batched_affine_levels_match_the_plain_accumulation(zkg, oracle, levels)
             bases[4 * g + 1] = q_; bases[4 * g + 2] = negated(q_); bases[4 * g + 3] = negated(p)
         else:
             bases[4 * g] = 0; bases[4 * g + 1] = 0; bases[4 * g + 2] = p; bases[4 * g + 3] = p
-    exp = oracle.msm_g1(bases, sc)
-    assert np.array_equal(zkg.msm_g1(bases, sc), exp)
-    assert np.array_equal(_with_env("ZKG_ACCUM_BA", levels, lambda: zkg.msm_g1(bases, sc)), exp)
-
-
-def test_batched_affine_levels_at_2p18(zkg):
-    """the same switch at a size where the levels are most of the work (2^18 points, 16-bit windows): equal to the default path"""
-    import torch
-    n = 1 << 18
-    d_bases, _, _ = dev_bases_g1(zkg, n, 0xBA9)
-    d_sc = torch.from_numpy(random_fr_canonical(n, 0xBAA).view(np.int64)).cuda()
-    exp = zkg.msm_g1_dev(d_bases.data_ptr(), d_sc.data_ptr(), n)
-    for levels in (2, 3):
-        assert np.array_equal(_with_env("ZKG_ACCUM_BA", levels, lambda: zkg.msm_g1_dev(d_bases.data_ptr(), d_sc.data_ptr(), n)), exp)
+    assert np.array_equal(zkg.msm_g1(bases, sc), oracle.msm_g1(bases, sc))
 
 
 @pytest.mark.parametrize("n", [3000, (1 << 19) + 777, 1 << 20])

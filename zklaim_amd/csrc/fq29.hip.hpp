@@ -139,9 +139,9 @@ ZK_D Fq from29(const Fq29 &a) {            // a: digits, value below 13 p
 // ---- inversion: constant-time safegcd (Bernstein-Yang divsteps; the layout of libsecp256k1's modinv32: nine signed 30-bit limbs, 30
 //      divsteps per round on the low limbs, the 2 x 2 transition matrix applied to (f, g) and — modulo q — to (d, e)).  libff's
 //      Fp_model::inverse() is what the reference reaches through to_affine / batch inversion; here the inversion feeds Montgomery's trick in
-//      the batched-affine accumulation (msm.hip), where ONE wavefront inverts 64 shared products for its workgroup: a Fermat chain
-//      (254 squarings + ~50 products = 300 product-times, 0.13 ms of latency on a lone wavefront) would stall the workgroup for longer than
-//      its additions take; 20 rounds of 30 divsteps are ~45 product-times, and every lane finishes in the same round count.
+//      the in-lane batched normalisations of msm.hip (inverse_fast: the table levels, the fixed-base batches): a Fermat chain is
+//      254 squarings + ~50 products = 300 product-times (0.13 ms of latency on a lone wavefront); 20 rounds of 30 divsteps are ~45
+//      product-times, and every lane finishes in the same round count.
 //      Proven bound for 256-bit inputs: 590 divsteps (20 rounds); random inputs are through after 18 — the loop leaves when every lane of
 //      the wavefront has g = 0 (further rounds change nothing: with g = 0 a round is the identity on f and d).
 __device__ static constexpr int32_t Q30[9] = {0x187cfd47, 0x3082305b, 0x071ca8d3, 0x205aa45a, 0x01585d97, 0x0116da06, 0x1a029b85, 0x139cb84c, 0x3064};

@@ -767,8 +767,6 @@ __global__ __launch_bounds__(256, WAVES) ZK_VGPR_CAP(ACC29_VGPRS) void k_bucket_
     }
 }
 
-#include "msm_ba.inc"
-
 // A point in LDS, padded to 144 B (G1) / 272 B (G2): at the natural 128 / 256-byte stride consecutive points start on the same four banks.
 // Measured effect: k_bucket_reduce 363 -> 354 us at 2^19 buckets — the kernels that use it are bound by the multiplications of their
 // addition chains (two wavefronts per SIMD: 1.16 us per dependent product), not by the LDS port.
@@ -926,6 +924,7 @@ ZK_D XYZZ<Fq> store_point29(const XYZZ29q &p) {
     if (p.is_inf()) return XYZZ<Fq>::inf().normalized();
     return {f29::from29(p.x), f29::from29(p.y), f29::from29(p.zz), f29::from29(p.zzz)};
 }
+// (only RED_L_LOG_TINY is instantiated: the longer chains take the pair and lane kernels below)
 template <int RED_L_LOG, bool IN29>
 __global__ __launch_bounds__(RedGeom<Fq>::THREADS) void k_bucket_reduce29(const void *buckets, uint32_t B, uint32_t chunks_per_window, XYZZ<Fq> *out,
                                                                           size_t in_set_stride, size_t out_set_stride, int critical) {
@@ -1314,7 +1313,6 @@ __global__ __launch_bounds__(256) void k_sum_partials(XYZZ<F> *partials_all, uin
 struct MsmGroup {                   // the base sets of one field in a launch: accumulators and the host landing zone of their chunk results
     DevBuf buckets, folded, red_out, heavy_items, heavy_buckets, heavy_counters, heavy_partials;
     DevBuf bases29;                                    // a plain G1 set's bases as 64-byte packed 29-bit records (Rec64, k_bases_to29), rebuilt per launch
-    DevBuf ba_start, ba_pre, ba_planes;                // batched-affine levels (msm_ba.inc): bucket-start bits, prefix-product scratch, the levels' coordinate planes
     void *host_red = nullptr; size_t host_cap = 0; bool g2 = false, table = false; int nsets = 0;
     int out_index[MSM_MAX_SETS] = {0};                 // position of each set among the launch's sets of this field
     int red_slots = 2; size_t red_stride = 0;                                // results per chunk (k_bucket_reduce29l: 3, see there), elements per set in red_out
@@ -1328,7 +1326,7 @@ struct MsmGroup {                   // the base sets of one field in a launch: a
         return 0;
     }
     void release() {
-        for (DevBuf *b : {&buckets, &folded, &red_out, &heavy_items, &heavy_buckets, &heavy_counters, &heavy_partials, &bases29, &ba_start, &ba_pre, &ba_planes}) b->release();
+        for (DevBuf *b : {&buckets, &folded, &red_out, &heavy_items, &heavy_buckets, &heavy_counters, &heavy_partials, &bases29}) b->release();
         if (host_red) (void)hipHostFree(host_red);
         host_red = nullptr; host_cap = 0;
     }
@@ -1349,8 +1347,7 @@ struct MsmJob {
     bool one_pass_sort = false;        // the caller knows the digits are skewed (a prover's 0/1 witness): skip the two-pass sort's attempt
     // piece-wise jobs (msm_g1_host_scalars): `resume` — this launch's accumulation continues the buckets of the launch before it;
     // `defer_reduce` — more pieces follow: no reduction, nothing copied back; `c_fixed` — every piece uses the whole job's window size
-    bool resume = false, defer_reduce = false; bool last_out29 = false;
-    hipEvent_t ev_tail = nullptr; bool tail_recorded = false;      // recorded behind the job's last accumulation (see msm_job_finish)
+    bool resume = false, defer_reduce = false;
     bool critical = false;                        // msm_job_set_critical: the accumulate / fold / reduce kernels raise their wavefronts' issue priority
     // a second job that alternates with this one over the pieces of one multi-exponentiation accumulates into THIS job's buckets
     MsmJob *bucket_owner = nullptr;
@@ -1405,80 +1402,28 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
     const size_t lanes = gr.table ? std::min(total_buckets, n_entries_max) : total_buckets;
     bool plain = !d_gather;
     for (unsigned i = 0; i < ns; ++i) plain = plain && sets[i].level_stride == 0 && sets[i].index_sub == 0 && !sets[i].remap;
-    // a plain G1 set takes the 29-bit accumulation (ZKG_ACCUM_32: the 8 x 32-bit kernel, kept for A/B runs and for several sets per launch)
-    static const bool accum32 = getenv("ZKG_ACCUM_32") != nullptr;
+    // a plain G1 set takes the 29-bit accumulation (several sets per launch keep the 8 x 32-bit kernel)
     bool use29 = false; const Rec64 *rec29 = nullptr; size_t stride29 = 0;
     if constexpr (sizeof(F) == sizeof(Fq)) {
-        if (ns == 1 && !accum32 && plain) {
+        if (ns == 1 && plain) {
             use29 = true;
             if (sets[0].p29) rec29 = reinterpret_cast<const Rec64 *>(sets[0].p29);       // the caller made the records (a piece of a piece-wise job)
             else {
-                if (job->converted_aside) ZK_HIP(hipStreamWaitEvent(s, job->ev_join, 0));   // converted beside the sort (msm_job_launch)
-                else {
-                    if (gr.bases29.reserve(n * sizeof(Rec64))) return ZKG_ERROR;
-                    hipLaunchKernelGGL(k_bases_to29, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const Affine<Fq> *>(sets[0].p), n, gr.bases29.as<Rec64>());
-                }
+                ZK_HIP(hipStreamWaitEvent(s, job->ev_join, 0));                          // converted beside the sort (msm_job_launch: the same conditions)
                 rec29 = gr.bases29.as<Rec64>();
             }
-        } else if (ns == 1 && !accum32 && !d_gather && sets[0].p29 && !sets[0].remap && sets[0].index_sub == 0) {
+        } else if (ns == 1 && !d_gather && sets[0].p29 && !sets[0].remap && sets[0].index_sub == 0) {
             use29 = true; rec29 = reinterpret_cast<const Rec64 *>(sets[0].p29); stride29 = sets[0].level_stride;      // a resident table's records
         }
     }
-    static const bool red32_env = getenv("ZKG_REDUCE_32") != nullptr;
     // plain G1 set on the 29-bit kernels: the buckets stay 29-bit records from the accumulation to the reduction
-    static const bool fold32_env = getenv("ZKG_FOLD_32") != nullptr;                                       // A/B switch: table launches keep canonical XYZZ buckets and the 32-bit fold
     // ... and so do a lone table set's (the prover's H query: accumulate -> k_bucket_fold29 -> reduce, all on the records)
     // — where the rows are few (8 after the row merge of the large tables: a bucket's rows are added in sequence, 4 us each; a one-payload key's 22
     // rows of 2048 buckets keep the 32-bit fold, a tree over the rows: 0.75 against 0.83 ms per proof)
-    const bool out29 = use29 && !red32_env && (stride29 == 0 ? !gr.table : (gr.table && ns == 1 && Wp <= 8 && !fold32_env));
-    const int resume = job->resume ? 1 : 0;
-    MsmJob *owner = job->bucket_owner ? job->bucket_owner : job;                // (whose buckets these are)
-    if (resume && !(out29 && owner->last_out29)) { set_error("msm: a piece can only continue 29-bit buckets"); return ZKG_ERROR; }
-    owner->last_out29 = out29;
+    const bool out29 = use29 && (stride29 == 0 ? !gr.table : (gr.table && ns == 1 && Wp <= 8));
+    const int resume = job->resume ? 1 : 0;                                     // (msm_g1_host_scalars' pieces: one plain G1 set with its records, so use29 and out29 hold)
     if (time_it) g_dominant_timer.begin(s);
-    bool done_ba = false;
     if constexpr (sizeof(F) == sizeof(Fq)) {
-        // batched-affine levels in front of the accumulation (msm_ba.inc): ZKG_ACCUM_BA = number of levels (1..4), ZKG_BA_K = nodes per lane
-        // (read per launch, not once: the parity tests switch it inside one process)
-        const char *e_ba = getenv("ZKG_ACCUM_BA"), *e_k = getenv("ZKG_BA_K");
-        const int ba_levels = e_ba ? std::max(0, std::min((int)ba::MAX_LEVELS, atoi(e_ba))) : 0;
-        const int ba_k = e_k ? std::max(2, std::min(32, atoi(e_k) & ~1)) : 16;
-        if (use29 && out29 && stride29 == 0 && !resume && ba_levels > 0 && n_entries_max >= 4096) {
-            const int R = ba_levels, K = ba_k;
-            const size_t per_wg = (size_t)ba::THREADS * K, words_start = n_entries_max / 32 + 2;
-            size_t stride[ba::MAX_LEVELS + 1] = {0}, plane_words = 0, grid1 = 0;
-            for (int l = 1; l <= R; ++l) {
-                const size_t nodes = (n_entries_max >> l) + 1, grid = (nodes + per_wg - 1) / per_wg;
-                stride[l] = grid * per_wg;                                     // a multiple of 512: every lane's node index stays inside the plane
-                plane_words += 18 * stride[l];
-                if (l == 1) grid1 = grid;
-            }
-            if (gr.ba_start.reserve(words_start * 4) || gr.ba_pre.reserve(grid1 * K * 9 * ba::THREADS * 4) || gr.ba_planes.reserve(plane_words * 4)) return ZKG_ERROR;
-            uint32_t *start = gr.ba_start.as<uint32_t>(), *planes = gr.ba_planes.as<uint32_t>();
-            ZK_HIP(hipMemsetAsync(start, 0, words_start * 4, s));
-            hipLaunchKernelGGL(k_ba_starts, dim3((unsigned)((total_buckets + 255) / 256)), dim3(256), 0, s, job->counts.as<uint32_t>(), job->offsets.as<uint32_t>(), total_buckets, start);
-            BaPlanes pl{}; size_t at = 0;
-            for (int l = 1; l <= R; ++l) { pl.X[l] = planes + at; pl.Y[l] = planes + at + 9 * stride[l]; pl.stride[l] = stride[l]; at += 18 * stride[l]; }
-            const uint32_t *n_entries = job->offsets.as<uint32_t>() + total_buckets;
-            for (int l = 1; l <= R; ++l) {
-                const unsigned grid = (unsigned)(stride[l] / per_wg);
-                uint32_t *oX = const_cast<uint32_t *>(pl.X[l]), *oY = const_cast<uint32_t *>(pl.Y[l]);
-                if (l == 1) {
-                    ba::Src src{rec29, job->sorted.as<uint32_t>(), nullptr, nullptr, 0};
-                    hipLaunchKernelGGL(k_ba_level<true>, dim3(grid), dim3(ba::THREADS), 0, s, src, start, n_entries, (uint32_t)l, K, oX, oY, stride[l], gr.ba_pre.as<uint32_t>());
-                } else {
-                    ba::Src src{nullptr, nullptr, pl.X[l - 1], pl.Y[l - 1], stride[l - 1]};
-                    hipLaunchKernelGGL(k_ba_level<false>, dim3(grid), dim3(ba::THREADS), 0, s, src, start, n_entries, (uint32_t)l, K, oX, oY, stride[l], gr.ba_pre.as<uint32_t>());
-                }
-            }
-            hipLaunchKernelGGL(k_bucket_accum_ba, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, rec29, job->sorted.as<uint32_t>(), pl, R, job->offsets.as<uint32_t>(),
-                               job->order.as<uint32_t>(), lanes, reinterpret_cast<Bucket29 *>(buckets), gr.heavy_items.as<HeavyItem>(), gr.heavy_buckets.as<HeavyBucket>(),
-                               gr.heavy_counters.as<uint32_t>(), L);
-            done_ba = true;
-        }
-    }
-    if (done_ba) {}
-    else if constexpr (sizeof(F) == sizeof(Fq)) {
         // wavefronts per SIMD: three (168 registers; the loop has no spill either way) when the launch has the chip to itself — a plain set sorted on
         // the job's own stream: the resident call, 1.17 -> 1.14 ms alone — and two capped at ACC29_VGPRS where something is meant to run beside it: the
         // next piece's sort of a piece-wise job, the witness multi-exponentiations of a proof (table launches)
@@ -1492,7 +1437,7 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
         if (use29 && waves29 == 3) { if (out29) launch29(k_bucket_accum29<3, true>); else launch29(k_bucket_accum29<3, false>); }
         else if (use29) { if (out29) launch29(k_bucket_accum29<2, true>); else launch29(k_bucket_accum29<2, false>); }
     }
-    if (use29 || done_ba) {}
+    if (use29) {}
     else if (plain)
         hipLaunchKernelGGL((k_bucket_accum<F, true>), dim3((unsigned)((lanes + 255) / 256), ns), dim3(256), 0, s,
                            views, job->sorted.as<uint32_t>(), job->offsets.as<uint32_t>(), job->order.as<uint32_t>(), lanes, buckets,
@@ -1502,10 +1447,6 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
                            views, job->sorted.as<uint32_t>(), job->offsets.as<uint32_t>(), job->order.as<uint32_t>(), lanes, buckets,
                            gr.heavy_items.as<HeavyItem>(), gr.heavy_buckets.as<HeavyBucket>(), gr.heavy_counters.as<uint32_t>(), L);
     if (time_it) g_dominant_timer.end(s);
-    if (!job->defer_reduce && host_pool_prewake_enabled()) {                    // (opt-in) msm_job_finish wakes the host pool when the stream gets here: what follows is 0.1 - 0.3 ms
-        if (!job->ev_tail && hipEventCreateWithFlags(&job->ev_tail, hipEventDisableTiming) != hipSuccess) job->ev_tail = nullptr;
-        job->tail_recorded = job->ev_tail && hipEventRecord(job->ev_tail, s) == hipSuccess;
-    }
     hipLaunchKernelGGL(k_heavy_parts<F>, dim3(HEAVY_PART_BLOCKS, ns), dim3(256), 256 * sizeof(LdsPoint<F>), s,
                        views, job->sorted.as<uint32_t>(), gr.heavy_items.as<HeavyItem>(), gr.heavy_counters.as<uint32_t>(), gr.heavy_partials.as<XYZZ<F>>(), buckets, L, (int)out29);
     hipLaunchKernelGGL(k_heavy_merge<F>, dim3(HEAVY_MERGE_BLOCKS, ns), dim3(256), 256 * sizeof(LdsPoint<F>), s,
@@ -1530,53 +1471,35 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
                            buckets, job->counts.as<uint32_t>(), Wp, BP, fold_b_log, gr.folded.as<XYZZ<F>>(), L);
         red_in = gr.folded.as<XYZZ<F>>(); in_stride = L.folded;
     }
-    bool reduce29 = false;
     if constexpr (sizeof(F) == sizeof(Fq)) {
-        reduce29 = !accum32 && !red32_env;                                                                 // (ZKG_REDUCE_32: A/B switch)
-        if (reduce29) {
-            const size_t lds = 2 * RG::LANES * sizeof(LdsPoint29);
-            const void *rin = red_in; XYZZ<Fq> *rout = reinterpret_cast<XYZZ<Fq> *>(gr.red_out.p);
-            static const bool red_quad = getenv("ZKG_REDUCE_QUAD") != nullptr;                            // A/B switch: round 3's quad kernel
-            auto launch_red = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)gr.nred, ns), dim3(RG::THREADS), lds, s, rin, g.B, gr.cpw, rout, in_stride, L.red_out, job->critical ? 1 : 0); };
-            auto launch_redp = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)gr.nred, ns), dim3(2 * RG::LANES), lds, s, rin, g.B, gr.cpw, rout, in_stride, L.red_out, job->critical ? 1 : 0); };
+        const size_t lds = 2 * RG::LANES * sizeof(LdsPoint29);
+        const void *rin = red_in; XYZZ<Fq> *rout = reinterpret_cast<XYZZ<Fq> *>(gr.red_out.p);
+        auto launch_red = [&](auto kern, unsigned threads) { hipLaunchKernelGGL(kern, dim3((unsigned)gr.nred, ns), dim3(threads), lds, s, rin, g.B, gr.cpw, rout, in_stride, L.red_out, job->critical ? 1 : 0); };
+        if (out29 && red_l_log == RED_L_LOG_LARGE) {
+            gr.red_slots = 3;
+            hipLaunchKernelGGL(k_bucket_reduce29l, dim3((unsigned)gr.nred, ns), dim3(2 * RG::LANES), 4 * RG::LANES * sizeof(LdsPoint29), s,
+                               reinterpret_cast<const Bucket29 *>(rin), g.B, gr.cpw, rout, in_stride, L.red_out, job->critical ? 1 : 0);
+        } else if (red_l_log != RED_L_LOG_TINY) {
+            if (red_l_log == RED_L_LOG_LARGE) launch_red(k_bucket_reduce29p<RED_L_LOG_LARGE, false>, 2 * RG::LANES);
+            else if (out29) launch_red(k_bucket_reduce29p<RED_L_LOG_SMALL, true>, 2 * RG::LANES);
+            else launch_red(k_bucket_reduce29p<RED_L_LOG_SMALL, false>, 2 * RG::LANES);
+        } else {
             // one bucket per logical lane (a table launch's folded set: the prover): the chain is 17 steps either way and the quad kernel's two
             // wavefronts per SIMD hide its LDS rounds a little better (90 against 94 us); the pair form is for the long chains
-            static const bool red_pair = getenv("ZKG_REDUCE_PAIR") != nullptr;                            // A/B switch: the pair kernel for the large reduction too
-            if (!red_quad && !red_pair && out29 && red_l_log == RED_L_LOG_LARGE) {
-                gr.red_slots = 3;
-                hipLaunchKernelGGL(k_bucket_reduce29l, dim3((unsigned)gr.nred, ns), dim3(2 * RG::LANES), 4 * RG::LANES * sizeof(LdsPoint29), s,
-                                   reinterpret_cast<const Bucket29 *>(rin), g.B, gr.cpw, rout, in_stride, L.red_out, job->critical ? 1 : 0);
-            } else if (!red_quad && red_l_log != RED_L_LOG_TINY) {
-                if (out29) {
-                    if (red_l_log == RED_L_LOG_LARGE) launch_redp(k_bucket_reduce29p<RED_L_LOG_LARGE, true>);
-                    else if (red_l_log == RED_L_LOG_SMALL) launch_redp(k_bucket_reduce29p<RED_L_LOG_SMALL, true>);
-                    else launch_redp(k_bucket_reduce29p<RED_L_LOG_TINY, true>);
-                } else {
-                    if (red_l_log == RED_L_LOG_LARGE) launch_redp(k_bucket_reduce29p<RED_L_LOG_LARGE, false>);
-                    else if (red_l_log == RED_L_LOG_SMALL) launch_redp(k_bucket_reduce29p<RED_L_LOG_SMALL, false>);
-                    else launch_redp(k_bucket_reduce29p<RED_L_LOG_TINY, false>);
-                }
-            } else if (out29) {
-                if (red_l_log == RED_L_LOG_LARGE) launch_red(k_bucket_reduce29<RED_L_LOG_LARGE, true>);
-                else if (red_l_log == RED_L_LOG_SMALL) launch_red(k_bucket_reduce29<RED_L_LOG_SMALL, true>);
-                else launch_red(k_bucket_reduce29<RED_L_LOG_TINY, true>);
-            } else {
-                if (red_l_log == RED_L_LOG_LARGE) launch_red(k_bucket_reduce29<RED_L_LOG_LARGE, false>);
-                else if (red_l_log == RED_L_LOG_SMALL) launch_red(k_bucket_reduce29<RED_L_LOG_SMALL, false>);
-                else launch_red(k_bucket_reduce29<RED_L_LOG_TINY, false>);
-            }
+            if (out29) launch_red(k_bucket_reduce29<RED_L_LOG_TINY, true>, RG::THREADS);
+            else launch_red(k_bucket_reduce29<RED_L_LOG_TINY, false>, RG::THREADS);
         }
+    } else {
+        if (red_l_log == RED_L_LOG_LARGE)
+            hipLaunchKernelGGL((k_bucket_reduce<F, RED_L_LOG_LARGE>), dim3((unsigned)gr.nred, ns), dim3(RG::THREADS), 2 * RG::LANES * sizeof(LdsPoint<F>), s,
+                               red_in, g.B, gr.cpw, gr.red_out.as<XYZZ<F>>(), in_stride, L.red_out);
+        else if (red_l_log == RED_L_LOG_SMALL)
+            hipLaunchKernelGGL((k_bucket_reduce<F, RED_L_LOG_SMALL>), dim3((unsigned)gr.nred, ns), dim3(RG::THREADS), 2 * RG::LANES * sizeof(LdsPoint<F>), s,
+                               red_in, g.B, gr.cpw, gr.red_out.as<XYZZ<F>>(), in_stride, L.red_out);
+        else
+            hipLaunchKernelGGL((k_bucket_reduce<F, RED_L_LOG_TINY>), dim3((unsigned)gr.nred, ns), dim3(RG::THREADS), 2 * RG::LANES * sizeof(LdsPoint<F>), s,
+                               red_in, g.B, gr.cpw, gr.red_out.as<XYZZ<F>>(), in_stride, L.red_out);
     }
-    if (reduce29) {}
-    else if (red_l_log == RED_L_LOG_LARGE)
-        hipLaunchKernelGGL((k_bucket_reduce<F, RED_L_LOG_LARGE>), dim3((unsigned)gr.nred, ns), dim3(RG::THREADS), 2 * RG::LANES * sizeof(LdsPoint<F>), s,
-                           red_in, g.B, gr.cpw, gr.red_out.as<XYZZ<F>>(), in_stride, L.red_out);
-    else if (red_l_log == RED_L_LOG_SMALL)
-        hipLaunchKernelGGL((k_bucket_reduce<F, RED_L_LOG_SMALL>), dim3((unsigned)gr.nred, ns), dim3(RG::THREADS), 2 * RG::LANES * sizeof(LdsPoint<F>), s,
-                           red_in, g.B, gr.cpw, gr.red_out.as<XYZZ<F>>(), in_stride, L.red_out);
-    else
-        hipLaunchKernelGGL((k_bucket_reduce<F, RED_L_LOG_TINY>), dim3((unsigned)gr.nred, ns), dim3(RG::THREADS), 2 * RG::LANES * sizeof(LdsPoint<F>), s,
-                           red_in, g.B, gr.cpw, gr.red_out.as<XYZZ<F>>(), in_stride, L.red_out);
     if (hipGetLastError() != hipSuccess) { set_error("msm kernel launch failed"); return ZKG_ERROR; }
     ZK_HIP(hipMemcpyAsync(gr.host_red, gr.red_out.p, ns * L.red_out * sizeof(XYZZ<F>), hipMemcpyDeviceToHost, s));
     return ZKG_OK;
@@ -1657,13 +1580,12 @@ static int sort_digits(MsmJob *job, const uint32_t *d_scalars, bool mont, const 
         job->order.reserve(total * 4) || job->sorted.reserve(std::max<size_t>(1, n * g.W) * 4)) return ZKG_ERROR;
     uint32_t *digits = job->digits.as<uint32_t>(), *hist = job->hist.as<uint32_t>(), *counts = job->counts.as<uint32_t>(),
              *offsets = job->offsets.as<uint32_t>(), *sums = job->scan_sums.as<uint32_t>(), *chist = job->class_hist.as<uint32_t>();
-    static const bool radix_off = getenv("ZKG_SORT_ONE_PASS") != nullptr;                       // A/B switch
     uint32_t cbits = 6;
     static const uint32_t bin_avg = getenv("ZKG_RX_AVG") ? (uint32_t)atoi(getenv("ZKG_RX_AVG")) : RX_BIN_AVG;     // tuning aid
     while (cbits < RX_MAX_CBITS && cbits + 1 < g.c - 1 && (n >> cbits) > bin_avg) ++cbits;  // bins average <= RX_BIN_AVG entries where possible, fbits >= 2
     // (below ~2^15.5 points the one-pass sort's six small launches beat the two-pass sort's eleven: a one-payload proof's H query, 2^15 - 1
     //  points, 0.657 -> 0.603 ms; equal at 2^16, the two-pass sort 5 % ahead at 2^17)
-    const bool two_pass = !radix_off && !job->one_pass_sort && g.c >= 12 && n >= 49152 && (n >> cbits) <= RX_FINE_MAX && n <= ((size_t)1 << (31 - (g.c - 1 - cbits)));
+    const bool two_pass = !job->one_pass_sort && g.c >= 12 && n >= 49152 && (n >> cbits) <= RX_FINE_MAX && n <= ((size_t)1 << (31 - (g.c - 1 - cbits)));
     {
         ZeroList zl{};
         int k = 0;
@@ -1677,7 +1599,6 @@ static int sort_digits(MsmJob *job, const uint32_t *d_scalars, bool mont, const 
             if (job->rx_meta.reserve((3 * (size_t)nbins + 8) * 4)) return ZKG_ERROR;
             zl.p[k] = job->rx_meta.as<uint32_t>(); zl.words[k++] = 3 * nbins + 8;
         }
-        static const bool generic_digits = getenv("ZKG_DIGITS_GENERIC") != nullptr;                     // A/B switch
         const dim3 dg((unsigned)((n0 + 255) / 256));                                                     // n >= 1 (msm_job_launch)
         const bool four = !d_gather && (n0 & 3) == 0 && g0.w0 == 0 && g0.ws == 1 && g0.W == g0.Wt;      // every window stored, rows 16-byte aligned
         const dim3 dg4((unsigned)((n0 / 4 + 255) / 256));
@@ -1687,10 +1608,10 @@ static int sort_digits(MsmJob *job, const uint32_t *d_scalars, bool mont, const 
             else if (g0.c == 12) hipLaunchKernelGGL(k_digits_multi<12>, dgm, dim3(256), 0, s, d_scalars, job->multi_stride, n0, (int)mont, job->merge, digits, zl);
             else hipLaunchKernelGGL(k_digits_multi_any, dgm, dim3(256), 0, s, d_scalars, job->multi_stride, n0, (int)mont, g0, job->merge, digits, zl);
         }
-        else if (!generic_digits && four && g0.c == 16) hipLaunchKernelGGL(k_digits_c4<16>, dg4, dim3(256), 0, s, d_scalars, n0, (int)mont, g0, digits, zl);
-        else if (!generic_digits && four && g0.c == 12) hipLaunchKernelGGL(k_digits_c4<12>, dg4, dim3(256), 0, s, d_scalars, n0, (int)mont, g0, digits, zl);
-        else if (!generic_digits && g0.c == 16) hipLaunchKernelGGL(k_digits_c<16>, dg, dim3(256), 0, s, d_scalars, d_gather, n0, (int)mont, g0, digits, zl);
-        else if (!generic_digits && g0.c == 12) hipLaunchKernelGGL(k_digits_c<12>, dg, dim3(256), 0, s, d_scalars, d_gather, n0, (int)mont, g0, digits, zl);
+        else if (four && g0.c == 16) hipLaunchKernelGGL(k_digits_c4<16>, dg4, dim3(256), 0, s, d_scalars, n0, (int)mont, g0, digits, zl);
+        else if (four && g0.c == 12) hipLaunchKernelGGL(k_digits_c4<12>, dg4, dim3(256), 0, s, d_scalars, n0, (int)mont, g0, digits, zl);
+        else if (g0.c == 16) hipLaunchKernelGGL(k_digits_c<16>, dg, dim3(256), 0, s, d_scalars, d_gather, n0, (int)mont, g0, digits, zl);
+        else if (g0.c == 12) hipLaunchKernelGGL(k_digits_c<12>, dg, dim3(256), 0, s, d_scalars, d_gather, n0, (int)mont, g0, digits, zl);
         else hipLaunchKernelGGL(k_digits, dg, dim3(256), 0, s, d_scalars, d_gather, n0, (int)mont, g0, digits, zl);
     }
     if (two_pass) {
@@ -1752,7 +1673,6 @@ void msm_job_destroy(MsmJob *j) {
     for (auto &gr : j->group) gr.release();
     if (j->aux) { (void)hipStreamSynchronize(j->aux); (void)hipStreamDestroy(j->aux); }
     if (j->ev_fork) (void)hipEventDestroy(j->ev_fork);
-    if (j->ev_tail) (void)hipEventDestroy(j->ev_tail);
     if (j->ev_join) (void)hipEventDestroy(j->ev_join);
     if (j->own_stream) (void)hipStreamDestroy(j->stream);
     delete j;
@@ -1789,9 +1709,8 @@ int msm_job_launch(MsmJob *job, const MsmBases *sets, int nsets, const uint32_t 
     }
     job->converted_aside = false;
     {
-        static const bool accum32 = getenv("ZKG_ACCUM_32") != nullptr, inline29 = getenv("ZKG_TO29_INLINE") != nullptr;       // A/B switches
         MsmGroup &g1 = job->group[0];
-        if (!accum32 && !inline29 && !any_table && !d_gather && g1.nsets == 1 && by_field[0][0].index_sub == 0 && !by_field[0][0].remap && !by_field[0][0].p29) {
+        if (!any_table && !d_gather && g1.nsets == 1 && by_field[0][0].index_sub == 0 && !by_field[0][0].remap && !by_field[0][0].p29) {
             if (!job->aux && (hipStreamCreateWithFlags(&job->aux, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&job->ev_fork, hipEventDisableTiming) != hipSuccess ||
                               hipEventCreateWithFlags(&job->ev_join, hipEventDisableTiming) != hipSuccess)) { set_error("msm: side stream"); return ZKG_ERROR; }
             if (g1.bases29.reserve(n * sizeof(Rec64))) return ZKG_ERROR;
@@ -1863,11 +1782,6 @@ int msm_job_finish_multi(MsmJob *job, G1 *out_g1, G2 *out_g2) {
 int msm_job_finish(MsmJob *job, G1 *out_g1, G2 *out_g2) {
     static const bool dbg = getenv("ZKG_DEBUG_TIMING") != nullptr;
     const auto t0 = std::chrono::steady_clock::now();
-    // The host's tail (host_combine) hands sixteen windows' chunk sums to the host pool the moment the stream has drained; its workers have been
-    // asleep for the whole call, and waking them through their condition variable costs that work ~12 us.  With ZKG_POOL_PREWAKE=1: wait for the last
-    // accumulation first, wake the pool then — it polls for the work while the fold / reduction run (0.1 - 0.3 ms) — and only then wait for the
-    // stream.  Off by default: see host_pool_prewake.
-    if (job->tail_recorded) { job->tail_recorded = false; if (hipEventSynchronize(job->ev_tail) == hipSuccess) host_pool_prewake(600); }
     ZK_HIP(hipStreamSynchronize(job->stream));
     const auto t1 = std::chrono::steady_clock::now();
     struct Lap { bool on; std::chrono::steady_clock::time_point a, b; ~Lap() { if (on) fprintf(stderr, "[zkg]     job finish: waited %.3f ms, host combine %.3f ms\n", std::chrono::duration<float, std::milli>(b - a).count(), std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - b).count()); } } lap_{dbg, t0, t1};
@@ -1921,8 +1835,7 @@ int msm_g1_host_scalars(const G1Affine *d_bases, const uint32_t *h_scalars, size
     if (n >= ((size_t)1 << 28)) { set_error("msm: at most 2^28 - 1 points per call"); return ZKG_ERROR; }
     if (!n) { *out = G1::inf(); return ZKG_OK; }
     static const int max_pieces = getenv("ZKG_MSM_PIECES") ? std::max(1, std::min(8, atoi(getenv("ZKG_MSM_PIECES")))) : 4;        // tuning aid (1: one upload, one launch); 2^20 points, sorts beside the accumulation (ACC29_VGPRS, sort_wave_priority): 3 / 4 / 5 pieces 1.99 / 1.94 / 2.02 ms (before: 2.19 / 2.27 / 2.41)
-    static const bool no29 = getenv("ZKG_ACCUM_32") != nullptr || getenv("ZKG_REDUCE_32") != nullptr;
-    const bool pieces = max_pieces > 1 && !no29 && n >= ((size_t)1 << 19) && n <= ((size_t)1 << 23);
+    const bool pieces = max_pieces > 1 && n >= ((size_t)1 << 19) && n <= ((size_t)1 << 23);
     if (n > ((size_t)1 << 23)) {                                                // huge: one upload, then the resident path's own 2^23-point pieces
         ScopedDevBuf tmp;
         if (tmp.reserve(n * 32)) return ZKG_ERROR;
@@ -1965,9 +1878,8 @@ int msm_g1_host_scalars(const G1Affine *d_bases, const uint32_t *h_scalars, size
     // (without the priority they crawl: k_rx_count 134 us instead of 11; and they only run BESIDE it because the accumulation leaves a
     // quarter of each SIMD's registers free and the sort's wavefronts raise their own issue priority — ACC29_VGPRS, sort_wave_priority).  The bases' 29-bit records are made once for all pieces, on
     // the side stream, under the first upload.
-    static const bool two_jobs = getenv("ZKG_MSM_PIECES_ONE_STREAM") == nullptr;                          // A/B switch
     MsmJob &K = g_piece_job;
-    if (two_jobs && !g_sort_hi) {
+    if (!g_sort_hi) {
         int lo = 0, hi = 0; (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
         // (confining this stream to 16 ... 128 compute units with a CU mask instead was measured: 2.11 -> 4.25 ... 2.70 ms — the sort needs the chip's width)
         bool ok = hipStreamCreateWithPriority(&g_sort_hi, hipStreamNonBlocking, hi) == hipSuccess;
@@ -1975,7 +1887,7 @@ int msm_g1_host_scalars(const G1Affine *d_bases, const uint32_t *h_scalars, size
         for (MsmJob *w : {&J, &K}) ok = ok && hipEventCreateWithFlags(&w->ev_sorted, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&w->ev_acc_done, hipEventDisableTiming) == hipSuccess;
         if (!ok) { g_sort_hi = nullptr; set_error("msm: sort stream"); return ZKG_ERROR; }
     }
-    hipStream_t s_hi = two_jobs ? g_sort_hi : nullptr;
+    hipStream_t s_hi = g_sort_hi;
     // all bases as 29-bit records, once (k_bases_to29 on the job's side stream: it runs under the first piece's upload)
     if (!J.aux && (hipStreamCreateWithFlags(&J.aux, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&J.ev_fork, hipEventDisableTiming) != hipSuccess ||
                    hipEventCreateWithFlags(&J.ev_join, hipEventDisableTiming) != hipSuccess)) { set_error("msm: side stream"); return ZKG_ERROR; }
@@ -1985,30 +1897,29 @@ int msm_g1_host_scalars(const G1Affine *d_bases, const uint32_t *h_scalars, size
     hipLaunchKernelGGL(k_bases_to29, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, J.aux, reinterpret_cast<const Affine<Fq> *>(d_bases), n, J.group[0].bases29.as<Rec64>());
     ZK_HIP(hipEventRecord(J.ev_join, J.aux));
     ZK_HIP(hipStreamWaitEvent(s, J.ev_join, 0));
-    if (s_hi) ZK_HIP(hipStreamWaitEvent(s_hi, J.ev_fork, 0));
+    ZK_HIP(hipStreamWaitEvent(s_hi, J.ev_fork, 0));
     const int c = (int)pick_geom(n, J.window_hint).c;                         // every piece under the whole job's window size
     const int saved_hint = J.window_hint, saved_hint_k = K.window_hint;
     J.window_hint = c; K.window_hint = c; K.bucket_owner = &J; K.w0 = 0; K.ws = 1; K.one_pass_sort = false; K.stream = s;
     int rc = ZKG_OK; bool started = false; bool used[2] = {false, false};
     for (int k = 0; k < P && rc == ZKG_OK; ++k) {
         if (cut[k + 1] == cut[k] && k + 1 < P) continue;                      // (an empty piece; the last one always runs: it carries the reduction)
-        const int which = (two_jobs && ((P - 1 - k) & 1)) ? 1 : 0;            // the last piece is the default job's: it carries the reduction and the result
+        const int which = (P - 1 - k) & 1;                                     // the last piece is the default job's: it carries the reduction and the result
         MsmJob &W = which ? K : J;
         MsmBases piece = set; piece.p = reinterpret_cast<const char *>(d_bases) + cut[k] * sizeof(G1Affine);
         piece.p29 = J.group[0].bases29.as<Rec64>() + cut[k];
         W.resume = started; W.defer_reduce = k + 1 < P; started = true;
         W.sort_stream = s_hi;
-        hipStream_t ss = s_hi ? s_hi : s;
         // this piece's sort: after its scalars have landed, and after the accumulation that last read this job's sort buffers
-        if (hipStreamWaitEvent(ss, J.ev_piece[k], 0) != hipSuccess) { rc = ZKG_ERROR; break; }
-        if (s_hi && used[which] && hipStreamWaitEvent(s_hi, W.ev_acc_done, 0) != hipSuccess) { rc = ZKG_ERROR; break; }
+        if (hipStreamWaitEvent(s_hi, J.ev_piece[k], 0) != hipSuccess) { rc = ZKG_ERROR; break; }
+        if (used[which] && hipStreamWaitEvent(s_hi, W.ev_acc_done, 0) != hipSuccess) { rc = ZKG_ERROR; break; }
         rc = msm_job_launch(&W, &piece, 1, d_sc + 8 * cut[k], cut[k + 1] - cut[k], mont, nullptr);
-        if (rc == ZKG_OK && s_hi && hipEventRecord(W.ev_acc_done, s) != hipSuccess) rc = ZKG_ERROR;
+        if (rc == ZKG_OK && hipEventRecord(W.ev_acc_done, s) != hipSuccess) rc = ZKG_ERROR;
         used[which] = true;
     }
     J.resume = false; J.defer_reduce = false; J.window_hint = saved_hint; J.sort_stream = nullptr;      // (the other entry points sort on the job's own stream)
     K.resume = false; K.defer_reduce = false; K.window_hint = saved_hint_k; K.bucket_owner = nullptr; K.sort_stream = nullptr; K.stream = nullptr;
-    if (rc != ZKG_OK) { (void)hipStreamSynchronize(J.copy); if (s_hi) (void)hipStreamSynchronize(s_hi); (void)hipStreamSynchronize(s); return ZKG_ERROR; }
+    if (rc != ZKG_OK) { (void)hipStreamSynchronize(J.copy); (void)hipStreamSynchronize(s_hi); (void)hipStreamSynchronize(s); return ZKG_ERROR; }
     return msm_job_finish(&J, out, nullptr);
 }
 
@@ -2232,7 +2143,6 @@ void msm_release_all() {
         for (auto &gr : k.group) gr.release();
         if (k.aux) { (void)hipStreamSynchronize(k.aux); (void)hipStreamDestroy(k.aux); k.aux = nullptr; }
         if (k.ev_fork) { (void)hipEventDestroy(k.ev_fork); k.ev_fork = nullptr; }
-        if (k.ev_tail) { (void)hipEventDestroy(k.ev_tail); k.ev_tail = nullptr; k.tail_recorded = false; }
         if (k.ev_join) { (void)hipEventDestroy(k.ev_join); k.ev_join = nullptr; }
         for (MsmJob *w : {&j, &k}) {
             if (w->ev_sorted) { (void)hipEventDestroy(w->ev_sorted); w->ev_sorted = nullptr; }
@@ -2243,7 +2153,6 @@ void msm_release_all() {
     if (j.copy) { (void)hipStreamSynchronize(j.copy); (void)hipStreamDestroy(j.copy); j.copy = nullptr; }
     for (auto &e : j.ev_piece) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     if (j.ev_fork) { (void)hipEventDestroy(j.ev_fork); j.ev_fork = nullptr; }
-    if (j.ev_tail) { (void)hipEventDestroy(j.ev_tail); j.ev_tail = nullptr; j.tail_recorded = false; }
     if (j.ev_join) { (void)hipEventDestroy(j.ev_join); j.ev_join = nullptr; }
 }
 

@@ -225,40 +225,32 @@ ZK_D void r1cs_long_entry(uint32_t e, uint32_t lane, const uint32_t *a_rp, const
     }
     if (lane == 0) (mtx == 0 ? aA : mtx == 1 ? aB : aC)[row] = acc.normalized();
 }
-// flag (or null): the satisfiability gate for rows without a long side, see below.  long_list (or null): the long row entries are filled in
-// by the first `long_blocks` workgroups of the SAME launch — they read z only and write what the others leave alone — instead of
-// by a launch of their own behind this one (k_r1cs_long: 12 ... 33 us and a launch boundary in front of the transforms).
+// flag (or null): the satisfiability gate for rows without a long side, see below.
 __global__ __launch_bounds__(256) void k_r1cs_eval(const uint32_t *a_rp, const uint32_t *a_col, const Fr *a_val,
                                                     const uint32_t *b_rp, const uint32_t *b_col, const Fr *b_val,
                                                     const uint32_t *c_rp, const uint32_t *c_col, const Fr *c_val,
-                                                    const Fr *z, uint32_t C, uint32_t l, size_t m, Fr *aA, Fr *aB, Fr *aC, int critical, uint32_t *flag /* or null */,
-                                                    const uint32_t *long_list /* or null */, uint32_t n_long, uint32_t long_blocks) {
+                                                    const Fr *z, uint32_t C, uint32_t l, size_t m, Fr *aA, Fr *aB, Fr *aC, int critical, uint32_t *flag /* or null */) {
     crit_wave_priority(critical);
-    if (blockIdx.x < long_blocks) {                                          // (first in the grid: their chains start with the launch, not at its tail)
-        const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-        if (wave < n_long) r1cs_long_entry(long_list[wave], threadIdx.x & 63, a_rp, a_col, a_val, b_rp, b_col, b_val, c_rp, c_col, c_val, z, aA, aB, aC);
-        return;
-    }
-    size_t i = (size_t)(blockIdx.x - long_blocks) * blockDim.x + threadIdx.x;
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
-    Fr a = Fr::zero(), b = Fr::zero(), c = Fr::zero();
-    bool la = false, lb = false, lc = false;
     if (i < C) {
-        a = row_dot_short(a_rp, a_col, a_val, z, i, la);
-        b = row_dot_short(b_rp, b_col, b_val, z, i, lb);
-        c = row_dot_short(c_rp, c_col, c_val, z, i, lc);
+        bool la = false, lb = false, lc = false;
+        const Fr a = row_dot_short(a_rp, a_col, a_val, z, i, la);
+        const Fr b = row_dot_short(b_rp, b_col, b_val, z, i, lb);
+        const Fr c = row_dot_short(c_rp, c_col, c_val, z, i, lc);
         // the satisfiability gate (snark.cpp:121-124) for this row, here where its three values are in registers: a kernel of its own over
         // the stored vectors stood 14 us (8 payloads) ... 53 us (37) in front of the transforms.  Rows with a long side: k_r1cs_check_rows.
         if (flag && !(la | lb | lc) && a * b != c) or_and_wait(flag);
-    } else if (i <= (size_t)C + l) {
-        a = z[i - C];
+        aA[i] = a.normalized();
+        aB[i] = b.normalized();
+        aC[i] = c.normalized();
+    } else {
+        aA[i] = (i <= (size_t)C + l ? z[i - C] : Fr::zero()).normalized();
+        aB[i] = Fr::zero().normalized();
+        aC[i] = Fr::zero().normalized();
     }
-    const bool keep_long = long_list != nullptr;                             // the long sides belong to the launch's first workgroups
-    if (!(keep_long && la)) aA[i] = a.normalized();
-    if (!(keep_long && lb)) aB[i] = b.normalized();
-    if (!(keep_long && lc)) aC[i] = c.normalized();
 }
-// long rows as a launch of their own (ZKG_CHECK_KERNEL=1: the round-3 sequence eval, long, check)
+// the long rows, a launch of their own behind k_r1cs_eval (see compute_h_matvec)
 __global__ __launch_bounds__(256) void k_r1cs_long(const uint32_t *list, uint32_t n_long,
                                                     const uint32_t *a_rp, const uint32_t *a_col, const Fr *a_val,
                                                     const uint32_t *b_rp, const uint32_t *b_col, const Fr *b_val,
@@ -268,16 +260,10 @@ __global__ __launch_bounds__(256) void k_r1cs_long(const uint32_t *list, uint32_
     if (wave >= n_long) return;
     r1cs_long_entry(list[wave], lane, a_rp, a_col, a_val, b_rp, b_col, b_val, c_rp, c_col, c_val, z, aA, aB, aC);
 }
-// flag[0] |= 1 when a row violates <A,z><B,z> = <C,z>: the pb.is_satisfied() gate of snark.cpp:121-124.  The last workgroup to finish
-// (ticket in flag[1]) writes the verdict straight into the caller's pinned word: no copy launch between the mat-vec and the transforms.
-__global__ __launch_bounds__(256) void k_r1cs_check(const Fr *aA, const Fr *aB, const Fr *aC, uint32_t C, uint32_t *flag, uint32_t *host_flag) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < C && aA[i] * aB[i] != aC[i]) or_and_wait(flag);
-    __syncthreads();
-    if (threadIdx.x == 0 && atomicAdd(flag + 1, 1u) == gridDim.x - 1) host_flag[0] = atomicOr(flag, 0u);
-}
-// the same gate over the rows k_r1cs_long filled in (entries of its list; a row listed twice is checked twice), behind it in stream order —
-// k_r1cs_eval has tested every other row — and the verdict to the caller's pinned word
+// flag[0] |= 1 when a row violates <A,z><B,z> = <C,z>: the pb.is_satisfied() gate of snark.cpp:121-124.  The gate over the rows k_r1cs_long
+// filled in (entries of its list; a row listed twice is checked twice), behind it in stream order — k_r1cs_eval has tested every other row.
+// The last workgroup to finish (ticket in flag[1]) writes the verdict straight into the caller's pinned word: no copy launch between the
+// mat-vec and the transforms.
 __global__ __launch_bounds__(256) void k_r1cs_check_rows(const uint32_t *list, uint32_t n_long, const Fr *aA, const Fr *aB, const Fr *aC, uint32_t *flag, uint32_t *host_flag) {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j < n_long) { const uint32_t row = list[j] & 0x3fffffffu; if (aA[row] * aB[row] != aC[row]) or_and_wait(flag); }
@@ -302,7 +288,7 @@ __global__ void k_set_one(Fr *z) { if (threadIdx.x == 0 && blockIdx.x == 0) z[0]
 // the zeros and ones and their tags and clears the proof's counters, k_scatter_full writes the listed values, tags each by its VALUE (a
 // listed 0 or 1 is a bit like any other), lists the others and tells the host how many there are — the last workgroup to finish writes
 // into the pinned words, so no fill, classify or copy launch stands between the upload and the mat-vec.
-// words: [0] satisfiability flag, [1] k_r1cs_check's ticket, [2] k_scatter_full's ticket, [3] bad listed entry; count: [0] listed, [1] a listed element misses the witness tables
+// words: [0] satisfiability flag, [1] k_r1cs_check_rows' ticket, [2] k_scatter_full's ticket, [3] bad listed entry; count: [0] listed, [1] a listed element misses the witness tables
 static constexpr uint32_t TAG_UNCLAIMED = 3;
 __global__ __launch_bounds__(256) void k_expand_tags(const uint8_t *tags, size_t n, Fr *z /* z[0] is the constant */, uint8_t *wtags, uint32_t *words, uint32_t *count) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -542,7 +528,6 @@ enum { ZW_NONE = 0, ZW_BAD_CONTEXT = 1, ZW_GENERATOR_ERROR = 2 };
 static unsigned floor_log2(size_t x) { unsigned r = 0; while (x >>= 1) ++r; return r; }
 static int compute_h_matvec(zkg_crs *crs, ProverSlot &S, const WitnessSrc &W, bool want_flag) {
     const int crit = crit_priority_for(1, floor_log2(crs->m)) ? 1 : 0;   // (see ntt_run_ex)
-    static const bool fused_check = getenv("ZKG_CHECK_KERNEL") == nullptr;                                // A/B switch: the satisfiability check as a kernel of its own over the stored vectors
     hipStream_t s = S.stream; uint32_t *flag_out = S.flag_host;
     const size_t m = crs->m;
     Fr *z = S.z.as<Fr>(), *aA = S.aABC.as<Fr>(), *aB = aA + m, *aC = aA + 2 * m;
@@ -597,26 +582,22 @@ static int compute_h_matvec(zkg_crs *crs, ProverSlot &S, const WitnessSrc &W, bo
                                     S.up_tags.as<uint8_t>(), S.wtags.as<uint8_t>(), S.wlisted.as<uint32_t>(), count, words, subset_pos, S.flag_host);
     }
     if (S.ev_ok) (void)hipEventRecord(S.ev[0], s);                      // z = [1 | w] is resident and split from here on
-    // ZKG_LONG_MERGED=1: the long rows' workgroups lead k_r1cs_eval's grid instead of being a launch of their own.  The stage gets shorter (8 payloads
-    // 0.069 -> 0.055 ms, 37 payloads 0.18 -> 0.13) and the proof does not: at 8 payloads it gets LONGER (1.13 -> 1.15 ms, three alternating runs) — the
-    // witness jobs' first small kernels used to slip onto the chip during the short launches in front of the first transform, and now find
-    // its workgroups holding every CU's LDS — and at 37 payloads it is inside the noise (3.06 against 3.08).  Off.
-    static const bool long_merged = getenv("ZKG_LONG_MERGED") != nullptr;
-    const unsigned eval_blocks = (unsigned)((m + 255) / 256), long_blocks = (fused_check && long_merged) ? (crs->n_long + 3) / 4 : 0;
-    hipLaunchKernelGGL(k_r1cs_eval, dim3(eval_blocks + long_blocks), dim3(256), 0, s,
+    // The long rows are a launch of their own.  With their workgroups leading k_r1cs_eval's grid instead the stage got shorter (8 payloads
+    // 0.069 -> 0.055 ms, 37 payloads 0.18 -> 0.13) and the proof did not: at 8 payloads it got LONGER (1.13 -> 1.15 ms, three alternating runs) — the
+    // witness jobs' first small kernels slip onto the chip during the short launches in front of the first transform, and then found
+    // its workgroups holding every CU's LDS — and at 37 payloads it was inside the noise (3.06 against 3.08).
+    hipLaunchKernelGGL(k_r1cs_eval, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s,
                        crs->A.rowptr.as<uint32_t>(), crs->A.col.as<uint32_t>(), crs->A.val.as<Fr>(),
                        crs->B.rowptr.as<uint32_t>(), crs->B.col.as<uint32_t>(), crs->B.val.as<Fr>(),
                        crs->Cm.rowptr.as<uint32_t>(), crs->Cm.col.as<uint32_t>(), crs->Cm.val.as<Fr>(),
-                       z, crs->C, crs->l, m, aA, aB, aC, crit, (want_flag && fused_check) ? words : nullptr,
-                       long_blocks ? crs->long_rows.as<uint32_t>() : nullptr, crs->n_long, long_blocks);
-    if (crs->n_long && !long_blocks)
+                       z, crs->C, crs->l, m, aA, aB, aC, crit, want_flag ? words : nullptr);
+    if (crs->n_long)
         hipLaunchKernelGGL(k_r1cs_long, dim3((crs->n_long + 3) / 4), dim3(256), 0, s, crs->long_rows.as<uint32_t>(), crs->n_long,
                            crs->A.rowptr.as<uint32_t>(), crs->A.col.as<uint32_t>(), crs->A.val.as<Fr>(),
                            crs->B.rowptr.as<uint32_t>(), crs->B.col.as<uint32_t>(), crs->B.val.as<Fr>(),
                            crs->Cm.rowptr.as<uint32_t>(), crs->Cm.col.as<uint32_t>(), crs->Cm.val.as<Fr>(), z, aA, aB, aC);
     if (want_flag) {
-        if (crs->C && fused_check) hipLaunchKernelGGL(k_r1cs_check_rows, dim3(std::max<uint32_t>(1, (crs->n_long + 255) / 256)), dim3(256), 0, s, crs->long_rows.as<uint32_t>(), crs->n_long, aA, aB, aC, words, flag_out);
-        else if (crs->C) hipLaunchKernelGGL(k_r1cs_check, dim3((crs->C + 255) / 256), dim3(256), 0, s, aA, aB, aC, crs->C, words, flag_out);
+        if (crs->C) hipLaunchKernelGGL(k_r1cs_check_rows, dim3(std::max<uint32_t>(1, (crs->n_long + 255) / 256)), dim3(256), 0, s, crs->long_rows.as<uint32_t>(), crs->n_long, aA, aB, aC, words, flag_out);
         if (S.ev_ok) (void)hipEventRecord(S.ev[3], s);
     }
     if (S.ev_ok) (void)hipEventRecord(S.ev[1], s);
@@ -767,8 +748,7 @@ static zkg_crs *zkg_crs_upload_impl(const zkg_pk *pk, bool queries_on_device = f
         if (ok) {
             DevBuf stage; const G1Affine *h_dev = (const G1Affine *)pk->H_query;
             if (!queries_on_device) { ok = upload(stage, pk->H_query, (m - 1) * 64) == 0; h_dev = stage.as<G1Affine>(); }
-            static const bool h32 = getenv("ZKG_ACCUM_32") != nullptr;                          // (A/B switch: no 29-bit records)
-            ok = ok && window_table_build_g1(crs->H_query, h_dev, m - 1, c_h, nullptr) == 0 && (h32 || window_table_records29(crs->H_query, nullptr) == 0) &&
+            ok = ok && window_table_build_g1(crs->H_query, h_dev, m - 1, c_h, nullptr) == 0 && window_table_records29(crs->H_query, nullptr) == 0 &&
                  hip_ok(hipDeviceSynchronize(), "sync", __FILE__, __LINE__);
             stage.release();
         }
@@ -1234,11 +1214,9 @@ static int prove_finish(zkg_crs *crs, ProverSlot &S, uint8_t *proof_out, size_t 
 // variable over PCIe (0.58 ms at 2^20 variables) against a read of the same bytes from host memory in 32 chunks (~0.2 ms) and an upload of one tag byte per
 // variable plus the listed values — the sparse form zkg_groth16_prove_sparse takes, built here for callers of the dense entry point.  Gives up (false: the
 // dense upload) as soon as more than 1/16 of the variables are not bits, and below 2^19 variables, where waking the pool costs what the upload did
-// (tools/r4_dense_scan_ab.sh, dense upload -> scan: 37 payloads / 2^20 domain 3.78 -> 3.53 ms, 8 payloads 1.29 -> 1.32, 2 payloads 0.78 -> 0.83).
-// ZKG_DENSE_UPLOAD=1 switches it off (A/B).
+// (measured, dense upload -> scan: 37 payloads / 2^20 domain 3.78 -> 3.53 ms, 8 payloads 1.29 -> 1.32, 2 payloads 0.78 -> 0.83).
 static bool witness_to_sparse(const uint64_t *w, size_t n, std::vector<uint8_t> &tags, std::vector<uint32_t> &idx, std::vector<uint64_t> &vals) {
-    static const bool off = getenv("ZKG_DENSE_UPLOAD") != nullptr;
-    if (off || n < ((size_t)1 << 19)) return false;
+    if (n < ((size_t)1 << 19)) return false;
     const Fr one_fr = Fr::one();
     uint64_t one[4]; memcpy(one, one_fr.v, 32);
     const size_t cap = n / 16;
