@@ -153,6 +153,37 @@ typedef struct zkg_msm_bases zkg_msm_bases;
 zkg_msm_bases *zkg_msm_g1_bases_upload(const void *d_bases, size_t n);
 int zkg_msm_g1_resident(zkg_msm_bases *bases, const void *d_scalars, size_t n, int scalars_mont, uint64_t out_jac[12], void *stream);
 void zkg_msm_g1_bases_free(zkg_msm_bases *bases);
+/* The same multi-exponentiation for a caller that stays on its stream: `count` scalar vectors over the handle's bases, the points left in
+ * DEVICE memory, no wait on the host.  Vector i is n Fr elements (n = the handle's point count) at d_scalars + i * stride * 32 bytes,
+ * stride >= n, aligned to 16 bytes; what lies between n and the stride is never read.  Point i lands at d_out_jac + i * 12 limbs, normalised
+ * exactly as zkg_msm_g1_resident returns it (X | Y | one, or (0, one, 0) for infinity): the same bytes, bit for bit.  The vectors are cut
+ * into groups of at most zkg_msm_g1_resident_batch_max; a group of several shares ONE sort, accumulation, fold and reduction (what
+ * zkg_groth16_prove_batch does with the H queries of its proofs), and a one-workgroup kernel per point (k_msm_combine) finishes the
+ * reduction's chunk sums and normalises on the device — the epilogue zkg_msm_g1_resident runs on the host.
+ * Ordering: the work runs on the handle's own stream, behind everything queued on `stream` (NULL: the null stream) at the time of the call —
+ * the work that writes d_scalars.  Before it returns the call records an event behind its last kernel and makes `stream` wait for it, so
+ * whatever the caller queues on `stream` afterwards sees the points; the host has to synchronise `stream` (or an event on it) before IT
+ * reads them.  The call itself does not wait: the caller keeps d_scalars and d_out_jac alive and unchanged until that later work has run.
+ * Calls on one handle run in call order; zkg_msm_g1_resident on the same handle stays correct beside them (it drains them first), and
+ * zkg_msm_g1_bases_free waits for the handle's stream.  The handle's workspace only grows.  A launch that needs more of any of its buffers
+ * than the handle holds — the first at a group size, and sometimes a SMALLER group after a larger one: the reduction's chunk records shrink
+ * as the group grows — waits for the handle's stream before that buffer is freed (earlier calls may still read it) and allocates, and may
+ * block; a call whose group sizes the handle has served before does neither.  zkg_msm_g1_resident takes the same care beside pending calls.
+ * Refused with ZKG_ERROR before any launch, nothing written: a null argument; n other than the handle's point count; stride < n; more
+ * than 2^24 vectors or a stride above 2^32 elements; a calling thread whose current device is not the handle's; d_scalars or d_out_jac that hipPointerGetAttributes does not report as device memory of
+ * the handle's device (pinned, managed and unregistered host memory are all refused), that is misaligned (16 / 8 bytes), or whose range runs
+ * past the end of its allocation where hipMemGetAddressRange knows it.  count == 0 is ZKG_OK and touches nothing.                          */
+int zkg_msm_g1_resident_async(zkg_msm_bases *bases, const void *d_scalars, size_t n, size_t stride /* Fr elements between vectors, >= n */, size_t count,
+                              int scalars_mont, void *d_out_jac /* count x 12 limbs, DEVICE */, void *stream);
+size_t zkg_msm_g1_resident_batch_max(const zkg_msm_bases *bases);   /* vectors one launch takes: what the sort's index space and bucket scan allow, at most 16 (the batched prover's largest launch; the workspace grows with it); >= 1, 0 for NULL */
+/* test hook: the calling thread's last zkg_msm_g1_resident_async — out[0] vectors enqueued, out[1] launch groups, out[2] host waits the
+ * entry made (one per buffer it had to grow: a stream drain and an allocation; 0 where nothing grew).  Counters, not clocks.                                  */
+void zkg_msm_resident_async_stats(size_t out[3]);
+/* test hook: the epilogue kernel alone, on chunk records the caller makes up.  records_jac (HOST): vectors x cpw x slots normalised points
+ * (12 limbs, infinity allowed) in the reduction's order — vector, chunk, slot; slots == 2: (P, U) per chunk, slots == 3: (P, T, A) with
+ * U = T + 8 A.  out_jac (HOST): per vector V = sum U_ch + 2^chunk_log * sum ch * P_ch + sum P_ch, normalised.  This reaches geometries a
+ * handle does not produce at test sizes (three slots, more chunks than the kernel has lanes).  Synchronous.                               */
+int zkg_msm_combine_gpu(const uint64_t *records_jac, size_t cpw, int slots /* 2|3 */, int chunk_log, size_t vectors, uint64_t *out_jac);
 /* Window-sharded variant for multi-GPU runs where every GPU holds every base: the partial
  * sum over the Pippenger windows first_window, first_window + window_stride, ... only, each
  * already weighted by 2^(c w) — the partials of ranks g = 0..G-1 (first_window = g,

@@ -30,6 +30,7 @@ DECLARED_SYMBOLS = [
     "zkg_fr29_op", "zkg_fq29_op", "zkg_fq29_op_chain",
     "zkg_zklaim_verify_batch", "zkg_zklaim_verify_batch_stats", "zkg_proof_decode_gpu", "zkg_zklaim_input_sums_gpu", "zkg_zklaim_input_map_mirror",
     "zkg_groth16_prove_dev", "zkg_groth16_prove_batch_dev", "zkg_prove_dev_stats",
+    "zkg_msm_g1_resident_async", "zkg_msm_g1_resident_batch_max", "zkg_msm_resident_async_stats", "zkg_msm_combine_gpu",
 ]
 # the reference's own seam, exported with its original names (zklaim.h:257-259)
 COMPAT_SYMBOLS = ["libsnark_trusted_setup", "libsnark_prove", "libsnark_verify"]
@@ -305,10 +306,43 @@ class ResidentBases:
         _check(lib().zkg_msm_g1_resident(C.c_void_p(self._h), _vp(d_scalars), C.c_size_t(self.n), SCALARS_MONT if scalars_mont else 0, _p(out), _vp(stream)), "zkg_msm_g1_resident")
         return out
 
+    def msm_async(self, d_scalars_ptr, d_out_ptr, count=1, stride=None, scalars_mont=False, stream=0):
+        """zkg_msm_g1_resident_async: `count` vectors of n Fr, `stride` elements apart (default n), at the device address d_scalars_ptr; the
+        normalised points (12 limbs each) are written to the device address d_out_ptr by work that `stream` is made to wait for.  Returns
+        without waiting: synchronise `stream` before reading the points on the host."""
+        lib().zkg_msm_g1_resident_async.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
+        _check(lib().zkg_msm_g1_resident_async(C.c_void_p(self._h), _vp(d_scalars_ptr), C.c_size_t(self.n), C.c_size_t(self.n if stride is None else stride),
+                                               C.c_size_t(count), SCALARS_MONT if scalars_mont else 0, _vp(d_out_ptr), _vp(stream)), "zkg_msm_g1_resident_async")
+
+    def batch_max(self):
+        """zkg_msm_g1_resident_batch_max: scalar vectors that share one launch sequence on this handle"""
+        lib().zkg_msm_g1_resident_batch_max.restype = C.c_size_t
+        lib().zkg_msm_g1_resident_batch_max.argtypes = [C.c_void_p]
+        return int(lib().zkg_msm_g1_resident_batch_max(C.c_void_p(self._h)))
+
     def free(self):
         if self._h:
             lib().zkg_msm_g1_bases_free.argtypes = [C.c_void_p]
             lib().zkg_msm_g1_bases_free(C.c_void_p(self._h)); self._h = None
+
+
+def msm_resident_async_stats():
+    """(vectors, launch groups, host waits) of the calling thread's last ResidentBases.msm_async"""
+    out = (C.c_size_t * 3)()
+    lib().zkg_msm_resident_async_stats(out)
+    return tuple(int(v) for v in out)
+
+
+def msm_combine_gpu(records_jac, cpw, slots, chunk_log, vectors=1):
+    """zkg_msm_combine_gpu: the MSM's device epilogue alone.  records_jac: vectors x cpw x slots normalised G1 points (12 limbs) in the order
+    vector, chunk, slot; returns (vectors, 12) normalised points."""
+    rec = _u64(records_jac)
+    if rec.size != vectors * cpw * slots * 12:
+        raise ZkgError("msm_combine_gpu: records_jac must hold vectors x cpw x slots points of 12 limbs")
+    out = np.zeros((vectors, 12), np.uint64)
+    lib().zkg_msm_combine_gpu.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_void_p]
+    _check(lib().zkg_msm_combine_gpu(_p(rec), C.c_size_t(cpw), int(slots), int(chunk_log), C.c_size_t(vectors), _p(out)), "zkg_msm_combine_gpu")
+    return out
 
 
 def msm_g1_windows_dev(d_bases, d_scalars, n, first_window, window_stride, scalars_mont=False, stream=0):

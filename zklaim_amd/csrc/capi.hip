@@ -28,8 +28,11 @@ bool hip_ok(hipError_t e, const char *what, const char *file, int line) {
     return false;
 }
 
+thread_local ReserveGuard *t_reserve_guard = nullptr;
 int DevBuf::reserve(size_t bytes) {
     if (bytes <= cap) return 0;
+    // growing frees the buffer: under a ReserveGuard (work of earlier calls may still read it) the guarded stream is drained first
+    if (t_reserve_guard) { (void)hip_ok(hipStreamSynchronize(t_reserve_guard->stream), "hipStreamSynchronize", __FILE__, __LINE__); ++t_reserve_guard->drains; }
     if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
     size_t want = bytes + bytes / 8 + 256;
     if (!hip_ok(hipMalloc(&p, want), "hipMalloc", __FILE__, __LINE__)) { p = nullptr; return 1; }
@@ -453,6 +456,21 @@ static int fq29_op_run(int op, int chain, const uint32_t *in, size_t n, uint32_t
 static std::mutex g_init_mu;
 static std::atomic<int> g_device{-1};                     // written under g_init_mu, read by entry points on any thread
 int initialised_device() { return g_device.load(); }
+// the pointer rule of the *_dev entries (zkg_groth16_prove_dev, zkg_msm_g1_resident_async): `what` must be device memory of `device` (pinned,
+// managed and unregistered host memory are refused), aligned, and `bytes` long inside its allocation where the runtime knows the allocation
+int dev_range_refused(const void *d, size_t bytes, size_t align, int device, const char *who, const char *what, const char *owner) {
+    auto refuse = [&](const std::string &why) { set_error(std::string(who) + ": " + what + " " + why); return ZKG_ERROR; };
+    if (reinterpret_cast<uintptr_t>(d) % align) return refuse("must be aligned to " + std::to_string(align) + " bytes");
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof at);
+    if (hipPointerGetAttributes(&at, d) != hipSuccess) { (void)hipGetLastError(); return refuse("is not device memory"); }
+    if (at.type != hipMemoryTypeDevice || at.isManaged || at.device != device) return refuse(std::string("is not device memory of the ") + owner + "'s device");
+    hipDeviceptr_t base = nullptr; size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)d) != hipSuccess) { (void)hipGetLastError(); return ZKG_OK; }
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(base), at_d = reinterpret_cast<uintptr_t>(d);
+    if (at_d < lo || at_d - lo > size || bytes > size - (at_d - lo)) return refuse("runs past the end of its allocation");
+    return ZKG_OK;
+}
 static void kernels_configure() { (void)ntt_configure(); (void)msm_configure(); }
 
 }  // namespace zk
@@ -588,7 +606,7 @@ int zkg_msm_g1_windows_dev(const void *d_bases, const void *d_scalars, size_t n,
     return ZKG_OK;
 }
 // ---- fixed bases kept resident with their per-window tables (what the prover's H query gets): include/zkg.h
-struct zkg_msm_bases { WindowTable table; MsmJob *job = nullptr; std::mutex mu; int device = 0; hipEvent_t ev_in = nullptr; };
+struct zkg_msm_bases { WindowTable table; MsmJob *job = nullptr; std::mutex mu; int device = 0; hipEvent_t ev_in = nullptr, ev_out = nullptr; };
 zkg_msm_bases *zkg_msm_g1_bases_upload(const void *d_bases, size_t n) {
     if (g_device < 0) { set_error("zkg_init not called"); return nullptr; }
     if (!d_bases || n == 0 || n >= ((size_t)1 << 27)) { set_error("zkg_msm_g1_bases_upload: bad argument"); return nullptr; }
@@ -596,7 +614,8 @@ zkg_msm_bases *zkg_msm_g1_bases_upload(const void *d_bases, size_t n) {
     if (!h) return nullptr;
     (void)hipGetDevice(&h->device);
     h->job = msm_job_create(nullptr, true);
-    bool ok = h->job != nullptr && hip_ok(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming), "hipEventCreate", __FILE__, __LINE__) && window_table_build_g1(h->table, (const G1Affine *)d_bases, n, table_window_bits(n), nullptr) == 0 && window_table_records29(h->table, nullptr) == 0 &&
+    bool ok = h->job != nullptr && hip_ok(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming), "hipEventCreate", __FILE__, __LINE__) &&
+              hip_ok(hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming), "hipEventCreate", __FILE__, __LINE__) && window_table_build_g1(h->table, (const G1Affine *)d_bases, n, table_window_bits(n), nullptr) == 0 && window_table_records29(h->table, nullptr) == 0 &&
               hip_ok(hipDeviceSynchronize(), "sync", __FILE__, __LINE__);
     if (!ok) { zkg_msm_g1_bases_free(h); return nullptr; }
     msm_job_set_window(h->job, h->table.c); msm_job_set_row_merge(h->job, n >= 49152 ? 2u : 1u);
@@ -608,6 +627,7 @@ void zkg_msm_g1_bases_free(zkg_msm_bases *h) {
     if (cur != h->device) (void)hipSetDevice(h->device);               // the handle's memory, stream and event live on the device it was made on
     if (h->job) { (void)hipStreamSynchronize(msm_job_stream(h->job)); msm_job_destroy(h->job); }
     if (h->ev_in) (void)hipEventDestroy(h->ev_in);
+    if (h->ev_out) (void)hipEventDestroy(h->ev_out);
     h->table.release();
     if (cur != h->device) (void)hipSetDevice(cur);
     delete h;
@@ -624,9 +644,72 @@ int zkg_msm_g1_resident(zkg_msm_bases *h, const void *d_scalars, size_t n, int s
     ZK_HIP(hipStreamWaitEvent(msm_job_stream(h->job), h->ev_in, 0));
     MsmBases b; b.p = h->table.buf.p; b.g2 = false; b.level_stride = h->table.n; b.p29 = h->table.rec29.p;
     G1 r;
-    if (msm_job_launch(h->job, &b, 1, (const uint32_t *)d_scalars, n, (scalars_mont & ZKG_SCALARS_MONT) != 0, nullptr) || msm_job_finish(h->job, &r, nullptr)) return ZKG_ERROR;
+    msm_job_set_device_finish(h->job, false);
+    int rc;
+    {   // asynchronous calls may still be running on the handle's stream: a buffer this launch has to grow is freed only after they have drained
+        ReserveGuard guard(msm_job_stream(h->job));
+        rc = msm_job_launch(h->job, &b, 1, (const uint32_t *)d_scalars, n, (scalars_mont & ZKG_SCALARS_MONT) != 0, nullptr);
+    }
+    if (rc || msm_job_finish(h->job, &r, nullptr)) return ZKG_ERROR;
     store_norm(out_jac, r);
     return ZKG_OK;
+}
+// ---- zkg_msm_g1_resident_async: the same multi-exponentiation for `count` scalar vectors, the points left in DEVICE memory, no host wait.
+static thread_local size_t t_resident_async_stats[3];
+// Vectors per launch: what msm_multi_supported allows (the sort's 32-bit index space and its 2^22-bucket scan), and never more than
+// MSM_MULTI_MAX_VECTORS, the largest batch the prover runs through msm_job_launch_multi — the workspace grows linearly with the group (at 2^12-bit
+// windows of 5000 points 128 vectors would ask for 0.6 GB of buckets for a 0.6 MB scalar batch) and nothing above that size is exercised.
+size_t zkg_msm_g1_resident_batch_max(const zkg_msm_bases *h) {
+    if (!h) return 0;
+    size_t p = MSM_MULTI_MAX_VECTORS;
+    while (p > 1 && !msm_multi_supported(h->table.n, h->table.c, (uint32_t)p)) --p;
+    return p;
+}
+void zkg_msm_resident_async_stats(size_t out[3]) { if (out) for (int i = 0; i < 3; ++i) out[i] = t_resident_async_stats[i]; }
+int zkg_msm_g1_resident_async(zkg_msm_bases *h, const void *d_scalars, size_t n, size_t stride, size_t count, int scalars_mont, void *d_out_jac, void *stream) {
+    static const char *who = "zkg_msm_g1_resident_async";
+    for (size_t &v : t_resident_async_stats) v = 0;
+    if (count == 0) return ZKG_OK;                                      // nothing to do, nothing touched
+    REQUIRE_INIT();
+    if (!h || !d_scalars || !d_out_jac || n != h->table.n) { set_error(std::string(who) + ": bad argument (n must be the handle's point count)"); return ZKG_ERROR; }
+    if (stride < n) { set_error(std::string(who) + ": stride must be at least n"); return ZKG_ERROR; }
+    if (count > ZKG_MSM_ASYNC_MAX_COUNT || stride > ZKG_MSM_ASYNC_MAX_STRIDE) { set_error(std::string(who) + ": at most 2^24 vectors, at most 2^32 elements apart"); return ZKG_ERROR; }
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != h->device) { (void)hipGetLastError(); set_error(std::string(who) + ": the calling thread's device is not the one the bases were uploaded on"); return ZKG_ERROR; }
+    if (dev_range_refused(d_scalars, ((count - 1) * stride + n) * 32, 16, h->device, who, "d_scalars", "handle") ||
+        dev_range_refused(d_out_jac, count * 96, 8, h->device, who, "d_out_jac", "handle")) return ZKG_ERROR;
+    const size_t bmax = zkg_msm_g1_resident_batch_max(h);
+    const bool mont = (scalars_mont & ZKG_SCALARS_MONT) != 0;
+    const uint32_t *sc = (const uint32_t *)d_scalars; uint64_t *out = (uint64_t *)d_out_jac;
+    std::lock_guard<std::mutex> lk(h->mu);                              // held for the enqueue only: calls on one handle run in call order on its stream
+    hipStream_t js = msm_job_stream(h->job);
+    ZK_HIP(hipEventRecord(h->ev_in, (hipStream_t)stream));              // behind the work that writes d_scalars (nothing is enqueued yet)
+    ZK_HIP(hipStreamWaitEvent(js, h->ev_in, 0));
+    MsmBases b; b.p = h->table.buf.p; b.g2 = false; b.level_stride = h->table.n; b.p29 = h->table.rec29.p;
+    msm_job_set_device_finish(h->job, true);
+    int rc = ZKG_OK;
+    size_t groups = 0, waits = 0, done = 0;
+    while (done < count && rc == ZKG_OK) {
+        const size_t g = std::min(bmax, count - done);
+        // The job's buffers only grow, but which of them a group needs more of does not follow from its size alone (the reduction's chunk records
+        // shrink as the group grows): every reserve that has to grow drains the handle's stream before it frees the buffer — earlier groups and
+        // earlier calls may still read it — and is counted.  A launch whose buffers all suffice allocates nothing and waits for nothing.
+        ReserveGuard guard(js);
+        const uint32_t *sg = sc + done * stride * 8;
+        rc = g > 1 ? msm_job_launch_multi(h->job, &b, 1, sg, n, stride * 8, (uint32_t)g, mont) : msm_job_launch(h->job, &b, 1, sg, n, mont, nullptr);
+        if (rc == ZKG_OK) rc = msm_job_finish_dev(h->job, out + done * 12);
+        waits += guard.drains;
+        if (rc == ZKG_OK) { done += g; ++groups; }
+    }
+    // whatever the caller queues on `stream` after this call sees the points — after a failure too: the groups enqueued before it still write theirs
+    const bool ordered = hip_ok(hipEventRecord(h->ev_out, js), "hipEventRecord", __FILE__, __LINE__) &&
+                         hip_ok(hipStreamWaitEvent((hipStream_t)stream, h->ev_out, 0), "hipStreamWaitEvent", __FILE__, __LINE__);
+    t_resident_async_stats[0] = done; t_resident_async_stats[1] = groups; t_resident_async_stats[2] = waits;
+    return rc == ZKG_OK && ordered ? ZKG_OK : ZKG_ERROR;
+}
+int zkg_msm_combine_gpu(const uint64_t *records_jac, size_t cpw, int slots, int chunk_log, size_t vectors, uint64_t *out_jac) {
+    REQUIRE_INIT();
+    return msm_combine_records(records_jac, cpw, slots, chunk_log, vectors, out_jac);
 }
 int zkg_msm_g2_dev(const void *d_bases, const void *d_scalars, size_t n, int scalars_mont, uint64_t out_jac[24], void *stream) {
     REQUIRE_INIT();

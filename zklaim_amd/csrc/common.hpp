@@ -27,6 +27,18 @@ struct DevBuf {
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// While one is alive on a thread, every DevBuf::reserve of that thread that has to GROW (free and reallocate) first waits for `stream`: for
+// workspaces that asynchronous work queued on that stream may still read (zkg_msm_g1_resident_async).  drains counts those waits.
+struct ReserveGuard;
+extern thread_local ReserveGuard *t_reserve_guard;
+struct ReserveGuard {
+    hipStream_t stream; size_t drains = 0; ReserveGuard *prev;
+    explicit ReserveGuard(hipStream_t s) : stream(s), prev(t_reserve_guard) { t_reserve_guard = this; }
+    ReserveGuard(const ReserveGuard &) = delete;
+    ReserveGuard &operator=(const ReserveGuard &) = delete;
+    ~ReserveGuard() { t_reserve_guard = prev; }
+};
+
 // a DevBuf that lives for one scope (staging of a key load, of a table build): released on every way out, an exception's included.
 // DevBuf itself has no destructor on purpose — resident buffers are members of objects with explicit lifetimes and are copied into caches.
 struct ScopedDevBuf : DevBuf {
@@ -150,8 +162,16 @@ int msm_job_finish(MsmJob *job, G1 *out_g1, G2 *out_g2);   // out_g1[k]: k-th G1
 // the dual: `count` scalar vectors of n elements, scalar_stride 32-bit words apart, over the same table sets (all windows, no gather /
 // remap / index_sub), as one launch sequence; out_g1[p * (G1 sets) + k] = vector p over the k-th G1 set, out_g2 likewise
 bool msm_multi_supported(size_t n, int c, uint32_t count);
+static constexpr uint32_t MSM_MULTI_MAX_VECTORS = 16;       // the largest `count` a caller passes: the batched prover's chunk, zkg_msm_g1_resident_batch_max
+static constexpr size_t ZKG_MSM_ASYNC_MAX_COUNT = (size_t)1 << 24, ZKG_MSM_ASYNC_MAX_STRIDE = (size_t)1 << 32;   // zkg_msm_g1_resident_async: vectors per call, elements between vectors
 int msm_job_launch_multi(MsmJob *job, const MsmBases *sets, int nsets, const uint32_t *d_scalars, size_t n, size_t scalar_stride, uint32_t count, bool scalars_mont);
 int msm_job_finish_multi(MsmJob *job, G1 *out_g1, G2 *out_g2);
+// The asynchronous end of a TABLE launch of G1 sets.  msm_job_set_device_finish(job, true) before the launch: its chunk records are not copied
+// to the host.  msm_job_finish_dev then queues the epilogue kernel (k_msm_combine) on the job's stream and returns without synchronising:
+// d_out (device, 12 limbs per point, normalised as store_norm writes them) gets point (p * sets + k) for vector p and the k-th set.
+void msm_job_set_device_finish(MsmJob *j, bool on);
+int msm_job_finish_dev(MsmJob *job, uint64_t *d_out);
+int msm_combine_records(const uint64_t *records_jac, size_t cpw, int slots, int chunk_log, size_t vectors, uint64_t *out_jac);   // zkg_msm_combine_gpu
 // the multi_exp_with_mixed_addition split of a witness z = [1 | w] (n1 elements, Montgomery): tags (0 zero, 1 one, 2 other), the
 // indices of the others and their count; and the flat sum of the bases tagged one (result lands in pinned host memory)
 // d_count: two words, [0] the number of listed elements, [1] set to 1 when a listed element has no entry in d_subset_pos (optional: position of
@@ -213,6 +233,8 @@ static constexpr size_t ZV_SUM_SLICES = 16;
 int verify_zklaim_input_sums(const uint8_t *d_pub, uint32_t npl, size_t base, const uint32_t *d_w, const uint8_t *d_mask, size_t lo, size_t hi,
                              void *d_part, void *d_out, hipStream_t s);
 int initialised_device();                                // the device zkg_init selected, -1 before (capi.hip)
+// ZKG_ERROR (message "<who>: <what> ...") unless d is `bytes` of device memory of `device`, aligned to `align` (capi.hip); owner: "key", "handle"
+int dev_range_refused(const void *d, size_t bytes, size_t align, int device, const char *who, const char *what, const char *owner);
 // a batch call's device workspace: grow-only buffer, two streams (the subgroup check runs beside the scalar multiplications), two events
 struct VerifyWorkspace { DevBuf buf; hipStream_t s = nullptr, s2 = nullptr; hipEvent_t ev = nullptr, ev2 = nullptr; };
 VerifyWorkspace *verify_workspace_acquire();             // a free one or a new one; null on a HIP failure (message set)

@@ -27,6 +27,8 @@
 //   7. k_bucket_reduce sum_b (b+1)*B_b per chunk of 128 ... 2048 buckets: per-lane running sums, then an LDS suffix
 //                      scan + tree reduction across the workgroup; every addition is shared by a DPP quad
 //   8. host            per-window chunk combine and the c-doublings Horner across windows
+//   8'. k_msm_combine  the same combine on the device for a table launch (no Horner there): the points stay in device memory and the job
+//                      ends without a host synchronisation (msm_job_finish_dev, zkg_msm_g1_resident_async)
 // Zero scalars are dropped in step 1 and scalars equal to one simply land in bucket (window 0, digit 1),
 // a "heavy" bucket: the effect of libff's multi_exp_with_mixed_addition prefilter without a special case.
 //
@@ -1356,6 +1358,7 @@ struct MsmJob {
     hipStream_t sort_stream = nullptr; hipEvent_t ev_sorted = nullptr, ev_acc_done = nullptr;
     uint32_t w0 = 0, ws = 1;           // window subset of the next launches (window-sharded multi-GPU runs)
     bool empty = false;
+    bool dev_finish = false;           // msm_job_set_device_finish: the next launches end in msm_job_finish_dev — their chunk records stay on the device
     // msm_job_launch_multi: `multi` scalar vectors, multi_stride words apart, over one table; the geometry then has W * multi rows (k_digits_multi)
     uint32_t multi = 1; size_t multi_stride = 0;
     // bases resident, scalars in host memory (msm_g1_host_scalars): device copy of the scalars, the copy stream and one event per piece
@@ -1388,7 +1391,7 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
     if (gr.heavy_items.reserve(ns * max_items * sizeof(HeavyItem)) || gr.heavy_buckets.reserve(ns * max_heavy * sizeof(HeavyBucket)) ||
         gr.heavy_counters.reserve(8 * MSM_MAX_SETS) || gr.heavy_partials.reserve(ns * max_items * sizeof(XYZZ<F>)) ||
         bucket_buf.reserve(ns * total_buckets * std::max(sizeof(XYZZ<F>), sizeof(Bucket29))) || gr.red_out.reserve(ns * L.red_out * sizeof(XYZZ<F>)) || ((gr.red_stride = L.red_out), false) ||
-        (gr.table && gr.folded.reserve(ns * (size_t)BP * std::max(sizeof(XYZZ<F>), sizeof(Bucket29)))) || gr.host_reserve(ns * L.red_out * sizeof(XYZZ<F>))) return ZKG_ERROR;
+        (gr.table && gr.folded.reserve(ns * (size_t)BP * std::max(sizeof(XYZZ<F>), sizeof(Bucket29)))) || (!job->dev_finish && gr.host_reserve(ns * L.red_out * sizeof(XYZZ<F>)))) return ZKG_ERROR;
     // (gr.heavy_counters: cleared by the job's k_digits)
     XYZZ<F> *buckets = bucket_buf.as<XYZZ<F>>();
     ViewSet<F> views;
@@ -1501,6 +1504,7 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
                                red_in, g.B, gr.cpw, gr.red_out.as<XYZZ<F>>(), in_stride, L.red_out);
     }
     if (hipGetLastError() != hipSuccess) { set_error("msm kernel launch failed"); return ZKG_ERROR; }
+    if (job->dev_finish) return ZKG_OK;                                         // msm_job_finish_dev reads gr.red_out where it is
     ZK_HIP(hipMemcpyAsync(gr.host_red, gr.red_out.p, ns * L.red_out * sizeof(XYZZ<F>), hipMemcpyDeviceToHost, s));
     return ZKG_OK;
 }
@@ -1563,6 +1567,69 @@ static XYZZ<F> host_combine(const MsmJob *job, const MsmGroup &gr, int set, int 
     if (!acc.is_inf()) for (uint32_t i = 0; i < g.c * g.w0; ++i) acc = acc.dbl();
     return acc;
 }
+
+// ---- 8'. the same epilogue on the device for a TABLE launch of G1 sets (msm_job_finish_dev): host_combine's window(w), no Horner.
+//      One workgroup per output point (blockIdx.x = the window of the reduction, i.e. the scalar vector of a multi launch; blockIdx.y = set).
+//      Lanes own chunks: n = the power of two that covers cpw (COMBINE_THREADS at the most) lanes take 2^l consecutive chunks each — one chunk
+//      in every geometry a table produces (cpw <= 256) — and sum them as host_combine's walk does (S = sum P, T0 = sum (ch - first) P, U, A).
+//      sum_ch ch P_ch = 2^l sum_{t >= 1} Q_t + sum_t T0_t with Q the inclusive suffix scan of S over the lanes (Hillis-Steele through LDS, as
+//      k_bucket_reduce's), so every lane weighs its own term — 2^chunk_log (2^l Q_t + T0_t), chunk_log + l doublings side by side — adds it to
+//      its U (+ 8 A), lane 0 adds Q_0 = sum P, and ONE tree (lds_tree_reduce) sums the lanes.  Chain: log2 n + 3 additions, chunk_log + l
+//      doublings, log2 n tree levels, one inversion.  Lane 0 stores the point as store_norm does: X | Y | one, or (0, one, 0) for infinity.
+static constexpr int COMBINE_THREADS = 256;
+ZK_D void store_norm_dev(uint32_t *out /* 24 words */, const XYZZ<Fq> &v) {
+    Fq X = Fq::zero(), Y = Fq::one(), Z = Fq::zero();
+    if (!v.is_inf()) { const Affine<Fq> a = v.to_affine().normalized(); X = a.x; Y = a.y; Z = Fq::one(); }
+    for (int i = 0; i < 8; ++i) { out[i] = X.v[i]; out[8 + i] = Y.v[i]; out[16 + i] = Z.v[i]; }
+}
+__global__ __launch_bounds__(COMBINE_THREADS) void k_msm_combine(const XYZZ<Fq> *red, uint32_t cpw, int slots, int chunk_log, size_t set_stride, uint32_t *out) {
+    extern __shared__ unsigned char red_smem[];
+    LdsPoint<Fq> *sh = reinterpret_cast<LdsPoint<Fq> *>(red_smem);            // n points
+    const uint32_t t = threadIdx.x, w = blockIdx.x, set = blockIdx.y;
+    uint32_t n = 1; while (n < cpw && n < (uint32_t)COMBINE_THREADS) n <<= 1;
+    int l_log = 0; while (((uint64_t)n << l_log) < cpw) ++l_log;
+    const XYZZ<Fq> *rec = red + (size_t)set * set_stride + (size_t)slots * w * cpw;
+    const uint64_t first = (uint64_t)t << l_log, end = first + ((uint64_t)1 << l_log) < cpw ? first + ((uint64_t)1 << l_log) : cpw;
+    XYZZ<Fq> U = XYZZ<Fq>::inf(), S = XYZZ<Fq>::inf(), T0 = XYZZ<Fq>::inf(), A = XYZZ<Fq>::inf();
+    for (uint64_t ch = end; ch > first; --ch) {                              // chunks end - 1 ... first (none for a lane behind the last chunk)
+        const XYZZ<Fq> *r = rec + (size_t)slots * (ch - 1);
+        S.add(r[0]); U.add(r[1]);
+        if (slots == 3) A.add(r[2]);
+        if (ch - 1 > first) T0.add(S);
+    }
+    XYZZ<Fq> Q = S;
+    for (uint32_t d = 1; d < n; d <<= 1) {
+        if (t < n) sh[t] = Q;
+        __syncthreads();
+        if (t + d < n) Q.add(sh[t + d]);
+        __syncthreads();
+    }
+    XYZZ<Fq> Wt = t >= 1 ? Q : XYZZ<Fq>::inf();
+    for (int i = 0; i < l_log; ++i) Wt = Wt.dbl();
+    Wt.add(T0);
+    for (int i = 0; i < chunk_log; ++i) Wt = Wt.dbl();                       // * buckets per chunk (dbl() returns infinity as it is: lanes whose term is infinity idle through the loop, where host_combine skips it)
+    if (slots == 3) { for (int i = 0; i < 3; ++i) A = A.dbl(); U.add(A); }    // U = T + 8 A (k_bucket_reduce29l)
+    U.add(Wt);
+    if (t == 0) U.add(Q);                                                    // Q_0 = sum_ch P_ch
+    if (t < n) sh[t] = U;
+    __syncthreads();
+    lds_tree_reduce<Fq>(sh, n, t, COMBINE_THREADS, [] { __syncthreads(); });
+    if (t == 0) store_norm_dev(out + 24 * ((size_t)w * gridDim.y + set), sh[0]);
+}
+// an empty job's points (no window owned): the infinity encoding
+__global__ __launch_bounds__(64) void k_msm_store_inf(uint32_t *out, uint32_t count) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) store_norm_dev(out + 24 * (size_t)i, XYZZ<Fq>::inf());
+}
+// the test hook's records: normalised Jacobian points (X | Y | Z, Z = one or zero) -> the reduction's record form
+__global__ __launch_bounds__(256) void k_jac_to_records(const uint32_t *jac, size_t count, XYZZ<Fq> *rec) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    Fq X, Y, Z;
+    for (int k = 0; k < 8; ++k) { X.v[k] = jac[24 * i + k]; Y.v[k] = jac[24 * i + 8 + k]; Z.v[k] = jac[24 * i + 16 + k]; }
+    rec[i] = Z.is_zero() ? XYZZ<Fq>::inf() : XYZZ<Fq>{X, Y, Fq::one(), Fq::one()};
+}
+static size_t combine_lds_bytes(uint32_t cpw) { uint32_t n = 1; while (n < cpw && n < (uint32_t)COMBINE_THREADS) n <<= 1; return n * sizeof(LdsPoint<Fq>); }
 
 static int sort_digits(MsmJob *job, const uint32_t *d_scalars, bool mont, const uint32_t *d_gather) {
     const MsmGeom g0 = job->g; const size_t n0 = job->n;                        // as the scalars see them (k_digits)
@@ -1787,6 +1854,44 @@ int msm_job_finish(MsmJob *job, G1 *out_g1, G2 *out_g2) {
     struct Lap { bool on; std::chrono::steady_clock::time_point a, b; ~Lap() { if (on) fprintf(stderr, "[zkg]     job finish: waited %.3f ms, host combine %.3f ms\n", std::chrono::duration<float, std::milli>(b - a).count(), std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - b).count()); } } lap_{dbg, t0, t1};
     for (int k = 0; k < job->group[0].nsets; ++k) out_g1[k] = job->empty ? G1::inf() : host_combine<Fq>(job, job->group[0], k);
     for (int k = 0; k < job->group[1].nsets; ++k) out_g2[k] = job->empty ? G2::inf() : host_combine<Fq2>(job, job->group[1], k);
+    return ZKG_OK;
+}
+
+void msm_job_set_device_finish(MsmJob *j, bool on) { if (j) j->dev_finish = on; }
+// The device epilogue of a launch made under msm_job_set_device_finish: nothing is copied back and nothing is waited for.  k_msm_combine goes
+// onto the job's stream behind the reduction with the launch's geometry by value, and writes the points of the launch's G1 table sets where
+// msm_job_finish / msm_job_finish_multi would return them — d_out[(p * sets + k) * 12 limbs], normalised as store_norm does.
+int msm_job_finish_dev(MsmJob *job, uint64_t *d_out) {
+    const MsmGroup &gr = job->group[0];
+    if (!job->dev_finish || job->group[1].nsets || gr.nsets < 1) { set_error("msm_job_finish_dev: a device-finish launch of G1 sets only"); return ZKG_ERROR; }
+    const uint32_t vectors = job->multi > 1 ? job->multi : 1;
+    uint32_t *out = reinterpret_cast<uint32_t *>(d_out);
+    if (job->empty) {
+        const uint32_t count = vectors * (uint32_t)gr.nsets;
+        hipLaunchKernelGGL(k_msm_store_inf, dim3((count + 63) / 64), dim3(64), 0, job->stream, out, count);
+    } else {
+        if (!gr.table || gr.red_windows != vectors) { set_error("msm_job_finish_dev: table sets only (a plain set's windows need the Horner doublings)"); return ZKG_ERROR; }
+        hipLaunchKernelGGL(k_msm_combine, dim3(vectors, (unsigned)gr.nsets), dim3(COMBINE_THREADS), combine_lds_bytes(gr.cpw), job->stream,
+                           gr.red_out.as<XYZZ<Fq>>(), gr.cpw, gr.red_slots, gr.chunk_log, gr.red_stride, out);
+    }
+    if (hipGetLastError() != hipSuccess) { set_error("msm combine launch failed"); return ZKG_ERROR; }
+    return ZKG_OK;
+}
+// zkg_msm_combine_gpu: k_msm_combine alone on records the caller makes up.  records_jac: vectors x cpw x slots normalised points in the
+// reduction's order (vector, chunk, slot); out_jac: one normalised point per vector.  Host pointers; synchronous.
+int msm_combine_records(const uint64_t *records_jac, size_t cpw, int slots, int chunk_log, size_t vectors, uint64_t *out_jac) {
+    if (!records_jac || !out_jac || cpw < 1 || cpw > ((size_t)1 << 16) || (slots != 2 && slots != 3) || chunk_log < 0 || chunk_log > 24 || vectors < 1 || vectors > 1024) {
+        set_error("zkg_msm_combine_gpu: bad argument (1 <= cpw <= 2^16, slots 2 or 3, 0 <= chunk_log <= 24, 1 <= vectors <= 1024)"); return ZKG_ERROR;
+    }
+    const size_t count = vectors * cpw * (size_t)slots;
+    ScopedDevBuf in, rec, out;
+    if (in.reserve(count * 96) || rec.reserve(count * sizeof(XYZZ<Fq>)) || out.reserve(vectors * 96)) return ZKG_ERROR;
+    ZK_HIP(hipMemcpy(in.p, records_jac, count * 96, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_jac_to_records, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, nullptr, in.as<uint32_t>(), count, rec.as<XYZZ<Fq>>());
+    hipLaunchKernelGGL(k_msm_combine, dim3((unsigned)vectors, 1), dim3(COMBINE_THREADS), combine_lds_bytes((uint32_t)cpw), nullptr,
+                       rec.as<XYZZ<Fq>>(), (uint32_t)cpw, slots, chunk_log, (size_t)0, out.as<uint32_t>());
+    if (hipGetLastError() != hipSuccess) { set_error("msm combine launch failed"); return ZKG_ERROR; }
+    ZK_HIP(hipMemcpy(out_jac, out.p, vectors * 96, hipMemcpyDeviceToHost));     // (waits for the null stream)
     return ZKG_OK;
 }
 

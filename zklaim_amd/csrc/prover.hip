@@ -1320,7 +1320,7 @@ static int groth16_prove_zklaim_impl(const zkg_crs *crs_, const zklaim_ctx *ctx,
 // sharded H query do not.  16 proofs up to m = 2^15, 8 above: the H launch's P x W x B buckets stay within the block scan of the digit sort.
 static uint32_t batch_chunk_for(const zkg_crs *crs) {
     if ((!crs->dom && !crs->sdom) || crs->m >= ((size_t)1 << 18) || crs->m < 2 || !crs->n || !crs->h_shards.empty()) return 0;
-    const uint32_t P = (crs->m <= ((size_t)1 << 15) && crs->c_w_forced < 15) ? 16 : 8;               // (a forced 15- or 16-bit witness window: as the large H windows)
+    const uint32_t P = (crs->m <= ((size_t)1 << 15) && crs->c_w_forced < 15) ? MSM_MULTI_MAX_VECTORS : MSM_MULTI_MAX_VECTORS / 2;               // (a forced 15- or 16-bit witness window: as the large H windows)
     return msm_multi_supported(crs->m - 1, crs->H_query.c, P) ? P : 0;
 }
 static void batch_destroy(BatchWs &B) {
@@ -1633,16 +1633,7 @@ static int dev_witness_refused(const zkg_crs *crs, const void *d, size_t elems, 
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess || cur != crs->device) { (void)hipGetLastError(); return refuse("the calling thread's device is not the key's"); }
     if (!elems) return ZKG_OK;                                                  // (a key without variables: nothing is read)
-    if (reinterpret_cast<uintptr_t>(d) % alignof(Fr)) return refuse("the witness must be aligned to 16 bytes");
-    hipPointerAttribute_t at;
-    memset(&at, 0, sizeof at);
-    if (hipPointerGetAttributes(&at, d) != hipSuccess) { (void)hipGetLastError(); return refuse("the witness is not device memory"); }
-    if (at.type != hipMemoryTypeDevice || at.isManaged || at.device != crs->device) return refuse("the witness is not device memory of the key's device");
-    hipDeviceptr_t base = nullptr; size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)d) != hipSuccess) { (void)hipGetLastError(); return ZKG_OK; }
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(base), at_d = reinterpret_cast<uintptr_t>(d);
-    if (at_d < lo || at_d - lo > size || elems > (size - (at_d - lo)) / 32) return refuse("the witness runs past the end of its allocation");
-    return ZKG_OK;
+    return dev_range_refused(d, elems * 32, alignof(Fr), crs->device, who, "the witness", "key");
 }
 // one proof from n elements at d_w, behind `stream`; counts into t_prove_dev_stats (the entries reset it)
 static int prove_dev_one(zkg_crs *crs, const Fr *d_w, const uint64_t r_[4], const uint64_t s_[4], int check_satisfied, uint8_t *proof_out, size_t *proof_len, hipStream_t stream) {
