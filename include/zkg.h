@@ -426,6 +426,28 @@ void zkg_verify_batch_stats(size_t out[3]);
  * contributes 1), serialised as zkg_pairing_probe's output.  Miller loops and their product on the GPU, the final exponentiation on
  * the host.  ZKG_ERROR for a point off its curve or a coordinate >= q.                                                          */
 int zkg_pairing_product(const uint64_t *g1_affine, const uint64_t *g2_affine, size_t n, uint8_t out[384]);
+/* ---- per-proof verification on the GPU: every item decided by its OWN equation
+ *      FE(ML(A,B) ML(-acc,gamma) ML(-C,delta)) == alpha_beta, Miller loops and final exponentiation on the GPU, all items side by side.
+ *      verdicts[i] == zkg_groth16_verify(items[i]) exactly (0 / 1 / 2): no random weights, no bisection, no probability attached, and a
+ *      cost that does not depend on how many proofs are bad.  Nothing is asked of B or of the key's gamma, delta and alpha_beta beyond
+ *      what zkg_groth16_verify asks (no subgroup tests).  The device decides an item whose key parses and holds canonical limbs, whose
+ *      sizes fit and whose points and inputs are canonical and decode; everything else goes through zkg_groth16_verify's own code on the
+ *      host pool.  Synchronous; host pointers; safe from several threads at once and beside the other verify entries.  ZKG_OK when every
+ *      verdict was written; count == 0 and null arguments behave as zkg_groth16_verify_batch's do.                                      */
+int  zkg_groth16_verify_each(const zkg_verify_item *items, size_t count, uint8_t *verdicts);
+/* the calling thread's last zkg_groth16_verify_each: out[0] items decided by the device equation, out[1] items decided by the single
+ * verifier's code, out[2] device rounds (chunks launched) */
+void zkg_verify_each_stats(size_t out[3]);
+/* test hook: positions per device round of zkg_groth16_verify_each (process-wide); 0 restores the default (64 MiB of staging) */
+void zkg_verify_each_set_chunk(size_t positions);
+/* reduced pairing product per ITEM, Miller loops AND final exponentiation on the GPU: item i uses pairs i*pairs .. i*pairs+pairs-1
+ * (layouts and infinity rule as zkg_pairing_product); out: items x 384 bytes, each as zkg_pairing_probe writes one.  ZKG_ERROR for a
+ * point off its curve or a coordinate >= q, and without a GPU (zkg_init).                                                       */
+int  zkg_pairing_each(const uint64_t *g1_affine, const uint64_t *g2_affine, size_t items, size_t pairs, uint8_t *out);
+/* test hook: the final exponentiation alone on n serialised Fq12 (384 bytes each, canonical coefficients, non-zero element; else
+ * ZKG_ERROR).  where 0: the host's final_exponentiation (the specification; no GPU, no zkg_init); 1: the kernel k_final_exp_check;
+ * 2: the kernel's device code compiled for the host (no GPU, no zkg_init).                                                        */
+int  zkg_final_exp(const uint8_t *in, size_t n, int where, uint8_t *out);
 /* test hook: Frobenius maps and the last chunk of the final exponentiation against plain square-and-multiply by q^k and by
  * the integer e (nlimbs x u32, little-endian); 0 = all agree */
 int zkg_pairing_selfcheck(const uint32_t *e, int nlimbs);

@@ -31,6 +31,7 @@ DECLARED_SYMBOLS = [
     "zkg_zklaim_verify_batch", "zkg_zklaim_verify_batch_stats", "zkg_proof_decode_gpu", "zkg_zklaim_input_sums_gpu", "zkg_zklaim_input_map_mirror",
     "zkg_groth16_prove_dev", "zkg_groth16_prove_batch_dev", "zkg_prove_dev_stats",
     "zkg_msm_g1_resident_async", "zkg_msm_g1_resident_batch_max", "zkg_msm_resident_async_stats", "zkg_msm_combine_gpu",
+    "zkg_groth16_verify_each", "zkg_verify_each_stats", "zkg_verify_each_set_chunk", "zkg_pairing_each", "zkg_final_exp",
 ]
 # the reference's own seam, exported with its original names (zklaim.h:257-259)
 COMPAT_SYMBOLS = ["libsnark_trusted_setup", "libsnark_prove", "libsnark_verify"]
@@ -727,6 +728,67 @@ def verify_batch_stats():
     out = (C.c_size_t * 3)()
     lib().zkg_verify_batch_stats(out)
     return tuple(int(v) for v in out)
+
+
+def groth16_verify_each(items):
+    """items: (vk_blob, primary_input, proof) triples.  Returns a uint8 array: verdicts[i] == groth16_verify(*items[i]) exactly, every
+    item decided by its own pairing equation on the GPU (no weights, no bisection).  Raises ZkgError when the call fails."""
+    L = lib()
+    L.zkg_groth16_verify_each.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+    arr = (VerifyItem * max(1, len(items)))()
+    keep = []
+    for k, (vk_blob, primary_input, proof) in enumerate(items):
+        vk = np.frombuffer(bytes(vk_blob), np.uint8); pr = np.frombuffer(bytes(proof), np.uint8); x = _u64(primary_input)
+        keep += [vk, pr, x]
+        arr[k] = VerifyItem(vk.ctypes.data if vk.size else None, vk.size, x.ctypes.data if x.size else None, x.size // 4,
+                            pr.ctypes.data if pr.size else None, pr.size)
+    verdicts = np.full(max(1, len(items)), 0xFF, np.uint8)
+    _check(L.zkg_groth16_verify_each(C.cast(arr, C.c_void_p), len(items), _p(verdicts)), "zkg_groth16_verify_each")
+    return verdicts[:len(items)]
+
+
+def verify_each_stats():
+    """(items decided by the device equation, items decided by the single verifier's code, device rounds) of this thread's last groth16_verify_each"""
+    out = (C.c_size_t * 3)()
+    lib().zkg_verify_each_stats(out)
+    return tuple(int(v) for v in out)
+
+
+def verify_each_set_chunk(positions):
+    """test hook: positions per device round of groth16_verify_each; 0 restores the default"""
+    L = lib()
+    L.zkg_verify_each_set_chunk.argtypes = [C.c_size_t]
+    L.zkg_verify_each_set_chunk.restype = None
+    L.zkg_verify_each_set_chunk(int(positions))
+
+
+def pairing_each(g1, g2, pairs):
+    """FE(prod_j ML(g1[i * pairs + j], g2[i * pairs + j])) per item i, Miller loops and final exponentiation on the GPU: g1 (items * pairs, 8),
+    g2 (items * pairs, 16) affine Montgomery limbs (all-zero = infinity) -> a list of 384-byte values as pairing_probe's"""
+    a = _u64(g1).reshape(-1, 8); b = _u64(g2).reshape(-1, 16)
+    pairs = int(pairs)
+    if a.shape[0] != b.shape[0] or pairs < 1 or a.shape[0] % pairs:
+        raise ZkgError("pairing_each: g1 and g2 must hold items * pairs points each")
+    items = a.shape[0] // pairs
+    out = np.zeros((max(1, items), 384), np.uint8)
+    L = lib()
+    L.zkg_pairing_each.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+    _check(L.zkg_pairing_each(_p(a) if a.size else None, _p(b) if b.size else None, items, pairs, _p(out)), "zkg_pairing_each")
+    return [out[i].tobytes() for i in range(items)]
+
+
+def final_exp(values, where):
+    """the final exponentiation of serialised Fq12 values (384 bytes each) -> a list of 384-byte values.  where 0: the host's (the
+    specification), 1: the GPU kernel, 2: the kernel's device code compiled for the host"""
+    vals = [bytes(v) for v in values]
+    if any(len(v) != 384 for v in vals):
+        raise ZkgError("final_exp: every value is 384 bytes")
+    buf = np.frombuffer(b"".join(vals), np.uint8).copy() if vals else np.zeros(0, np.uint8)
+    out = np.zeros((max(1, len(vals)), 384), np.uint8)
+    L = lib()
+    L.zkg_final_exp.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    _check(L.zkg_final_exp(_p(buf) if buf.size else None, len(vals), int(where), _p(out)), "zkg_final_exp")
+    return [out[i].tobytes() for i in range(len(vals))]
 
 
 class ProveItem(C.Structure):

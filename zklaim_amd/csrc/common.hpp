@@ -235,6 +235,12 @@ int verify_zklaim_input_sums(const uint8_t *d_pub, uint32_t npl, size_t base, co
 int initialised_device();                                // the device zkg_init selected, -1 before (capi.hip)
 // ZKG_ERROR (message "<who>: <what> ...") unless d is `bytes` of device memory of `device`, aligned to `align` (capi.hip); owner: "key", "handle"
 int dev_range_refused(const void *d, size_t bytes, size_t align, int device, const char *who, const char *what, const char *owner);
+// the per-proof verifier (zkg_groth16_verify_each, zkg_pairing_each, zkg_final_exp)
+int verify_ic_each(const G1Affine *d_ic0, const G1Affine *d_ic, uint32_t nidx, const void *d_x, size_t n, G1Affine *d_out, hipStream_t s);
+int verify_g2_replicate(const G2Affine *d_key2, size_t n, G2Affine *d_Q, hipStream_t s);     // d_Q[n + i] = key2[0], d_Q[2 n + i] = key2[1]
+size_t verify_final_exp_ws_bytes(size_t n);              // the slot workspace of n lanes
+int verify_final_exp_check(const void *d_M, size_t n, uint32_t pairs, void *d_ws, const void *d_ab, uint8_t *d_verdict, void *d_gt, hipStream_t s);
+void final_exp_device_code_on_host(const uint8_t in[384], uint8_t out[384]);
 // a batch call's device workspace: grow-only buffer, two streams (the subgroup check runs beside the scalar multiplications), two events
 struct VerifyWorkspace { DevBuf buf; hipStream_t s = nullptr, s2 = nullptr; hipEvent_t ev = nullptr, ev2 = nullptr; };
 VerifyWorkspace *verify_workspace_acquire();             // a free one or a new one; null on a HIP failure (message set)

@@ -6,6 +6,8 @@
 // lane and normalised when they leave it, so the host reads the same canonical limbs its own loop would produce.
 // The constants that the host derives by inversion or exponentiation (3b', gamma_1^2, gamma_1^3, N^2, N^3) are computed there once and
 // passed in MillerConsts.
+// The tower is host and device code (ZK_HD), as fp.hip.hpp's field operations are: compiled for the host it computes on canonical values,
+// which is how the final exponentiation built on it (final_exp.hip.hpp) is checked against the specification without a GPU.
 #pragma once
 #include "curve.hip.hpp"
 
@@ -15,46 +17,46 @@ struct MillerConsts { Fq2 b3, g2, g3, n2, n3; };      // 3b' = 9 / xi;  pi(Q) = 
 
 namespace dev {
 
-ZK_D Fq2 mul_xi(const Fq2 &a) {                           // (9 + u)(a0 + a1 u) = (9 a0 - a1) + (9 a1 + a0) u
+ZK_HD Fq2 mul_xi(const Fq2 &a) {                           // (9 + u)(a0 + a1 u) = (9 a0 - a1) + (9 a1 + a0) u
     Fq2 a8 = a.dbl().dbl().dbl();
     return {a8.c0 + a.c0 - a.c1, a8.c1 + a.c1 + a.c0};
 }
-ZK_D Fq2 conj(const Fq2 &a) { return {a.c0, a.c1.neg()}; }
-ZK_D Fq2 scale(const Fq2 &a, const Fq &s) { return {a.c0 * s, a.c1 * s}; }
+ZK_HD Fq2 conj(const Fq2 &a) { return {a.c0, a.c1.neg()}; }
+ZK_HD Fq2 scale(const Fq2 &a, const Fq &s) { return {a.c0 * s, a.c1 * s}; }
 
 struct Fq6 {
     Fq2 c0, c1, c2;
-    static ZK_D Fq6 zero() { return {Fq2::zero(), Fq2::zero(), Fq2::zero()}; }
-    static ZK_D Fq6 one() { return {Fq2::one(), Fq2::zero(), Fq2::zero()}; }
-    friend ZK_D Fq6 operator+(const Fq6 &a, const Fq6 &b) { return {a.c0 + b.c0, a.c1 + b.c1, a.c2 + b.c2}; }
-    friend ZK_D Fq6 operator-(const Fq6 &a, const Fq6 &b) { return {a.c0 - b.c0, a.c1 - b.c1, a.c2 - b.c2}; }
-    friend ZK_D Fq6 operator*(const Fq6 &a, const Fq6 &o) {                     // schoolbook with v^3 = xi (host Fq6::operator*)
+    static ZK_HD Fq6 zero() { return {Fq2::zero(), Fq2::zero(), Fq2::zero()}; }
+    static ZK_HD Fq6 one() { return {Fq2::one(), Fq2::zero(), Fq2::zero()}; }
+    friend ZK_HD Fq6 operator+(const Fq6 &a, const Fq6 &b) { return {a.c0 + b.c0, a.c1 + b.c1, a.c2 + b.c2}; }
+    friend ZK_HD Fq6 operator-(const Fq6 &a, const Fq6 &b) { return {a.c0 - b.c0, a.c1 - b.c1, a.c2 - b.c2}; }
+    friend ZK_HD Fq6 operator*(const Fq6 &a, const Fq6 &o) {                     // schoolbook with v^3 = xi (host Fq6::operator*)
         Fq2 a0 = a.c0 * o.c0, a1 = a.c1 * o.c1, a2 = a.c2 * o.c2;
         Fq2 t0 = a0 + mul_xi((a.c1 + a.c2) * (o.c1 + o.c2) - a1 - a2);
         Fq2 t1 = (a.c0 + a.c1) * (o.c0 + o.c1) - a0 - a1 + mul_xi(a2);
         Fq2 t2 = (a.c0 + a.c2) * (o.c0 + o.c2) - a0 - a2 + a1;
         return {t0, t1, t2};
     }
-    ZK_D Fq6 mul_by_v() const { return {mul_xi(c2), c0, c1}; }
-    ZK_D Fq6 normalized() const { return {c0.normalized(), c1.normalized(), c2.normalized()}; }
+    ZK_HD Fq6 mul_by_v() const { return {mul_xi(c2), c0, c1}; }
+    ZK_HD Fq6 normalized() const { return {c0.normalized(), c1.normalized(), c2.normalized()}; }
 };
 
 struct Fq12 {
     Fq6 c0, c1;
-    static ZK_D Fq12 one() { return {Fq6::one(), Fq6::zero()}; }
-    friend ZK_D Fq12 operator*(const Fq12 &x, const Fq12 &o) {
+    static ZK_HD Fq12 one() { return {Fq6::one(), Fq6::zero()}; }
+    friend ZK_HD Fq12 operator*(const Fq12 &x, const Fq12 &o) {
         Fq6 a = x.c0 * o.c0, b = x.c1 * o.c1;
         return {a + b.mul_by_v(), (x.c0 + x.c1) * (o.c0 + o.c1) - a - b};
     }
-    ZK_D Fq12 sqr() const {                                                     // complex squaring (host Fq12::sqr)
+    ZK_HD Fq12 sqr() const {                                                     // complex squaring (host Fq12::sqr)
         Fq6 ab = c0 * c1;
         return {(c0 + c1) * (c0 + c1.mul_by_v()) - ab - ab.mul_by_v(), ab + ab};
     }
-    ZK_D Fq12 normalized() const { return {c0.normalized(), c1.normalized()}; }
+    ZK_HD Fq12 normalized() const { return {c0.normalized(), c1.normalized()}; }
 };
 
 // f * (a + b w + c w^3), a, b, c in Fq2 (host mul_by_line2)
-ZK_D Fq12 mul_by_line2(const Fq12 &f, const Fq2 &a, const Fq2 &b, const Fq2 &c) {
+ZK_HD Fq12 mul_by_line2(const Fq12 &f, const Fq2 &a, const Fq2 &b, const Fq2 &c) {
     auto sparse = [](const Fq6 &x, const Fq2 &b_, const Fq2 &c_) {             // x * (b_ + c_ v)
         Fq2 x0b = x.c0 * b_, x1c = x.c1 * c_;
         Fq2 mid = (x.c0 + x.c1) * (b_ + c_) - x0b - x1c;
@@ -67,14 +69,14 @@ ZK_D Fq12 mul_by_line2(const Fq12 &f, const Fq2 &a, const Fq2 &b, const Fq2 &c) 
 // host LineWalker: homogeneous projective T = (X : Y : Z) on the twist; each step returns its line (a, b, c) and moves T
 struct LineWalker {
     Fq2 X, Y, Z;
-    ZK_D void dbl(const Fq2 &b3, Fq2 &la, Fq2 &lb, Fq2 &lc) {
+    ZK_HD void dbl(const Fq2 &b3, Fq2 &la, Fq2 &lb, Fq2 &lc) {
         Fq2 B = Y.sqr(), C = Z.sqr(), E = C * b3, F = E.dbl() + E, H = (Y + Z).sqr() - B - C, J = X.sqr();
         la = H; lb = J.dbl() + J; lc = B - E;
         Fq2 E2 = E.sqr(), E4 = E2.dbl().dbl();
         Fq2 X3 = ((X * Y) * (B - F)).dbl(), Y3 = (B + F).sqr() - (E4.dbl() + E4), Z3 = (B * H).dbl().dbl();
         X = X3; Y = Y3; Z = Z3;
     }
-    ZK_D void add(const G2Affine &R, Fq2 &la, Fq2 &lb, Fq2 &lc) {
+    ZK_HD void add(const G2Affine &R, Fq2 &la, Fq2 &lb, Fq2 &lc) {
         Fq2 theta = Y - R.y * Z, mu = X - R.x * Z;
         la = mu; lb = theta; lc = theta * R.x - mu * R.y;
         Fq2 C = theta.sqr(), D = mu.sqr(), E = mu * D, F = Z * C, G = X * D, H = E + F - G.dbl();
@@ -85,7 +87,7 @@ struct LineWalker {
 
 // ML(P, Q) of one finite pair: miller_schedule's 64 doublings of 6z + 2 = 2^64 + 0x9d797039be763ba8, an addition of Q after each
 // doubling whose bit is set, then the additions of pi(Q) and -pi^2(Q) (miller_addends)
-ZK_D Fq12 miller_loop(const G1Affine &P, const G2Affine &Q, const MillerConsts &k) {
+ZK_HD Fq12 miller_loop(const G1Affine &P, const G2Affine &Q, const MillerConsts &k) {
     constexpr uint64_t S_LO = 0x9d797039be763ba8ull;
     Fq12 f = Fq12::one();
     LineWalker T{Q.x, Q.y, Fq2::one()};

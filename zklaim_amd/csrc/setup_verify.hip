@@ -12,6 +12,7 @@
 // Verifier: host pairing (host/pairing.hpp); the public input is folded into gamma_ABC with host scalar multiplications.
 #include "common.hpp"
 #include <algorithm>
+#include <atomic>
 #include <functional>
 #include <map>
 #include <memory>
@@ -462,13 +463,17 @@ static bool coords_canonical(const uint8_t *rec, int nfq) {                // th
 }
 // what the combination needs of a key beyond what the single verifier checks: gamma and delta in G2, alpha_beta of order r (then it lies
 // in the cyclotomic subgroup, and alpha_beta^(sum r_i) can be taken with cyclotomic squarings)
-static bool vk_batchable(const PreparedVk &vk) {
-    const uint32_t *r = FrParams::P;
+static bool vk_limbs_canonical(const PreparedVk &vk) {
     auto canon = [](const Fq &x) { return limbs_below(x.v, FqParams::P); };  // the single verifier reads limbs >= q too; only canonical keys enter
     auto canon2 = [&](const Fq2 &x) { return canon(x.c0) && canon(x.c1); };
     for (const Fq6 *h : {&vk.alpha_beta.c0, &vk.alpha_beta.c1}) if (!canon2(h->c0) || !canon2(h->c1) || !canon2(h->c2)) return false;
     if (!canon2(vk.gamma_g2.x) || !canon2(vk.gamma_g2.y) || !canon2(vk.delta_g2.x) || !canon2(vk.delta_g2.y) || !canon(vk.ic0.x) || !canon(vk.ic0.y)) return false;
     for (const G1Affine &q : vk.ic) if (!canon(q.x) || !canon(q.y)) return false;
+    return true;
+}
+static bool vk_batchable(const PreparedVk &vk) {
+    const uint32_t *r = FrParams::P;
+    if (!vk_limbs_canonical(vk)) return false;
     if (!G2::from_affine(vk.gamma_g2).mul(r, 8).is_inf() || !G2::from_affine(vk.delta_g2).mul(r, 8).is_inf()) return false;
     return vk.alpha_beta.pow(r, 8) == Fq12::one();
 }
@@ -546,7 +551,9 @@ struct BatchFrontEnd {
 
 // steps 1 and 2 of a batch: group by the key's bytes; per key the prepared form (shared with zkg_groth16_verify's cache) and the checks
 // the weights rely on, once per key.  blob_of(i, len): item i's key (null: the single verifier decides it).
-static void batch_group_keys(size_t count, const std::function<const uint8_t *(size_t, size_t &)> &blob_of, std::vector<BatchGroup> &groups, std::vector<char> &own) {
+// weights == false (zkg_groth16_verify_each draws none): only the canonical-limbs half of those checks.
+static void batch_group_keys(size_t count, const std::function<const uint8_t *(size_t, size_t &)> &blob_of, std::vector<BatchGroup> &groups, std::vector<char> &own,
+                             bool weights = true) {
     std::multimap<uint64_t, size_t> by_digest;
     for (size_t i = 0; i < count; ++i) {
         if (own[i]) continue;
@@ -567,7 +574,7 @@ static void batch_group_keys(size_t count, const std::function<const uint8_t *(s
         try {
             int rc = 0;
             G.vk = prepared_vk(G.blob, G.len, rc);
-            G.batchable = G.vk && vk_batchable_cached(*G.vk);
+            G.batchable = G.vk && (weights ? vk_batchable_cached(*G.vk) : vk_limbs_canonical(*G.vk));
         } catch (...) { G.vk = nullptr; G.batchable = false; }              // the single verifier decides these items (and meets the same failure)
     });
     for (const BatchGroup &G : groups) if (!G.batchable) for (size_t i : G.items) own[i] = 1;
@@ -718,16 +725,10 @@ struct ItemFrontEnd : BatchFrontEnd {
 };
 }  // namespace
 
-// zkg_groth16_verify_batch without its thread's counters: what the entry and the seam's host leg share
-static int verify_batch_items(const zkg_verify_item *items, size_t count, uint8_t *verdicts, BatchCounts &cnt) {
-    BatchLaps lap(count);
-    std::vector<char> own(count, 0);                                        // decided by the single verifier's code
-    // 1, 2. group by the key's bytes; per key the prepared form and the checks the weights rely on
-    std::vector<BatchGroup> groups;
-    batch_group_keys(count, [&](size_t i, size_t &len) { len = items[i].vk_len; return items[i].vk_blob; }, groups, own);
-    lap("keys");
-    // 3. per proof: sizes, encodings and inputs as the single verifier reads them; the proof's points decoded on the host pool
-    std::vector<G1Affine> hA(count), hC(count); std::vector<G2Affine> hB(count);
+// step 3 of a batch, per proof: sizes, encodings and inputs as the single verifier reads them; the proof's points decoded on the host pool.
+// own[i] = 1 for every item that the single verifier's code has to decide.
+static void decode_items(const zkg_verify_item *items, size_t count, const std::vector<BatchGroup> &groups, std::vector<char> &own,
+                         std::vector<G1Affine> &hA, std::vector<G2Affine> &hB, std::vector<G1Affine> &hC) {
     std::vector<int> group_of(count, -1);
     for (size_t g = 0; g < groups.size(); ++g) for (size_t i : groups[g].items) group_of[i] = (int)g;
     host_parallel_for((int)std::min<size_t>(64, count), [&](int c) {
@@ -745,6 +746,19 @@ static int verify_batch_items(const zkg_verify_item *items, size_t count, uint8_
             if (!ok) own[i] = 1;
         }
     });
+}
+
+// zkg_groth16_verify_batch without its thread's counters: what the entry and the seam's host leg share
+static int verify_batch_items(const zkg_verify_item *items, size_t count, uint8_t *verdicts, BatchCounts &cnt) {
+    BatchLaps lap(count);
+    std::vector<char> own(count, 0);                                        // decided by the single verifier's code
+    // 1, 2. group by the key's bytes; per key the prepared form and the checks the weights rely on
+    std::vector<BatchGroup> groups;
+    batch_group_keys(count, [&](size_t i, size_t &len) { len = items[i].vk_len; return items[i].vk_blob; }, groups, own);
+    lap("keys");
+    // 3. per proof: sizes, encodings, inputs, points
+    std::vector<G1Affine> hA(count), hC(count); std::vector<G2Affine> hB(count);
+    decode_items(items, count, groups, own, hA, hB, hC);
     lap("decode");
     ItemFrontEnd fe(items, hA.data(), hB.data(), hC.data());
     return verify_batch_core(groups, own, count, fe, verdicts, lap, cnt);
@@ -768,6 +782,106 @@ int zkg_groth16_verify_batch(const zkg_verify_item *items, size_t count, uint8_t
     catch (const std::exception &e) { set_error(std::string("zkg_groth16_verify_batch: ") + e.what()); return ZKG_ERROR; }
     catch (...) { set_error("zkg_groth16_verify_batch: unexpected exception"); return ZKG_ERROR; }
 }
+
+// ---- per-proof verification (zkg_groth16_verify_each).  Every item is decided by its own equation
+//   FE( ML(A_i, B_i) * ML(-acc_i, gamma) * ML(-C_i, delta) ) == alpha_beta,   acc_i = IC_0 + sum_k x_ik IC_k,
+// on the GPU, all items of a key side by side: k_ic_each forms -acc_i, k_miller runs over the 3 n pairs [A | -acc | -C] x [B | gamma.. | delta..],
+// k_final_exp_check multiplies an item's three values, raises the product and compares it.  No weights are drawn, so nothing is asked of the
+// key or of B beyond what the single verifier asks: a B outside G2, or a key whose gamma, delta or alpha_beta lie outside their groups, is
+// decided here by the same field operations as on the host.  What the device does not take is what its arithmetic cannot read as the host's
+// does: limbs >= q or >= r, and whatever the single verifier rejects before it computes (sizes, encodings, a malformed key).
+// A key's points go up once per call; its positions are cut into rounds whose staging stays within VERIFY_EACH_STAGE_MAX.
+static constexpr size_t VERIFY_EACH_STAGE_MAX = (size_t)64 << 20;
+static std::atomic<size_t> g_each_chunk{0};                                 // zkg_verify_each_set_chunk: positions per round (0: by the staging limit)
+static thread_local size_t t_each_stats[3] = {0, 0, 0};
+
+static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+// positions per round of a key with nidx inputs; per position: P 3 x 64, Q 3 x 128, Miller values 3 x 384, inputs, slots, verdict
+static size_t verify_each_round_positions(size_t nidx, size_t key_bytes) {
+    if (const size_t forced = g_each_chunk.load()) return forced;
+    const size_t per = 3 * 64 + 3 * 128 + 3 * 384 + 32 * nidx + verify_final_exp_ws_bytes(64) / 64 + 1;
+    const size_t room = VERIFY_EACH_STAGE_MAX > key_bytes + 4096 ? VERIFY_EACH_STAGE_MAX - key_bytes - 4096 : 0;
+    return std::max<size_t>(64, room / per / 64 * 64);
+}
+
+static int verify_each_impl(const zkg_verify_item *items, size_t count, uint8_t *verdicts) {
+    if (initialised_device() < 0) { set_error("zkg_groth16_verify_each: zkg_init not called (no GPU: there is no CPU path)"); return ZKG_ERROR; }
+    if (count && (!items || !verdicts)) { set_error("zkg_groth16_verify_each: null argument"); return ZKG_ERROR; }
+    t_each_stats[0] = t_each_stats[1] = t_each_stats[2] = 0;
+    if (!count) return ZKG_OK;
+    std::vector<char> own(count, 0);                                        // decided by the single verifier's code
+    std::vector<BatchGroup> groups;
+    batch_group_keys(count, [&](size_t i, size_t &len) { len = items[i].vk_len; return items[i].vk_blob; }, groups, own, false);
+    std::vector<G1Affine> hA(count), hC(count); std::vector<G2Affine> hB(count);
+    decode_items(items, count, groups, own, hA, hB, hC);
+    size_t on_device = 0, rounds = 0;
+    WorkspaceLease lease;
+    std::vector<G1Affine> pA, pC; std::vector<G2Affine> pB; std::vector<uint64_t> px; std::vector<uint8_t> v;
+    for (const BatchGroup &G : groups) {
+        std::vector<size_t> pos;
+        for (size_t i : G.items) if (!own[i]) pos.push_back(i);
+        if (pos.empty()) continue;
+        const PreparedVk &vk = *G.vk;
+        const size_t nidx = vk.ic.size();
+        // the key: [alpha_beta 384 | gamma, delta 256 | IC_0 64 | IC 64 nidx]
+        const size_t k_ab = 0, k_g2 = 384, k_ic0 = k_g2 + 256, k_ic = k_ic0 + 64, key_bytes = align16(k_ic + 64 * nidx);
+        const size_t chunk = std::min(pos.size(), verify_each_round_positions(nidx, key_bytes));
+        // a round of n <= chunk positions: [P 3 n x 64 | Q 3 n x 128 | M 3 n x 384 | x n nidx x 32 | slots | verdicts n]
+        const size_t o_P = key_bytes, o_Q = o_P + 192 * chunk, o_M = o_Q + 384 * chunk, o_x = o_M + 1152 * chunk, o_ws = o_x + 32 * nidx * chunk,
+                     o_v = o_ws + verify_final_exp_ws_bytes(chunk), total = o_v + chunk + 16;
+        if (!lease.w && !(lease.w = verify_workspace_acquire())) return ZKG_ERROR;
+        ZK_HIP(hipStreamSynchronize(lease.w->s));                           // (the previous key's rounds are done: the buffer may move)
+        if (lease.w->buf.reserve(total)) return ZKG_ERROR;
+        uint8_t *d = lease.w->buf.as<uint8_t>(); hipStream_t s = lease.w->s;
+        const G2Affine key2[2] = {vk.gamma_g2, vk.delta_g2};
+        ZK_HIP(hipMemcpyAsync(d + k_ab, &vk.alpha_beta, 384, hipMemcpyHostToDevice, s));
+        ZK_HIP(hipMemcpyAsync(d + k_g2, key2, 256, hipMemcpyHostToDevice, s));
+        ZK_HIP(hipMemcpyAsync(d + k_ic0, &vk.ic0, 64, hipMemcpyHostToDevice, s));
+        if (nidx) ZK_HIP(hipMemcpyAsync(d + k_ic, vk.ic.data(), 64 * nidx, hipMemcpyHostToDevice, s));
+        for (size_t lo = 0; lo < pos.size(); lo += chunk) {
+            const size_t n = std::min(chunk, pos.size() - lo);
+            pA.resize(n); pC.resize(n); pB.resize(n); px.resize(4 * nidx * n); v.assign(n, 0xFF);
+            for (size_t t = 0; t < n; ++t) {
+                const size_t i = pos[lo + t];
+                pA[t] = hA[i]; pB[t] = hB[i]; pC[t] = hC[i].neg();
+                for (size_t k = 0; k < nidx; ++k) memcpy(&px[4 * (t * nidx + k)], items[i].primary_input + 4 * vk.idx[k], 32);
+            }
+            G1Affine *dP = (G1Affine *)(d + o_P); G2Affine *dQ = (G2Affine *)(d + o_Q);
+            ZK_HIP(hipMemcpyAsync(dP, pA.data(), 64 * n, hipMemcpyHostToDevice, s));
+            ZK_HIP(hipMemcpyAsync(dP + 2 * n, pC.data(), 64 * n, hipMemcpyHostToDevice, s));
+            ZK_HIP(hipMemcpyAsync(dQ, pB.data(), 128 * n, hipMemcpyHostToDevice, s));
+            if (nidx) ZK_HIP(hipMemcpyAsync(d + o_x, px.data(), 32 * nidx * n, hipMemcpyHostToDevice, s));
+            if (verify_g2_replicate((const G2Affine *)(d + k_g2), n, dQ, s) ||
+                verify_ic_each((const G1Affine *)(d + k_ic0), (const G1Affine *)(d + k_ic), (uint32_t)nidx, d + o_x, n, dP + n, s) ||
+                verify_miller(dP, dQ, nullptr, 3 * n, d + o_M, s) ||
+                verify_final_exp_check(d + o_M, n, 3, d + o_ws, d + k_ab, d + o_v, nullptr, s)) return ZKG_ERROR;
+            ZK_HIP(hipMemcpyAsync(v.data(), d + o_v, n, hipMemcpyDeviceToHost, s));
+            ZK_HIP(hipStreamSynchronize(s));
+            for (size_t t = 0; t < n; ++t) verdicts[pos[lo + t]] = v[t];
+            ++rounds;
+        }
+        on_device += pos.size();
+    }
+    // everything else: the single verifier's code, on the host pool
+    std::vector<size_t> decide_alone;
+    for (size_t i = 0; i < count; ++i) if (own[i]) decide_alone.push_back(i);
+    host_parallel_for((int)decide_alone.size(), [&](int t) {
+        const zkg_verify_item &it = items[decide_alone[t]];
+        int r;
+        try { r = groth16_verify_impl(it.vk_blob, it.vk_len, it.primary_input, it.n_inputs, it.proof, it.proof_len); } catch (...) { r = 2; }
+        verdicts[decide_alone[t]] = (uint8_t)r;
+    });
+    t_each_stats[0] = on_device; t_each_stats[1] = decide_alone.size(); t_each_stats[2] = rounds;
+    return ZKG_OK;
+}
+
+int zkg_groth16_verify_each(const zkg_verify_item *items, size_t count, uint8_t *verdicts) {
+    try { return verify_each_impl(items, count, verdicts); }
+    catch (const std::exception &e) { set_error(std::string("zkg_groth16_verify_each: ") + e.what()); return ZKG_ERROR; }
+    catch (...) { set_error("zkg_groth16_verify_each: unexpected exception"); return ZKG_ERROR; }
+}
+void zkg_verify_each_stats(size_t out[3]) { if (out) for (int i = 0; i < 3; ++i) out[i] = t_each_stats[i]; }
+void zkg_verify_each_set_chunk(size_t positions) { g_each_chunk.store(positions); }
 
 // ---- zkg_zklaim_verify_batch: many libsnark_verify calls in one.  The contexts of one key are one group of the batch above; by default its
 // front end is the device's (ZKG_SEAM_GPU_VERIFY=0: the host's, zkg_zklaim_input_map per item and then zkg_groth16_verify_batch's path; a
@@ -1048,6 +1162,88 @@ int zkg_pairing_product(const uint64_t *g1_affine, const uint64_t *g2_affine, si
     try { return pairing_product_impl(g1_affine, g2_affine, n, out); }
     catch (const std::exception &e) { set_error(std::string("zkg_pairing_product: ") + e.what()); return ZKG_ERROR; }
     catch (...) { set_error("zkg_pairing_product: unexpected exception"); return ZKG_ERROR; }
+}
+
+static bool point_pair_ok(const G1Affine &P, const G2Affine &Q) {             // canonical limbs, on the curves (zkg_pairing_product's rule)
+    return limbs_below(P.x.v, FqParams::P) && limbs_below(P.y.v, FqParams::P) && limbs_below(Q.x.c0.v, FqParams::P) && limbs_below(Q.x.c1.v, FqParams::P) &&
+           limbs_below(Q.y.c0.v, FqParams::P) && limbs_below(Q.y.c1.v, FqParams::P) && pairing::on_curve_g1(P) && pairing::on_curve_g2(Q);
+}
+static int pairing_each_impl(const uint64_t *g1_affine, const uint64_t *g2_affine, size_t items, size_t pairs, uint8_t *out) {
+    if (initialised_device() < 0) { set_error("zkg_pairing_each: zkg_init not called (no GPU: there is no CPU path)"); return ZKG_ERROR; }
+    if (items && (!out || (pairs && (!g1_affine || !g2_affine)))) { set_error("zkg_pairing_each: null argument"); return ZKG_ERROR; }
+    if (!items) return ZKG_OK;
+    if (pairs > 4096 || items > ((size_t)1 << 24)) { set_error("zkg_pairing_each: at most 2^24 items of 4096 pairs"); return ZKG_ERROR; }
+    if (!pairs) { for (size_t i = 0; i < items; ++i) ser::put_fq12(out + 384 * i, Fq12::one()); return ZKG_OK; }
+    const G1Affine *P = reinterpret_cast<const G1Affine *>(g1_affine); const G2Affine *Q = reinterpret_cast<const G2Affine *>(g2_affine);
+    std::vector<G1Affine> tP; std::vector<G2Affine> tQ;
+    for (size_t i = 0; i < items * pairs; ++i) {
+        G1Affine p; G2Affine q; memcpy(&p, P + i, 64); memcpy(&q, Q + i, 128);
+        if (!point_pair_ok(p, q)) { set_error("zkg_pairing_each: point " + std::to_string(i) + " is not on its curve"); return ZKG_ERROR; }
+    }
+    // rounds of `chunk` items within the staging limit; pair j of item t of a round at j n + t
+    const size_t per = pairs * (64 + 128 + 384) + verify_final_exp_ws_bytes(64) / 64 + 384;
+    const size_t chunk = std::min(items, std::max<size_t>(64, VERIFY_EACH_STAGE_MAX / per / 64 * 64));
+    const size_t o_P = 0, o_Q = o_P + 64 * pairs * chunk, o_M = o_Q + 128 * pairs * chunk, o_ws = o_M + 384 * pairs * chunk,
+                 o_gt = o_ws + verify_final_exp_ws_bytes(chunk), total = o_gt + 384 * chunk + 16;
+    WorkspaceLease lease;
+    if (!(lease.w = verify_workspace_acquire()) || lease.w->buf.reserve(total)) return ZKG_ERROR;
+    uint8_t *d = lease.w->buf.as<uint8_t>(); hipStream_t s = lease.w->s;
+    for (size_t lo = 0; lo < items; lo += chunk) {
+        const size_t n = std::min(chunk, items - lo);
+        tP.resize(pairs * n); tQ.resize(pairs * n);
+        for (size_t t = 0; t < n; ++t) for (size_t j = 0; j < pairs; ++j) { memcpy(&tP[j * n + t], P + (lo + t) * pairs + j, 64); memcpy(&tQ[j * n + t], Q + (lo + t) * pairs + j, 128); }
+        ZK_HIP(hipMemcpyAsync(d + o_P, tP.data(), 64 * pairs * n, hipMemcpyHostToDevice, s));
+        ZK_HIP(hipMemcpyAsync(d + o_Q, tQ.data(), 128 * pairs * n, hipMemcpyHostToDevice, s));
+        if (verify_miller((const G1Affine *)(d + o_P), (const G2Affine *)(d + o_Q), nullptr, pairs * n, d + o_M, s) ||
+            verify_final_exp_check(d + o_M, n, (uint32_t)pairs, d + o_ws, nullptr, nullptr, d + o_gt, s)) return ZKG_ERROR;
+        ZK_HIP(hipMemcpyAsync(out + 384 * lo, d + o_gt, 384 * n, hipMemcpyDeviceToHost, s));
+        ZK_HIP(hipStreamSynchronize(s));
+    }
+    return ZKG_OK;
+}
+int zkg_pairing_each(const uint64_t *g1_affine, const uint64_t *g2_affine, size_t items, size_t pairs, uint8_t *out) {
+    try { return pairing_each_impl(g1_affine, g2_affine, items, pairs, out); }
+    catch (const std::exception &e) { set_error(std::string("zkg_pairing_each: ") + e.what()); return ZKG_ERROR; }
+    catch (...) { set_error("zkg_pairing_each: unexpected exception"); return ZKG_ERROR; }
+}
+
+static int final_exp_impl(const uint8_t *in, size_t n, int where, uint8_t *out) {
+    if (where < 0 || where > 2) { set_error("zkg_final_exp: where is 0 (host), 1 (GPU) or 2 (the device code on the host)"); return ZKG_ERROR; }
+    if (where == 1 && initialised_device() < 0) { set_error("zkg_final_exp: zkg_init not called (no GPU: the kernel has no CPU path)"); return ZKG_ERROR; }
+    if (n && (!in || !out)) { set_error("zkg_final_exp: null argument"); return ZKG_ERROR; }
+    if (n > ((size_t)1 << 20)) { set_error("zkg_final_exp: at most 2^20 elements"); return ZKG_ERROR; }
+    for (size_t i = 0; i < n; ++i) {
+        bool any = false;
+        for (int k = 0; k < 12; ++k) {
+            uint32_t x[8]; memcpy(x, in + 384 * i + 32 * k, 32);
+            if (!limbs_below(x, FqParams::P)) { set_error("zkg_final_exp: element " + std::to_string(i) + " has a coefficient >= q"); return ZKG_ERROR; }
+            for (int j = 0; j < 8; ++j) any = any || x[j];
+        }
+        if (!any) { set_error("zkg_final_exp: element " + std::to_string(i) + " is zero"); return ZKG_ERROR; }
+    }
+    if (!n) return ZKG_OK;
+    if (where == 0) {
+        for (size_t i = 0; i < n; ++i) { Fq12 f; ser::get_fq12(in + 384 * i, f); ser::put_fq12(out + 384 * i, pairing::final_exponentiation(f)); }
+        return ZKG_OK;
+    }
+    if (where == 2) {
+        for (size_t i = 0; i < n; ++i) final_exp_device_code_on_host(in + 384 * i, out + 384 * i);
+        return ZKG_OK;
+    }
+    const size_t o_in = 0, o_ws = 384 * n, o_gt = o_ws + verify_final_exp_ws_bytes(n), total = o_gt + 384 * n + 16;
+    WorkspaceLease lease;
+    if (!(lease.w = verify_workspace_acquire()) || lease.w->buf.reserve(total)) return ZKG_ERROR;
+    uint8_t *d = lease.w->buf.as<uint8_t>(); hipStream_t s = lease.w->s;
+    ZK_HIP(hipMemcpyAsync(d + o_in, in, 384 * n, hipMemcpyHostToDevice, s));
+    if (verify_final_exp_check(d + o_in, n, 1, d + o_ws, nullptr, nullptr, d + o_gt, s)) return ZKG_ERROR;
+    ZK_HIP(hipMemcpyAsync(out, d + o_gt, 384 * n, hipMemcpyDeviceToHost, s));
+    ZK_HIP(hipStreamSynchronize(s));
+    return ZKG_OK;
+}
+int zkg_final_exp(const uint8_t *in, size_t n, int where, uint8_t *out) {
+    try { return final_exp_impl(in, n, where, out); }
+    catch (const std::exception &e) { set_error(std::string("zkg_final_exp: ") + e.what()); return ZKG_ERROR; }
+    catch (...) { set_error("zkg_final_exp: unexpected exception"); return ZKG_ERROR; }
 }
 
 // bilinearity probe for the tests: writes e(a*G1, b*G2) (384 B) for canonical scalars a, b

@@ -7,6 +7,11 @@
 //   k_miller        ML(P_i, Q_i) (pairing.hip.hpp), 1 for a pair with a point at infinity or flagged out
 //   k_fq12_prod     the product of the Miller values of an index range [lo, hi): per block a strided product and an LDS tree; a second
 //                   launch of one block folds the block results
+// the per-proof verifier (zkg_groth16_verify_each, zkg_pairing_each), which decides every item by its own equation:
+//   k_ic_each           -(IC_0 + sum_k x_ik IC_k) per item: a block per item, lanes stride over k, an LDS tree adds the lanes
+//   k_g2_replicate      the key's gamma and delta behind the proofs' B, so that k_miller runs over [A | -acc | -C] x [B | gamma.. | delta..]
+//   k_final_exp_check   per lane the product of an item's Miller values and its final exponentiation (final_exp.hip.hpp); the verdict
+//                       (== the key's alpha_beta) or the GT value itself
 // and the device front end of the seam's batch entry (zkg_zklaim_verify_batch), which leaves the host neither square roots nor input sums:
 //   k_proof_decode        a compressed point of a 134-byte proof record per lane -> the affine Montgomery point ser::get_g1 / ser::get_g2
 //                         produce and a flag byte per item (the single verifier's acceptance rule and coords_canonical, bit for bit)
@@ -14,6 +19,7 @@
 //                         payloads' public bytes (zklaim_public.hip.hpp); a block per (element, slice), k_fr_fold adds the slices
 #include "common.hpp"
 #include "pairing.hip.hpp"
+#include "final_exp.hip.hpp"
 #include "sqrt.hip.hpp"
 #include "zklaim_public.hip.hpp"
 #include "host/pairing.hpp"
@@ -77,6 +83,67 @@ __global__ __launch_bounds__(VB) void k_fq12_prod(const dev::Fq12 *in, size_t lo
         __syncthreads();
     }
     if (threadIdx.x == 0) out[blockIdx.x] = sh[0].normalized();
+}
+
+// out[i] = -(ic0 + sum_k x[i * nidx + k] * ic[k]), affine and canonical (infinity: all-zero).  x: Montgomery Fr, as the verifier's inputs are
+// given.  One block per item; lane t takes the terms t, t + VB, ..: a 254-step double-and-add each (the scalars differ per lane, so the
+// additions diverge), summed per lane, then an LDS tree over the lanes.
+__global__ __launch_bounds__(VB) void k_ic_each(size_t n, uint32_t nidx, const G1Affine *ic0, const G1Affine *ic, const Fr *x, G1Affine *out) {
+    __shared__ G1 sh[VB];
+    const size_t i = blockIdx.x;                        // gridDim.x == n
+    G1 sum = G1::inf();
+#pragma unroll 1
+    for (uint32_t k = threadIdx.x; k < nidx; k += VB) {
+        const G1Affine b = ic[k];
+        const Fr e = x[i * nidx + k].from_mont();
+        G1 acc = G1::inf();
+#pragma unroll 1
+        for (int bit = 253; bit >= 0; --bit) {          // x < r < 2^254
+            acc = acc.dbl();
+            if ((e.v[bit >> 5] >> (bit & 31)) & 1u) acc.madd(b);
+        }
+        sum.add(acc);
+    }
+    sh[threadIdx.x] = sum;
+    __syncthreads();
+#pragma unroll 1
+    for (int s = VB / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) { G1 a = sh[threadIdx.x]; a.add(sh[threadIdx.x + s]); sh[threadIdx.x] = a; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && i < n) {
+        G1 acc = G1::from_affine(*ic0);
+        acc.add(sh[0]);
+        out[i] = acc.neg().to_affine().normalized();
+    }
+}
+// Q[n + i] = key[0], Q[2 n + i] = key[1] for i < n
+__global__ __launch_bounds__(VB) void k_g2_replicate(size_t n, const G2Affine *key, G2Affine *Q) {
+    const size_t i = (size_t)blockIdx.x * VB + threadIdx.x;
+    if (i < 2 * n) Q[n + i] = key[i / n];
+}
+// lane i: f = M[i] M[n + i] .. M[(pairs - 1) n + i], then FE(f).  ab != null: verdict[i] = FE(f) == *ab ? 0 : 1 (ab canonical);
+// gt != null: gt[i] = FE(f), canonical.  pairs >= 1.  ws: FE_SLOTS x 96 x stride words, stride >= n.
+__global__ __launch_bounds__(VB) void k_final_exp_check(size_t n, const dev::Fq12 *M, uint32_t pairs, uint32_t *ws, size_t stride, FrobConsts fc,
+                                                        const dev::Fq12 *ab, uint8_t *verdict, dev::Fq12 *gt) {
+    // the Frobenius constants in LDS: as kernel arguments their 240 words are all loaded ahead of the chain's loop and spilled
+    __shared__ FrobConsts sfc;
+    for (uint32_t t = threadIdx.x; t < sizeof(FrobConsts) / 4; t += VB) reinterpret_cast<uint32_t *>(&sfc)[t] = reinterpret_cast<const uint32_t *>(&fc)[t];
+    __syncthreads();
+    const size_t i = (size_t)blockIdx.x * VB + threadIdx.x;
+    if (i >= n) return;
+    const dev::FeSlots slots{ws, (uint32_t)i, stride};
+    dev::Fq12 g = dev::final_exponentiation(M[i], (int)pairs - 1, [&](int j) { return M[(size_t)j * n + i]; }, sfc, slots).normalized();
+    if (gt) gt[i] = g;
+    if (ab) {
+        const uint32_t *a = reinterpret_cast<const uint32_t *>(ab);
+        uint32_t diff = 0;
+        dev::FeSlots::each_fq(g, [&](Fq &c, int k) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) diff |= c.v[j] ^ a[8 * k + j];
+        });
+        verdict[i] = diff ? 1 : 0;
+    }
 }
 
 // ---- the device front end
@@ -184,6 +251,49 @@ MillerConsts miller_consts() {
         return MillerConsts{fq2(9, 0) * fq2_inverse_host(xi()), g2, g3, n2, n3};
     }();
     return k;
+}
+
+FrobConsts frob_consts() {
+    static const FrobConsts k = [] {
+        using namespace pairing;
+        const Fq2 g1 = gamma1(), g2 = g1 * conj(g1), g3 = g2 * g1;
+        FrobConsts c;
+        const Fq2 *g[3] = {&g1, &g2, &g3};
+        for (int j = 0; j < 3; ++j) { c.g[j][0] = *g[j]; for (int i = 1; i < 5; ++i) c.g[j][i] = c.g[j][i - 1] * *g[j]; }
+        return c;
+    }();
+    return k;
+}
+size_t verify_final_exp_ws_bytes(size_t n) { return (size_t)dev::FE_SLOTS * dev::FE_WORDS * 4 * ((n + VB - 1) / VB * VB); }
+// d_out[i] = -(ic0 + sum_k x_ik ic_k), i < n (d_x: n x nidx Montgomery Fr)
+int verify_ic_each(const G1Affine *d_ic0, const G1Affine *d_ic, uint32_t nidx, const void *d_x, size_t n, G1Affine *d_out, hipStream_t s) {
+    if (!n) return ZKG_OK;
+    hipLaunchKernelGGL(k_ic_each, dim3((unsigned)n), dim3(VB), 0, s, n, nidx, d_ic0, d_ic, (const Fr *)d_x, d_out);
+    ZK_HIP(hipGetLastError());
+    return ZKG_OK;
+}
+int verify_g2_replicate(const G2Affine *d_key2, size_t n, G2Affine *d_Q, hipStream_t s) {
+    if (!n) return ZKG_OK;
+    hipLaunchKernelGGL(k_g2_replicate, dim3(blocks_for(2 * n)), dim3(VB), 0, s, n, d_key2, d_Q);
+    ZK_HIP(hipGetLastError());
+    return ZKG_OK;
+}
+// d_M: pairs x n Miller values (pair j of item i at j n + i); d_ws: verify_final_exp_ws_bytes(n); d_ab (verdicts) or d_gt (values) may be null
+int verify_final_exp_check(const void *d_M, size_t n, uint32_t pairs, void *d_ws, const void *d_ab, uint8_t *d_verdict, void *d_gt, hipStream_t s) {
+    if (!n) return ZKG_OK;
+    hipLaunchKernelGGL(k_final_exp_check, dim3(blocks_for(n)), dim3(VB), 0, s, n, (const dev::Fq12 *)d_M, pairs, (uint32_t *)d_ws,
+                       (size_t)blocks_for(n) * VB, frob_consts(), (const dev::Fq12 *)d_ab, d_verdict, (dev::Fq12 *)d_gt);
+    ZK_HIP(hipGetLastError());
+    return ZKG_OK;
+}
+// the device tower compiled for the host: final_exp.hip.hpp's text on one lane (zkg_final_exp, where = 2)
+void final_exp_device_code_on_host(const uint8_t in[384], uint8_t out[384]) {
+    static_assert(sizeof(dev::Fq12) == 384, "an Fq12 is 12 Fq");
+    dev::Fq12 f;
+    memcpy(&f, in, 384);
+    std::vector<uint32_t> ws((size_t)dev::FE_SLOTS * dev::FE_WORDS);
+    const dev::Fq12 g = dev::final_exponentiation(f, 0, [&](int) { return f; }, frob_consts(), dev::FeSlots{ws.data(), 0, 1}).normalized();
+    memcpy(out, &g, 384);
 }
 
 int verify_g2_subgroup(const G2Affine *d_B, size_t n, uint8_t *d_ok, hipStream_t s) {
