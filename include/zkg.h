@@ -550,6 +550,18 @@ int zkg_fr29_op(int op, const uint32_t *in, size_t n, uint32_t *out);
 int zkg_fq29_op(int op, const uint32_t *in, size_t n, uint32_t *out);
 int zkg_fq29_op_chain(int op, int chain, const uint32_t *in, size_t n, uint32_t *out);
 
+/* known-answer hook for the pairing's device tower (csrc/pairing.hip.hpp, csrc/final_exp.hip.hpp: Fq12 over Fq6 over Fq2 on values kept lazily
+ * in [0, 2q)): the functions of those files themselves on RAW limbs.  An element is 96 32-bit words, the twelve Fq coefficients in the order
+ * c0.c0.c0, c0.c0.c1, c0.c1.c0 .. c1.c2.c1 (FeSlots::each_fq), eight little-endian words of Montgomery form each; element i of a, b and out
+ * is at word 96 i.  No word is normalised on the way in or out, so a caller can place coefficients anywhere in the lazy range and sees the
+ * representative an operation leaves.  b is read by ops 0 and 2 only.
+ *   op  0  a * b (Fq12 operator*)          1  a.sqr() (complex squaring)          2  mul_by_line2(a, l0, l1, l2): the line's three Fq2 in the
+ *       first 48 words of b's element      3  cyclotomic_sqr(a) (specified in the cyclotomic subgroup only)      4  inverse(a) (0 -> 0)
+ *       5  conjugate(a)      6 - 8  frobenius<1>, <2>, <3>(a) with the verifier's FrobConsts      9  Fq6::mul_by_v on both halves of a
+ * where 1: one lane per element on the GPU (kernel k_fq12_op; needs zkg_init); 2: the same text compiled for the host, which computes on
+ * canonical values: a coefficient >= q is ZKG_ERROR.  n at most 2^20.                                                                   */
+int zkg_fq12_op(int op, const uint32_t *a, const uint32_t *b, size_t n, int where, uint32_t *out);
+
 /* known-answer hook for the 29-bit group law of the bucket-reduction kernels (csrc/fq29.hip.hpp, xyzz29_add_quad): on the GPU,
  * out[i] = a[i] + b[i], then `chain` rounds of x <- 2x + b[i]; points as normalised Jacobian (12 limbs), host pointers.          */
 int zkg_g1_add_quad29(const uint64_t *a_jac, const uint64_t *b_jac, size_t n, int chain, uint64_t *out_jac);

@@ -472,6 +472,153 @@ def ser_proof(proof):
     return ser_g1(proof[0]) + ser_g2(proof[1]) + ser_g1(proof[2])
 
 
+# ---------------------------------------------------------------- the pairing, from the definition
+# Fq12 = Fq[w]/(w^12 - 18 w^6 + 82): w^6 = xi = 9 + u and u^2 = -1 give (w^6 - 9)^2 = -1.  An element is a list of 12 integers,
+# the coefficients of w^0 .. w^11.  Schoolbook product, square-and-multiply, Fermat inverse: no tower, no Karatsuba, no sparse
+# products, no cyclotomic squaring, no Frobenius constants.
+ATE_Z = 4965661367192848881                     # the curve parameter: q = 36z^4 + 36z^3 + 24z^2 + 6z + 1
+ATE_LOOP = 6 * ATE_Z + 2
+GT_COFACTOR = 2 * ATE_Z * (6 * ATE_Z * ATE_Z + 3 * ATE_Z + 1)   # libff's last chunk raises to this multiple of (q^4 - q^2 + 1)/r
+FINAL_EXP = (Q ** 12 - 1) // R * GT_COFACTOR
+P_ONE = [1] + [0] * 11
+XI = (9, 1)
+
+
+def p_mul(a, b):
+    t = [0] * 23
+    for i, x in enumerate(a):
+        if x:
+            for j, y in enumerate(b):
+                t[i + j] += x * y
+    for i in range(22, 11, -1):                 # w^i = 18 w^(i-6) - 82 w^(i-12)
+        c = t[i]
+        t[i - 6] += 18 * c
+        t[i - 12] -= 82 * c
+    return [v % Q for v in t[:12]]
+
+
+def p_pow(x, e):
+    acc, base = P_ONE, list(x)
+    while e:
+        if e & 1:
+            acc = p_mul(acc, base)
+        base = p_mul(base, base)
+        e >>= 1
+    return acc
+
+
+def p_inv(x):
+    return p_pow(x, Q ** 12 - 2)
+
+
+def p_from_f2(a, k):
+    """(alpha + beta u) w^k, k < 6, as a polynomial: u = w^6 - 9"""
+    out = [0] * 12
+    out[k] = (a[0] - 9 * a[1]) % Q
+    out[k + 6] = a[1] % Q
+    return out
+
+
+def p_add(a, b): return [(x + y) % Q for x, y in zip(a, b)]
+
+
+def f2_pow(a, e):
+    acc = (1, 0)
+    while e:
+        if e & 1:
+            acc = f2_mul(acc, a)
+        a = f2_mul(a, a)
+        e >>= 1
+    return acc
+
+
+def f2_conj(a): return (a[0], (-a[1]) % Q)
+
+
+def twist_frobenius(S):
+    """pi(x', y') = (conj(x') xi^((q-1)/3), conj(y') xi^((q-1)/2)): the q-power map of the curve carried to the twist"""
+    return (f2_mul(f2_conj(S[0]), f2_pow(XI, (Q - 1) // 3)), f2_mul(f2_conj(S[1]), f2_pow(XI, (Q - 1) // 2)))
+
+
+def miller_addends(S):
+    """pi(Q) and -pi^2(Q), the two points the optimal ate loop adds after the 6z + 2 schedule"""
+    s1 = twist_frobenius(S)
+    return s1, ec_neg(Field2, twist_frobenius(s1))
+
+
+def line_at(T, S, P):
+    """the line through the twist points T and S (the tangent when T == S), untwisted by (x', y') -> (x' w^2, y' w^3) and evaluated
+    at P = (x_P, y_P) in G1: y_P - lambda' x_P w + (lambda' x_T - y_T) w^3.  A vertical line is dropped (1)."""
+    (xt, yt), (xs, ys) = T, S
+    if xt == xs:
+        if yt != ys or yt == (0, 0):
+            return P_ONE
+        lam = f2_mul(f2_mul((3, 0), f2_mul(xt, xt)), f2_inv(f2_add(yt, yt)))
+    else:
+        lam = f2_mul(f2_sub(ys, yt), f2_inv(f2_sub(xs, xt)))
+    out = p_from_f2(f2_neg(f2_mul(lam, (P[0], 0))), 1)
+    out = p_add(out, p_from_f2(f2_sub(f2_mul(lam, xt), yt), 3))
+    out[0] = (out[0] + P[1]) % Q
+    return out
+
+
+def miller(P, S):
+    """f_{6z+2,S}(P) l_{[6z+2]S, pi(S)}(P) l_{[6z+2]S + pi(S), -pi^2(S)}(P): affine steps on the twist (ec_add over Field2), the plain
+    binary expansion of 6z + 2"""
+    f, T = P_ONE, S
+    for bit in bin(ATE_LOOP)[3:]:
+        f = p_mul(p_mul(f, f), line_at(T, T, P))
+        T = ec_add(Field2, T, T)
+        if bit == '1':
+            f = p_mul(f, line_at(T, S, P))
+            T = ec_add(Field2, T, S)
+    for A in miller_addends(S):
+        f = p_mul(f, line_at(T, A, P))
+        T = ec_add(Field2, T, A)
+    return f
+
+
+def final_exp_ref(x, cofactor=GT_COFACTOR):
+    """x^E for any non-zero x, E = (q^12 - 1)/r * cofactor"""
+    return p_pow(x, (Q ** 12 - 1) // R * cofactor)
+
+
+def frobenius_ref(x, k):
+    return p_pow(x, Q ** k)
+
+
+def pairing(P, S, cofactor=GT_COFACTOR):
+    """the reduced pairing of P in G1 and S in G2 (affine, None = infinity) as libff's alt_bn128 defines its value; cofactor 1 gives
+    the optimal ate pairing itself"""
+    if P is None or S is None:
+        return list(P_ONE)
+    return final_exp_ref(miller(P, S), cofactor)
+
+
+# the 384-byte form (libff Fp12_2over3over2 operator<<): c0 = (a_0, a_2, a_4), c1 = (a_1, a_3, a_5) with a_i in Fq2 the coefficient of
+# w^i, real part first, every Fq as ser_fq writes it
+GT_ORDER = (0, 2, 4, 1, 3, 5)
+
+
+def ser_gt(p):
+    out = b''
+    for i in GT_ORDER:
+        beta = p[i + 6]
+        out += ser_fq((p[i] + 9 * beta) % Q) + ser_fq(beta)
+    return out
+
+
+def parse_gt(b):
+    assert len(b) == 384
+    v = [from_mont(int.from_bytes(b[32 * k:32 * k + 32], 'little') % Q, Q) for k in range(12)]
+    p = [0] * 12
+    for pos, i in enumerate(GT_ORDER):
+        alpha, beta = v[2 * pos], v[2 * pos + 1]
+        p[i] = (alpha - 9 * beta) % Q
+        p[i + 6] = beta
+    return p
+
+
 # ---------------------------------------------------------------- deterministic RNG used by benches/tests
 class SplitMix64:
     def __init__(self, seed): self.s = seed & 0xFFFFFFFFFFFFFFFF

@@ -168,5 +168,29 @@ def gen_step_domain():
     dump("groth16_step.json", groth16_cases(((1, 2, 8, "step10"), (2, 3, 14, "step17"), (3, 4, 17, "step24_from21"), (2, 6, 40, "step48_from43"))))
 
 
+def pairing_scalars():
+    """(a, b) of the pairing records: e(a G1, b G2).  P = G1 = (1, 2) and -G1 with y = q - 2, small and large multiples, a point at infinity
+    on either side, four random pairs.  Its own generator: the records do not depend on what was drawn before them."""
+    r = random.Random(0x50414952)
+    return [(a, b) for a in (1, 2, P.R - 1, P.R - 2) for b in (1, P.R - 1)] + [(0, 5), (5, 0)] + [(r.randrange(1, P.R), r.randrange(1, P.R)) for _ in range(4)]
+
+
+def gen_pairing():
+    """the reduced pairing and the final exponentiation from oracle/pyref.py's polynomial Fq12 (affine Miller loop, one pow): the 384-byte
+    values as libff writes them, the known-answer record of the reference itself"""
+    r = random.Random(0x46455850)
+    out = {"pairing": [dict(a=H(a), b=H(b), gt_hex=P.ser_gt(P.pairing(P.g1_mul(a), P.g2_mul(b))).hex()) for a, b in pairing_scalars()], "final_exp": []}
+    xs = [[r.randrange(P.Q) for _ in range(12)] for _ in range(6)]
+    xs.append([r.randrange(P.Q) if i % 2 == 0 else 0 for i in range(12)])          # an element of Fq6: no odd power of w
+    xs.append(P.miller(P.g1_mul(2), P.g2_mul(3)))                                    # a Miller value: its record is e(2 G1, 3 G2)
+    for x in xs:
+        out["final_exp"].append(dict(in_hex=P.ser_gt(x).hex(), out_hex=P.ser_gt(P.final_exp_ref(x)).hex()))
+    dump("pairing.json", out)
+
+
 if __name__ == "__main__":
-    gen_field(); gen_curve(); gen_ntt(); gen_msm(); gen_groth16(); gen_step_domain()
+    only = sys.argv[1:]                                  # e.g. `gen_golden.py pairing`: that file alone (the others share one generator, in order)
+    if only == ["pairing"]:
+        gen_pairing()
+    else:
+        gen_field(); gen_curve(); gen_ntt(); gen_msm(); gen_groth16(); gen_step_domain(); gen_pairing()

@@ -128,3 +128,18 @@ def test_step_domain_transforms(oracle):
         u, z = oracle.domain_lagrange(c["m"], limbs(h(c["t"])))
         assert ints(u, R) == [h(x) for x in c["u"]], c["m"]
         assert ints(z, R)[0] == h(c["Z"]), c["m"]
+
+
+def test_pairing_records_are_what_the_reference_computes():
+    """tests/golden/pairing.json is the known-answer record of oracle/pyref.py's pairing: two records of each kind recomputed.  (The
+    library is compared with the reference itself in tests/test_pairing_reference.py and, on the GPU, with these records.)"""
+    import pyref as P
+    g = golden("pairing.json")
+    assert len(g["pairing"]) == 14 and len(g["final_exp"]) == 8
+    for c in (g["pairing"][3], g["pairing"][-1]):
+        assert P.ser_gt(P.pairing(P.g1_mul(h(c["a"])), P.g2_mul(h(c["b"])))).hex() == c["gt_hex"]
+    for c in (g["final_exp"][0], g["final_exp"][-1]):
+        assert P.ser_gt(P.final_exp_ref(P.parse_gt(bytes.fromhex(c["in_hex"])))).hex() == c["out_hex"]
+    assert g["final_exp"][-1]["out_hex"] == P.ser_gt(P.pairing(P.g1_mul(2), P.g2_mul(3))).hex()      # that input is the Miller value of (2, 3)
+    one = P.ser_gt(P.P_ONE).hex()
+    assert [c["gt_hex"] == one for c in g["pairing"]] == [False] * 8 + [True, True] + [False] * 4    # infinity on either side pairs to 1

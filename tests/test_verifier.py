@@ -55,7 +55,8 @@ def ser_g2_aff(p16):
     return b"0" + ser_fq(x0) + ser_fq(x1) + (b"1" if y0 & 1 else b"0")
 
 
-def build_vk(oracle, case, keep):
+def build_vk(oracle, case, keep, gt_source=None):
+    """gt_source(alpha, beta) -> the key's first 384 bytes, alpha_g1_beta_g2; by default the library's own pairing"""
     A, B, C, pts, w, r, s = golden_case_arrays(case)
     ocs = oracle.make_r1cs(case["num_variables"], case["num_inputs"], A, B, C, keep)
     td = {k: h(v) for k, v in case["trapdoor"].items()}
@@ -67,7 +68,9 @@ def build_vk(oracle, case, keep):
     IC = oracle.g1_fixed_base(oracle.g1_generator(), arr(ic_scalars))
     gamma_g2 = oracle.g2_scalar_mul(oracle.g2_generator(), limbs(td["gamma"]))[:16]
     delta_g2 = oracle.g2_scalar_mul(oracle.g2_generator(), limbs(td["delta"]))[:16]
-    blob = zkg.pairing_probe(limbs(td["alpha"]), limbs(td["beta"]))                 # alpha_g1_beta_g2 = e(alpha G1, beta G2)
+    gt_source = gt_source or (lambda a, b: zkg.pairing_probe(limbs(a), limbs(b)))
+    blob = gt_source(td["alpha"], td["beta"])                                       # alpha_g1_beta_g2 = e(alpha G1, beta G2)
+    assert len(blob) == 384
     blob += ser_g2_aff(gamma_g2) + ser_g2_aff(delta_g2) + ser_g1_aff(IC[0])
     blob += b"%d\n%d\n" % (l, l) + b"".join(b"%d\n" % i for i in range(l)) + b"%d\n" % l + b"".join(ser_g1_aff(IC[i + 1]) for i in range(l))
     return blob, w[:l]

@@ -32,6 +32,7 @@ DECLARED_SYMBOLS = [
     "zkg_groth16_prove_dev", "zkg_groth16_prove_batch_dev", "zkg_prove_dev_stats",
     "zkg_msm_g1_resident_async", "zkg_msm_g1_resident_batch_max", "zkg_msm_resident_async_stats", "zkg_msm_combine_gpu",
     "zkg_groth16_verify_each", "zkg_verify_each_stats", "zkg_verify_each_set_chunk", "zkg_pairing_each", "zkg_final_exp",
+    "zkg_fq12_op",
 ]
 # the reference's own seam, exported with its original names (zklaim.h:257-259)
 COMPAT_SYMBOLS = ["libsnark_trusted_setup", "libsnark_prove", "libsnark_verify"]
@@ -789,6 +790,30 @@ def final_exp(values, where):
     L.zkg_final_exp.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
     _check(L.zkg_final_exp(_p(buf) if buf.size else None, len(vals), int(where), _p(out)), "zkg_final_exp")
     return [out[i].tobytes() for i in range(len(vals))]
+
+
+FQ12_OPS = {"mul": 0, "sqr": 1, "mul_by_line2": 2, "cyclotomic_sqr": 3, "inverse": 4, "conjugate": 5, "frobenius1": 6, "frobenius2": 7,
+            "frobenius3": 8, "mul_by_v": 9}                                                                     # name -> op of zkg_fq12_op
+
+
+def fq12_op(name, a, b=None, where=1):
+    """one operation of the pairing's device tower on raw limbs (zkg_fq12_op): a is (n, 96) uint32, twelve Fq of eight little-endian words in
+    the tower's order, taken as given; b likewise for "mul", and for "mul_by_line2" the line's three Fq2 in its first 48 words.  The
+    result is (n, 96) uint32, not normalised.  where 1: the GPU kernel, 2: the same text on the host (canonical inputs only)"""
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    if a.ndim != 2 or a.shape[1] != 96:
+        raise ZkgError(f"fq12_op {name}: a must be (n, 96), got {a.shape}")
+    bb = None
+    if name in ("mul", "mul_by_line2"):
+        bb = np.ascontiguousarray(b, dtype=np.uint32)
+        if bb.shape != a.shape:
+            raise ZkgError(f"fq12_op {name}: b must be {a.shape}, got {bb.shape}")
+    out = np.zeros((max(1, a.shape[0]), 96), np.uint32)
+    L = lib()
+    L.zkg_fq12_op.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    _check(L.zkg_fq12_op(FQ12_OPS[name], _p(a) if a.size else None, _p(bb) if bb is not None and bb.size else None, a.shape[0], int(where), _p(out)),
+           "zkg_fq12_op")
+    return out[:a.shape[0]]
 
 
 class ProveItem(C.Structure):

@@ -241,6 +241,10 @@ int verify_g2_replicate(const G2Affine *d_key2, size_t n, G2Affine *d_Q, hipStre
 size_t verify_final_exp_ws_bytes(size_t n);              // the slot workspace of n lanes
 int verify_final_exp_check(const void *d_M, size_t n, uint32_t pairs, void *d_ws, const void *d_ab, uint8_t *d_verdict, void *d_gt, hipStream_t s);
 void final_exp_device_code_on_host(const uint8_t in[384], uint8_t out[384]);
+// the known-answer hook of the device tower (zkg_fq12_op): the operation numbers of include/zkg.h; raw 96-word Fq12, nothing normalised
+enum { FQ12_MUL = 0, FQ12_SQR, FQ12_LINE, FQ12_CSQR, FQ12_INV, FQ12_CONJ, FQ12_FROB1, FQ12_FROB2, FQ12_FROB3, FQ12_MUL_BY_V, FQ12_OPS };
+int verify_fq12_op(int op, const void *d_a, const void *d_b, size_t n, void *d_out, hipStream_t s);      // k_fq12_op; d_b: FQ12_MUL and FQ12_LINE only
+void fq12_op_device_code_on_host(int op, const uint32_t a[96], const uint32_t b[96], uint32_t out[96]);  // the same text on the host, one element
 // a batch call's device workspace: grow-only buffer, two streams (the subgroup check runs beside the scalar multiplications), two events
 struct VerifyWorkspace { DevBuf buf; hipStream_t s = nullptr, s2 = nullptr; hipEvent_t ev = nullptr, ev2 = nullptr; };
 VerifyWorkspace *verify_workspace_acquire();             // a free one or a new one; null on a HIP failure (message set)

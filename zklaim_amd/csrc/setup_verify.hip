@@ -1246,6 +1246,41 @@ int zkg_final_exp(const uint8_t *in, size_t n, int where, uint8_t *out) {
     catch (...) { set_error("zkg_final_exp: unexpected exception"); return ZKG_ERROR; }
 }
 
+static int fq12_op_impl(int op, const uint32_t *a, const uint32_t *b, size_t n, int where, uint32_t *out) {
+    if (op < 0 || op >= FQ12_OPS) { set_error("zkg_fq12_op: unknown operation"); return ZKG_ERROR; }
+    if (where != 1 && where != 2) { set_error("zkg_fq12_op: where is 1 (GPU) or 2 (the device code on the host)"); return ZKG_ERROR; }
+    if (where == 1 && initialised_device() < 0) { set_error("zkg_fq12_op: zkg_init not called (no GPU: the kernel has no CPU path)"); return ZKG_ERROR; }
+    const bool binary = op == FQ12_MUL || op == FQ12_LINE;
+    if (n && (!a || !out || (binary && !b))) { set_error("zkg_fq12_op: null argument"); return ZKG_ERROR; }
+    if (n > ((size_t)1 << 20)) { set_error("zkg_fq12_op: at most 2^20 elements"); return ZKG_ERROR; }
+    if (!n) return ZKG_OK;
+    if (where == 2) {
+        // the host build of fp.hip.hpp computes on canonical values: a coefficient >= q is refused, not reduced
+        for (size_t i = 0; i < n; ++i)
+            for (int k = 0; k < 12; ++k)
+                if (!limbs_below(a + 96 * i + 8 * k, FqParams::P) || (binary && (op == FQ12_MUL || k < 6) && !limbs_below(b + 96 * i + 8 * k, FqParams::P))) {
+                    set_error("zkg_fq12_op: element " + std::to_string(i) + " has a coefficient >= q (where = 2 takes canonical values)"); return ZKG_ERROR;
+                }
+        for (size_t i = 0; i < n; ++i) fq12_op_device_code_on_host(op, a + 96 * i, binary ? b + 96 * i : nullptr, out + 96 * i);
+        return ZKG_OK;
+    }
+    const size_t o_a = 0, o_b = 384 * n, o_out = 2 * 384 * n, total = 3 * 384 * n;
+    WorkspaceLease lease;
+    if (!(lease.w = verify_workspace_acquire()) || lease.w->buf.reserve(total)) return ZKG_ERROR;
+    uint8_t *d = lease.w->buf.as<uint8_t>(); hipStream_t s = lease.w->s;
+    ZK_HIP(hipMemcpyAsync(d + o_a, a, 384 * n, hipMemcpyHostToDevice, s));
+    if (binary) ZK_HIP(hipMemcpyAsync(d + o_b, b, 384 * n, hipMemcpyHostToDevice, s));
+    if (verify_fq12_op(op, d + o_a, binary ? d + o_b : nullptr, n, d + o_out, s)) return ZKG_ERROR;
+    ZK_HIP(hipMemcpyAsync(out, d + o_out, 384 * n, hipMemcpyDeviceToHost, s));
+    ZK_HIP(hipStreamSynchronize(s));
+    return ZKG_OK;
+}
+int zkg_fq12_op(int op, const uint32_t *a, const uint32_t *b, size_t n, int where, uint32_t *out) {
+    try { return fq12_op_impl(op, a, b, n, where, out); }
+    catch (const std::exception &e) { set_error(std::string("zkg_fq12_op: ") + e.what()); return ZKG_ERROR; }
+    catch (...) { set_error("zkg_fq12_op: unexpected exception"); return ZKG_ERROR; }
+}
+
 // bilinearity probe for the tests: writes e(a*G1, b*G2) (384 B) for canonical scalars a, b
 int zkg_pairing_probe(const uint64_t a[4], const uint64_t b[4], uint8_t out[384]) {
     uint32_t ea[8], eb[8]; memcpy(ea, a, 32); memcpy(eb, b, 32);

@@ -12,6 +12,7 @@
 //   k_g2_replicate      the key's gamma and delta behind the proofs' B, so that k_miller runs over [A | -acc | -C] x [B | gamma.. | delta..]
 //   k_final_exp_check   per lane the product of an item's Miller values and its final exponentiation (final_exp.hip.hpp); the verdict
 //                       (== the key's alpha_beta) or the GT value itself
+//   k_fq12_op           one operation of the tower per lane on raw, unnormalised limbs: the known-answer hook zkg_fq12_op, on no verifier's path
 // and the device front end of the seam's batch entry (zkg_zklaim_verify_batch), which leaves the host neither square roots nor input sums:
 //   k_proof_decode        a compressed point of a 134-byte proof record per lane -> the affine Montgomery point ser::get_g1 / ser::get_g2
 //                         produce and a flag byte per item (the single verifier's acceptance rule and coords_canonical, bit for bit)
@@ -144,6 +145,29 @@ __global__ __launch_bounds__(VB) void k_final_exp_check(size_t n, const dev::Fq1
         });
         verdict[i] = diff ? 1 : 0;
     }
+}
+
+// one operation of the tower on raw limbs (the known-answer hook zkg_fq12_op): the functions of pairing.hip.hpp and final_exp.hip.hpp
+// themselves.  Nothing is normalised, so a caller sees the lazy representative the operation leaves.  b: the second factor (FQ12_MUL) or
+// the line's a, b, c in its c0 (FQ12_LINE).
+template <int OP> ZK_HD dev::Fq12 fq12_op_apply(const dev::Fq12 &a, const dev::Fq12 &b, const FrobConsts &fc) {
+    if constexpr (OP == FQ12_MUL) return a * b;
+    else if constexpr (OP == FQ12_SQR) return a.sqr();
+    else if constexpr (OP == FQ12_LINE) return dev::mul_by_line2(a, b.c0.c0, b.c0.c1, b.c0.c2);
+    else if constexpr (OP == FQ12_CSQR) return dev::cyclotomic_sqr(a);
+    else if constexpr (OP == FQ12_INV) return dev::inverse(a);
+    else if constexpr (OP == FQ12_CONJ) return dev::conjugate(a);
+    else if constexpr (OP == FQ12_FROB1) return dev::frobenius<1>(a, fc);
+    else if constexpr (OP == FQ12_FROB2) return dev::frobenius<2>(a, fc);
+    else if constexpr (OP == FQ12_FROB3) return dev::frobenius<3>(a, fc);
+    else return {a.c0.mul_by_v(), a.c1.mul_by_v()};
+}
+// lane i: out[i] = op(a[i], b[i]); b is read by the operations that have a second operand only
+template <int OP> __global__ __launch_bounds__(VB) void k_fq12_op(size_t n, const dev::Fq12 *a, const dev::Fq12 *b, FrobConsts fc, dev::Fq12 *out) {
+    const size_t i = (size_t)blockIdx.x * VB + threadIdx.x;
+    if (i >= n) return;
+    const dev::Fq12 x = a[i];
+    out[i] = fq12_op_apply<OP>(x, (OP == FQ12_MUL || OP == FQ12_LINE) ? b[i] : x, fc);
 }
 
 // ---- the device front end
@@ -294,6 +318,37 @@ void final_exp_device_code_on_host(const uint8_t in[384], uint8_t out[384]) {
     std::vector<uint32_t> ws((size_t)dev::FE_SLOTS * dev::FE_WORDS);
     const dev::Fq12 g = dev::final_exponentiation(f, 0, [&](int) { return f; }, frob_consts(), dev::FeSlots{ws.data(), 0, 1}).normalized();
     memcpy(out, &g, 384);
+}
+
+// d_out[i] = op(d_a[i], d_b[i]) on raw 384-byte Fq12 (zkg_fq12_op, where = 1); d_b may be null for an operation without a second operand
+int verify_fq12_op(int op, const void *d_a, const void *d_b, size_t n, void *d_out, hipStream_t s) {
+    if (!n) return ZKG_OK;
+    const dim3 g(blocks_for(n)), b(VB);
+    const dev::Fq12 *A = (const dev::Fq12 *)d_a, *B = (const dev::Fq12 *)d_b; dev::Fq12 *O = (dev::Fq12 *)d_out;
+    const FrobConsts fc = frob_consts();
+    switch (op) {
+#define ZK_FQ12_CASE(OP) case OP: hipLaunchKernelGGL(k_fq12_op<OP>, g, b, 0, s, n, A, B, fc, O); break;
+    ZK_FQ12_CASE(FQ12_MUL) ZK_FQ12_CASE(FQ12_SQR) ZK_FQ12_CASE(FQ12_LINE) ZK_FQ12_CASE(FQ12_CSQR) ZK_FQ12_CASE(FQ12_INV) ZK_FQ12_CASE(FQ12_CONJ)
+    ZK_FQ12_CASE(FQ12_FROB1) ZK_FQ12_CASE(FQ12_FROB2) ZK_FQ12_CASE(FQ12_FROB3) ZK_FQ12_CASE(FQ12_MUL_BY_V)
+#undef ZK_FQ12_CASE
+    default: return ZKG_ERROR;
+    }
+    ZK_HIP(hipGetLastError());
+    return ZKG_OK;
+}
+// the same text on the host, one element (zkg_fq12_op, where = 2): canonical values in, canonical values out
+void fq12_op_device_code_on_host(int op, const uint32_t a[96], const uint32_t b[96], uint32_t out[96]) {
+    dev::Fq12 x, y, r;
+    memcpy(&x, a, 384); memcpy(&y, b ? b : a, 384);
+    const FrobConsts fc = frob_consts();
+    switch (op) {
+#define ZK_FQ12_CASE(OP) case OP: r = fq12_op_apply<OP>(x, y, fc); break;
+    ZK_FQ12_CASE(FQ12_MUL) ZK_FQ12_CASE(FQ12_SQR) ZK_FQ12_CASE(FQ12_LINE) ZK_FQ12_CASE(FQ12_CSQR) ZK_FQ12_CASE(FQ12_INV) ZK_FQ12_CASE(FQ12_CONJ)
+    ZK_FQ12_CASE(FQ12_FROB1) ZK_FQ12_CASE(FQ12_FROB2) ZK_FQ12_CASE(FQ12_FROB3)
+#undef ZK_FQ12_CASE
+    default: r = fq12_op_apply<FQ12_MUL_BY_V>(x, y, fc); break;
+    }
+    memcpy(out, &r, 384);
 }
 
 int verify_g2_subgroup(const G2Affine *d_B, size_t n, uint8_t *d_ok, hipStream_t s) {
