@@ -11,6 +11,7 @@ import pytest
 from gpu_util import credential_payloads, zkg  # noqa: F401
 from test_gpu_prove_batch import _synthetic_key, _to_sparse, _witness
 from util import R, arr, random_fr_canonical
+from zklaim_witness_cases import host_pass
 
 pytestmark = pytest.mark.gpu
 N_BATCH = 3200            # m = 4096, radix-2, batched: z has 3201 elements, one lane in the last wavefront
@@ -160,6 +161,39 @@ def test_batch_unsatisfied_item_fails_alone(zkg):
     crs.free(); kp.free()
     for c in cks:
         c.free()
+
+
+def test_three_sources_one_driver_across_a_chunk_boundary(zkg):
+    """chunk + 1 credentials of a one-payload key (m = 2^15, the smallest zklaim key that batches): two chunks, the second of one item.  The
+    same credentials and the same (r, s) through prove_batch (host sparse witnesses), prove_batch_zklaim (contexts, witnesses generated on
+    the device) and prove_batch_dev (the mirror's witnesses, expanded and copied to the device): one chunk driver, three sources, the
+    same bytes and the same chunk counts"""
+    keep = []
+    payloads = lambda v: [dict(credential_payloads(1)[0], salt=0x3600 + v)]      # noqa: E731
+    ck = zkg.ZklaimCircuit(zkg.make_ctx(payloads(0), keep))
+    kp = zkg.Keypair(ck.r1cs, random_fr_canonical(5, 0x5DF1))
+    assert (kp.pk.domain_size or (1 << kp.pk.log_m)) == 1 << 15
+    crs = zkg.Crs(kp.pk)
+    chunk = crs.prove_batch_chunk()
+    assert chunk > 0
+    P, n = chunk + 1, ck.r1cs.num_variables
+    ctxs = [zkg.make_ctx(payloads(v), keep) for v in range(P)]
+    rss = [tuple(random_fr_canonical(2, 0x5DF200 + v)) for v in range(P)]
+    host = crs.prove_batch([(*host_pass(zkg, c), r, s) for c, (r, s) in zip(ctxs, rss)])
+    assert zkg.prove_batch_stats() == (P, 0, 2)
+    assert all(g[0] == 0 and len(g[1]) == 134 for g in host)
+    gen = crs.prove_batch_zklaim(ctxs, rss)
+    assert zkg.prove_batch_stats() == (P, 0, 2) and zkg.zklaim_witness_stats() == (P, 0)
+    dense = np.zeros((P, n, 4), np.uint64)
+    for j, c in enumerate(ctxs):
+        tags, idx, vals = zkg.zklaim_witness_mirror(c)
+        dense[j, tags == 1] = arr([1], R)[0]
+        dense[j, idx] = vals
+    d = _dev(dense)
+    rc, dev = crs.prove_batch_dev(d.data_ptr(), n, P, rss)
+    assert rc == 0 and zkg.prove_batch_stats() == (P, 0, 2) and zkg.prove_dev_stats() == (P, 0)
+    assert gen == host and dev == host
+    crs.free(); kp.free(); ck.free()
 
 
 def test_batch_on_keys_that_do_not_batch(zkg, oracle):

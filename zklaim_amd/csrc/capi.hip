@@ -950,9 +950,7 @@ static zkg_msm_shards *zkg_msm_g1_shards_upload_impl(const uint64_t *bases, size
     return holder.release();
 }
 zkg_msm_shards *zkg_msm_g1_shards_upload(const uint64_t *bases, size_t n, const int *devices, int ndev) {
-    try { return zkg_msm_g1_shards_upload_impl(bases, n, devices, ndev); }                      // nothing propagates through the C boundary
-    catch (const std::exception &e) { zk::set_error(std::string("zkg_msm_g1_shards_upload: ") + e.what()); return nullptr; }
-    catch (...) { zk::set_error("zkg_msm_g1_shards_upload: unexpected exception"); return nullptr; }
+    return zk::c_boundary<zkg_msm_shards *>("zkg_msm_g1_shards_upload", nullptr, [&] { return zkg_msm_g1_shards_upload_impl(bases, n, devices, ndev); });
 }
 
 void zkg_msm_g1_shards_free(zkg_msm_shards *h) {
@@ -1030,9 +1028,7 @@ static int zkg_msm_g1_multi_impl(const zkg_msm_shards *h_, const uint64_t *scala
     return ZKG_OK;
 }
 int zkg_msm_g1_multi(const zkg_msm_shards *h_, const uint64_t *scalars, uint64_t out_jac[12], uint64_t *partials_jac) {
-    try { return zkg_msm_g1_multi_impl(h_, scalars, out_jac, partials_jac); }                      // nothing propagates through the C boundary
-    catch (const std::exception &e) { zk::set_error(std::string("zkg_msm_g1_multi: ") + e.what()); return ZKG_ERROR; }
-    catch (...) { zk::set_error("zkg_msm_g1_multi: unexpected exception"); return ZKG_ERROR; }
+    return zk::c_boundary("zkg_msm_g1_multi", ZKG_ERROR, [&] { return zkg_msm_g1_multi_impl(h_, scalars, out_jac, partials_jac); });
 }
 
 

@@ -288,14 +288,10 @@ static int pk_blob_inspect_impl(const void *blob, size_t len, uint64_t out[8]) {
     return ZKG_OK;
 }
 extern "C" int zkg_pk_blob_inspect(const void *blob, size_t len, uint64_t out[8]) {
-    try { return pk_blob_inspect_impl(blob, len, out); }
-    catch (const std::exception &e) { set_error(std::string("zkg_pk_blob_inspect: ") + e.what()); return ZKG_ERROR; }
-    catch (...) { set_error("zkg_pk_blob_inspect: unexpected exception"); return ZKG_ERROR; }
+    return c_boundary("zkg_pk_blob_inspect", ZKG_ERROR, [&] { return pk_blob_inspect_impl(blob, len, out); });
 }
 
 // Nothing may propagate through the C boundary: allocation failures on hostile sizes end up here as an error return.
 extern "C" zkg_crs *zkg_crs_upload_blob(const void *blob, size_t len) {
-    try { return crs_upload_blob_impl(blob, len); }
-    catch (const std::exception &e) { set_error(std::string("zkg_crs_upload_blob: ") + e.what()); return nullptr; }
-    catch (...) { set_error("zkg_crs_upload_blob: unexpected exception"); return nullptr; }
+    return c_boundary<zkg_crs *>("zkg_crs_upload_blob", nullptr, [&] { return crs_upload_blob_impl(blob, len); });
 }

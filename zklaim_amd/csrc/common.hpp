@@ -9,12 +9,12 @@
 #include <map>
 #include <mutex>
 #include "curve.hip.hpp"
+#include "c_boundary.hpp"                // set_error, c_boundary
 
 struct zklaim_ctx;                       // include/zklaim_abi.h
 
 namespace zk {
 
-void set_error(const std::string &msg);
 bool hip_ok(hipError_t e, const char *what, const char *file, int line);
 #define ZK_HIP(expr) do { if (!::zk::hip_ok((expr), #expr, __FILE__, __LINE__)) return ZKG_ERROR; } while (0)
 #define ZK_HIP_V(expr) do { if (!::zk::hip_ok((expr), #expr, __FILE__, __LINE__)) return; } while (0)

@@ -207,9 +207,7 @@ static int libsnark_trusted_setup_impl(zklaim_ctx *ctx) {
     return ZKLAIM_OK;
 }
 int libsnark_trusted_setup(zklaim_ctx *ctx) {
-    try { return libsnark_trusted_setup_impl(ctx); }                      // nothing propagates through the C boundary
-    catch (const std::exception &e) { zk::set_error(std::string("libsnark_trusted_setup: ") + e.what()); return ZKLAIM_ERROR; }
-    catch (...) { zk::set_error("libsnark_trusted_setup: unexpected exception"); return ZKLAIM_ERROR; }
+    return zk::c_boundary("libsnark_trusted_setup", ZKLAIM_ERROR, [&] { return libsnark_trusted_setup_impl(ctx); });
 }
 
 
@@ -322,9 +320,7 @@ static int libsnark_prove_impl(zklaim_ctx *ctx) {
     return rc;
 }
 int libsnark_prove(zklaim_ctx *ctx) {
-    try { return libsnark_prove_impl(ctx); }                      // nothing propagates through the C boundary
-    catch (const std::exception &e) { zk::set_error(std::string("libsnark_prove: ") + e.what()); return ZKLAIM_ERROR; }
-    catch (...) { zk::set_error("libsnark_prove: unexpected exception"); return ZKLAIM_ERROR; }
+    return zk::c_boundary("libsnark_prove", ZKLAIM_ERROR, [&] { return libsnark_prove_impl(ctx); });
 }
 
 
@@ -446,17 +442,13 @@ static int zklaim_prove_batch_impl(zklaim_ctx *const *ctxs, size_t count, int *r
     for (SeamGroup &g : groups) {
         size_t made[2] = {0, 0};
         struct Add { size_t *all, *one; ~Add() { all[0] += one[0]; all[1] += one[1]; } } add{made_all, made};
-        try { prove_group(ctxs, g, rc, made); }                        // a group that fails leaves its items at 1 and the other groups alone
-        catch (const std::exception &e) { zk::set_error(std::string("zkg_zklaim_prove_batch: ") + e.what()); }
-        catch (...) { zk::set_error("zkg_zklaim_prove_batch: unexpected exception"); }
+        // a group that fails (a throw included) leaves its items at 1 and the other groups alone
+        (void)zk::c_boundary("zkg_zklaim_prove_batch", 0, [&] { prove_group(ctxs, g, rc, made); return 0; });
     }
     return ZKG_OK;
 }
 int zkg_zklaim_prove_batch(zklaim_ctx *const *ctxs, size_t count, int *rc) {
-    try { return zklaim_prove_batch_impl(ctxs, count, rc); }     // nothing propagates through the C boundary
-    catch (const std::exception &e) { zk::set_error(std::string("zkg_zklaim_prove_batch: ") + e.what()); }
-    catch (...) { zk::set_error("zkg_zklaim_prove_batch: unexpected exception"); }
-    return ZKG_ERROR;
+    return zk::c_boundary("zkg_zklaim_prove_batch", ZKG_ERROR, [&] { return zklaim_prove_batch_impl(ctxs, count, rc); });
 }
 
 
@@ -468,9 +460,7 @@ static int libsnark_verify_impl(zklaim_ctx *ctx) {
     return zkg_groth16_verify(ctx->vk, ctx->vk_size, input.data(), n, ctx->proof, ctx->proof_size) == 0 ? 0 : 1;
 }
 int libsnark_verify(zklaim_ctx *ctx) {
-    try { return libsnark_verify_impl(ctx); }                      // nothing propagates through the C boundary
-    catch (const std::exception &e) { zk::set_error(std::string("libsnark_verify: ") + e.what()); return 1; }
-    catch (...) { zk::set_error("libsnark_verify: unexpected exception"); return 1; }
+    return zk::c_boundary("libsnark_verify", 1, [&] { return libsnark_verify_impl(ctx); });
 }
 
 
@@ -489,10 +479,7 @@ static int zklaim_verify_batch_impl(zklaim_ctx *const *ctxs, size_t count, int *
     return seam_verify_batch(ctxs, count, rc, seam_gpu_verify());
 }
 int zkg_zklaim_verify_batch(zklaim_ctx *const *ctxs, size_t count, int *rc) {
-    try { return zklaim_verify_batch_impl(ctxs, count, rc); }    // nothing propagates through the C boundary
-    catch (const std::exception &e) { zk::set_error(std::string("zkg_zklaim_verify_batch: ") + e.what()); }
-    catch (...) { zk::set_error("zkg_zklaim_verify_batch: unexpected exception"); }
-    return ZKG_ERROR;
+    return zk::c_boundary("zkg_zklaim_verify_batch", ZKG_ERROR, [&] { return zklaim_verify_batch_impl(ctxs, count, rc); });
 }
 
 

@@ -311,6 +311,36 @@ ZK_D bool claim_listed_tag(uint8_t *wtags, uint32_t pos, uint32_t tag) {
         old = prev;
     }
 }
+// the tag of an element by its VALUE: 0 zero, 1 one, 2 anything else (k_classify in msm.hip keeps a copy of this rule, and records a subset miss with a plain store)
+ZK_D uint32_t tag_by_value(const Fr &v) {
+    uint32_t any = 0, diff = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { any |= v.v[j]; diff |= v.v[j] ^ FrParams::ONE[j]; }
+    return any == 0 ? 0u : (diff == 0 ? 1u : 2u);
+}
+// Every lane of the wavefront arrives here; those with is_listed append pos to listed[] — a ballot, ONE atomicAdd on count[0] by the leader, the
+// base handed round by a shuffle (unordered across wavefronts) — and raise count[1] when the witness tables do not cover pos (yet).
+ZK_D void wave_list_append(bool is_listed, uint32_t pos, uint32_t *listed, uint32_t *count, const uint32_t *subset_pos) {
+    const unsigned long long mask = __ballot(is_listed);
+    if (!mask) return;
+    const uint32_t lane = threadIdx.x & 63, leader = (uint32_t)__ffsll((long long)mask) - 1;
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(count, (uint32_t)__popcll(mask));
+    base = __shfl(base, leader, 64);
+    if (is_listed) {
+        listed[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1))] = pos;
+        if (subset_pos && subset_pos[pos] == SUBSET_NONE) or_and_wait(count + 1);
+    }
+}
+// The last workgroup to finish (ticket) hands the split's counts to the pinned words: [1] listed, [2] a listed element misses the witness tables,
+// and [3] bad listed entry / [4] the witness generator's error word where the kernel has one: no copy launch between the split and the mat-vec.
+ZK_D void publish_split_words(uint32_t *ticket, uint32_t *count, uint32_t *host_words, uint32_t *bad /* or null */, const uint32_t *gen_err /* or null */) {
+    __syncthreads();
+    if (threadIdx.x != 0 || atomicAdd(ticket, 1u) != gridDim.x - 1) return;
+    host_words[1] = atomicOr(count, 0u); host_words[2] = atomicOr(count + 1, 0u);
+    if (bad) host_words[3] = atomicOr(bad, 0u);
+    if (gen_err) host_words[4] = *gen_err;
+}
 // entry i of one witness' listing (every lane of the wavefront takes part: the list positions come from a ballot); bad: the call's "bad listed entry" word
 ZK_D void scatter_full_entry(size_t i, const uint32_t *idx, const Fr *vals, size_t cnt, size_t n, Fr *z, const uint8_t *tags, uint8_t *wtags,
                              uint32_t *listed, uint32_t *count, uint32_t *bad, const uint32_t *subset_pos) {
@@ -320,34 +350,18 @@ ZK_D void scatter_full_entry(size_t i, const uint32_t *idx, const Fr *vals, size
         if (v >= n || tags[v] != 2) or_and_wait(bad);                          // a listed index must be in range and tagged 2 (and listed once)
         else {
             const Fr val = vals[i];
-            uint32_t any = 0, diff = 0;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { any |= val.v[j]; diff |= val.v[j] ^ FrParams::ONE[j]; }
-            tag = any == 0 ? 0u : (diff == 0 ? 1u : 2u);
+            tag = tag_by_value(val);
             pos = v + 1;
             if (claim_listed_tag(wtags, pos, tag)) z[pos] = val;
             else { or_and_wait(bad); tag = 0; }                                 // listed twice: the call fails (words[3]), nothing is listed again
         }
     }
-    const unsigned long long mask = __ballot(tag == 2);
-    if (mask) {
-        const uint32_t lane = threadIdx.x & 63, leader = (uint32_t)__ffsll((long long)mask) - 1;
-        uint32_t base = 0;
-        if (lane == leader) base = atomicAdd(count, (uint32_t)__popcll(mask));
-        base = __shfl(base, leader, 64);
-        if (tag == 2) {
-            listed[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1))] = pos;
-            if (subset_pos && subset_pos[pos] == SUBSET_NONE) or_and_wait(count + 1);    // the witness tables do not cover this element (yet)
-        }
-    }
+    wave_list_append(tag == 2, pos, listed, count, subset_pos);
 }
 __global__ __launch_bounds__(256) void k_scatter_full(const uint32_t *idx, const Fr *vals, size_t cnt, size_t n, Fr *z, const uint8_t *tags, uint8_t *wtags,
                                                       uint32_t *listed, uint32_t *count, uint32_t *words, const uint32_t *subset_pos, uint32_t *host_words) {
     scatter_full_entry((size_t)blockIdx.x * blockDim.x + threadIdx.x, idx, vals, cnt, n, z, tags, wtags, listed, count, words + 3, subset_pos);
-    __syncthreads();
-    if (threadIdx.x == 0 && atomicAdd(words + 2, 1u) == gridDim.x - 1) {
-        host_words[1] = atomicOr(count, 0u); host_words[2] = atomicOr(count + 1, 0u); host_words[3] = atomicOr(words + 3, 0u);
-    }
+    publish_split_words(words + 2, count, host_words, words + 3, nullptr);
 }
 
 // the same for a listing made on the device (k_zklaim_witness_par): its length is desc[1], known there only, so the launch covers the
@@ -356,10 +370,7 @@ __global__ __launch_bounds__(256) void k_scatter_full_counted(const uint32_t *de
                                                               uint32_t *listed, uint32_t *count, uint32_t *words, const uint32_t *subset_pos, uint32_t *host_words, const uint32_t *gen_err) {
     const size_t cnt = desc[1] < cap ? desc[1] : cap;
     scatter_full_entry((size_t)blockIdx.x * blockDim.x + threadIdx.x, idx + desc[0], vals + desc[0], cnt, n, z, tags, wtags, listed, count, words + 3, subset_pos);
-    __syncthreads();
-    if (threadIdx.x == 0 && atomicAdd(words + 2, 1u) == gridDim.x - 1) {
-        host_words[1] = atomicOr(count, 0u); host_words[2] = atomicOr(count + 1, 0u); host_words[3] = atomicOr(words + 3, 0u); host_words[4] = *gen_err;
-    }
+    publish_split_words(words + 2, count, host_words, words + 3, gen_err);
 }
 
 // Witnesses ALREADY on the device (zkg_groth16_prove_dev, zkg_groth16_prove_batch_dev): this kernel is the whole way in — no staging, no tags
@@ -377,26 +388,11 @@ __global__ __launch_bounds__(256) void k_split_dev(const Fr *src, size_t src_str
     uint32_t tag = 0;
     if (i < n1) {
         const Fr v = i ? src[i - 1] : Fr::one();
-        uint32_t any = 0, diff = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { any |= v.v[j]; diff |= v.v[j] ^ FrParams::ONE[j]; }
-        tag = any == 0 ? 0u : (diff == 0 ? 1u : 2u);
+        tag = tag_by_value(v);
         z[i] = v; wtags[i] = (uint8_t)tag;
     }
-    const unsigned long long mask = __ballot(tag == 2);                         // (every lane of the wavefront arrives here)
-    if (mask) {
-        const uint32_t lane = threadIdx.x & 63, leader = (uint32_t)__ffsll((long long)mask) - 1;
-        uint32_t base = 0;
-        if (lane == leader) base = atomicAdd(count, (uint32_t)__popcll(mask));
-        base = __shfl(base, leader, 64);
-        if (tag == 2) {
-            listed[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1))] = (uint32_t)i;
-            if (subset_pos && subset_pos[i] == SUBSET_NONE) or_and_wait(count + 1);     // the witness tables do not cover this element (yet)
-        }
-    }
-    if (!host_words) return;
-    __syncthreads();
-    if (threadIdx.x == 0 && atomicAdd(words + 2, 1u) == gridDim.x - 1) { host_words[1] = atomicOr(count, 0u); host_words[2] = atomicOr(count + 1, 0u); }
+    wave_list_append(tag == 2, (uint32_t)i, listed, count, subset_pos);
+    if (host_words) publish_split_words(words + 2, count, host_words, nullptr, nullptr);
 }
 
 // H_tmp = (aA . aB - aC) * Zinv  (divide_by_Z_on_coset fused with the pointwise product)
@@ -791,12 +787,7 @@ static zkg_crs *zkg_crs_upload_impl(const zkg_pk *pk, bool queries_on_device = f
     if (!ok) { zkg_crs_free(crs); return nullptr; }
     return crs;
 }
-zkg_crs *zkg_crs_upload(const zkg_pk *pk) {
-    try { return zkg_crs_upload_impl(pk); }                      // nothing propagates through the C boundary
-    catch (const std::exception &e) { zk::set_error(std::string("zkg_crs_upload: ") + e.what()); return nullptr; }
-    catch (...) { zk::set_error("zkg_crs_upload: unexpected exception"); return nullptr; }
-}
-
+zkg_crs *zkg_crs_upload(const zkg_pk *pk) { return c_boundary<zkg_crs *>("zkg_crs_upload", nullptr, [&] { return zkg_crs_upload_impl(pk); }); }
 
 static void slot_release_h_runs(ProverSlot &S) {                              // leaves the current device changed; callers restore it
     for (auto &r : S.h_runs) {
@@ -883,12 +874,9 @@ static int zkg_qap_witness_h_impl(const zkg_crs *crs_, const uint64_t *witness, 
     memset(h_out + 4 * crs->m, 0, 32);                                      // coefficients_for_H[m] = 0
     return ZKG_OK;
 }
-int zkg_qap_witness_h(const zkg_crs *crs_, const uint64_t *witness, uint64_t *h_out) {
-    try { return zkg_qap_witness_h_impl(crs_, witness, h_out); }                      // nothing propagates through the C boundary
-    catch (const std::exception &e) { zk::set_error(std::string("zkg_qap_witness_h: ") + e.what()); return ZKG_ERROR; }
-    catch (...) { zk::set_error("zkg_qap_witness_h: unexpected exception"); return ZKG_ERROR; }
+int zkg_qap_witness_h(const zkg_crs *crs, const uint64_t *witness, uint64_t *h_out) {
+    return c_boundary("zkg_qap_witness_h", ZKG_ERROR, [&] { return zkg_qap_witness_h_impl(crs, witness, h_out); });
 }
-
 
 // ---- one proof = prove_enqueue (everything the GPU does, queued without waiting) + prove_finish (host tails, assembly, bytes)
 static const bool g_dbg_timing = getenv("ZKG_DEBUG_TIMING") != nullptr, g_serial_msm = getenv("ZKG_SERIAL_MSM") != nullptr;
@@ -905,7 +893,7 @@ static MsmBases query_set(const DevBuf &q, bool g2, uint32_t index_sub) { MsmBas
 // The witness tables grow to cover `listed` more elements (the first proof on a key; later only when a witness has a non-bit value where
 // every earlier one had a bit).  Host: membership -> ascending element list and positions; device: level 0 gathered from the queries, then
 // the levels.  Runs on the helper thread with the ones-sum stream, which has nothing of this proof queued yet.
-static int subset_extend(zkg_crs *crs, ProverSlot &S, size_t listed, const std::vector<uint32_t> *listed_host = nullptr /* a batch: the union of its witnesses' lists */) {
+static int subset_extend(zkg_crs *crs, ProverSlot &S, size_t listed, const std::vector<uint32_t> *listed_host /* a batch: the union of its witnesses' lists; or null: the slot's list */) {
     zkg_crs::SubsetTables &T = crs->sub;
     const size_t n1 = (size_t)crs->n + 1; hipStream_t s = S.stream_o;
     // From here until one of the two success exits the key has NO witness tables: pos / idx / the tables / the window size are rewritten
@@ -1014,6 +1002,20 @@ static int subset_extend(zkg_crs *crs, ProverSlot &S, size_t listed, const std::
     if (g_dbg_timing) fprintf(stderr, "[zkg]     witness tables over %zu of %zu elements (rebuild %u)\n", count, n1, T.rebuilds);
     return ZKG_OK;
 }
+// subset_extend under the key's protocol (see zkg_crs): the tables are shared by the key's slots, so the caller — holding its lease — waits until
+// every other proof in flight has finished or waits here too, extends alone, and lets the others go on.  No new proof starts meanwhile.
+static int extend_tables_exclusive(zkg_crs *crs, ProverSlot &S, size_t listed, const std::vector<uint32_t> *host_list) {
+    std::unique_lock<std::mutex> lk(crs->mu);
+    ++crs->waiting_ext; crs->cv.notify_all();
+    crs->cv.wait(lk, [&] { return !crs->extending && crs->leases - crs->waiting_ext == 0; });
+    --crs->waiting_ext; crs->extending = true;
+    lk.unlock();
+    int rc = ZKG_ERROR;
+    try { rc = subset_extend(crs, S, listed, host_list); } catch (...) { set_error("prover: witness table extension failed"); }   // the flag below must be cleared whatever happens
+    lk.lock();
+    crs->extending = false; crs->cv.notify_all();
+    return rc;
+}
 // ---- H over several devices: launch (after the transforms, in the slot's stream order) and finish
 static int h_shards_launch(zkg_crs *crs, ProverSlot &S) {
     int cur = 0; (void)hipGetDevice(&cur);
@@ -1077,20 +1079,7 @@ static int prove_enqueue(zkg_crs *crs, ProverSlot &S, const WitnessSrc &witness,
         if (S.flag_host[3]) { set_error("prover: a listed witness index is out of range, not tagged 2 or listed twice"); return ZKG_ERROR; }
         if (listed > n + 1) { set_error("prover: witness split out of range"); return ZKG_ERROR; }
         const uint8_t *tags = S.wtags.as<uint8_t>(); const uint32_t *gather = S.wlisted.as<uint32_t>(), *z = S.z.as<uint32_t>();
-        if (listed && (S.flag_host[2] || !crs->sub.count)) {
-            // the tables are shared by the key's slots: extend them only while no other proof is using them (see zkg_crs)
-            std::unique_lock<std::mutex> lk(crs->mu);
-            ++crs->waiting_ext; crs->cv.notify_all();
-            crs->cv.wait(lk, [&] { return !crs->extending && crs->leases - crs->waiting_ext == 0; });
-            --crs->waiting_ext; crs->extending = true;
-            lk.unlock();
-            int rc_ext = ZKG_ERROR;
-            try { rc_ext = subset_extend(crs, S, listed); } catch (...) { set_error("prover: witness table extension failed"); }   // the flag below must be cleared whatever happens
-            lk.lock();
-            crs->extending = false; crs->cv.notify_all();
-            lk.unlock();
-            if (rc_ext) return ZKG_ERROR;
-        }
+        if (listed && (S.flag_host[2] || !crs->sub.count) && extend_tables_exclusive(crs, S, listed, nullptr)) return ZKG_ERROR;
         msm_job_set_window(S.job_w1, crs->c_w); msm_job_set_window(S.job_w2, crs->c_w);   // (another slot's proof may have built the tables)
         const uint32_t *pos = crs->sub.pos.as<uint32_t>();
         // bucket method: the subset tables, addressed through the element positions; flat sums over the ones: the queries as uploaded
@@ -1245,18 +1234,40 @@ static bool witness_to_sparse(const uint64_t *w, size_t n, std::vector<uint8_t> 
     for (size_t i = 0; i < total; ++i) memcpy(&vals[4 * i], w + 4 * (size_t)idx[i], 32);
     return true;
 }
+// The body of every single-proof entry: a slot lease, prove_enqueue (nothing of the slot is left running when it fails), prove_finish (which writes
+// `out` as the pieces land: see prove_single_staged).  A dense host witness goes up sparse where that pays.  A device witness is ordered behind `caller`,
+// the stream whose queued work wrote it (unused otherwise): the proof runs on the slot's own (non-blocking) streams, and the call returns after the proof
+// has landed, so nothing of it is left running for the caller to order after.
+struct SingleOutcome { bool enqueued = false; int zw_state = ZW_NONE; };     // prove_enqueue succeeded; what became of a generated witness (ZW_*)
+static int prove_single(zkg_crs *crs, const WitnessSrc &witness, const uint64_t r_[4], const uint64_t s_[4], bool check, hipStream_t caller, uint8_t *out, size_t *len,
+                        SingleOutcome *outcome = nullptr) {
+    SlotLease lease(crs);
+    if (!lease.ok()) return ZKG_ERROR;
+    ProverSlot &S = lease.S();
+    WitnessSrc W = witness;
+    if (W.dense && witness_to_sparse(W.dense, crs->n, S.scan_tags, S.scan_idx, S.scan_vals)) {
+        W.dense = nullptr; W.tags = S.scan_tags.data(); W.idx = S.scan_idx.data(); W.vals = S.scan_vals.data(); W.count = S.scan_idx.size();
+    }
+    if (W.dev) { ZK_HIP(hipEventRecord(S.ev[12], caller)); ZK_HIP(hipStreamWaitEvent(S.stream, S.ev[12], 0)); }
+    const int rc = prove_enqueue(crs, S, W, r_, s_, check);
+    if (outcome) { outcome->enqueued = rc == ZKG_OK; outcome->zw_state = S.zw_state; }
+    if (rc) { slot_drain(crs, S); return ZKG_ERROR; }
+    return prove_finish(crs, S, out, len);
+}
+// the same with the proof staged: nothing is written unless the proof is made
+static int prove_single_staged(zkg_crs *crs, const WitnessSrc &W, const uint64_t r_[4], const uint64_t s_[4], bool check, hipStream_t caller, uint8_t *proof_out, size_t *proof_len,
+                               SingleOutcome *outcome = nullptr) {
+    uint8_t buf[256]; size_t len = 0;
+    const int rc = prove_single(crs, W, r_, s_, check, caller, buf, &len, outcome);
+    if (rc == ZKG_OK) { memcpy(proof_out, buf, len); *proof_len = len; }
+    return rc;
+}
 static int groth16_prove_impl(const zkg_crs *crs_, const uint64_t *witness, const uint64_t r_[4], const uint64_t s_[4], int check_satisfied,
                               uint8_t *proof_out, size_t *proof_len) {
     zkg_crs *crs = const_cast<zkg_crs *>(crs_);
     if (!crs || !r_ || !s_ || !proof_out || !proof_len || (crs->n && !witness)) { set_error("zkg_groth16_prove: bad argument"); return ZKG_ERROR; }
-    SlotLease lease(crs);
-    if (!lease.ok()) return ZKG_ERROR;
-    ProverSlot &S = lease.S();
-    WitnessSrc W;
-    if (witness_to_sparse(witness, crs->n, S.scan_tags, S.scan_idx, S.scan_vals)) { W.tags = S.scan_tags.data(); W.idx = S.scan_idx.data(); W.vals = S.scan_vals.data(); W.count = S.scan_idx.size(); }
-    else W.dense = witness;
-    if (prove_enqueue(crs, S, W, r_, s_, check_satisfied != 0)) { slot_drain(crs, S); return ZKG_ERROR; }
-    return prove_finish(crs, S, proof_out, proof_len);
+    WitnessSrc W; W.dense = witness;
+    return prove_single(crs, W, r_, s_, check_satisfied != 0, nullptr, proof_out, proof_len);
 }
 
 // the same proof from a sparse description of the witness: tags[n] (0 = zero, 1 = one, 2 = listed) and `count` listed variables as
@@ -1268,12 +1279,8 @@ static int groth16_prove_sparse_impl(const zkg_crs *crs_, const uint8_t *tags, c
     if (!crs || !r_ || !s_ || !proof_out || !proof_len || (crs->n && !tags) || (count && (!full_index || !full_values)) || count > crs->n) {
         set_error("zkg_groth16_prove_sparse: bad argument"); return ZKG_ERROR;
     }
-    SlotLease lease(crs);
-    if (!lease.ok()) return ZKG_ERROR;
-    ProverSlot &S = lease.S();
     WitnessSrc W; W.tags = tags; W.idx = full_index; W.vals = full_values; W.count = count;
-    if (prove_enqueue(crs, S, W, r_, s_, check_satisfied != 0)) { slot_drain(crs, S); return ZKG_ERROR; }
-    return prove_finish(crs, S, proof_out, proof_len);
+    return prove_single(crs, W, r_, s_, check_satisfied != 0, nullptr, proof_out, proof_len);
 }
 
 // ---- zkg_groth16_prove_zklaim: one credential of a resident key, its witness generated on the device (k_zklaim_witness_par, launched by
@@ -1296,20 +1303,11 @@ static int groth16_prove_zklaim_impl(const zkg_crs *crs_, const zklaim_ctx *ctx,
     if (!crs || !ctx || !r_ || !s_ || !proof_out || !proof_len) { set_error("zkg_groth16_prove_zklaim: bad argument"); return ZKG_ERROR; }
     ZwPlan pl;
     if (zklaim_witness_plan_for_n(crs->n, pl) && zklaim_witness_par_ready(pl)) {
-        SlotLease lease(crs);
-        if (!lease.ok()) return ZKG_ERROR;
-        ProverSlot &S = lease.S();
         WitnessSrc W; W.ctx = ctx; W.plan = &pl;
-        uint8_t buf[256]; size_t len = 0;                                       // nothing is written unless the proof is made
-        if (prove_enqueue(crs, S, W, r_, s_, check_satisfied != 0)) {
-            slot_drain(crs, S);
-            if (S.zw_state != ZW_GENERATOR_ERROR) return ZKG_ERROR;
-        } else {
-            const int rc = prove_finish(crs, S, buf, &len);
-            if (rc == ZKG_OK) { memcpy(proof_out, buf, len); *proof_len = len; }
-            if (rc == ZKG_OK || rc == ZKG_UNSATISFIED) t_prove_zklaim_stats[0] = 1;
-            return rc;
-        }
+        SingleOutcome outcome;
+        const int rc = prove_single_staged(crs, W, r_, s_, check_satisfied != 0, nullptr, proof_out, proof_len, &outcome);
+        if (rc == ZKG_OK || rc == ZKG_UNSATISFIED) t_prove_zklaim_stats[0] = 1;
+        if (outcome.zw_state != ZW_GENERATOR_ERROR) return rc;                  // (the generator's error: the host witness below)
     }
     return prove_zklaim_host_witness(crs, ctx, r_, s_, check_satisfied, proof_out, proof_len);
 }
@@ -1394,17 +1392,32 @@ static void assemble_proof(const zkg_crs *crs, const Fr &r, const Fr &s, const G
 }
 static thread_local size_t t_batch_stats[3] = {0, 0, 0};
 
-// where a chunk's witnesses come from when they are not items: zklaim contexts of the key's payload count, generated on the device
-struct ZklaimChunk { const zklaim_ctx *const *ctxs; const uint64_t *rs; /* 8 limbs per item: r | s */ const ZwPlan *plan; bool cursor_error; };
-// or dense witnesses already on the device (zkg_groth16_prove_batch_dev): item p at src + p * stride
-struct DevChunk { const Fr *src; size_t stride; const uint64_t *rs; /* 8 limbs per item: r | s */ };
+// Where a batch's witnesses come from (what WitnessSrc is to a single proof), one kind per entry:
+//   HOST_ITEMS  zkg_groth16_prove_batch: items[p], a dense or a sparse witness and its (r, s); packed on the host, one upload per chunk
+//   ZKLAIM      zkg_groth16_prove_batch_zklaim: ctxs[p], credentials of the key's payload count; a few bytes each go up and k_zklaim_witness
+//               writes the same packed form into the device stage
+//   DEVICE      zkg_groth16_prove_batch_dev: dense witnesses already in device memory, item p at dev + p * stride, behind the caller's `stream`;
+//               split in place by k_split_dev, nothing is packed, staged or uploaded
+struct ChunkSource {
+    enum Kind { HOST_ITEMS, ZKLAIM, DEVICE } kind = HOST_ITEMS;
+    const zkg_prove_item *items = nullptr;
+    const zklaim_ctx *const *ctxs = nullptr; const ZwPlan *plan = nullptr;
+    const Fr *dev = nullptr; size_t stride = 0; hipStream_t stream = nullptr;
+    const uint64_t *rs = nullptr;                                             // ZKLAIM, DEVICE: 8 limbs per item, r | s
+    const uint64_t *r(size_t p) const { return kind == HOST_ITEMS ? items[p].r : rs + 8 * p; }
+    const uint64_t *s(size_t p) const { return kind == HOST_ITEMS ? items[p].s : rs + 8 * p + 4; }
+    ChunkSource from(size_t first) const {                                    // the same source, item `first` as item 0
+        ChunkSource c = *this;
+        if (items) c.items += first; if (ctxs) c.ctxs += first; if (dev) c.dev += first * stride; if (rs) c.rs += 8 * first;
+        return c;
+    }
+};
+enum { CHUNK_CURSOR_ERROR = -1 };             // prove_chunk (ZKLAIM): the generator raised its cursor error; the chunk's witnesses have to come from the host
 
-// one chunk: P <= B.P items, under the batch mutex and a slot lease (the lease is the chunk's place in the key's extension protocol; its
-// slot lends the streams of a table extension).  Three ways in: `items` (the witnesses are packed on the host and uploaded), `zc` (a
-// few bytes per credential go up and k_zklaim_witness writes the same packed form into the device stage), or `dc` (the caller's device buffer,
-// split in place by k_split_dev: nothing is packed, staged or uploaded); from the split on they are one.
-static int prove_chunk(zkg_crs *crs, BatchWs &B, ProverSlot &S, const zkg_prove_item *items, ZklaimChunk *zc, uint32_t P, bool check, uint8_t *proofs_out, int *status,
-                       const DevChunk *dc = nullptr) {
+// one chunk: P <= B.P items 0 .. P of `src`, under the batch mutex and a slot lease (the lease is the chunk's place in the key's extension protocol;
+// its slot lends the streams of a table extension).  The source's kind decides how the stage is built, which split is launched and where (r, s) are
+// read; from the split on the three are one.
+static int prove_chunk(zkg_crs *crs, BatchWs &B, ProverSlot &S, const ChunkSource &src, uint32_t P, bool check, uint8_t *proofs_out, int *status) {
     const size_t n = crs->n, n1 = n + 1, m = crs->m, l = crs->l, tag_stride = round_up(n, 16), wtag_stride = round_up(n1, 16);
     hipStream_t s = B.stream;
     const auto t0 = std::chrono::steady_clock::now();
@@ -1422,8 +1435,10 @@ static int prove_chunk(zkg_crs *crs, BatchWs &B, ProverSlot &S, const zkg_prove_
     std::vector<uint32_t> off(P + 1, 0);
     size_t o_vals = round_up((size_t)P * sizeof(BatchDesc), 64), o_idx = 0, o_tags = 0, o_gen = 0;
     uint32_t max_cnt = 0;
-    if (dc) o_vals = 0;                                                          // resident already: no stage (the offsets below stay 0)
-    else if (!zc) {                                                              // packed on the host, one upload
+    switch (src.kind) {
+    case ChunkSource::DEVICE: o_vals = 0; break;                                 // resident already: no stage (the offsets below stay 0)
+    case ChunkSource::HOST_ITEMS: {                                              // packed on the host, one upload
+        const zkg_prove_item *items = src.items;
         host_parallel_for((int)P, [&](int p) {
             const zkg_prove_item &it = items[p];
             if (!it.r || !it.s) skip[p] = 1;
@@ -1448,19 +1463,23 @@ static int prove_chunk(zkg_crs *crs, BatchWs &B, ProverSlot &S, const zkg_prove_
         lap("witnesses packed");
         ZK_HIP(hipMemcpyAsync(B.stage.p, hs, bytes, hipMemcpyHostToDevice, s));
         max_cnt = *std::max_element(cnt.begin(), cnt.end());
-    } else {                                                                     // generated in place: fixed-capacity listed slots per item, counts made on the device
-        const ZwPlan &pl = *zc->plan;
+        break;
+    }
+    case ChunkSource::ZKLAIM: {                                                  // generated in place: fixed-capacity listed slots per item, counts made on the device
+        const ZwPlan &pl = *src.plan;
         if (pl.n != n) { set_error("zkg_groth16_prove_batch_zklaim: plan does not fit the key"); return ZKG_ERROR; }
         const size_t total = (size_t)P * pl.cap, in_bytes = zklaim_witness_input_bytes(pl, P);
         o_idx = o_vals + total * 32; o_tags = round_up(o_idx + total * 4, 64); o_gen = round_up(o_tags + P * tag_stride, 64);
         if (host_stage_for(in_bytes) || B.stage.reserve(o_gen + in_bytes)) return ZKG_ERROR;
-        zklaim_witness_pack(pl, zc->ctxs, P, B.host_stage, skip.data());
+        zklaim_witness_pack(pl, src.ctxs, P, B.host_stage, skip.data());
         for (uint32_t p = 0; p < P; ++p) skip[p] = !skip[p];                      // (pack reports the good ones)
         lap("credentials packed");
         uint8_t *st = B.stage.as<uint8_t>();
         ZK_HIP(hipMemcpyAsync(st + o_gen, B.host_stage, in_bytes, hipMemcpyHostToDevice, s));
         if (zklaim_witness_launch(pl, P, st + o_gen, reinterpret_cast<uint32_t *>(st), reinterpret_cast<Fr *>(st + o_vals), reinterpret_cast<uint32_t *>(st + o_idx), st + o_tags, tag_stride, s)) return ZKG_ERROR;
         max_cnt = pl.cap;
+        break;
+    }
     }
     const uint8_t *st = B.stage.as<uint8_t>();
     const BatchDesc *d_desc = reinterpret_cast<const BatchDesc *>(st); const Fr *d_vals = reinterpret_cast<const Fr *>(st + o_vals);
@@ -1471,16 +1490,16 @@ static int prove_chunk(zkg_crs *crs, BatchWs &B, ProverSlot &S, const zkg_prove_
     const uint32_t *subset_pos = crs->sub.count ? crs->sub.pos.as<uint32_t>() : nullptr;
     uint32_t *hw_gen = B.host_words + (size_t)2 * B.P * BATCH_WORDS;
     // ---- 2. split, mat-vec, transforms, H: one launch sequence for the chunk
-    if (dc) {
+    if (src.kind == ChunkSource::DEVICE) {
         ZK_HIP(hipMemsetAsync(words, 0, (size_t)P * BATCH_WORDS * 4, s));
-        hipLaunchKernelGGL(k_split_dev, dim3((unsigned)((n1 + 255) / 256), P), dim3(256), 0, s, dc->src, dc->stride, n, z, wtags, wtag_stride, wlisted, words, words + 4, BATCH_WORDS,
+        hipLaunchKernelGGL(k_split_dev, dim3((unsigned)((n1 + 255) / 256), P), dim3(256), 0, s, src.dev, src.stride, n, z, wtags, wtag_stride, wlisted, words, words + 4, BATCH_WORDS,
                            subset_pos, (uint32_t *)nullptr);
     } else {
-    hipLaunchKernelGGL(k_expand_tags_batch, dim3((unsigned)((n + 255) / 256), P), dim3(256), 0, s, d_tags, tag_stride, n, z, wtags, wtag_stride, words);
-    if (max_cnt) hipLaunchKernelGGL(k_scatter_full_batch, dim3((max_cnt + 255) / 256, P), dim3(256), 0, s, d_desc, d_idx, d_vals, d_tags, tag_stride, n, z, wtags, wtag_stride, wlisted, words, subset_pos);
+        hipLaunchKernelGGL(k_expand_tags_batch, dim3((unsigned)((n + 255) / 256), P), dim3(256), 0, s, d_tags, tag_stride, n, z, wtags, wtag_stride, words);
+        if (max_cnt) hipLaunchKernelGGL(k_scatter_full_batch, dim3((max_cnt + 255) / 256, P), dim3(256), 0, s, d_desc, d_idx, d_vals, d_tags, tag_stride, n, z, wtags, wtag_stride, wlisted, words, subset_pos);
     }
     ZK_HIP(hipMemcpyAsync(hw_split, words, (size_t)P * BATCH_WORDS * 4, hipMemcpyDeviceToHost, s));
-    if (zc) ZK_HIP(hipMemcpyAsync(hw_gen, st + o_gen, 4, hipMemcpyDeviceToHost, s));
+    if (src.kind == ChunkSource::ZKLAIM) ZK_HIP(hipMemcpyAsync(hw_gen, st + o_gen, 4, hipMemcpyDeviceToHost, s));
     ZK_HIP(hipEventRecord(B.ev_split, s));
     const unsigned grid_m = (unsigned)((m + 255) / 256);
     hipLaunchKernelGGL(k_r1cs_eval_batch, dim3(grid_m, P), dim3(256), 0, s, crs->A.rowptr.as<uint32_t>(), crs->A.col.as<uint32_t>(), crs->A.val.as<Fr>(),
@@ -1517,7 +1536,7 @@ static int prove_chunk(zkg_crs *crs, BatchWs &B, ProverSlot &S, const zkg_prove_
     // ---- 3. the split has landed: per-item verdicts, the witness tables, the witness jobs
     ZK_HIP(hipEventSynchronize(B.ev_split));
     lap("split landed");
-    if (zc && *hw_gen) { zc->cursor_error = true; set_error("zklaim witness generator: a cursor left its range (host witnesses are used)"); return ZKG_ERROR; }
+    if (src.kind == ChunkSource::ZKLAIM && *hw_gen) { set_error("zklaim witness generator: a cursor left its range (host witnesses are used)"); return CHUNK_CURSOR_ERROR; }
     std::vector<uint8_t> good(P, 0);
     bool extend = false;
     for (uint32_t p = 0; p < P; ++p) {
@@ -1537,17 +1556,7 @@ static int prove_chunk(zkg_crs *crs, BatchWs &B, ProverSlot &S, const zkg_prove_
             li.resize(at + k);
             if (k) ZK_HIP(hipMemcpy(li.data() + at, wlisted + (size_t)p * n1, k * 4, hipMemcpyDeviceToHost));
         }
-        std::unique_lock<std::mutex> lk(crs->mu);
-        ++crs->waiting_ext; crs->cv.notify_all();
-        crs->cv.wait(lk, [&] { return !crs->extending && crs->leases - crs->waiting_ext == 0; });
-        --crs->waiting_ext; crs->extending = true;
-        lk.unlock();
-        int rc_ext = ZKG_ERROR;
-        try { rc_ext = subset_extend(crs, S, li.size(), &li); } catch (...) { set_error("prover: witness table extension failed"); }
-        lk.lock();
-        crs->extending = false; crs->cv.notify_all();
-        lk.unlock();
-        if (rc_ext) return ZKG_ERROR;
+        if (extend_tables_exclusive(crs, S, li.size(), &li)) return ZKG_ERROR;
     }
     // bucket method: every proof's non-bit values over the subset tables, two multi launches; flat sums over the ones: the queries as uploaded, per proof
     const size_t sub_n = crs->sub.count;
@@ -1581,8 +1590,7 @@ static int prove_chunk(zkg_crs *crs, BatchWs &B, ProverSlot &S, const zkg_prove_
         G1 W1[3] = {Wg1[3 * (size_t)p], Wg1[3 * (size_t)p + 1], Wg1[3 * (size_t)p + 2]}; G2 Wb2 = Wg2[p];
         for (int i = 0; i < 3; ++i) W1[i].add(B.ones_g1.g1(3 * p + i));
         Wb2.add(B.ones_g2.g2pt(p));
-        const uint64_t *rs_p = zc ? zc->rs + 8 * (size_t)p : dc ? dc->rs + 8 * (size_t)p : nullptr;
-        Fr r, sv; memcpy(r.v, rs_p ? rs_p : items[p].r, 32); memcpy(sv.v, rs_p ? rs_p + 4 : items[p].s, 32);
+        Fr r, sv; memcpy(r.v, src.r((size_t)p), 32); memcpy(sv.v, src.s((size_t)p), 32);
         assemble_proof(crs, r, sv, W1, Wb2, Ht[p], proofs_out + (size_t)p * ZKG_PROOF_BYTES);
         status[p] = ZKG_OK;
     });
@@ -1590,39 +1598,69 @@ static int prove_chunk(zkg_crs *crs, BatchWs &B, ProverSlot &S, const zkg_prove_
     for (uint32_t p = 0; p < P; ++p) if (status[p] == ZKG_UNSATISFIED) set_error("constraint system not satisfied; not creating proof");
     return ZKG_OK;
 }
-static int groth16_prove_batch_impl(const zkg_crs *crs_, const zkg_prove_item *items, size_t count, int check_satisfied, uint8_t *proofs_out, int *status) {
-    t_batch_stats[0] = t_batch_stats[1] = t_batch_stats[2] = 0;
-    if (!count) return ZKG_OK;
-    zkg_crs *crs = const_cast<zkg_crs *>(crs_);
-    if (!crs || !items || !proofs_out || !status) { set_error("zkg_groth16_prove_batch: bad argument"); return ZKG_ERROR; }
+// one proof from n elements at d_w, behind `stream`; counts into t_prove_dev_stats (the entries reset it)
+static int prove_dev_one(zkg_crs *crs, const Fr *d_w, const uint64_t r_[4], const uint64_t s_[4], int check_satisfied, uint8_t *proof_out, size_t *proof_len, hipStream_t stream) {
+    WitnessSrc W; W.dev = d_w;
+    SingleOutcome outcome;
+    const int rc = prove_single_staged(crs, W, r_, s_, check_satisfied != 0, stream, proof_out, proof_len, &outcome);
+    if (outcome.enqueued) ++t_prove_dev_stats[0];
+    return rc;
+}
+
+// ---- the one driver of the batch entries: `count` items of `src` as chunks of the key's workspace, or — a key whose proofs do not batch — item by
+// item through the single-proof path.  Counts into t_batch_stats (the entries reset it): items proved in chunks, items proved singly, chunks.
+struct BatchHooks {                                                          // what an entry adds to the chunk loop
+    std::function<int(BatchWs &)> before_chunks;                             // under the batch mutex, the workspace standing, in front of the first chunk
+    size_t *chunk_items = nullptr;                                           // the entry's own counter of items proved in chunks
+    std::vector<std::pair<size_t, uint32_t>> *redo = nullptr;                // chunks (first, P) that ended in CHUNK_CURSOR_ERROR are listed here and the call goes on
+};
+static int prove_batch_chunks(zkg_crs *crs, const ChunkSource &src, size_t count, int check_satisfied, uint8_t *proofs_out, int *status, const BatchHooks &hooks) {
     const uint32_t chunk = batch_chunk_for(crs);
-    if (!chunk) {                                                            // this key's proofs do not batch: the single-proof path, item by item
+    if (!chunk) {                                                            // this key's proofs do not batch: the single-proof path of the same source, item by item
         for (size_t i = 0; i < count; ++i) {
-            const zkg_prove_item &it = items[i];
             uint8_t buf[256]; size_t len = 0;
-            status[i] = it.witness ? groth16_prove_impl(crs, it.witness, it.r, it.s, check_satisfied, buf, &len)
-                                   : groth16_prove_sparse_impl(crs, it.tags, it.full_index, it.full_values, it.count, it.r, it.s, check_satisfied, buf, &len);
+            switch (src.kind) {
+            case ChunkSource::HOST_ITEMS: {
+                const zkg_prove_item &it = src.items[i];
+                status[i] = it.witness ? groth16_prove_impl(crs, it.witness, it.r, it.s, check_satisfied, buf, &len)
+                                       : groth16_prove_sparse_impl(crs, it.tags, it.full_index, it.full_values, it.count, it.r, it.s, check_satisfied, buf, &len);
+                break;
+            }
+            case ChunkSource::DEVICE: status[i] = prove_dev_one(crs, src.dev + i * src.stride, src.r(i), src.s(i), check_satisfied, buf, &len, src.stream); break;
+            case ChunkSource::ZKLAIM: set_error("prover: contexts on a key that does not batch"); return ZKG_ERROR;   // (the entry sends such a key to host witnesses: items by the time they are here)
+            }
             if (status[i] == ZKG_OK) memcpy(proofs_out + i * ZKG_PROOF_BYTES, buf, ZKG_PROOF_BYTES);
             ++t_batch_stats[1];
         }
         return ZKG_OK;
     }
     std::lock_guard<std::mutex> batch_lock(crs->batch_mu);
-    if (batch_create(crs, crs->batch, chunk)) return ZKG_ERROR;
+    BatchWs &B = crs->batch;
+    if (batch_create(crs, B, chunk)) return ZKG_ERROR;
+    if (hooks.before_chunks && hooks.before_chunks(B)) return ZKG_ERROR;
     for (size_t first = 0; first < count; first += chunk) {
         const uint32_t P = (uint32_t)std::min<size_t>(chunk, count - first);
         SlotLease lease(crs);                                                // per chunk: between chunks other callers may extend the witness tables
         if (!lease.ok()) return ZKG_ERROR;
-        int rc = ZKG_ERROR;
-        try { rc = prove_chunk(crs, crs->batch, lease.S(), items + first, nullptr, P, check_satisfied != 0, proofs_out + first * ZKG_PROOF_BYTES, status + first); }
-        catch (const std::exception &e) { set_error(std::string("zkg_groth16_prove_batch: ") + e.what()); }
-        catch (...) { set_error("zkg_groth16_prove_batch: unexpected exception"); }
-        if (rc) { batch_drain(crs->batch); return ZKG_ERROR; }                  // nothing of the chunk may still be running when the workspace changes hands
+        // nothing of the chunk may still be running when the workspace changes hands: drained on every way out but success, a throw included
+        struct Drain { BatchWs &B; bool armed; ~Drain() { if (armed) batch_drain(B); } } drain{B, true};
+        const int rc = prove_chunk(crs, B, lease.S(), src.from(first), P, check_satisfied != 0, proofs_out + first * ZKG_PROOF_BYTES, status + first);
+        if (rc == CHUNK_CURSOR_ERROR && hooks.redo) { hooks.redo->push_back({first, P}); continue; }
+        if (rc) return ZKG_ERROR;
+        drain.armed = false;
         t_batch_stats[0] += P; ++t_batch_stats[2];
+        if (hooks.chunk_items) *hooks.chunk_items += P;
     }
     return ZKG_OK;
 }
-
+static int groth16_prove_batch_impl(const zkg_crs *crs_, const zkg_prove_item *items, size_t count, int check_satisfied, uint8_t *proofs_out, int *status) {
+    t_batch_stats[0] = t_batch_stats[1] = t_batch_stats[2] = 0;
+    if (!count) return ZKG_OK;
+    zkg_crs *crs = const_cast<zkg_crs *>(crs_);
+    if (!crs || !items || !proofs_out || !status) { set_error("zkg_groth16_prove_batch: bad argument"); return ZKG_ERROR; }
+    ChunkSource src; src.kind = ChunkSource::HOST_ITEMS; src.items = items;
+    return prove_batch_chunks(crs, src, count, check_satisfied, proofs_out, status, BatchHooks{});
+}
 
 // ---- zkg_groth16_prove_dev / zkg_groth16_prove_batch_dev: witnesses that are already in device memory.  The refusals come first, before any
 // launch: the calling thread on another device than the key's, a pointer that is not device memory of that device (pinned, managed and
@@ -1634,23 +1672,6 @@ static int dev_witness_refused(const zkg_crs *crs, const void *d, size_t elems, 
     if (hipGetDevice(&cur) != hipSuccess || cur != crs->device) { (void)hipGetLastError(); return refuse("the calling thread's device is not the key's"); }
     if (!elems) return ZKG_OK;                                                  // (a key without variables: nothing is read)
     return dev_range_refused(d, elems * 32, alignof(Fr), crs->device, who, "the witness", "key");
-}
-// one proof from n elements at d_w, behind `stream`; counts into t_prove_dev_stats (the entries reset it)
-static int prove_dev_one(zkg_crs *crs, const Fr *d_w, const uint64_t r_[4], const uint64_t s_[4], int check_satisfied, uint8_t *proof_out, size_t *proof_len, hipStream_t stream) {
-    SlotLease lease(crs);
-    if (!lease.ok()) return ZKG_ERROR;
-    ProverSlot &S = lease.S();
-    // the proof runs on the slot's own (non-blocking) streams: order it behind whatever the caller queued on `stream` — the work that wrote the
-    // witness.  The call returns after the proof has landed, so nothing of it is left running for the caller to order after.
-    ZK_HIP(hipEventRecord(S.ev[12], stream));
-    ZK_HIP(hipStreamWaitEvent(S.stream, S.ev[12], 0));
-    WitnessSrc W; W.dev = d_w;
-    uint8_t buf[256]; size_t len = 0;                                           // nothing is written unless the proof is made
-    if (prove_enqueue(crs, S, W, r_, s_, check_satisfied != 0)) { slot_drain(crs, S); return ZKG_ERROR; }
-    ++t_prove_dev_stats[0];
-    const int rc = prove_finish(crs, S, buf, &len);
-    if (rc == ZKG_OK) { memcpy(proof_out, buf, len); *proof_len = len; }
-    return rc;
 }
 static int groth16_prove_dev_impl(const zkg_crs *crs_, const void *d_witness, const uint64_t r_[4], const uint64_t s_[4], int check_satisfied,
                                   uint8_t *proof_out, size_t *proof_len, void *stream) {
@@ -1669,76 +1690,13 @@ static int groth16_prove_batch_dev_impl(const zkg_crs *crs_, const void *d_witne
     if (stride < crs->n) { set_error("zkg_groth16_prove_batch_dev: stride is shorter than the witness"); return ZKG_ERROR; }
     if (stride && count - 1 > (SIZE_MAX / 64 - crs->n) / stride) { set_error("zkg_groth16_prove_batch_dev: count x stride out of range"); return ZKG_ERROR; }
     if (dev_witness_refused(crs, d_witnesses, crs->n ? (count - 1) * stride + crs->n : 0, "zkg_groth16_prove_batch_dev")) return ZKG_ERROR;
-    const Fr *src = static_cast<const Fr *>(d_witnesses);
-    const uint32_t chunk = batch_chunk_for(crs);
-    if (!chunk) {                                                            // this key's proofs do not batch: the single-proof path from the same buffer, item by item
-        for (size_t i = 0; i < count; ++i) {
-            uint8_t buf[256]; size_t len = 0;
-            status[i] = prove_dev_one(crs, src + i * stride, rs + 8 * i, rs + 8 * i + 4, check_satisfied, buf, &len, (hipStream_t)stream);
-            if (status[i] == ZKG_OK) memcpy(proofs_out + i * ZKG_PROOF_BYTES, buf, ZKG_PROOF_BYTES);
-            ++t_batch_stats[1];
-        }
-        return ZKG_OK;
-    }
-    std::lock_guard<std::mutex> batch_lock(crs->batch_mu);
-    if (batch_create(crs, crs->batch, chunk)) return ZKG_ERROR;
+    ChunkSource src; src.kind = ChunkSource::DEVICE; src.dev = static_cast<const Fr *>(d_witnesses); src.stride = stride; src.stream = (hipStream_t)stream; src.rs = rs;
+    BatchHooks hooks; hooks.chunk_items = &t_prove_dev_stats[0];
     // every chunk runs on the workspace's stream, in order: ONE wait puts the whole call behind the caller's stream
-    ZK_HIP(hipEventRecord(crs->batch.ev_in, (hipStream_t)stream));
-    ZK_HIP(hipStreamWaitEvent(crs->batch.stream, crs->batch.ev_in, 0));
-    for (size_t first = 0; first < count; first += chunk) {
-        const uint32_t P = (uint32_t)std::min<size_t>(chunk, count - first);
-        SlotLease lease(crs);                                                // per chunk, as zkg_groth16_prove_batch
-        if (!lease.ok()) return ZKG_ERROR;
-        const DevChunk dc{src + first * stride, stride, rs + 8 * first};
-        int rc = ZKG_ERROR;
-        try { rc = prove_chunk(crs, crs->batch, lease.S(), nullptr, nullptr, P, check_satisfied != 0, proofs_out + first * ZKG_PROOF_BYTES, status + first, &dc); }
-        catch (const std::exception &e) { set_error(std::string("zkg_groth16_prove_batch_dev: ") + e.what()); }
-        catch (...) { set_error("zkg_groth16_prove_batch_dev: unexpected exception"); }
-        if (rc) { batch_drain(crs->batch); return ZKG_ERROR; }
-        t_batch_stats[0] += P; ++t_batch_stats[2]; t_prove_dev_stats[0] += P;
-    }
-    return ZKG_OK;
+    hooks.before_chunks = [&](BatchWs &B) -> int { ZK_HIP(hipEventRecord(B.ev_in, src.stream)); ZK_HIP(hipStreamWaitEvent(B.stream, B.ev_in, 0)); return ZKG_OK; };
+    return prove_batch_chunks(crs, src, count, check_satisfied, proofs_out, status, hooks);
 }
 
-// helper threads and host containers are used below these two: nothing may propagate through the C boundary
-int zkg_groth16_prove(const zkg_crs *crs, const uint64_t *witness, const uint64_t r[4], const uint64_t s[4], int check_satisfied,
-                      uint8_t *proof_out, size_t *proof_len) {
-    try { return groth16_prove_impl(crs, witness, r, s, check_satisfied, proof_out, proof_len); }
-    catch (const std::exception &e) { set_error(std::string("zkg_groth16_prove: ") + e.what()); return ZKG_ERROR; }
-    catch (...) { set_error("zkg_groth16_prove: unexpected exception"); return ZKG_ERROR; }
-}
-int zkg_groth16_prove_sparse(const zkg_crs *crs, const uint8_t *tags, const uint32_t *full_index, const uint64_t *full_values, size_t count,
-                             const uint64_t r[4], const uint64_t s[4], int check_satisfied, uint8_t *proof_out, size_t *proof_len) {
-    try { return groth16_prove_sparse_impl(crs, tags, full_index, full_values, count, r, s, check_satisfied, proof_out, proof_len); }
-    catch (const std::exception &e) { set_error(std::string("zkg_groth16_prove_sparse: ") + e.what()); return ZKG_ERROR; }
-    catch (...) { set_error("zkg_groth16_prove_sparse: unexpected exception"); return ZKG_ERROR; }
-}
-
-int zkg_groth16_prove_zklaim(const zkg_crs *crs, const struct zklaim_ctx *ctx, const uint64_t r[4], const uint64_t s[4], int check_satisfied, uint8_t *proof_out, size_t *proof_len) {
-    try { return groth16_prove_zklaim_impl(crs, ctx, r, s, check_satisfied, proof_out, proof_len); }
-    catch (const std::exception &e) { set_error(std::string("zkg_groth16_prove_zklaim: ") + e.what()); return ZKG_ERROR; }
-    catch (...) { set_error("zkg_groth16_prove_zklaim: unexpected exception"); return ZKG_ERROR; }
-}
-void zkg_prove_zklaim_stats(size_t out[2]) { if (out) { out[0] = zk::t_prove_zklaim_stats[0]; out[1] = zk::t_prove_zklaim_stats[1]; } }
-
-int zkg_groth16_prove_batch(const zkg_crs *crs, const zkg_prove_item *items, size_t count, int check_satisfied, uint8_t *proofs_out, int *status) {
-    try { return groth16_prove_batch_impl(crs, items, count, check_satisfied, proofs_out, status); }
-    catch (const std::exception &e) { set_error(std::string("zkg_groth16_prove_batch: ") + e.what()); }
-    catch (...) { set_error("zkg_groth16_prove_batch: unexpected exception"); }
-    return ZKG_ERROR;
-}
-int zkg_groth16_prove_dev(const zkg_crs *crs, const void *d_witness, const uint64_t r[4], const uint64_t s[4], int check_satisfied, uint8_t *proof_out, size_t *proof_len, void *stream) {
-    try { return groth16_prove_dev_impl(crs, d_witness, r, s, check_satisfied, proof_out, proof_len, stream); }
-    catch (const std::exception &e) { set_error(std::string("zkg_groth16_prove_dev: ") + e.what()); return ZKG_ERROR; }
-    catch (...) { set_error("zkg_groth16_prove_dev: unexpected exception"); return ZKG_ERROR; }
-}
-int zkg_groth16_prove_batch_dev(const zkg_crs *crs, const void *d_witnesses, size_t stride, size_t count, const uint64_t *rs, int check_satisfied, uint8_t *proofs_out, int *status, void *stream) {
-    try { return groth16_prove_batch_dev_impl(crs, d_witnesses, stride, count, rs, check_satisfied, proofs_out, status, stream); }
-    catch (const std::exception &e) { set_error(std::string("zkg_groth16_prove_batch_dev: ") + e.what()); }
-    catch (...) { set_error("zkg_groth16_prove_batch_dev: unexpected exception"); }
-    return ZKG_ERROR;
-}
-void zkg_prove_dev_stats(size_t out[2]) { if (out) { out[0] = zk::t_prove_dev_stats[0]; out[1] = zk::t_prove_dev_stats[1]; } }
 // ---- zkg_groth16_prove_batch_zklaim: the same chunks, their witnesses generated on the device from the contexts
 // host witnesses for ctxs[0 .. count) through zkg_groth16_prove_batch (which takes the single-proof path for keys that do not batch)
 static int prove_zklaim_host_witnesses(const zkg_crs *crs, const zklaim_ctx *const *ctxs, size_t count, const uint64_t *rs, int check_satisfied, uint8_t *proofs_out, int *status) {
@@ -1763,7 +1721,7 @@ static int prove_zklaim_host_witnesses(const zkg_crs *crs, const zklaim_ctx *con
     zk::t_zklaim_witness_stats[1] += which.size();
     const size_t before[3] = {t_batch_stats[0], t_batch_stats[1], t_batch_stats[2]};
     std::vector<uint8_t> out(batch.size() * ZKG_PROOF_BYTES); std::vector<int> st(batch.size(), ZKG_ERROR);
-    const int rc = groth16_prove_batch_impl(crs, batch.data(), batch.size(), check_satisfied, out.data(), st.data());
+    const int rc = c_boundary("zkg_groth16_prove_batch", ZKG_ERROR, [&] { return groth16_prove_batch_impl(crs, batch.data(), batch.size(), check_satisfied, out.data(), st.data()); });
     for (int j = 0; j < 3; ++j) t_batch_stats[j] += before[j];
     if (rc != ZKG_OK) return rc;
     for (size_t j = 0; j < which.size(); ++j) { status[which[j]] = st[j]; if (st[j] == ZKG_OK) memcpy(proofs_out + which[j] * ZKG_PROOF_BYTES, out.data() + j * ZKG_PROOF_BYTES, ZKG_PROOF_BYTES); }
@@ -1774,41 +1732,44 @@ static int groth16_prove_batch_zklaim_impl(const zkg_crs *crs_, const zklaim_ctx
     if (!count) return ZKG_OK;
     zkg_crs *crs = const_cast<zkg_crs *>(crs_);
     if (!crs || !ctxs || !rs || !proofs_out || !status) { set_error("zkg_groth16_prove_batch_zklaim: bad argument"); return ZKG_ERROR; }
-    const uint32_t chunk = batch_chunk_for(crs);
     ZwPlan pl;
     // a key that does not batch, or a generator that disagrees with the host pass about the circuit: host witnesses, the existing paths
-    if (!chunk || !zklaim_witness_plan_for_n(crs->n, pl)) return prove_zklaim_host_witnesses(crs, ctxs, count, rs, check_satisfied, proofs_out, status);
+    if (!batch_chunk_for(crs) || !zklaim_witness_plan_for_n(crs->n, pl)) return prove_zklaim_host_witnesses(crs, ctxs, count, rs, check_satisfied, proofs_out, status);
     std::vector<std::pair<size_t, uint32_t>> redo;                            // chunks whose generator reported a stray cursor
-    {
-        std::lock_guard<std::mutex> batch_lock(crs->batch_mu);
-        if (batch_create(crs, crs->batch, chunk)) return ZKG_ERROR;
-        for (size_t first = 0; first < count; first += chunk) {
-            const uint32_t P = (uint32_t)std::min<size_t>(chunk, count - first);
-            SlotLease lease(crs);
-            if (!lease.ok()) return ZKG_ERROR;
-            ZklaimChunk zc{ctxs + first, rs + 8 * first, &pl, false};
-            int rc = ZKG_ERROR;
-            try { rc = prove_chunk(crs, crs->batch, lease.S(), nullptr, &zc, P, check_satisfied != 0, proofs_out + first * ZKG_PROOF_BYTES, status + first); }
-            catch (const std::exception &e) { set_error(std::string("zkg_groth16_prove_batch_zklaim: ") + e.what()); }
-            catch (...) { set_error("zkg_groth16_prove_batch_zklaim: unexpected exception"); }
-            if (rc) {
-                batch_drain(crs->batch);
-                if (!zc.cursor_error) return ZKG_ERROR;
-                redo.push_back({first, P});
-                continue;
-            }
-            t_batch_stats[0] += P; ++t_batch_stats[2]; zk::t_zklaim_witness_stats[0] += P;
-        }
-    }
+    ChunkSource src; src.kind = ChunkSource::ZKLAIM; src.ctxs = ctxs; src.plan = &pl; src.rs = rs;
+    BatchHooks hooks; hooks.chunk_items = &zk::t_zklaim_witness_stats[0]; hooks.redo = &redo;
+    if (prove_batch_chunks(crs, src, count, check_satisfied, proofs_out, status, hooks)) return ZKG_ERROR;
+    // (the batch mutex is free again: the host witnesses go through zkg_groth16_prove_batch's path, which takes it)
     for (auto &c : redo)
         if (prove_zklaim_host_witnesses(crs, ctxs + c.first, c.second, rs + 8 * c.first, check_satisfied, proofs_out + c.first * ZKG_PROOF_BYTES, status + c.first)) return ZKG_ERROR;
     return ZKG_OK;
 }
+
+// helper threads and host containers are used below these: nothing may propagate through the C boundary
+int zkg_groth16_prove(const zkg_crs *crs, const uint64_t *witness, const uint64_t r[4], const uint64_t s[4], int check_satisfied,
+                      uint8_t *proof_out, size_t *proof_len) {
+    return c_boundary("zkg_groth16_prove", ZKG_ERROR, [&] { return groth16_prove_impl(crs, witness, r, s, check_satisfied, proof_out, proof_len); });
+}
+int zkg_groth16_prove_sparse(const zkg_crs *crs, const uint8_t *tags, const uint32_t *full_index, const uint64_t *full_values, size_t count,
+                             const uint64_t r[4], const uint64_t s[4], int check_satisfied, uint8_t *proof_out, size_t *proof_len) {
+    return c_boundary("zkg_groth16_prove_sparse", ZKG_ERROR, [&] { return groth16_prove_sparse_impl(crs, tags, full_index, full_values, count, r, s, check_satisfied, proof_out, proof_len); });
+}
+int zkg_groth16_prove_zklaim(const zkg_crs *crs, const struct zklaim_ctx *ctx, const uint64_t r[4], const uint64_t s[4], int check_satisfied, uint8_t *proof_out, size_t *proof_len) {
+    return c_boundary("zkg_groth16_prove_zklaim", ZKG_ERROR, [&] { return groth16_prove_zklaim_impl(crs, ctx, r, s, check_satisfied, proof_out, proof_len); });
+}
+void zkg_prove_zklaim_stats(size_t out[2]) { if (out) { out[0] = zk::t_prove_zklaim_stats[0]; out[1] = zk::t_prove_zklaim_stats[1]; } }
+int zkg_groth16_prove_batch(const zkg_crs *crs, const zkg_prove_item *items, size_t count, int check_satisfied, uint8_t *proofs_out, int *status) {
+    return c_boundary("zkg_groth16_prove_batch", ZKG_ERROR, [&] { return groth16_prove_batch_impl(crs, items, count, check_satisfied, proofs_out, status); });
+}
+int zkg_groth16_prove_dev(const zkg_crs *crs, const void *d_witness, const uint64_t r[4], const uint64_t s[4], int check_satisfied, uint8_t *proof_out, size_t *proof_len, void *stream) {
+    return c_boundary("zkg_groth16_prove_dev", ZKG_ERROR, [&] { return groth16_prove_dev_impl(crs, d_witness, r, s, check_satisfied, proof_out, proof_len, stream); });
+}
+int zkg_groth16_prove_batch_dev(const zkg_crs *crs, const void *d_witnesses, size_t stride, size_t count, const uint64_t *rs, int check_satisfied, uint8_t *proofs_out, int *status, void *stream) {
+    return c_boundary("zkg_groth16_prove_batch_dev", ZKG_ERROR, [&] { return groth16_prove_batch_dev_impl(crs, d_witnesses, stride, count, rs, check_satisfied, proofs_out, status, stream); });
+}
+void zkg_prove_dev_stats(size_t out[2]) { if (out) { out[0] = zk::t_prove_dev_stats[0]; out[1] = zk::t_prove_dev_stats[1]; } }
 int zkg_groth16_prove_batch_zklaim(const zkg_crs *crs, const struct zklaim_ctx *const *ctxs, size_t count, const uint64_t *rs, int check_satisfied, uint8_t *proofs_out, int *status) {
-    try { return groth16_prove_batch_zklaim_impl(crs, ctxs, count, rs, check_satisfied, proofs_out, status); }
-    catch (const std::exception &e) { set_error(std::string("zkg_groth16_prove_batch_zklaim: ") + e.what()); }
-    catch (...) { set_error("zkg_groth16_prove_batch_zklaim: unexpected exception"); }
-    return ZKG_ERROR;
+    return c_boundary("zkg_groth16_prove_batch_zklaim", ZKG_ERROR, [&] { return groth16_prove_batch_zklaim_impl(crs, ctxs, count, rs, check_satisfied, proofs_out, status); });
 }
 void zkg_zklaim_witness_stats(size_t out[2]) { if (out) { out[0] = zk::t_zklaim_witness_stats[0]; out[1] = zk::t_zklaim_witness_stats[1]; } }
 void zkg_prove_batch_stats(size_t out[3]) { if (out) for (int i = 0; i < 3; ++i) out[i] = t_batch_stats[i]; }
@@ -1848,11 +1809,7 @@ static int crs_shard_h_impl(zkg_crs *crs, const int *devices, int ndev) {
     for (auto &sh : shards) { (void)hipSetDevice(sh.device); sh.table.release(); }     // a previous sharding's tables
     return ZKG_OK;
 }
-int zkg_crs_shard_h(zkg_crs *crs, const int *devices, int ndev) {
-    try { return crs_shard_h_impl(crs, devices, ndev); }
-    catch (const std::exception &e) { set_error(std::string("zkg_crs_shard_h: ") + e.what()); return ZKG_ERROR; }
-    catch (...) { set_error("zkg_crs_shard_h: unexpected exception"); return ZKG_ERROR; }
-}
+int zkg_crs_shard_h(zkg_crs *crs, const int *devices, int ndev) { return c_boundary("zkg_crs_shard_h", ZKG_ERROR, [&] { return crs_shard_h_impl(crs, devices, ndev); }); }
 
 int zkg_prover_peak_in_flight(int reset) {
     const int v = g_peak_in_flight.load();

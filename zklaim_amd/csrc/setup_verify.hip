@@ -439,9 +439,7 @@ static int groth16_verify_impl(const uint8_t *vk_blob, size_t vk_len, const uint
 }
 
 int zkg_groth16_verify(const uint8_t *vk_blob, size_t vk_len, const uint64_t *primary_input, size_t n_inputs, const uint8_t *proof, size_t proof_len) {
-    try { return groth16_verify_impl(vk_blob, vk_len, primary_input, n_inputs, proof, proof_len); }       // nothing propagates through the C boundary
-    catch (const std::exception &e) { set_error(std::string("zkg_groth16_verify: ") + e.what()); return 2; }
-    catch (...) { set_error("zkg_groth16_verify: unexpected exception"); return 2; }
+    return c_boundary("zkg_groth16_verify", 2, [&] { return groth16_verify_impl(vk_blob, vk_len, primary_input, n_inputs, proof, proof_len); });
 }
 
 // ---- batch verification (zkg_groth16_verify_batch).  For the N proofs of one key, with fresh 128-bit weights r_i:
@@ -778,9 +776,7 @@ static int verify_batch_impl(const zkg_verify_item *items, size_t count, uint8_t
 void zkg_verify_batch_stats(size_t out[3]) { if (out) for (int i = 0; i < 3; ++i) out[i] = t_batch_stats[i]; }
 
 int zkg_groth16_verify_batch(const zkg_verify_item *items, size_t count, uint8_t *verdicts) {
-    try { return verify_batch_impl(items, count, verdicts); }
-    catch (const std::exception &e) { set_error(std::string("zkg_groth16_verify_batch: ") + e.what()); return ZKG_ERROR; }
-    catch (...) { set_error("zkg_groth16_verify_batch: unexpected exception"); return ZKG_ERROR; }
+    return c_boundary("zkg_groth16_verify_batch", ZKG_ERROR, [&] { return verify_batch_impl(items, count, verdicts); });
 }
 
 // ---- per-proof verification (zkg_groth16_verify_each).  Every item is decided by its own equation
@@ -876,9 +872,7 @@ static int verify_each_impl(const zkg_verify_item *items, size_t count, uint8_t 
 }
 
 int zkg_groth16_verify_each(const zkg_verify_item *items, size_t count, uint8_t *verdicts) {
-    try { return verify_each_impl(items, count, verdicts); }
-    catch (const std::exception &e) { set_error(std::string("zkg_groth16_verify_each: ") + e.what()); return ZKG_ERROR; }
-    catch (...) { set_error("zkg_groth16_verify_each: unexpected exception"); return ZKG_ERROR; }
+    return c_boundary("zkg_groth16_verify_each", ZKG_ERROR, [&] { return verify_each_impl(items, count, verdicts); });
 }
 void zkg_verify_each_stats(size_t out[3]) { if (out) for (int i = 0; i < 3; ++i) out[i] = t_each_stats[i]; }
 void zkg_verify_each_set_chunk(size_t positions) { g_each_chunk.store(positions); }
@@ -1077,9 +1071,7 @@ static int proof_decode_gpu_impl(const uint8_t *proofs, size_t count, uint64_t *
     return ZKG_OK;
 }
 int zkg_proof_decode_gpu(const uint8_t *proofs, size_t count, uint64_t *A, uint64_t *B, uint64_t *C, uint8_t *ok) {
-    try { return proof_decode_gpu_impl(proofs, count, A, B, C, ok); }
-    catch (const std::exception &e) { set_error(std::string("zkg_proof_decode_gpu: ") + e.what()); return ZKG_ERROR; }
-    catch (...) { set_error("zkg_proof_decode_gpu: unexpected exception"); return ZKG_ERROR; }
+    return c_boundary("zkg_proof_decode_gpu", ZKG_ERROR, [&] { return proof_decode_gpu_impl(proofs, count, A, B, C, ok); });
 }
 
 static int input_sums_gpu_impl(const zklaim_ctx *const *ctxs, size_t count, const uint32_t *weights, const uint8_t *mask, size_t lo, size_t hi,
@@ -1111,9 +1103,7 @@ static int input_sums_gpu_impl(const zklaim_ctx *const *ctxs, size_t count, cons
 }
 int zkg_zklaim_input_sums_gpu(const zklaim_ctx *const *ctxs, size_t count, const uint32_t *weights, const uint8_t *mask, size_t lo, size_t hi,
                               uint64_t *sums_out, size_t cap_elems, size_t *n_elems) {
-    try { return input_sums_gpu_impl(ctxs, count, weights, mask, lo, hi, sums_out, cap_elems, n_elems); }
-    catch (const std::exception &e) { set_error(std::string("zkg_zklaim_input_sums_gpu: ") + e.what()); return ZKG_ERROR; }
-    catch (...) { set_error("zkg_zklaim_input_sums_gpu: unexpected exception"); return ZKG_ERROR; }
+    return c_boundary("zkg_zklaim_input_sums_gpu", ZKG_ERROR, [&] { return input_sums_gpu_impl(ctxs, count, weights, mask, lo, hi, sums_out, cap_elems, n_elems); });
 }
 
 // the kernel's bit rule (zv_input_element) on the host: same outputs as zkg_zklaim_input_map
@@ -1159,9 +1149,7 @@ static int pairing_product_impl(const uint64_t *g1_affine, const uint64_t *g2_af
 }
 
 int zkg_pairing_product(const uint64_t *g1_affine, const uint64_t *g2_affine, size_t n, uint8_t out[384]) {
-    try { return pairing_product_impl(g1_affine, g2_affine, n, out); }
-    catch (const std::exception &e) { set_error(std::string("zkg_pairing_product: ") + e.what()); return ZKG_ERROR; }
-    catch (...) { set_error("zkg_pairing_product: unexpected exception"); return ZKG_ERROR; }
+    return c_boundary("zkg_pairing_product", ZKG_ERROR, [&] { return pairing_product_impl(g1_affine, g2_affine, n, out); });
 }
 
 static bool point_pair_ok(const G1Affine &P, const G2Affine &Q) {             // canonical limbs, on the curves (zkg_pairing_product's rule)
@@ -1202,9 +1190,7 @@ static int pairing_each_impl(const uint64_t *g1_affine, const uint64_t *g2_affin
     return ZKG_OK;
 }
 int zkg_pairing_each(const uint64_t *g1_affine, const uint64_t *g2_affine, size_t items, size_t pairs, uint8_t *out) {
-    try { return pairing_each_impl(g1_affine, g2_affine, items, pairs, out); }
-    catch (const std::exception &e) { set_error(std::string("zkg_pairing_each: ") + e.what()); return ZKG_ERROR; }
-    catch (...) { set_error("zkg_pairing_each: unexpected exception"); return ZKG_ERROR; }
+    return c_boundary("zkg_pairing_each", ZKG_ERROR, [&] { return pairing_each_impl(g1_affine, g2_affine, items, pairs, out); });
 }
 
 static int final_exp_impl(const uint8_t *in, size_t n, int where, uint8_t *out) {
@@ -1241,9 +1227,7 @@ static int final_exp_impl(const uint8_t *in, size_t n, int where, uint8_t *out) 
     return ZKG_OK;
 }
 int zkg_final_exp(const uint8_t *in, size_t n, int where, uint8_t *out) {
-    try { return final_exp_impl(in, n, where, out); }
-    catch (const std::exception &e) { set_error(std::string("zkg_final_exp: ") + e.what()); return ZKG_ERROR; }
-    catch (...) { set_error("zkg_final_exp: unexpected exception"); return ZKG_ERROR; }
+    return c_boundary("zkg_final_exp", ZKG_ERROR, [&] { return final_exp_impl(in, n, where, out); });
 }
 
 static int fq12_op_impl(int op, const uint32_t *a, const uint32_t *b, size_t n, int where, uint32_t *out) {
@@ -1276,9 +1260,7 @@ static int fq12_op_impl(int op, const uint32_t *a, const uint32_t *b, size_t n, 
     return ZKG_OK;
 }
 int zkg_fq12_op(int op, const uint32_t *a, const uint32_t *b, size_t n, int where, uint32_t *out) {
-    try { return fq12_op_impl(op, a, b, n, where, out); }
-    catch (const std::exception &e) { set_error(std::string("zkg_fq12_op: ") + e.what()); return ZKG_ERROR; }
-    catch (...) { set_error("zkg_fq12_op: unexpected exception"); return ZKG_ERROR; }
+    return c_boundary("zkg_fq12_op", ZKG_ERROR, [&] { return fq12_op_impl(op, a, b, n, where, out); });
 }
 
 // bilinearity probe for the tests: writes e(a*G1, b*G2) (384 B) for canonical scalars a, b

@@ -346,16 +346,10 @@ static int witness_mirror_impl(const zklaim_ctx *ctx, uint8_t *tags_out, uint32_
     }
 }
 int zkg_zklaim_witness_mirror(const zklaim_ctx *ctx, uint8_t *tags_out, uint32_t *index_out, uint64_t *values_out, size_t cap_listed, size_t *listed_count) {
-    try { return witness_mirror_impl(ctx, tags_out, index_out, values_out, cap_listed, listed_count, false); }
-    catch (const std::exception &e) { set_error(std::string("zkg_zklaim_witness_mirror: ") + e.what()); }
-    catch (...) { set_error("zkg_zklaim_witness_mirror: unexpected exception"); }
-    return ZKG_ERROR;
+    return c_boundary("zkg_zklaim_witness_mirror", ZKG_ERROR, [&] { return witness_mirror_impl(ctx, tags_out, index_out, values_out, cap_listed, listed_count, false); });
 }
 int zkg_zklaim_witness_mirror_parallel(const zklaim_ctx *ctx, uint8_t *tags_out, uint32_t *index_out, uint64_t *values_out, size_t cap_listed, size_t *listed_count) {
-    try { return witness_mirror_impl(ctx, tags_out, index_out, values_out, cap_listed, listed_count, true); }
-    catch (const std::exception &e) { set_error(std::string("zkg_zklaim_witness_mirror_parallel: ") + e.what()); }
-    catch (...) { set_error("zkg_zklaim_witness_mirror_parallel: unexpected exception"); }
-    return ZKG_ERROR;
+    return c_boundary("zkg_zklaim_witness_mirror_parallel", ZKG_ERROR, [&] { return witness_mirror_impl(ctx, tags_out, index_out, values_out, cap_listed, listed_count, true); });
 }
 
 static int witness_gpu_impl(const zklaim_ctx *const *ctxs, size_t count, uint8_t *tags_out, uint32_t *index_out, uint64_t *values_out, size_t cap_listed, size_t *listed_counts, bool par) {
@@ -396,16 +390,10 @@ static int witness_gpu_impl(const zklaim_ctx *const *ctxs, size_t count, uint8_t
     return ZKG_OK;
 }
 int zkg_zklaim_witness_gpu(const zklaim_ctx *const *ctxs, size_t count, uint8_t *tags_out, uint32_t *index_out, uint64_t *values_out, size_t cap_listed, size_t *listed_counts) {
-    try { return witness_gpu_impl(ctxs, count, tags_out, index_out, values_out, cap_listed, listed_counts, false); }
-    catch (const std::exception &e) { set_error(std::string("zkg_zklaim_witness_gpu: ") + e.what()); }
-    catch (...) { set_error("zkg_zklaim_witness_gpu: unexpected exception"); }
-    return ZKG_ERROR;
+    return c_boundary("zkg_zklaim_witness_gpu", ZKG_ERROR, [&] { return witness_gpu_impl(ctxs, count, tags_out, index_out, values_out, cap_listed, listed_counts, false); });
 }
 int zkg_zklaim_witness_gpu_parallel(const zklaim_ctx *const *ctxs, size_t count, uint8_t *tags_out, uint32_t *index_out, uint64_t *values_out, size_t cap_listed, size_t *listed_counts) {
-    try { return witness_gpu_impl(ctxs, count, tags_out, index_out, values_out, cap_listed, listed_counts, true); }
-    catch (const std::exception &e) { set_error(std::string("zkg_zklaim_witness_gpu_parallel: ") + e.what()); }
-    catch (...) { set_error("zkg_zklaim_witness_gpu_parallel: unexpected exception"); }
-    return ZKG_ERROR;
+    return c_boundary("zkg_zklaim_witness_gpu_parallel", ZKG_ERROR, [&] { return witness_gpu_impl(ctxs, count, tags_out, index_out, values_out, cap_listed, listed_counts, true); });
 }
 
 }  // extern "C"
