@@ -9,7 +9,7 @@
 // followed by conflict-free accumulation:
 //   1. k_digits        signed c-bit digits of every scalar, written window-major (4 B per digit)
 //   2-4. the sort, in one of two forms (sort_digits picks):
-//        two-pass (uniform scalars, 4096 <= n < 2^23, c >= 12): k_rx_count / k_rx_scan count and lay out coarse bins of buckets per
+//        two-pass (uniform scalars, 4096 <= n < 2^23, c >= 12): k_rx_count counts the coarse bins of buckets per
 //                      window; k_rx_scatter splits each 16K-point slice into those bins inside LDS and writes every bin's run
 //                      contiguously; k_rx_fine sorts one bin by the remaining bucket bits inside LDS and writes the final list and
 //                      the bucket counts / offsets in order.  No single-word scatter to global memory anywhere.
@@ -42,6 +42,7 @@
 // Also here: the generator's fixed-base batch (k_fixed_table, k_fixed_base: byte windows, in-lane batched normalisation).
 #include "common.hpp"
 #include "fq29.hip.hpp"
+#include "host/horner_jac.hpp"
 #include "../../include/zkg.h"
 #include <algorithm>
 #include <chrono>
@@ -72,6 +73,7 @@ static constexpr size_t RED_SMALL_BUCKETS = (size_t)1 << 16, RED_LARGE_BUCKETS =
 static constexpr int MAX_C = 16;             // LDS histogram: 2^(c-1) u32 counters <= 128 KiB
 static constexpr uint32_t HEAVY_S = 512;     // entries per heavy part (one wavefront sums one part)
 static constexpr uint32_t HEAVY_T_MAX = 1024;
+static constexpr uint32_t CLASS_HIST_COPIES = 8;     // of the class histogram (HEAVY_T_MAX + 2 counters each), see rx_fine_offsets
 static constexpr int HEAVY_PART_BLOCKS = 512, HEAVY_MERGE_BLOCKS = 128;
 static constexpr int SORT_THREADS = 1024;
 static constexpr int SCAN_ITEMS = 4;         // per thread in the block scan
@@ -386,11 +388,37 @@ static constexpr uint32_t RX_MAX_CBITS = 10, RX_MAX_CB = 1u << RX_MAX_CBITS, RX_
 // per window, chosen on the host so that a bin averages <= 4096 entries, half of what the second pass holds in LDS (measured: 1365 ...
 // 8192 all within 2 %).  The top window of a 254-bit scalar populates only 38 % of its buckets, so its bins are 2.65x as full and go to
 // the streamed path of k_rx_fine (rx_fine_big_bin).
-__global__ __launch_bounds__(1024) void k_rx_count(const uint32_t *digits, size_t n, uint32_t fbits, uint32_t cbits, uint32_t *cnt) {
+// Heavy threshold, computed on the device from the real list lengths: a lane walks its bucket's list alone (~7 us per G1
+// addition at low occupancy), so the longest non-heavy list bounds the kernel's latency however little total work there is.
+// Lists are cut at 4x the true average length + 32 (the partly filled top window of uniform scalars averages ~2.7x the other
+// windows and stays on the lane-per-bucket path; a sparse bit-witness MSM gets a small threshold and a short tail).
+ZK_D uint32_t heavy_threshold_dev(const uint32_t *offsets, size_t total_buckets, uint32_t divisor) {
+    uint32_t entries = offsets[total_buckets];
+    // the slack shrinks with the average: a sparse launch (a witness' few non-bit scalars over 2^19 buckets) is pure latency, and its
+    // longest lane-walked list is its duration
+    uint32_t avg6 = (uint32_t)(6 * (uint64_t)entries / total_buckets), slack = 8 + avg6 > 32 ? 32 : 8 + avg6;
+    uint32_t t = (uint32_t)(4 * (uint64_t)entries / total_buckets) + slack;
+    t = t > HEAVY_T_MAX ? HEAVY_T_MAX : t;
+    t /= divisor;
+    return t < 4 ? 4 : t;
+}
+// sum over the 64 lanes of a wavefront (every lane gets it)
+ZK_D uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+// The bin start positions are not laid out by a launch of their own: k_rx_count also adds every slice's entries to its window's total, wtot[w],
+// and the workgroups of the two passes work out what they need from the counts — start of window w = sum of wtot below w, start of a bin = that
+// plus the window's bin counts below it (rx_entries_before).  Each is a few hundred cached words per workgroup against one more dependent
+// launch (a single workgroup, 10 us with its gap) at the head of every sort.
+__global__ __launch_bounds__(1024) void k_rx_count(const uint32_t *digits, size_t n, uint32_t fbits, uint32_t cbits, uint32_t *cnt, uint32_t *wtot) {
     sort_wave_priority();
     __shared__ uint32_t c[RX_MAX_CB];
+    __shared__ uint32_t tot;
     const uint32_t sl = blockIdx.x, w = blockIdx.y, t = threadIdx.x, CB = 1u << cbits;
     if (t < CB) c[t] = 0;
+    if (t == 0) tot = 0;
     __syncthreads();
     size_t lo = (size_t)sl * RX_SLICE, hi = lo + RX_SLICE < n ? lo + RX_SLICE : n;
     const uint32_t *d = digits + (size_t)w * n;
@@ -405,41 +433,54 @@ __global__ __launch_bounds__(1024) void k_rx_count(const uint32_t *digits, size_
     } else
     for (size_t i = lo + t; i < hi; i += 1024) { uint32_t code = d[i]; if (code) atomicAdd(&c[((code >> 1) - 1) >> fbits], 1u); }
     __syncthreads();
-    if (t < CB && c[t]) atomicAdd(&cnt[w * CB + t], c[t]);
-}
-// exclusive scan of the W * 2^cbits bin counts (<= 16384 of them, 16 per thread) -> bin start positions; base[nbins] = number of entries
-__global__ __launch_bounds__(1024) void k_rx_scan(const uint32_t *cnt, uint32_t nbins, uint32_t *base, uint32_t *cursor, uint32_t *grand_total) {
-    sort_wave_priority();
-    __shared__ uint32_t part[1024];
-    const uint32_t t = threadIdx.x, per = (nbins + 1023) / 1024, lo = t * per, hi = lo + per < nbins ? lo + per : nbins;
-    uint32_t sum = 0;
-    for (uint32_t i = lo; i < hi; ++i) sum += cnt[i];
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
-        uint32_t x = (t >= d) ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += x;
-        __syncthreads();
+    if (t < CB) {                                                         // (CB >= 64: whole wavefronts)
+        const uint32_t mine = c[t];
+        if (mine) atomicAdd(&cnt[w * CB + t], mine);
+        const uint32_t in_wave = wave_sum(mine);
+        if ((t & 63) == 0 && in_wave) atomicAdd(&tot, in_wave);
     }
-    uint32_t run = part[t] - sum;
-    for (uint32_t i = lo; i < hi; ++i) { base[i] = run; cursor[i] = 0; run += cnt[i]; }
-    if (t == 1023) { base[nbins] = part[1023]; *grand_total = part[1023]; }
+    __syncthreads();
+    if (t == 0 && tot) atomicAdd(&wtot[w], tot);
+}
+// This thread's share of the entries that lie before bin (w, cb) in the list: the windows below w, and w's bins below cb.  Summed over the
+// workgroup's threads (wave_sum, then one LDS atomic per wavefront) it is the bin's start; cb = 0: the window's.
+ZK_D uint32_t rx_entries_before(const uint32_t *cnt, const uint32_t *wtot, uint32_t w, uint32_t cb, uint32_t cbits) {
+    uint32_t v = 0;
+    for (uint32_t i = threadIdx.x; i < w; i += blockDim.x) v += wtot[i];
+    for (uint32_t b = threadIdx.x; b < cb; b += blockDim.x) v += cnt[(w << cbits) + b];
+    return v;
 }
 // T threads per workgroup take a slice of 16 T digits.  T = 1024 (16K-digit slices, 64 KiB of LDS) when the sort has the chip to itself; T = 512 for
 // the sorts of a piece-wise job, which run BESIDE the accumulation of the piece before: two wavefronts per SIMD of 56 registers fit into what
 // k_bucket_accum29 leaves free (ACC29_VGPRS), four do not.
+// The start of every bin of the window comes from an exclusive scan of the window's 2^cbits counts (it shares the barriers of the slice's own
+// scan) on top of the window's start; `cursor` counts, per bin, the entries that the slices before this one (in atomic order) have reserved.
+// Workgroup (0, 0) also stores the number of entries of the whole list, offsets[total buckets], for the kernels of the later launches.
 template <int T>
-__global__ __launch_bounds__(T) void k_rx_scatter(const uint32_t *digits, size_t n, uint32_t fbits, uint32_t cbits, const uint32_t *base, uint32_t *cursor,
-                                                   uint32_t *tmp) {
+__global__ __launch_bounds__(T) void k_rx_scatter(const uint32_t *digits, size_t n, uint32_t fbits, uint32_t cbits, const uint32_t *cnt, const uint32_t *wtot, uint32_t W,
+                                                   uint32_t *cursor, uint32_t *tmp, uint32_t *grand_total) {
     sort_wave_priority();
     extern __shared__ uint32_t lds_u32[];
     constexpr uint32_t SLICE = RX_PER_THREAD * T;
     const uint32_t CB = 1u << cbits;
-    uint32_t *stage = lds_u32, *c = lds_u32 + SLICE, *off = c + RX_MAX_CB, *gb = off + RX_MAX_CB + 1, *cur = gb + RX_MAX_CB;
+    uint32_t *stage = lds_u32, *c = lds_u32 + SLICE, *off = c + RX_MAX_CB, *gb = off + RX_MAX_CB + 1, *cur = gb + RX_MAX_CB, *wsum = cur + RX_MAX_CB;   // wsum[0]: start of the window, [1]: all entries
     const uint32_t sl = blockIdx.x, w = blockIdx.y, t = threadIdx.x;
     for (uint32_t b = t; b < CB; b += T) c[b] = 0;
+    if (t < 2) wsum[t] = 0;
     __syncthreads();
+    // a thread owns bins t and t + T (CB <= 1024 <= 2 T) in both scans
+    const uint32_t b0 = t, b1 = t + T;
+    const uint32_t g0 = b0 < CB ? cnt[w * CB + b0] : 0, g1 = b1 < CB ? cnt[w * CB + b1] : 0;
+    {
+        const uint32_t below = wave_sum(rx_entries_before(cnt, wtot, w, 0, cbits));
+        if ((t & 63) == 0 && below) atomicAdd(&wsum[0], below);
+        if (sl == 0 && w == 0) {                                          // (uniform across the workgroup)
+            uint32_t all = 0;
+            for (uint32_t i = t; i < W; i += T) all += wtot[i];
+            all = wave_sum(all);
+            if ((t & 63) == 0 && all) atomicAdd(&wsum[1], all);
+        }
+    }
     size_t lo = (size_t)sl * SLICE, hi = lo + SLICE < n ? lo + SLICE : n;
     const uint32_t *d = digits + (size_t)w * n;
     uint32_t code[RX_PER_THREAD];                                    // this thread's 16 digits stay in registers between the two passes
@@ -461,21 +502,24 @@ __global__ __launch_bounds__(T) void k_rx_scatter(const uint32_t *digits, size_t
 #pragma unroll
     for (uint32_t j = 0; j < RX_PER_THREAD; ++j) if (code[j]) atomicAdd(&c[((code[j] >> 1) - 1) >> fbits], 1u);
     __syncthreads();
-    // exclusive scan of the bin counts (Hillis-Steele; a thread owns bins t and t + T: CB <= 1024 <= 2 T), off[CB] = entries of the slice
-    const uint32_t b0 = t, b1 = t + T;
-    if (b0 < CB) off[b0] = c[b0];
-    if (b1 < CB) off[b1] = c[b1];
+    // exclusive scans of the slice's bin counts (off; off[CB] = entries of the slice) and of the window's (gb), Hillis-Steele side by side
+    if (b0 < CB) { off[b0] = c[b0]; gb[b0] = g0; }
+    if (b1 < CB) { off[b1] = c[b1]; gb[b1] = g1; }
     __syncthreads();
     for (uint32_t dd = 1; dd < CB; dd <<= 1) {
-        const uint32_t x0 = (b0 < CB && b0 >= dd) ? off[b0 - dd] : 0, x1 = (b1 < CB && b1 >= dd) ? off[b1 - dd] : 0;
+        const bool in0 = b0 < CB && b0 >= dd, in1 = b1 < CB && b1 >= dd;
+        const uint32_t x0 = in0 ? off[b0 - dd] : 0, x1 = in1 ? off[b1 - dd] : 0, y0 = in0 ? gb[b0 - dd] : 0, y1 = in1 ? gb[b1 - dd] : 0;
         __syncthreads();
-        if (b0 < CB) off[b0] += x0;
-        if (b1 < CB) off[b1] += x1;
+        if (b0 < CB) { off[b0] += x0; gb[b0] += y0; }
+        if (b1 < CB) { off[b1] += x1; gb[b1] += y1; }
         __syncthreads();
     }
     if (t == 0) off[CB] = off[CB - 1];
+    if (t == 0 && sl == 0 && w == 0) *grand_total = wsum[1];
     __syncthreads();
-    for (uint32_t b = t; b < CB; b += T) { off[b] -= c[b]; gb[b] = c[b] ? base[w * CB + b] + atomicAdd(&cursor[w * CB + b], c[b]) : 0; cur[b] = 0; }
+    const uint32_t wstart = wsum[0];
+    if (b0 < CB) { off[b0] -= c[b0]; gb[b0] = c[b0] ? wstart + (gb[b0] - g0) + atomicAdd(&cursor[w * CB + b0], c[b0]) : 0; cur[b0] = 0; }
+    if (b1 < CB) { off[b1] -= c[b1]; gb[b1] = c[b1] ? wstart + (gb[b1] - g1) + atomicAdd(&cursor[w * CB + b1], c[b1]) : 0; cur[b1] = 0; }
     __syncthreads();
     const uint32_t fmask = (1u << fbits) - 1;
 #pragma unroll
@@ -493,10 +537,13 @@ __global__ __launch_bounds__(T) void k_rx_scatter(const uint32_t *digits, size_t
         for (uint32_t p = a + lane; p < b; p += 64) tmp[g + (p - a)] = stage[p];
     }
 }
-// shared by the two second-pass kernels: exclusive scan of the FB <= 512 counters (Hillis-Steele in LDS), counts / offsets to global
-ZK_D void rx_fine_offsets(uint32_t *cf, uint32_t *of, uint32_t FB, uint32_t t, uint32_t start, size_t gb0, uint32_t *counts, uint32_t *offsets) {
+// shared by the two second-pass paths: exclusive scan of the FB <= 512 counters (Hillis-Steele in LDS), counts / offsets to global — and the
+// bin's share of the class histogram (buckets per list length, k_class_hist's classes; h: heavy_t + 2 zeroed LDS counters), which the bucket
+// order needs: the counts are in LDS here, so the two-pass sort has no k_class_hist launch
+ZK_D void rx_fine_offsets(uint32_t *cf, uint32_t *of, uint32_t FB, uint32_t t, uint32_t start, size_t gb0, uint32_t *counts, uint32_t *offsets, uint32_t *h, uint32_t heavy_t,
+                          uint32_t *class_hist) {
     const uint32_t T = blockDim.x;                                    // FB <= 512 <= T
-    if (t < FB) of[t] = cf[t];
+    if (t < FB) { const uint32_t c = cf[t]; of[t] = c; atomicAdd(&h[c > heavy_t ? heavy_t + 1 : c], 1u); }
     __syncthreads();
     for (uint32_t d = 1; d < FB; d <<= 1) {
         uint32_t x = (t < FB && t >= d) ? of[t - d] : 0;
@@ -507,13 +554,16 @@ ZK_D void rx_fine_offsets(uint32_t *cf, uint32_t *of, uint32_t FB, uint32_t t, u
     if (t < FB) of[t] -= cf[t];
     __syncthreads();
     for (uint32_t f = t; f < FB; f += T) { counts[gb0 + f] = cf[f]; offsets[gb0 + f] = start + of[f]; }
+    // (every workgroup adds to the same few classes: the copies spread them over CLASS_HIST_COPIES times as many addresses, k_order_place sums them)
+    uint32_t *copy = class_hist + ((blockIdx.x + blockIdx.y) % CLASS_HIST_COPIES) * (HEAVY_T_MAX + 2);
+    for (uint32_t i = t; i < heavy_t + 2; i += T) if (h[i]) atomicAdd(&copy[i], h[i]);
 }
 // A bin with more entries than LDS holds, i.e. many equal digits (a 0/1 witness without ZKG_SCALARS_MOSTLY_BITS, adversarial input, the
 // partly filled top window): the workgroup streams the bin twice; lanes of a wavefront that hold the same fine bucket share one LDS atomic
 // and get consecutive positions, so the stores of the dominant bucket are coalesced.  (Round 2 ran this as a kernel of its own: one
 // more launch per sort whose workgroups all returned at once for uniform scalars.)
 ZK_D void rx_fine_big_bin(const uint32_t *tmp, uint32_t fbits, uint32_t start, uint32_t cnt, size_t gb0, uint32_t *cf, uint32_t *of, uint32_t *cur, uint32_t *counts,
-                          uint32_t *offsets, uint32_t *sorted) {
+                          uint32_t *offsets, uint32_t *sorted, uint32_t *h, uint32_t heavy_t, uint32_t *class_hist) {
     const uint32_t FB = 1u << fbits, sh = 32 - fbits, low = (1u << sh) - 1, t = threadIdx.x, T = blockDim.x;
     const bool giant = cnt > 8 * RX_FINE_MAX;                         // many equal digits; below that (a dense top window) plain atomics are faster
     if (!giant) {
@@ -528,7 +578,7 @@ ZK_D void rx_fine_big_bin(const uint32_t *tmp, uint32_t fbits, uint32_t start, u
         }
     }
     __syncthreads();
-    rx_fine_offsets(cf, of, FB, t, start, gb0, counts, offsets);
+    rx_fine_offsets(cf, of, FB, t, start, gb0, counts, offsets, h, heavy_t, class_hist);
     if (!giant) {
         for (uint32_t p = t; p < cnt; p += T) { uint32_t e = tmp[start + p], f = e >> sh; sorted[start + of[f] + atomicAdd(&cur[f], 1u)] = e & low; }
         return;
@@ -549,18 +599,28 @@ ZK_D void rx_fine_big_bin(const uint32_t *tmp, uint32_t fbits, uint32_t start, u
 // registers between the count and the placement, the sorted bin is assembled in LDS and written out in order
 // (T threads: 1024, or 512 beside a running accumulation — see k_rx_scatter; the bin size the workgroup holds is the same)
 template <int T>
-__global__ __launch_bounds__(T) void k_rx_fine(const uint32_t *tmp, uint32_t fbits, uint32_t cbits, uint32_t B, const uint32_t *base, uint32_t *counts, uint32_t *offsets,
-                                                uint32_t *sorted) {
+__global__ __launch_bounds__(T) void k_rx_fine(const uint32_t *tmp, uint32_t fbits, uint32_t cbits, uint32_t B, const uint32_t *bin_cnt, const uint32_t *wtot, uint32_t *counts,
+                                                uint32_t *offsets, size_t total, uint32_t *class_hist, uint32_t *sorted) {
     sort_wave_priority();
     extern __shared__ uint32_t lds_u32[];
     const uint32_t FB = 1u << fbits, sh = 32 - fbits, low = (1u << sh) - 1;
-    uint32_t *bufB = lds_u32, *cf = bufB + RX_FINE_MAX, *of = cf + FB, *cur = of + FB;       // 64 KiB + counters: two workgroups per CU
+    // (the class counters and the start's accumulator lie in bufB, which is filled only after them: 38 KiB with 512 fine buckets, four workgroups per CU)
+    uint32_t *bufB = lds_u32, *cf = bufB + RX_FINE_MAX, *of = cf + FB, *cur = of + FB, *h = bufB, *before = h + HEAVY_T_MAX + 2;
     const uint32_t cb = blockIdx.x, w = blockIdx.y, t = threadIdx.x, bin = (w << cbits) + cb;
-    const uint32_t start = base[bin], cnt = base[bin + 1] - start;
     const size_t gb0 = (size_t)w * B + (size_t)cb * FB;
     for (uint32_t f = t; f < FB; f += T) { cf[f] = 0; cur[f] = 0; }
+    for (uint32_t i = t; i < HEAVY_T_MAX + 2; i += T) h[i] = 0;
+    // (one thread works the threshold out for the workgroup: its two 64-bit divisions in every wavefront of every bin are issue slots
+    //  taken from the accumulation this kernel runs beside)
+    if (t == 0) { before[0] = 0; before[1] = heavy_threshold_dev(offsets, total, 1); }       // (offsets[total]: k_rx_scatter stored it)
     __syncthreads();
-    if (cnt > RX_FINE_MAX) { rx_fine_big_bin(tmp, fbits, start, cnt, gb0, cf, of, cur, counts, offsets, sorted); return; }     // (uniform across the workgroup)
+    {
+        const uint32_t v = wave_sum(rx_entries_before(bin_cnt, wtot, w, cb, cbits));
+        if ((t & 63) == 0 && v) atomicAdd(&before[0], v);
+    }
+    __syncthreads();
+    const uint32_t start = before[0], heavy_t = before[1], cnt = bin_cnt[bin];
+    if (cnt > RX_FINE_MAX) { rx_fine_big_bin(tmp, fbits, start, cnt, gb0, cf, of, cur, counts, offsets, sorted, h, heavy_t, class_hist); return; }     // (uniform across the workgroup)
     uint32_t ent[RX_FINE_MAX / T];
 #pragma unroll
     for (uint32_t j = 0; j < RX_FINE_MAX / T; ++j) {
@@ -569,7 +629,8 @@ __global__ __launch_bounds__(T) void k_rx_fine(const uint32_t *tmp, uint32_t fbi
         if (p < cnt) atomicAdd(&cf[ent[j] >> sh], 1u);
     }
     __syncthreads();
-    rx_fine_offsets(cf, of, FB, t, start, gb0, counts, offsets);
+    rx_fine_offsets(cf, of, FB, t, start, gb0, counts, offsets, h, heavy_t, class_hist);
+    __syncthreads();                                                  // h (in bufB) has been flushed
 #pragma unroll
     for (uint32_t j = 0; j < RX_FINE_MAX / T; ++j) {
         if (t + j * T >= cnt) continue;
@@ -580,22 +641,8 @@ __global__ __launch_bounds__(T) void k_rx_fine(const uint32_t *tmp, uint32_t fbi
     for (uint32_t p = t; p < cnt; p += T) sorted[start + p] = bufB[p];
 }
 
-// Heavy threshold, computed on the device from the real list lengths: a lane walks its bucket's list alone (~7 us per G1
-// addition at low occupancy), so the longest non-heavy list bounds the kernel's latency however little total work there is.
-// Lists are cut at 4x the true average length + 32 (the partly filled top window of uniform scalars averages ~2.7x the other
-// windows and stays on the lane-per-bucket path; a sparse bit-witness MSM gets a small threshold and a short tail).
-ZK_D uint32_t heavy_threshold_dev(const uint32_t *offsets, size_t total_buckets, uint32_t divisor) {
-    uint32_t entries = offsets[total_buckets];
-    // the slack shrinks with the average: a sparse launch (a witness' few non-bit scalars over 2^19 buckets) is pure latency, and its
-    // longest lane-walked list is its duration
-    uint32_t avg6 = (uint32_t)(6 * (uint64_t)entries / total_buckets), slack = 8 + avg6 > 32 ? 32 : 8 + avg6;
-    uint32_t t = (uint32_t)(4 * (uint64_t)entries / total_buckets) + slack;
-    t = t > HEAVY_T_MAX ? HEAVY_T_MAX : t;
-    t /= divisor;
-    return t < 4 ? 4 : t;
-}
-
 // ---- 5. bucket order by descending length (classes 0..heavy_t, heavy_t+1 = heavy) ------------------------
+// (the two-pass sort counts the classes in k_rx_fine, where the bucket counts are made: this launch is the one-pass sort's)
 __global__ __launch_bounds__(1024) void k_class_hist(const uint32_t *counts, const uint32_t *offsets, size_t total, uint32_t *class_hist) {
     sort_wave_priority();
     __shared__ uint32_t h[HEAVY_T_MAX + 2];
@@ -608,37 +655,44 @@ __global__ __launch_bounds__(1024) void k_class_hist(const uint32_t *counts, con
     __syncthreads();
     for (uint32_t i = t; i < nc; i += 1024) if (h[i]) atomicAdd(&class_hist[i], h[i]);
 }
-// in place: start position of every class, longest first (one 1024-thread workgroup; class c is scanned at position nc - 1 - c)
-__global__ __launch_bounds__(1024) void k_class_scan(uint32_t *class_hist, const uint32_t *offsets, size_t total) {
+// Every workgroup works out where the classes start itself — longest first: class c is scanned at position nc - 1 - c, an exclusive scan of
+// the <= 1026 class counts — where a single-workgroup launch between the histogram and this kernel used to; the ranges inside a class are
+// reserved from class_cursor, which the job's first kernel zeroes with the histogram.  The kernel runs beside an accumulation in a piece-wise
+// job, so the scan is kept off its issue slots: inside the wavefronts that hold classes (two positions per thread; a uniform 2^20-point job has
+// ~50 classes: one wavefront), their totals through LDS, and one thread's threshold for all.
+__global__ __launch_bounds__(1024) void k_order_place(const uint32_t *counts, const uint32_t *offsets, size_t total, const uint32_t *class_hist, uint32_t *class_cursor,
+                                                       uint32_t *order) {
     sort_wave_priority();
-    __shared__ uint32_t part[1024];
-    const uint32_t heavy_t = heavy_threshold_dev(offsets, total, 1), nc = heavy_t + 2, t = threadIdx.x;
-    // HEAVY_T_MAX + 2 = 1026 classes at most: thread t takes positions 2t and 2t + 1 of the reversed order
-    uint32_t v0 = 2 * t < nc ? class_hist[nc - 1 - 2 * t] : 0, v1 = 2 * t + 1 < nc ? class_hist[nc - 2 - 2 * t] : 0;
-    part[t] = v0 + v1;
+    __shared__ uint32_t h[HEAVY_T_MAX + 2], first[HEAVY_T_MAX + 2], wave_total[16], threshold;
+    const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    for (uint32_t i = t; i < HEAVY_T_MAX + 2; i += 1024) h[i] = 0;
+    if (t == 0) threshold = heavy_threshold_dev(offsets, total, 1);
     __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
-        uint32_t x = (t >= d) ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += x;
-        __syncthreads();
-    }
-    const uint32_t before = part[t] - v0 - v1;
-    if (2 * t < nc) class_hist[nc - 1 - 2 * t] = before;
-    if (2 * t + 1 < nc) class_hist[nc - 2 - 2 * t] = before + v0;
-}
-__global__ __launch_bounds__(1024) void k_order_place(const uint32_t *counts, const uint32_t *offsets, size_t total, uint32_t *class_cursor, uint32_t *order) {
-    sort_wave_priority();
-    __shared__ uint32_t h[HEAVY_T_MAX + 2];
-    const uint32_t heavy_t = heavy_threshold_dev(offsets, total, 1);
-    const uint32_t t = threadIdx.x, nc = heavy_t + 2;
-    for (uint32_t i = t; i < nc; i += 1024) h[i] = 0;
-    __syncthreads();
+    const uint32_t heavy_t = threshold, nc = heavy_t + 2;
     size_t gb = (size_t)blockIdx.x * 1024 + t;
     uint32_t cls = 0, rank = 0;
     if (gb < total) { uint32_t c = counts[gb]; cls = c > heavy_t ? heavy_t + 1 : c; rank = atomicAdd(&h[cls], 1u); }
+    // HEAVY_T_MAX + 2 = 1026 classes at most: thread t takes positions 2t and 2t + 1 of the reversed order
+    uint32_t v0 = 0, v1 = 0, incl = 0;
+    if (128 * wave < nc) {                                              // (uniform in the wavefront)
+        for (uint32_t k = 0; k < CLASS_HIST_COPIES; ++k) {
+            const uint32_t *copy = class_hist + k * (HEAVY_T_MAX + 2);
+            if (2 * t < nc) v0 += copy[nc - 1 - 2 * t];
+            if (2 * t + 1 < nc) v1 += copy[nc - 2 - 2 * t];
+        }
+        incl = v0 + v1;
+        for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(incl, d, 64); if (lane >= d) incl += y; }
+    }
+    if (lane == 63) wave_total[wave] = incl;
     __syncthreads();
-    for (uint32_t i = t; i < nc; i += 1024) if (h[i]) h[i] = atomicAdd(&class_cursor[i], h[i]);      // reserve a range per class
+    if (128 * wave < nc) {
+        uint32_t before = incl - v0 - v1;
+        for (uint32_t k = 0; k < wave; ++k) before += wave_total[k];
+        if (2 * t < nc) first[nc - 1 - 2 * t] = before;
+        if (2 * t + 1 < nc) first[nc - 2 - 2 * t] = before + v0;
+    }
+    __syncthreads();
+    for (uint32_t i = t; i < nc; i += 1024) if (h[i]) h[i] = first[i] + atomicAdd(&class_cursor[i], h[i]);      // reserve a range per class
     __syncthreads();
     if (gb < total) order[h[cls] + rank] = (uint32_t)gb;
 }
@@ -1390,7 +1444,7 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
     SetLayout L; L.buckets = total_buckets; L.items = max_items; L.heavy = max_heavy; L.partials = max_items; L.folded = BP; L.red_out = gr.nred * 3;      // two results per chunk, three from k_bucket_reduce29l (gr.red_slots)
     if (gr.heavy_items.reserve(ns * max_items * sizeof(HeavyItem)) || gr.heavy_buckets.reserve(ns * max_heavy * sizeof(HeavyBucket)) ||
         gr.heavy_counters.reserve(8 * MSM_MAX_SETS) || gr.heavy_partials.reserve(ns * max_items * sizeof(XYZZ<F>)) ||
-        bucket_buf.reserve(ns * total_buckets * std::max(sizeof(XYZZ<F>), sizeof(Bucket29))) || gr.red_out.reserve(ns * L.red_out * sizeof(XYZZ<F>)) || ((gr.red_stride = L.red_out), false) ||
+        bucket_buf.reserve(ns * total_buckets * std::max(sizeof(XYZZ<F>), sizeof(Bucket29))) || (job->dev_finish && gr.red_out.reserve(ns * L.red_out * sizeof(XYZZ<F>))) || ((gr.red_stride = L.red_out), false) ||
         (gr.table && gr.folded.reserve(ns * (size_t)BP * std::max(sizeof(XYZZ<F>), sizeof(Bucket29)))) || (!job->dev_finish && gr.host_reserve(ns * L.red_out * sizeof(XYZZ<F>)))) return ZKG_ERROR;
     // (gr.heavy_counters: cleared by the job's k_digits)
     XYZZ<F> *buckets = bucket_buf.as<XYZZ<F>>();
@@ -1431,6 +1485,8 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
         // the job's own stream: the resident call, 1.17 -> 1.14 ms alone — and two capped at ACC29_VGPRS where something is meant to run beside it: the
         // next piece's sort of a piece-wise job, the witness multi-exponentiations of a proof (table launches)
         static const int waves_env = getenv("ZKG_ACC29_WAVES") ? atoi(getenv("ZKG_ACC29_WAVES")) : 0;               // tuning aid: 2 or 3 everywhere
+        // (the last piece of a piece-wise job has no sort beside it; three wavefronts for it alone were measured: 1.837 against 1.850 ms over three
+        //  alternating runs each, one of the three pairs the other way round — inside the runs' own spread, so it keeps the two)
         const int waves29 = waves_env ? waves_env : (job->sort_stream || gr.table || job->bucket_owner) ? 2 : 3;
         auto launch29 = [&](auto kern) {
             hipLaunchKernelGGL(kern, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, rec29, stride29, BP, job->sorted.as<uint32_t>(),
@@ -1459,6 +1515,9 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
         return ZKG_OK;
     }
     const XYZZ<F> *red_in = buckets; size_t in_stride = L.buckets;
+    // The chunk results of a job that finishes on the host are stored where host_combine reads them: gr.host_red is the library's own pinned
+    // memory, so the reduction's few records cross the bus as the kernel's stores and no copy (its packet, and the gap in front of it) follows it.
+    XYZZ<F> *red_dst = job->dev_finish ? gr.red_out.as<XYZZ<F>>() : reinterpret_cast<XYZZ<F> *>(gr.host_red);
     bool folded29 = false;
     if constexpr (sizeof(F) == sizeof(Fq)) {
         if (gr.table && out29) {
@@ -1476,7 +1535,7 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
     }
     if constexpr (sizeof(F) == sizeof(Fq)) {
         const size_t lds = 2 * RG::LANES * sizeof(LdsPoint29);
-        const void *rin = red_in; XYZZ<Fq> *rout = reinterpret_cast<XYZZ<Fq> *>(gr.red_out.p);
+        const void *rin = red_in; XYZZ<Fq> *rout = reinterpret_cast<XYZZ<Fq> *>(red_dst);
         auto launch_red = [&](auto kern, unsigned threads) { hipLaunchKernelGGL(kern, dim3((unsigned)gr.nred, ns), dim3(threads), lds, s, rin, g.B, gr.cpw, rout, in_stride, L.red_out, job->critical ? 1 : 0); };
         if (out29 && red_l_log == RED_L_LOG_LARGE) {
             gr.red_slots = 3;
@@ -1495,18 +1554,16 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
     } else {
         if (red_l_log == RED_L_LOG_LARGE)
             hipLaunchKernelGGL((k_bucket_reduce<F, RED_L_LOG_LARGE>), dim3((unsigned)gr.nred, ns), dim3(RG::THREADS), 2 * RG::LANES * sizeof(LdsPoint<F>), s,
-                               red_in, g.B, gr.cpw, gr.red_out.as<XYZZ<F>>(), in_stride, L.red_out);
+                               red_in, g.B, gr.cpw, red_dst, in_stride, L.red_out);
         else if (red_l_log == RED_L_LOG_SMALL)
             hipLaunchKernelGGL((k_bucket_reduce<F, RED_L_LOG_SMALL>), dim3((unsigned)gr.nred, ns), dim3(RG::THREADS), 2 * RG::LANES * sizeof(LdsPoint<F>), s,
-                               red_in, g.B, gr.cpw, gr.red_out.as<XYZZ<F>>(), in_stride, L.red_out);
+                               red_in, g.B, gr.cpw, red_dst, in_stride, L.red_out);
         else
             hipLaunchKernelGGL((k_bucket_reduce<F, RED_L_LOG_TINY>), dim3((unsigned)gr.nred, ns), dim3(RG::THREADS), 2 * RG::LANES * sizeof(LdsPoint<F>), s,
-                               red_in, g.B, gr.cpw, gr.red_out.as<XYZZ<F>>(), in_stride, L.red_out);
+                               red_in, g.B, gr.cpw, red_dst, in_stride, L.red_out);
     }
     if (hipGetLastError() != hipSuccess) { set_error("msm kernel launch failed"); return ZKG_ERROR; }
-    if (job->dev_finish) return ZKG_OK;                                         // msm_job_finish_dev reads gr.red_out where it is
-    ZK_HIP(hipMemcpyAsync(gr.host_red, gr.red_out.p, ns * L.red_out * sizeof(XYZZ<F>), hipMemcpyDeviceToHost, s));
-    return ZKG_OK;
+    return ZKG_OK;                                                              // (msm_job_finish_dev reads gr.red_out, host_combine gr.host_red)
 }
 
 // host: window value V_w = sum_b (b+1) X_b = U_w + P_w, with chunk ch contributing U_ch + (ch*RED_CHUNK) * P_ch to U_w
@@ -1527,8 +1584,8 @@ static XYZZ<F> host_combine(const MsmJob *job, const MsmGroup &gr, int set, int 
             if (ch >= 1) { suffix.add(P); weighted.add(suffix); }           // sum_ch ch * P_ch
             else suffix.add(P);                                             // suffix == P_w now
         }
-        if (sl == 3 && !Asum.is_inf()) { for (int i = 0; i < 3; ++i) Asum = Asum.dbl(); Usum.add(Asum); }
-        if (!weighted.is_inf()) for (int i = 0; i < gr.chunk_log; ++i) weighted = weighted.dbl();         // * buckets per chunk
+        if (sl == 3 && !Asum.is_inf()) Usum.add(xyzz_times_pow2(Asum, 3));
+        weighted = xyzz_times_pow2(weighted, (uint32_t)gr.chunk_log);                                     // * buckets per chunk (runs of doublings: host/horner_jac.hpp)
         Usum.add(weighted); Usum.add(suffix);
         V[w] = Usum;
     };
@@ -1551,9 +1608,8 @@ static XYZZ<F> host_combine(const MsmJob *job, const MsmGroup &gr, int set, int 
         });
         XYZZ<F> Usum = XYZZ<F>::inf(), suffix = XYZZ<F>::inf(), seg_weighted = XYZZ<F>::inf(), weighted = XYZZ<F>::inf();
         for (int sg = nseg - 1; sg >= 0; --sg) { Usum.add(Us[sg]); weighted.add(Wt[sg]); suffix.add(Ps[sg]); if (sg >= 1) seg_weighted.add(suffix); }
-        if (!seg_weighted.is_inf()) for (int i = 0; i < 4; ++i) seg_weighted = seg_weighted.dbl();        // * 16 chunks per segment
-        weighted.add(seg_weighted);
-        if (!weighted.is_inf()) for (int i = 0; i < gr.chunk_log; ++i) weighted = weighted.dbl();         // * buckets per chunk
+        weighted.add(xyzz_times_pow2(seg_weighted, 4));                                                   // * 16 chunks per segment
+        weighted = xyzz_times_pow2(weighted, (uint32_t)gr.chunk_log);                                     // * buckets per chunk
         Usum.add(weighted); Usum.add(suffix);
         return Usum;
     }
@@ -1561,11 +1617,10 @@ static XYZZ<F> host_combine(const MsmJob *job, const MsmGroup &gr, int set, int 
     // sum_j 2^(c (w0 + j ws)) V_j: Horner with c*ws doublings per owned window, then the shift of the lowest one
     XYZZ<F> acc = XYZZ<F>::inf();
     for (int w = (int)W - 1; w >= 0; --w) {
-        if (!acc.is_inf()) for (uint32_t i = 0; i < g.c * g.ws; ++i) acc = acc.dbl();
+        acc = xyzz_times_pow2(acc, g.c * g.ws);
         acc.add(V[w]);
     }
-    if (!acc.is_inf()) for (uint32_t i = 0; i < g.c * g.w0; ++i) acc = acc.dbl();
-    return acc;
+    return xyzz_times_pow2(acc, g.c * g.w0);
 }
 
 // ---- 8'. the same epilogue on the device for a TABLE launch of G1 sets (msm_job_finish_dev): host_combine's window(w), no Horner.
@@ -1643,7 +1698,7 @@ static int sort_digits(MsmJob *job, const uint32_t *d_scalars, bool mont, const 
     size_t nblk = (total + 1024 * SCAN_ITEMS - 1) / (1024 * SCAN_ITEMS);
     if (nblk > 1024) { set_error("msm: too many buckets for the block scan"); return ZKG_ERROR; }
     if (job->digits.reserve(std::max<size_t>(1, n * g.W) * 4) || job->hist.reserve((size_t)g.W * S * g.B * 4) || job->counts.reserve(total * 4) ||
-        job->offsets.reserve((total + 1) * 4) || job->scan_sums.reserve(1024 * 4) || job->class_hist.reserve((HEAVY_T_MAX + 2) * 4) ||
+        job->offsets.reserve((total + 1) * 4) || job->scan_sums.reserve(1024 * 4) || job->class_hist.reserve((CLASS_HIST_COPIES + 1) * (HEAVY_T_MAX + 2) * 4) ||
         job->order.reserve(total * 4) || job->sorted.reserve(std::max<size_t>(1, n * g.W) * 4)) return ZKG_ERROR;
     uint32_t *digits = job->digits.as<uint32_t>(), *hist = job->hist.as<uint32_t>(), *counts = job->counts.as<uint32_t>(),
              *offsets = job->offsets.as<uint32_t>(), *sums = job->scan_sums.as<uint32_t>(), *chist = job->class_hist.as<uint32_t>();
@@ -1656,15 +1711,15 @@ static int sort_digits(MsmJob *job, const uint32_t *d_scalars, bool mont, const 
     {
         ZeroList zl{};
         int k = 0;
-        zl.p[k] = chist; zl.words[k++] = HEAVY_T_MAX + 2;
+        zl.p[k] = chist; zl.words[k++] = (CLASS_HIST_COPIES + 1) * (HEAVY_T_MAX + 2);     // the class histogram's copies and, behind them, k_order_place's cursors
         for (MsmGroup &gr : job->group) if (gr.nsets) {
             if (gr.heavy_counters.reserve(8 * MSM_MAX_SETS)) return ZKG_ERROR;
             zl.p[k] = gr.heavy_counters.as<uint32_t>(); zl.words[k++] = 2 * MSM_MAX_SETS;
         }
         if (two_pass) {
             const uint32_t nbins = g.W << cbits;
-            if (job->rx_meta.reserve((3 * (size_t)nbins + 8) * 4)) return ZKG_ERROR;
-            zl.p[k] = job->rx_meta.as<uint32_t>(); zl.words[k++] = 3 * nbins + 8;
+            if (job->rx_meta.reserve((2 * (size_t)nbins + g.W) * 4)) return ZKG_ERROR;       // bin counts, bin cursors, window totals
+            zl.p[k] = job->rx_meta.as<uint32_t>(); zl.words[k++] = 2 * nbins + g.W;
         }
         const dim3 dg((unsigned)((n0 + 255) / 256));                                                     // n >= 1 (msm_job_launch)
         const bool four = !d_gather && (n0 & 3) == 0 && g0.w0 == 0 && g0.ws == 1 && g0.W == g0.Wt;      // every window stored, rows 16-byte aligned
@@ -1684,21 +1739,21 @@ static int sort_digits(MsmJob *job, const uint32_t *d_scalars, bool mont, const 
     if (two_pass) {
         // two-pass sort: 2^cbits coarse bins per window, then the remaining fbits inside LDS
         const uint32_t fbits = g.c - 1 - cbits, CB = 1u << cbits, nbins = g.W * CB, S1 = (uint32_t)((n + RX_SLICE - 1) / RX_SLICE);
-        if (job->rx_tmp.reserve(n * g.W * 4) || job->rx_meta.reserve((3 * (size_t)nbins + 8) * 4)) return ZKG_ERROR;
-        uint32_t *cnt = job->rx_meta.as<uint32_t>(), *base = cnt + nbins, *cursor = base + nbins + 1, *tmp = job->rx_tmp.as<uint32_t>();
-        hipLaunchKernelGGL(k_rx_count, dim3(S1, g.W), dim3(1024), 0, s, digits, n, fbits, cbits, cnt);
-        hipLaunchKernelGGL(k_rx_scan, dim3(1), dim3(1024), 0, s, cnt, nbins, base, cursor, offsets + total);
+        if (job->rx_tmp.reserve(n * g.W * 4)) return ZKG_ERROR;
+        uint32_t *cnt = job->rx_meta.as<uint32_t>(), *cursor = cnt + nbins, *wtot = cursor + nbins, *tmp = job->rx_tmp.as<uint32_t>();      // (zeroed by the digits kernel)
+        const size_t fine_lds = (RX_FINE_MAX + 3 * (1u << fbits)) * 4;
+        hipLaunchKernelGGL(k_rx_count, dim3(S1, g.W), dim3(1024), 0, s, digits, n, fbits, cbits, cnt, wtot);
         // (a sort on a stream of its own runs beside an accumulation: half-size workgroups fit into the registers that one leaves free)
         static const int wg_env = getenv("ZKG_SORT_WG") ? atoi(getenv("ZKG_SORT_WG")) : 0;                 // A/B switch: 512 / 1024 everywhere
         const bool half = (wg_env ? wg_env == 512 : job->sort_stream != nullptr) && fbits <= 9;           // (k_rx_fine's scan: one fine bucket per thread)
         if (half) {
             const uint32_t S2 = (uint32_t)((n + 512 * RX_PER_THREAD - 1) / (512 * RX_PER_THREAD));
-            hipLaunchKernelGGL(k_rx_scatter<512>, dim3(S2, g.W), dim3(512), (512 * RX_PER_THREAD + 4 * RX_MAX_CB + 8) * 4, s, digits, n, fbits, cbits, base, cursor, tmp);
-            hipLaunchKernelGGL(k_rx_fine<512>, dim3(CB, g.W), dim3(512), (RX_FINE_MAX + 3 * (1u << fbits)) * 4, s, tmp, fbits, cbits, g.B, base, counts, offsets,
+            hipLaunchKernelGGL(k_rx_scatter<512>, dim3(S2, g.W), dim3(512), (512 * RX_PER_THREAD + 4 * RX_MAX_CB + 8) * 4, s, digits, n, fbits, cbits, cnt, wtot, g.W, cursor, tmp, offsets + total);
+            hipLaunchKernelGGL(k_rx_fine<512>, dim3(CB, g.W), dim3(512), fine_lds, s, tmp, fbits, cbits, g.B, cnt, wtot, counts, offsets, total, chist,
                                job->sorted.as<uint32_t>());
         } else {
-            hipLaunchKernelGGL(k_rx_scatter<1024>, dim3(S1, g.W), dim3(1024), (RX_SLICE + 4 * RX_MAX_CB + 8) * 4, s, digits, n, fbits, cbits, base, cursor, tmp);
-            hipLaunchKernelGGL(k_rx_fine<1024>, dim3(CB, g.W), dim3(1024), (RX_FINE_MAX + 3 * (1u << fbits)) * 4, s, tmp, fbits, cbits, g.B, base, counts, offsets,
+            hipLaunchKernelGGL(k_rx_scatter<1024>, dim3(S1, g.W), dim3(1024), (RX_SLICE + 4 * RX_MAX_CB + 8) * 4, s, digits, n, fbits, cbits, cnt, wtot, g.W, cursor, tmp, offsets + total);
+            hipLaunchKernelGGL(k_rx_fine<1024>, dim3(CB, g.W), dim3(1024), fine_lds, s, tmp, fbits, cbits, g.B, cnt, wtot, counts, offsets, total, chist,
                                job->sorted.as<uint32_t>());
         }
     } else {                                                                                    // one pass: histogram, scans, k_place
@@ -1708,10 +1763,9 @@ static int sort_digits(MsmJob *job, const uint32_t *d_scalars, bool mont, const 
     hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, s, sums, (uint32_t)nblk, offsets + total);
     hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nblk), dim3(1024), 0, s, offsets, sums, total);
     hipLaunchKernelGGL(k_place, dim3(S, g.W), dim3(SORT_THREADS), g.B * 4, s, digits, n, g.B, S, slice_len, hist, offsets, job->sorted.as<uint32_t>());
-    }
     hipLaunchKernelGGL(k_class_hist, dim3((unsigned)((total + 1023) / 1024)), dim3(1024), 0, s, counts, offsets, total, chist);
-    hipLaunchKernelGGL(k_class_scan, dim3(1), dim3(1024), 0, s, chist, offsets, total);
-    hipLaunchKernelGGL(k_order_place, dim3((unsigned)((total + 1023) / 1024)), dim3(1024), 0, s, counts, offsets, total, chist, job->order.as<uint32_t>());
+    }
+    hipLaunchKernelGGL(k_order_place, dim3((unsigned)((total + 1023) / 1024)), dim3(1024), 0, s, counts, offsets, total, chist, chist + CLASS_HIST_COPIES * (HEAVY_T_MAX + 2), job->order.as<uint32_t>());
     if (hipGetLastError() != hipSuccess) { set_error("msm sort launch failed"); return ZKG_ERROR; }
     return ZKG_OK;
 }
