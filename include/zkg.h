@@ -500,6 +500,25 @@ int zkg_zklaim_input_sums_gpu(const struct zklaim_ctx *const *ctxs, size_t count
 /* the kernel's bit rule compiled for the host: same outputs as zkg_zklaim_input_map.  No GPU, no zkg_init. */
 size_t zkg_zklaim_input_map_mirror(const struct zklaim_ctx *ctx, uint64_t *out, size_t cap_elems);
 
+/* ---- test hooks of the key blob's point codec (csrc/codec.hip).  The decoding rule of a compressed point, shared by the key loader, the
+ *      proof decoder, the host's decoder and the single verifier: '1' first is infinity and nothing else is read; otherwise the flag is
+ *      '0', the parity byte '0' or '1', every x coordinate's limbs are below q, x^3 + b is a square, and y is the root whose canonical lsb
+ *      (of y.c0 in G2) is the parity byte.  Anything else is refused.
+ * zkg_point_decompress: n records `stride` bytes apart, the point `offset` bytes into its record, in the loader's layouts: G1 (g2 = 0)
+ *   at stride 34 offset 0 or stride 100 offset 66, G2 (g2 = 1) at stride 66 or 100, offset 0.  out: n x 8 (G2: 16) limbs, affine Montgomery,
+ *   all-zero for infinity AND for a refused record; *flag: non-zero iff a record was refused.
+ *   where 1: the loader's own path (decompress_dev with k_decompress_g1 / k_decompress_g2; needs zkg_init); 0: the host's ser::get_g1 /
+ *   get_g2 with the canonical check (no GPU, no zkg_init).
+ * zkg_point_compress: rec 34: record i = G1 g1[i], i < n <= npoints.  rec 100: record i = G2 g2[idx[i]] then G1 g1[idx[i]], idx[i] <
+ *   npoints (a knowledge commitment of the sparse B query; g2 and idx are read for rec 100 only).  Points as above.  out: n x rec bytes.
+ *   guard (optional): 16 bytes placed behind the run before it is written and read back afterwards: a writer that stays inside its run
+ *   leaves them as they were.  where 1: compress_g1_records / compress_kc_records into 16-byte aligned device staging, as the key
+ *   writer of libsnark_trusted_setup calls them (needs zkg_init); 0: the host's ser::put_g1 / put_g2.
+ * Both: ZKG_ERROR for a null argument, another layout or record size, an index beyond the points, n (or npoints) above 2^20. */
+int zkg_point_decompress(const uint8_t *records, size_t stride, size_t offset, size_t n, int g2, int where, uint64_t *out, uint32_t *flag);
+int zkg_point_compress(const uint64_t *g1, const uint64_t *g2, const uint32_t *idx, size_t npoints, size_t n, int rec, int where, uint8_t *out,
+                       uint8_t guard[16]);
+
 /* ---- known-answer hook for the device arithmetic (libff Fp_model<4,...>::mul_reduce, Fp2_model —
  *      here the generated v_mad_u64_u32 streams of csrc/mont_asm.inc).  Element-wise ON THE GPU, host pointers:
  *      field 0 = Fq, 1 = Fr (4 limbs per element), 2 = Fq2 (8 limbs);  op 0 mul, 1 add, 2 sub, 3 inverse, 4 to Montgomery form,

@@ -472,6 +472,88 @@ def ser_proof(proof):
     return ser_g1(proof[0]) + ser_g2(proof[1]) + ser_g1(proof[2])
 
 
+# ---------------------------------------------------------------- point decompression (operator>> with point compression)
+# The rule every decoder of the product follows: libff's decompression, plus the demand that a stored coordinate is a canonical value.
+#   '1' first: infinity, nothing else is read.  Otherwise the flag is '0', the parity byte '0' or '1', every x coordinate read as a
+#   little-endian integer is below q, x^3 + b is a square, and y is the root whose canonical lsb (of y, of y.c0 on the twist) is the byte.
+# Anything else is refused (None is infinity here, so a refusal is the string REFUSED).
+REFUSED = "refused"
+
+
+def fq_sqrt(a):
+    """a root of a in Fq (q = 3 mod 4), or None"""
+    s = pow(a, (Q + 1) // 4, Q)
+    return s if s * s % Q == a % Q else None
+
+
+def f2_sqrt(a):
+    """a root of a in Fq2, or None.  q = 3 mod 4 (Adj, Rodriguez-Henriquez, "Square root computation over even extension fields",
+    algorithm 9): with a1 = a^((q-3)/4) and alpha = a1^2 a, a is a square iff alpha^(q+1) != -1; the root is u a1 a when alpha = -1 and
+    (1 + alpha)^((q-1)/2) a1 a otherwise.  Not the complex method the product uses; the result is checked by squaring."""
+    a = (a[0] % Q, a[1] % Q)
+    if a == (0, 0):
+        return (0, 0)
+    a1 = f2_pow(a, (Q - 3) // 4)
+    x0 = f2_mul(a1, a)
+    alpha = f2_mul(a1, x0)
+    if f2_mul(f2_conj(alpha), alpha) == (Q - 1, 0):             # alpha^q = conj(alpha)
+        return None
+    y = f2_mul((0, 1), x0) if alpha == (Q - 1, 0) else f2_mul(f2_pow(f2_add((1, 0), alpha), (Q - 1) // 2), x0)
+    assert f2_mul(y, y) == a
+    return y
+
+
+def _deser_x(b):
+    x = int.from_bytes(b, 'little')
+    return None if x >= Q else from_mont(x, Q)
+
+
+def deser_g1(rec):
+    """34 bytes -> (x, y), None (infinity) or REFUSED"""
+    assert len(rec) == 34
+    if rec[0:1] == b'1':
+        return None
+    if rec[0:1] != b'0' or rec[33:34] not in (b'0', b'1'):
+        return REFUSED
+    x = _deser_x(rec[1:33])
+    if x is None:
+        return REFUSED
+    y = fq_sqrt((x * x * x + G1_B) % Q)
+    if y is None:
+        return REFUSED
+    if (y & 1) != (rec[33:34] == b'1'):
+        y = (-y) % Q
+    return (x, y)
+
+
+def deser_g2(rec):
+    """66 bytes -> ((x0, x1), (y0, y1)), None (infinity) or REFUSED.  A purely imaginary root (y.c0 = 0) leaves the parity byte nothing
+    to choose by; libff's algorithm then returns its candidate (0, (-rhs)^((q+1)/4)) for '0' and the negated one for '1' (the lsb of 0
+    is 0, so '1' "disagrees" and negates), and this restates that choice."""
+    assert len(rec) == 66
+    if rec[0:1] == b'1':
+        return None
+    if rec[0:1] != b'0' or rec[65:66] not in (b'0', b'1'):
+        return REFUSED
+    x0, x1 = _deser_x(rec[1:33]), _deser_x(rec[33:65])
+    if x0 is None or x1 is None:
+        return REFUSED
+    x = (x0, x1)
+    rhs = f2_add(f2_mul(f2_mul(x, x), x), G2_B)
+    y = f2_sqrt(rhs)
+    if y is None:
+        return REFUSED
+    odd = rec[65:66] == b'1'
+    if y[0] == 0:
+        assert rhs[1] == 0
+        t = pow((-rhs[0]) % Q, (Q + 1) // 4, Q)
+        assert t * t % Q == (-rhs[0]) % Q
+        return (x, (0, (-t) % Q if odd else t))
+    if (y[0] & 1) != odd:
+        y = f2_neg(y)
+    return (x, y)
+
+
 # ---------------------------------------------------------------- the pairing, from the definition
 # Fq12 = Fq[w]/(w^12 - 18 w^6 + 82): w^6 = xi = 9 + u and u^2 = -1 give (w^6 - 9)^2 = -1.  An element is a list of 12 integers,
 # the coefficients of w^0 .. w^11.  Schoolbook product, square-and-multiply, Fermat inverse: no tower, no Karatsuba, no sparse

@@ -32,7 +32,7 @@ DECLARED_SYMBOLS = [
     "zkg_groth16_prove_dev", "zkg_groth16_prove_batch_dev", "zkg_prove_dev_stats",
     "zkg_msm_g1_resident_async", "zkg_msm_g1_resident_batch_max", "zkg_msm_resident_async_stats", "zkg_msm_combine_gpu",
     "zkg_groth16_verify_each", "zkg_verify_each_stats", "zkg_verify_each_set_chunk", "zkg_pairing_each", "zkg_final_exp",
-    "zkg_fq12_op",
+    "zkg_fq12_op", "zkg_point_decompress", "zkg_point_compress",
 ]
 # the reference's own seam, exported with its original names (zklaim.h:257-259)
 COMPAT_SYMBOLS = ["libsnark_trusted_setup", "libsnark_prove", "libsnark_verify"]
@@ -1059,6 +1059,44 @@ def proof_decode_gpu(proofs):
     L.zkg_proof_decode_gpu.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _check(L.zkg_proof_decode_gpu(_p(pr), n, _p(A), _p(B), _p(Cc), _p(ok)), "zkg_proof_decode_gpu")
     return A, B, Cc, ok
+
+
+def point_decompress(records, stride, offset, n, g2, where=1):
+    """zkg_point_decompress: n compressed records `stride` bytes apart, the point `offset` bytes into its record -> ((n, 8) or (n, 16)
+    affine Montgomery limbs, flag word).  where 1: the key loader's kernels, 0: the host's decoder.  A refused record is all-zero and
+    sets the flag."""
+    buf = np.frombuffer(bytes(records), np.uint8)
+    n = int(n)
+    if buf.size < n * int(stride):
+        raise ZkgError("point_decompress: fewer than n * stride bytes")
+    out = np.zeros((max(1, n), 16 if g2 else 8), np.uint64); flag = C.c_uint32(0xFFFFFFFF)
+    L = lib()
+    L.zkg_point_decompress.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    _check(L.zkg_point_decompress(_p(buf) if buf.size else None, int(stride), int(offset), n, int(g2), int(where), _p(out), C.byref(flag)), "zkg_point_decompress")
+    return out[:n], int(flag.value)
+
+
+def point_compress(g1, g2=None, idx=None, rec=34, where=1, n=None, guard=None):
+    """zkg_point_compress: rec 34: G1 points (npoints, 8) -> n records of 34 bytes (n defaults to all); rec 100: record i = G2 g2[idx[i]]
+    then G1 g1[idx[i]].  -> (n * rec bytes, the 16 guard bytes as they were found behind the run afterwards).  where 1: the key writer's
+    kernels, 0: the host's writer."""
+    a = _u64(g1).reshape(-1, 8); npoints = a.shape[0]
+    b = None if g2 is None else _u64(g2).reshape(-1, 16)
+    ix = None if idx is None else np.ascontiguousarray(idx, np.uint32).reshape(-1)
+    if b is not None and b.shape[0] != npoints:
+        raise ZkgError("point_compress: as many G2 points as G1 points")
+    n = (npoints if ix is None else ix.size) if n is None else int(n)
+    if ix is not None and ix.size < n:
+        raise ZkgError("point_compress: fewer than n indices")
+    out = np.zeros(max(1, n * int(rec)), np.uint8)
+    g = np.frombuffer(bytes(guard) if guard is not None else bytes(16), np.uint8).copy()
+    if g.size != 16:
+        raise ZkgError("point_compress: the guard is 16 bytes")
+    L = lib()
+    L.zkg_point_compress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    _check(L.zkg_point_compress(_p(a) if a.size else None, _p(b) if b is not None and b.size else None, _p(ix) if ix is not None and ix.size else None,
+                                npoints, n, int(rec), int(where), _p(out), _p(g)), "zkg_point_compress")
+    return out[:n * int(rec)].tobytes(), g.tobytes()
 
 
 def zklaim_input_sums_gpu(ctxs, weights, mask=None, lo=0, hi=None):

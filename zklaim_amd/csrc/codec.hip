@@ -18,6 +18,7 @@
 //   linear_combination             : #terms '\n' , (index '\n' coeff(32 B))*
 #include "common.hpp"
 #include "sqrt.hip.hpp"
+#include "host/serialize.hpp"
 #include "../../include/zkg.h"
 #include <chrono>
 #include <cstdio>
@@ -32,17 +33,21 @@ namespace zk {
 
 // (square roots and the limb loader of the decompression kernels: sqrt.hip.hpp, shared with verify.hip's k_proof_decode)
 
-// records of `stride` bytes starting at rec: G1 at offset off (34 B).  flag |= 1 on a malformed point.
+// records of `stride` bytes starting at rec: G1 at offset off (34 B).  flag |= 1 on a malformed point, which is stored as infinity.
+// The rule is the one of ser::get_g1 with coords_canonical and of verify.hip's decode_g1: '1' first is infinity and nothing else is read;
+// otherwise the flag is '0', the parity byte '0' or '1' and the x limbs below q — asked before any arithmetic sees x, whose lazy range is
+// [0, 2q) — and x^3 + 3 is a square.
 __global__ __launch_bounds__(256) void k_decompress_g1(const uint8_t *rec, size_t stride, size_t off, size_t n, G1Affine *out, uint32_t *flag) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint8_t *p = rec + i * stride + off;
     if (p[0] == '1') { out[i] = G1Affine::inf(); return; }
     Fq x = load_fq_bytes(p + 1);
+    if (p[0] != '0' || (p[33] != '0' && p[33] != '1') || !limbs_below_q(x)) { atomicOr(flag, 1u); out[i] = G1Affine::inf(); return; }
     Fq b; { Fq three = Fq::from_u64(3); b = three; }
     Fq rhs = x.sqr() * x + b;
     Fq y = fq_sqrt_candidate(rhs);
-    if (y.sqr() != rhs || p[0] != '0') { atomicOr(flag, 1u); out[i] = G1Affine::inf(); return; }
+    if (y.sqr() != rhs) { atomicOr(flag, 1u); out[i] = G1Affine::inf(); return; }
     bool want_odd = p[33] == '1';
     if (((y.from_mont().v[0] & 1u) != 0) != want_odd) y = y.neg();
     out[i] = G1Affine{x, y}.normalized();
@@ -53,13 +58,14 @@ __global__ __launch_bounds__(256) void k_decompress_g2(const uint8_t *rec, size_
     const uint8_t *p = rec + i * stride + off;
     if (p[0] == '1') { out[i] = G2Affine::inf(); return; }
     Fq2 x = {load_fq_bytes(p + 1), load_fq_bytes(p + 33)};
+    if (p[0] != '0' || (p[65] != '0' && p[65] != '1') || !limbs_below_q(x.c0) || !limbs_below_q(x.c1)) { atomicOr(flag, 1u); out[i] = G2Affine::inf(); return; }
     // twist coefficient b' = 3 / (9 + u), Montgomery limbs
     Fq2 b;
     { const uint32_t b0[8] = {0x77b802a8u, 0x3bf938e3u, 0x3633535du, 0x020b1b27u, 0x49755260u, 0x26b7edf0u, 0x4384a86du, 0x2514c632u};
       const uint32_t b1[8] = {0xd1dcff67u, 0x38e7ecccu, 0x93ce0d3eu, 0x65f0b37du, 0x22ac00aau, 0xd749d0ddu, 0x4a688d4du, 0x0141b9ceu};
       for (int k = 0; k < 8; ++k) { b.c0.v[k] = b0[k]; b.c1.v[k] = b1[k]; } }
     Fq2 rhs = x.sqr() * x + b, y;
-    if (!fq2_sqrt(rhs, y) || p[0] != '0') { atomicOr(flag, 1u); out[i] = G2Affine::inf(); return; }
+    if (!fq2_sqrt(rhs, y)) { atomicOr(flag, 1u); out[i] = G2Affine::inf(); return; }
     bool want_odd = p[65] == '1';
     if (((y.c0.from_mont().v[0] & 1u) != 0) != want_odd) y = y.neg();
     out[i] = G2Affine{x, y}.normalized();
@@ -187,7 +193,12 @@ static bool walk_sections(Reader &rd, Sections &s) {
     size_t domain = rd.count(0), nidx = rd.count(2);                      // an index is at least one digit and a newline
     if (!rd.ok || domain != s.nA || nidx > domain) { set_error("pk blob: bad B_query header"); return false; }
     s.idx.resize(nidx);
-    for (size_t i = 0; i < nidx; ++i) { size_t v = rd.decimal(); if (!rd.ok || v >= domain) { set_error("pk blob: bad B_query index"); return false; } s.idx[i] = (uint32_t)v; }
+    // strictly increasing, as libsnark's sparse_vector is by construction: a repeated index would have two lanes of the scatter write one slot
+    for (size_t i = 0; i < nidx; ++i) {
+        size_t v = rd.decimal();
+        if (!rd.ok || v >= domain || (i && v <= s.idx[i - 1])) { set_error("pk blob: bad B_query index (out of range or not strictly increasing)"); return false; }
+        s.idx[i] = (uint32_t)v;
+    }
     size_t nval = rd.count(100); s.recB = rd.take_records(nval, 100);
     if (!rd.ok || nval != nidx) { set_error("pk blob: bad B_query values"); return false; }
     s.nH = rd.count(34); s.recH = rd.take_records(s.nH, 34);
@@ -248,7 +259,7 @@ static zkg_crs *crs_upload_blob_impl(const void *blob, size_t len) {
     uint32_t flag = 0; uint64_t small[3 * 8 + 2 * 16];
     if (!hip_ok(hipMemcpy(&flag, d_flag.p, 4, hipMemcpyDeviceToHost), "D2H", __FILE__, __LINE__) ||
         !hip_ok(hipMemcpy(small, d_small.p, sizeof(small), hipMemcpyDeviceToHost), "D2H", __FILE__, __LINE__)) return fail(nullptr);
-    if (flag) return fail("pk blob: a compressed point is not on the curve");
+    if (flag) return fail("pk blob: a compressed point is malformed or not on the curve");
     lap("points decompressed (GPU)");
     zkg_pk pk; memset(&pk, 0, sizeof(pk));
     pk.cs.num_variables = (uint32_t)(nA - 1); pk.cs.num_inputs = (uint32_t)primary; pk.cs.num_constraints = (uint32_t)ncons;
@@ -294,4 +305,95 @@ extern "C" int zkg_pk_blob_inspect(const void *blob, size_t len, uint64_t out[8]
 // Nothing may propagate through the C boundary: allocation failures on hostile sizes end up here as an error return.
 extern "C" zkg_crs *zkg_crs_upload_blob(const void *blob, size_t len) {
     return c_boundary<zkg_crs *>("zkg_crs_upload_blob", nullptr, [&] { return crs_upload_blob_impl(blob, len); });
+}
+
+// ---- test hooks of the point codec: the loader's decompression (decompress_dev with its kernels) and the key writer's compression
+//      (compress_g1_records / compress_kc_records) on a caller's records and points, and the host's ser:: functions on the same
+static constexpr size_t CODEC_HOOK_MAX = (size_t)1 << 20;
+static bool host_decode(const uint8_t *p, G1Affine &a) {                      // ser::get_g1 && coords_canonical
+    if (p[0] == '1') { a = G1Affine::inf(); return true; }
+    Fq x; memcpy(x.v, p + 1, 32);
+    return limbs_below_q(x) && ser::get_g1(p, a);
+}
+static bool host_decode(const uint8_t *p, G2Affine &a) {
+    if (p[0] == '1') { a = G2Affine::inf(); return true; }
+    Fq x0, x1; memcpy(x0.v, p + 1, 32); memcpy(x1.v, p + 33, 32);
+    return limbs_below_q(x0) && limbs_below_q(x1) && ser::get_g2(p, a);
+}
+template <class A, class K>
+static int point_decompress_run(K kernel, const uint8_t *records, size_t stride, size_t off, size_t n, int where, uint64_t *out, uint32_t *flag) {
+    static_assert(sizeof(A) % 8 == 0, "affine points are whole 64-bit limbs");
+    if (where == 0) {
+        for (size_t i = 0; i < n; ++i) {
+            A a;
+            if (!host_decode(records + i * stride + off, a)) { *flag |= 1u; a = A::inf(); }
+            memcpy(out + i * (sizeof(A) / 8), &a, sizeof(A));
+        }
+        return ZKG_OK;
+    }
+    ScopedDevBuf d_rec, d_flag, d_out;
+    if (d_out.reserve(n * sizeof(A)) || d_flag.reserve(4)) return ZKG_ERROR;
+    ZK_HIP(hipMemset(d_flag.p, 0, 4));
+    ZK_HIP(hipMemset(d_out.p, 0xA5, n * sizeof(A)));                           // a lane that stores nothing shows
+    if (decompress_dev<A>(kernel, records, stride, off, n, d_out.as<A>(), d_rec, d_flag)) return ZKG_ERROR;
+    ZK_HIP(hipMemcpy(out, d_out.p, n * sizeof(A), hipMemcpyDeviceToHost));
+    ZK_HIP(hipMemcpy(flag, d_flag.p, 4, hipMemcpyDeviceToHost));
+    return ZKG_OK;
+}
+static int point_decompress_impl(const uint8_t *records, size_t stride, size_t offset, size_t n, int g2, int where, uint64_t *out, uint32_t *flag) {
+    if (where != 0 && where != 1) { set_error("zkg_point_decompress: where is 0 (host) or 1 (GPU)"); return ZKG_ERROR; }
+    if (where == 1 && initialised_device() < 0) { set_error("zkg_point_decompress: zkg_init not called (no GPU: the kernels have no CPU path)"); return ZKG_ERROR; }
+    if (!flag || (n && (!records || !out))) { set_error("zkg_point_decompress: null argument"); return ZKG_ERROR; }
+    const bool layout = g2 == 1 ? (offset == 0 && (stride == 66 || stride == 100)) : g2 == 0 && ((stride == 34 && offset == 0) || (stride == 100 && offset == 66));
+    if (!layout) { set_error("zkg_point_decompress: the layouts are G1 at stride 34 offset 0 or stride 100 offset 66, G2 at stride 66 or 100 offset 0"); return ZKG_ERROR; }
+    if (n > CODEC_HOOK_MAX) { set_error("zkg_point_decompress: at most 2^20 records"); return ZKG_ERROR; }
+    *flag = 0;
+    if (!n) return ZKG_OK;
+    return g2 ? point_decompress_run<G2Affine>(k_decompress_g2, records, stride, offset, n, where, out, flag)
+              : point_decompress_run<G1Affine>(k_decompress_g1, records, stride, offset, n, where, out, flag);
+}
+extern "C" int zkg_point_decompress(const uint8_t *records, size_t stride, size_t offset, size_t n, int g2, int where, uint64_t *out, uint32_t *flag) {
+    return c_boundary("zkg_point_decompress", ZKG_ERROR, [&] { return point_decompress_impl(records, stride, offset, n, g2, where, out, flag); });
+}
+
+static int point_compress_impl(const uint64_t *g1, const uint64_t *g2, const uint32_t *idx, size_t npoints, size_t n, int rec, int where, uint8_t *out, uint8_t *guard) {
+    if (where != 0 && where != 1) { set_error("zkg_point_compress: where is 0 (host) or 1 (GPU)"); return ZKG_ERROR; }
+    if (where == 1 && initialised_device() < 0) { set_error("zkg_point_compress: zkg_init not called (no GPU: the kernels have no CPU path)"); return ZKG_ERROR; }
+    if (rec != 34 && rec != 100) { set_error("zkg_point_compress: a record is 34 bytes (G1) or 100 bytes (G2 then G1)"); return ZKG_ERROR; }
+    if (n > CODEC_HOOK_MAX || npoints > CODEC_HOOK_MAX) { set_error("zkg_point_compress: at most 2^20 records of 2^20 points"); return ZKG_ERROR; }
+    if ((n && !out) || (npoints && !g1) || (rec == 100 && ((npoints && !g2) || (n && !idx)))) { set_error("zkg_point_compress: null argument"); return ZKG_ERROR; }
+    if (rec == 34 && n > npoints) { set_error("zkg_point_compress: more records than points"); return ZKG_ERROR; }
+    if (rec == 100) for (size_t i = 0; i < n; ++i) if (idx[i] >= npoints) { set_error("zkg_point_compress: index " + std::to_string(i) + " is beyond the points"); return ZKG_ERROR; }
+    uint8_t none[16] = {0};
+    if (!guard) guard = none;
+    const size_t bytes = n * (size_t)rec;
+    if (where == 0) {
+        std::vector<uint8_t> buf(bytes + 16);
+        memcpy(buf.data() + bytes, guard, 16);
+        for (size_t i = 0; i < n; ++i) {
+            const size_t e = rec == 100 ? idx[i] : i;
+            G1Affine a; memcpy(&a, g1 + 8 * e, sizeof(a));
+            if (rec == 100) { G2Affine b; memcpy(&b, g2 + 16 * e, sizeof(b)); ser::put_g2(buf.data() + i * 100, b); ser::put_g1(buf.data() + i * 100 + 66, a); }
+            else ser::put_g1(buf.data() + i * 34, a);
+        }
+        if (bytes) memcpy(out, buf.data(), bytes);
+        memcpy(guard, buf.data() + bytes, 16);
+        return ZKG_OK;
+    }
+    // the seam's arrangement: the run starts 16-byte aligned in device staging
+    ScopedDevBuf d_g1, d_g2, d_idx, d_rec;
+    if (d_g1.reserve(npoints * 64 + 16) || d_rec.reserve(bytes + 16) || (rec == 100 && (d_g2.reserve(npoints * 128 + 16) || d_idx.reserve(n * 4 + 16)))) return ZKG_ERROR;
+    if (npoints) ZK_HIP(hipMemcpy(d_g1.p, g1, npoints * 64, hipMemcpyHostToDevice));
+    if (rec == 100 && npoints) ZK_HIP(hipMemcpy(d_g2.p, g2, npoints * 128, hipMemcpyHostToDevice));
+    if (rec == 100 && n) ZK_HIP(hipMemcpy(d_idx.p, idx, n * 4, hipMemcpyHostToDevice));
+    ZK_HIP(hipMemset(d_rec.p, 0xA5, bytes));
+    ZK_HIP(hipMemcpy(d_rec.as<uint8_t>() + bytes, guard, 16, hipMemcpyHostToDevice));
+    if (rec == 34 ? compress_g1_records(d_g1.as<G1Affine>(), n, d_rec.as<uint8_t>(), nullptr)
+                  : compress_kc_records(d_g2.as<G2Affine>(), d_g1.as<G1Affine>(), d_idx.as<uint32_t>(), n, d_rec.as<uint8_t>(), nullptr)) { set_error("zkg_point_compress: launch failed"); return ZKG_ERROR; }
+    if (bytes) ZK_HIP(hipMemcpy(out, d_rec.p, bytes, hipMemcpyDeviceToHost));
+    ZK_HIP(hipMemcpy(guard, d_rec.as<uint8_t>() + bytes, 16, hipMemcpyDeviceToHost));
+    return ZKG_OK;
+}
+extern "C" int zkg_point_compress(const uint64_t *g1, const uint64_t *g2, const uint32_t *idx, size_t npoints, size_t n, int rec, int where, uint8_t *out, uint8_t guard[16]) {
+    return c_boundary("zkg_point_compress", ZKG_ERROR, [&] { return point_compress_impl(g1, g2, idx, npoints, n, rec, where, out, guard); });
 }

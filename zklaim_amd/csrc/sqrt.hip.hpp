@@ -37,5 +37,11 @@ ZK_D Fq load_fq_bytes(const uint8_t *p) {
     for (int i = 0; i < 8; ++i) r.v[i] = (uint32_t)p[4 * i] | ((uint32_t)p[4 * i + 1] << 8) | ((uint32_t)p[4 * i + 2] << 16) | ((uint32_t)p[4 * i + 3] << 24);
     return r;
 }
+// the stored limbs of a coordinate are a canonical value, x < q: asked of every encoded point before any arithmetic touches it (the
+// device's lazy range is [0, 2q), and a second encoding of one point is refused).  Host and device: the host decoders ask the same.
+ZK_HD bool limbs_below_q(const Fq &x) {
+    for (int i = 7; i >= 0; --i) if (x.v[i] != FqParams::P[i]) return x.v[i] < FqParams::P[i];
+    return false;
+}
 
 }  // namespace zk

@@ -170,11 +170,7 @@ template <int OP> __global__ __launch_bounds__(VB) void k_fq12_op(size_t n, cons
     out[i] = fq12_op_apply<OP>(x, (OP == FQ12_MUL || OP == FQ12_LINE) ? b[i] : x, fc);
 }
 
-// ---- the device front end
-ZK_D bool limbs_below_q(const Fq &x) {                  // coords_canonical: the stored limbs are a canonical value
-    for (int i = 7; i >= 0; --i) if (x.v[i] != FqParams::P[i]) return x.v[i] < FqParams::P[i];
-    return false;
-}
+// ---- the device front end (limbs_below_q, coords_canonical's test: sqrt.hip.hpp)
 ZK_D bool decode_g1(const uint8_t *p, G1Affine &out) {   // ser::get_g1 && coords_canonical
     out = G1Affine::inf();
     if (p[0] == '1') return true;                       // infinity: nothing else is read
