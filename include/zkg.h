@@ -438,7 +438,8 @@ int  zkg_groth16_verify_each(const zkg_verify_item *items, size_t count, uint8_t
 /* the calling thread's last zkg_groth16_verify_each: out[0] items decided by the device equation, out[1] items decided by the single
  * verifier's code, out[2] device rounds (chunks launched) */
 void zkg_verify_each_stats(size_t out[3]);
-/* test hook: positions per device round of zkg_groth16_verify_each (process-wide); 0 restores the default (64 MiB of staging) */
+/* test hook: positions per device round of zkg_groth16_verify_each and of zkg_zklaim_verify_each (process-wide); 0 restores the default
+ * (64 MiB of staging, worked out for each entry's own layout) */
 void zkg_verify_each_set_chunk(size_t positions);
 /* reduced pairing product per ITEM, Miller loops AND final exponentiation on the GPU: item i uses pairs i*pairs .. i*pairs+pairs-1
  * (layouts and infinity rule as zkg_pairing_product); out: items x 384 bytes, each as zkg_pairing_probe writes one.  ZKG_ERROR for a
@@ -499,6 +500,30 @@ int zkg_zklaim_input_sums_gpu(const struct zklaim_ctx *const *ctxs, size_t count
                               size_t lo, size_t hi, uint64_t *sums_out, size_t cap_elems, size_t *n_elems);
 /* the kernel's bit rule compiled for the host: same outputs as zkg_zklaim_input_map.  No GPU, no zkg_init. */
 size_t zkg_zklaim_input_map_mirror(const struct zklaim_ctx *ctx, uint64_t *out, size_t cap_elems);
+/* ---- many libsnark_verify calls in one, every context decided by its OWN pairing equation on the GPU (zkg_groth16_verify_each's kernels
+ * behind zkg_zklaim_verify_batch's device front end).  rc[i] == libsnark_verify(ctxs[i]) exactly: 0 valid, 1 otherwise.  No weights, no
+ * bisection, no probability attached, no G2 test, and a cost that does not depend on how many proofs are bad.
+ * A null ctx, or one without vk / vk_size or without proof, is rc 1, decided before any GPU call.  count == 0 touches nothing and returns
+ * ZKG_OK; a null ctxs or rc with count > 0 is ZKG_ERROR and nothing is written; no GPU is ZKG_ERROR.  Synchronous; host pointers; the
+ * calling thread is bound to the seam's device as zkg_zklaim_verify_batch binds it; safe from several threads at once and beside every
+ * other verify and prove entry; the same context may appear more than once; nothing is written into a ctx.
+ * Contexts are grouped by the bytes of ctx->vk.  A group goes to the device when its key parses, holds canonical limbs and takes
+ * zv_input_count(npl) inputs for some payload count npl; an item of it enters when proof_size == ZKG_PROOF_BYTES and its payload list
+ * (walked as zkg_zklaim_input_map walks it; num_of_payloads is not trusted) has npl payloads.  Per round 134 bytes per proof and 80 bytes
+ * per payload go up; A, B and C are decoded on the device, and -(IC_0 + sum_k x_ik IC_k) is the sum, over the set bits of the item's input
+ * string, of the entries of a per-key table T[253 k + b] = 2^b IC_k that the first call meeting the key builds on the device (it stays with
+ * the verifier's cached key, at most 8 keys, about 82 KB per payload).  Everything else, and an entering item whose A, B or C does not
+ * decode, is decided by the single verifier's own code on the host pool.  Rounds follow zkg_verify_each_set_chunk.                      */
+int  zkg_zklaim_verify_each(struct zklaim_ctx *const *ctxs, size_t count, int *rc);
+/* the calling thread's last zkg_zklaim_verify_each: out[0] items decided by the device equation, out[1] items decided by the single
+ * verifier's code, out[2] device rounds, out[3] key bit tables this call had to build.  Counters, not clocks. */
+void zkg_zklaim_verify_each_stats(size_t out[4]);
+/* test hook of the accumulator.
+ * out[i] = -(IC_0 + sum_k x_ik IC_k), affine Montgomery, all-zero = infinity; x_i = the input map of ctxs[i].
+ * ic0: 8 limbs; ic: l x 8 limbs affine (all-zero = infinity), l = zv_input_count(payloads of the first non-null ctx);
+ * a null ctx or another payload count: ZKG_ERROR.  where 1: table build + k_zklaim_ic_each on the GPU (needs zkg_init);
+ * where 2: the same device text compiled for the host (no GPU, no zkg_init). */
+int zkg_zklaim_ic_each(const uint64_t *ic0, const uint64_t *ic, const struct zklaim_ctx *const *ctxs, size_t count, int where, uint64_t *out);
 
 /* ---- test hooks of the key blob's point codec (csrc/codec.hip).  The decoding rule of a compressed point, shared by the key loader, the
  *      proof decoder, the host's decoder and the single verifier: '1' first is infinity and nothing else is read; otherwise the flag is

@@ -33,6 +33,7 @@ DECLARED_SYMBOLS = [
     "zkg_msm_g1_resident_async", "zkg_msm_g1_resident_batch_max", "zkg_msm_resident_async_stats", "zkg_msm_combine_gpu",
     "zkg_groth16_verify_each", "zkg_verify_each_stats", "zkg_verify_each_set_chunk", "zkg_pairing_each", "zkg_final_exp",
     "zkg_fq12_op", "zkg_point_decompress", "zkg_point_compress",
+    "zkg_zklaim_verify_each", "zkg_zklaim_verify_each_stats", "zkg_zklaim_ic_each",
 ]
 # the reference's own seam, exported with its original names (zklaim.h:257-259)
 COMPAT_SYMBOLS = ["libsnark_trusted_setup", "libsnark_prove", "libsnark_verify"]
@@ -1047,6 +1048,40 @@ def zklaim_verify_batch_stats():
     out = (C.c_size_t * 4)()
     lib().zkg_zklaim_verify_batch_stats(out)
     return tuple(int(v) for v in out)
+
+
+def zklaim_verify_each(ctxs):
+    """zkg_zklaim_verify_each: one libsnark_verify per ZklaimCtx (None: a null entry), every context by its own equation on the GPU -> [rc, ...]"""
+    L = lib()
+    L.zkg_zklaim_verify_each.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+    n = len(ctxs)
+    ptrs = _ctx_ptrs(ctxs)
+    rc = (C.c_int * max(1, n))(*([-1] * max(1, n)))
+    _check(L.zkg_zklaim_verify_each(ptrs, n, rc), "zkg_zklaim_verify_each")
+    return [int(rc[i]) for i in range(n)]
+
+
+def zklaim_verify_each_stats():
+    """(items decided by the device equation, items decided by the single verifier's code, device rounds, key bit tables built) of this
+    thread's last zklaim_verify_each"""
+    out = (C.c_size_t * 4)()
+    lib().zkg_zklaim_verify_each_stats(out)
+    return tuple(int(v) for v in out)
+
+
+def zklaim_ic_each(ic0, ic, ctxs, where=1):
+    """zkg_zklaim_ic_each: ic0 (8,), ic (l, 8) affine Montgomery limbs (all-zero = infinity), contexts of one payload count ->
+    (n, 8) limbs of -(IC_0 + sum_k x_ik IC_k).  where 1: the GPU's table build and k_zklaim_ic_each, 2: the same code on the host"""
+    a0 = _u64(ic0).reshape(8); a = _u64(ic).reshape(-1, 8)
+    k = next((int(c.num_of_payloads) for c in ctxs if c is not None), 0)
+    if a.shape[0] != (1280 * k + 252) // 253:
+        raise ZkgError("zklaim_ic_each: one IC point per input element of the first context")
+    n = len(ctxs)
+    out = np.zeros((max(1, n), 8), np.uint64)
+    L = lib()
+    L.zkg_zklaim_ic_each.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    _check(L.zkg_zklaim_ic_each(_p(a0), _p(a) if a.size else None, _ctx_ptrs(ctxs), n, int(where), _p(out)), "zkg_zklaim_ic_each")
+    return out[:n]
 
 
 def proof_decode_gpu(proofs):

@@ -498,6 +498,7 @@ void zkg_shutdown(void) {
     (void)hipDeviceSynchronize();
     ntt_release_all();
     msm_release_all();
+    verify_keys_release_all();
     verify_release_all();
     zklaim_witness_release_all();
     g_device = -1;

@@ -232,6 +232,16 @@ int verify_use_mask(size_t n, const uint8_t *d_in_g2, const uint8_t *d_dec_b, co
 static constexpr size_t ZV_SUM_SLICES = 16;
 int verify_zklaim_input_sums(const uint8_t *d_pub, uint32_t npl, size_t base, const uint32_t *d_w, const uint8_t *d_mask, size_t lo, size_t hi,
                              void *d_part, void *d_out, hipStream_t s);
+// the seam's per-proof entry (zkg_zklaim_verify_each): a key's bit table T[s] = 2^(s mod 253) IC_(s / 253), s < zklaim_bit_table_entries(npl)
+// (the string bits npl payloads can set), built from the key's l = zv_input_count(npl) dense IC points (infinity where the key has none);
+// then d_out[i] = -(ic0 + sum_k x_ik IC_k) from item i's npl public records at d_pub + i * npl * 80, and (d_c given) d_negc[i] = -d_c[i]
+size_t zklaim_bit_table_entries(uint32_t npl);
+size_t zklaim_bit_table_tmp_bytes(uint32_t npl);         // the build's XYZZ staging
+int verify_zklaim_bit_table(const G1Affine *d_ic, uint32_t npl, void *d_tmp, G1Affine *d_T, hipStream_t s);
+int verify_zklaim_ic_each(const G1Affine *d_ic0, const G1Affine *d_T, const uint8_t *d_pub, uint32_t npl, size_t n, G1Affine *d_out,
+                          const G1Affine *d_c, G1Affine *d_negc, hipStream_t s);
+void zklaim_ic_each_device_code_on_host(const G1Affine &ic0, const G1Affine *ic, const uint8_t *pub, uint32_t npl, size_t n, G1Affine *out);
+void verify_keys_release_all();                          // zkg_shutdown: the prepared keys and their bit tables (setup_verify.hip)
 int initialised_device();                                // the device zkg_init selected, -1 before (capi.hip)
 // ZKG_ERROR (message "<who>: <what> ...") unless d is `bytes` of device memory of `device`, aligned to `align` (capi.hip); owner: "key", "handle"
 int dev_range_refused(const void *d, size_t bytes, size_t align, int device, const char *who, const char *what, const char *owner);

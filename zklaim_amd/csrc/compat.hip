@@ -2,8 +2,9 @@
 //     int libsnark_trusted_setup(zklaim_ctx*), int libsnark_prove(zklaim_ctx*), int libsnark_verify(zklaim_ctx*)
 // (declared /root/reference/zklaim/zklaim.h:257-259, defined zklaim/libsnark_wrapper.cpp:195-276, called from
 // zklaim_trusted_setup / zklaim_proof_generate / zklaim_proof_verify at zklaim/zklaim.c:77-91).
-// and two entries the reference does not have: int zkg_zklaim_prove_batch(zklaim_ctx *const *, size_t, int *rc), many libsnark_prove calls in
-// one, and int zkg_zklaim_verify_batch(zklaim_ctx *const *, size_t, int *rc), many libsnark_verify calls in one.
+// and three entries the reference does not have: int zkg_zklaim_prove_batch(zklaim_ctx *const *, size_t, int *rc), many libsnark_prove calls in
+// one, and int zkg_zklaim_verify_batch / zkg_zklaim_verify_each(zklaim_ctx *const *, size_t, int *rc), many libsnark_verify calls in one
+// (one random linear combination per key, or every context by its own equation).
 // Behaviour kept: 0 on success; prove returns 1 for an unsatisfied credential (libsnark_wrapper.cpp:233-240); verify returns
 // !valid (:269); ctx->pk / vk / proof are malloc'd here and freed by zklaim_ctx_free (zklaim.c:57-72).
 // Behaviour changed on purpose: file descriptor 1 is never closed (the reference closes stdout around every call,
@@ -43,6 +44,8 @@ void seam_keygen_quiesce();                                                     
 void circuit_release_csr(zkg_circuit *c, zk::OwnedCsr &out);                                                            // zklaim_circuit.hip
 int seam_verify_batch(const zklaim_ctx *const *ctxs, size_t count, int *rc, int front_end);                              // setup_verify.hip
 void seam_verify_batch_stats_clear();                                                                                    // setup_verify.hip
+int seam_verify_each(const zklaim_ctx *const *ctxs, size_t count, int *rc);                                              // setup_verify.hip
+void seam_verify_each_stats_clear();                                                                                     // setup_verify.hip
 
 namespace {
 
@@ -480,6 +483,22 @@ static int zklaim_verify_batch_impl(zklaim_ctx *const *ctxs, size_t count, int *
 }
 int zkg_zklaim_verify_batch(zklaim_ctx *const *ctxs, size_t count, int *rc) {
     return zk::c_boundary("zkg_zklaim_verify_batch", ZKG_ERROR, [&] { return zklaim_verify_batch_impl(ctxs, count, rc); });
+}
+
+
+// ---- zkg_zklaim_verify_each: many libsnark_verify calls in one, every context by its own equation (setup_verify.hip, seam_verify_each) ---
+static int zklaim_verify_each_impl(zklaim_ctx *const *ctxs, size_t count, int *rc) {
+    if (!count) return ZKG_OK;
+    if (!ctxs || !rc) { set_error("zkg_zklaim_verify_each: null argument"); return ZKG_ERROR; }
+    seam_verify_each_stats_clear();
+    bool any = false;
+    for (size_t i = 0; i < count && !any; ++i) any = ctxs[i] && ctxs[i]->vk && ctxs[i]->vk_size && ctxs[i]->proof;
+    if (!any) { for (size_t i = 0; i < count; ++i) rc[i] = 1; return ZKG_OK; }      // decided before any GPU call
+    { std::lock_guard<std::mutex> lk(g_mu); if (ensure_init()) return ZKG_ERROR; }
+    return seam_verify_each(ctxs, count, rc);
+}
+int zkg_zklaim_verify_each(zklaim_ctx *const *ctxs, size_t count, int *rc) {
+    return zk::c_boundary("zkg_zklaim_verify_each", ZKG_ERROR, [&] { return zklaim_verify_each_impl(ctxs, count, rc); });
 }
 
 

@@ -343,6 +343,13 @@ struct PreparedVk {
     std::vector<size_t> idx; std::vector<G1Affine> ic;                          // gamma_ABC: indices and decompressed values
     std::vector<pairing::LineCoeff> gamma_lines, delta_lines;                   // empty when the point is infinity
     mutable std::once_flag batch_once; mutable bool batchable = false;          // vk_batchable, computed on the first batch call that meets the key
+    // the key's bit table on the device (verify.hip, k_zklaim_ic_each), built by the first zkg_zklaim_verify_each that meets the key; it
+    // lives as long as the cache entry and whatever call still holds the key, and goes in zkg_shutdown with the cache (verify_keys_release_all)
+    mutable std::once_flag bits_once; mutable DevBuf bits; mutable int bits_device = -1; mutable bool bits_ok = false;
+    PreparedVk() = default;
+    PreparedVk(const PreparedVk &) = delete;
+    PreparedVk &operator=(const PreparedVk &) = delete;
+    ~PreparedVk() { bits.release(); }
 };
 static int prepare_vk(const uint8_t *vk_blob, size_t vk_len, PreparedVk &v) {   // 0, or 2 = malformed (message set)
     ser::Reader rd{vk_blob, vk_blob + vk_len};
@@ -391,6 +398,13 @@ static std::shared_ptr<const PreparedVk> prepared_vk(const uint8_t *vk_blob, siz
     g_vk_cache[key] = v;
     return v;
 }
+}  // extern "C"
+// zkg_shutdown: the cached keys go, and their bit tables with them, while the device is still there
+void zk::verify_keys_release_all() {
+    std::lock_guard<std::mutex> lk(g_vk_mu);
+    g_vk_cache.clear();
+}
+extern "C" {
 
 // sum_k x_k * IC_k over the key's gamma_ABC entries (Montgomery scalars x_k from scalar_of(k, x)), in up to 16 chunks on the host pool.
 // A chunk shares its doublings (Straus, one bit at a time: 254 doublings and on average 127 mixed additions per point instead of a
@@ -1047,6 +1061,168 @@ void seam_verify_batch_stats_clear() { for (size_t i = 0; i < 4; ++i) t_seam_bat
 extern "C" {
 
 void zkg_zklaim_verify_batch_stats(size_t out[4]) { if (out) for (int i = 0; i < 4; ++i) out[i] = t_seam_batch_stats[i]; }
+
+// ---- zkg_zklaim_verify_each: every context decided by its own equation, as zkg_groth16_verify_each decides its items, with the batch
+// entry's device front end in front: per round one upload [key (first round) | proof records 134 B x n | public records 80 B x npl x n],
+// k_proof_decode for A, B and C, and -acc_i from the key's bit table (k_zklaim_ic_each, which also turns C into -C), then k_g2_replicate,
+// k_miller over [A | -acc | -C] x [B | gamma.. | delta..] and k_final_exp_check.  Neither a square root nor a public input exists on the
+// host for an entering item.  The table build and the accumulator run on the workspace's second stream beside the decode of B; the
+// Miller launch waits for them.  An item whose A, B or C did not decode is decided by the single verifier afterwards.
+static thread_local size_t t_seam_each_stats[4] = {0, 0, 0, 0};
+
+// positions per round of a key at npl payloads; per position: P 3 x 64, Q 3 x 128, Miller values 3 x 384, the proof record, the public
+// records, slots, verdict and three flags
+static size_t seam_each_round_positions(uint32_t npl) {
+    if (const size_t forced = g_each_chunk.load()) return forced;
+    const size_t per = 3 * 64 + 3 * 128 + 3 * 384 + ZKG_PROOF_BYTES + (size_t)ZV_REC * npl + verify_final_exp_ws_bytes(64) / 64 + 4;
+    return std::max<size_t>(64, (VERIFY_EACH_STAGE_MAX - 4096) / per / 64 * 64);
+}
+// the key's bit table: built on s2 by the first call that meets the key (a second caller of the same key waits for that build), then read-only
+static int seam_each_bit_table(const PreparedVk &vk, uint32_t npl, hipStream_t s2, size_t &built) {
+    std::call_once(vk.bits_once, [&] {
+        const uint32_t l = zv_input_count(npl);
+        std::vector<G1Affine> dense(l, G1Affine::inf());                    // an absent index: infinity, its entries are skipped
+        for (size_t j = 0; j < vk.idx.size(); ++j) dense[vk.idx[j]] = vk.ic[j];
+        ScopedDevBuf d_ic, d_tmp;
+        bool ok = !d_ic.reserve(64 * (size_t)l) && !d_tmp.reserve(zklaim_bit_table_tmp_bytes(npl)) && !vk.bits.reserve(64 * zklaim_bit_table_entries(npl)) &&
+                  hip_ok(hipMemcpyAsync(d_ic.p, dense.data(), 64 * (size_t)l, hipMemcpyHostToDevice, s2), "H2D", __FILE__, __LINE__) &&
+                  verify_zklaim_bit_table(d_ic.as<G1Affine>(), npl, d_tmp.p, vk.bits.as<G1Affine>(), s2) == ZKG_OK;
+        ok = hip_ok(hipStreamSynchronize(s2), "sync", __FILE__, __LINE__) && ok;
+        vk.bits_device = initialised_device(); vk.bits_ok = ok;
+        if (ok) ++built;
+    });
+    if (!vk.bits_ok || vk.bits_device != initialised_device()) { set_error("zkg_zklaim_verify_each: the key's bit table is not on this device"); return ZKG_ERROR; }
+    return ZKG_OK;
+}
+
+static int seam_verify_each_impl(const zklaim_ctx *const *ctxs, size_t count, int *rc) {
+    if (initialised_device() < 0) { set_error("zkg_zklaim_verify_each: zkg_init not called (no GPU: there is no CPU path)"); return ZKG_ERROR; }
+    std::vector<uint8_t> verdicts(count, 1);
+    std::vector<char> own(count, 0);                                        // 1: decided by the single verifier's code
+    for (size_t i = 0; i < count; ++i) if (!ctxs[i] || !ctxs[i]->vk || !ctxs[i]->vk_size || !ctxs[i]->proof) own[i] = 2;       // rc 1, nothing to verify
+    std::vector<BatchGroup> groups;
+    batch_group_keys(count, [&](size_t i, size_t &len) { len = ctxs[i]->vk_size; return (const uint8_t *)ctxs[i]->vk; }, groups, own, false);
+    size_t on_device = 0, rounds = 0, built = 0;
+    WorkspaceLease lease;
+    std::vector<uint8_t> host, back;
+    for (const BatchGroup &G : groups) {
+        if (!G.batchable) continue;
+        const PreparedVk &vk = *G.vk;
+        // a key's input count names its payload count, as in seam_verify_batch_impl; the table takes one point per input element
+        const size_t domain = vk.domain;
+        uint32_t npl = (uint32_t)std::min<size_t>(domain * ZV_FR_CAPACITY / (ZV_STRING_BYTES * 8), (size_t)1 << 20);
+        if (!npl || zv_input_count(npl) != domain) npl = 0;
+        if (npl) { std::vector<char> seen(domain, 0); for (size_t k : vk.idx) { if (seen[k]) npl = 0; seen[k] = 1; } }
+        std::vector<size_t> pos;
+        for (size_t i : G.items) {
+            if (npl && ctxs[i]->proof_size == ZKG_PROOF_BYTES && payloads_walked(ctxs[i], npl) == npl) pos.push_back(i); else own[i] = 1;
+        }
+        if (pos.empty()) continue;
+        const size_t chunk = std::min(pos.size(), seam_each_round_positions(npl));
+        // the key: [alpha_beta 384 | gamma, delta 256 | IC_0 64]; a round of n <= chunk positions: [records 134 n | public records 80 npl n]
+        // behind the key (the upload), then [P 3 n x 64 | Q 3 n x 128 | M 3 n x 384 | slots | verdicts n, B decoded n, A decoded n, C decoded n]
+        const size_t k_ab = 0, k_g2 = 384, k_ic0 = k_g2 + 256, o_rec = k_ic0 + 64, o_P = align16(o_rec + align16(ZKG_PROOF_BYTES * chunk) + (size_t)ZV_REC * npl * chunk),
+                     o_Q = o_P + 192 * chunk, o_M = o_Q + 384 * chunk, o_ws = o_M + 1152 * chunk, o_v = o_ws + verify_final_exp_ws_bytes(chunk), total = o_v + 4 * chunk + 16;
+        if (!lease.w && !(lease.w = verify_workspace_acquire())) return ZKG_ERROR;
+        ZK_HIP(hipStreamSynchronize(lease.w->s));                           // (the previous key's rounds are done: the buffer may move)
+        ZK_HIP(hipStreamSynchronize(lease.w->s2));
+        if (lease.w->buf.reserve(total)) return ZKG_ERROR;
+        uint8_t *d = lease.w->buf.as<uint8_t>(); hipStream_t s = lease.w->s, s2 = lease.w->s2;
+        for (size_t lo = 0; lo < pos.size(); lo += chunk) {
+            const size_t n = std::min(chunk, pos.size() - lo), up0 = lo ? o_rec : 0, o_pub = o_rec + align16(ZKG_PROOF_BYTES * n);
+            host.assign(o_pub + (size_t)ZV_REC * npl * n, 0);
+            if (!lo) {
+                const G2Affine key2[2] = {vk.gamma_g2, vk.delta_g2};
+                memcpy(host.data() + k_ab, &vk.alpha_beta, 384); memcpy(host.data() + k_g2, key2, 256); memcpy(host.data() + k_ic0, &vk.ic0, 64);
+            }
+            const int parts = (int)std::min<size_t>(64, n);
+            host_parallel_for(parts, [&](int c) {
+                for (size_t t = n * (size_t)c / parts; t < n * (size_t)(c + 1) / parts; ++t) {
+                    const zklaim_ctx *ctx = ctxs[pos[lo + t]];
+                    memcpy(host.data() + o_rec + ZKG_PROOF_BYTES * t, ctx->proof, ZKG_PROOF_BYTES);
+                    pack_public_records(ctx, npl, host.data() + o_pub + t * npl * ZV_REC);
+                }
+            });
+            G1Affine *dP = (G1Affine *)(d + o_P); G2Affine *dQ = (G2Affine *)(d + o_Q);
+            ZK_HIP(hipMemcpyAsync(d + up0, host.data() + up0, host.size() - up0, hipMemcpyHostToDevice, s));
+            if (verify_proof_decode_ac(d + o_rec, n, dP, d + o_v + 2 * n, s)) return ZKG_ERROR;        // A at 0, C at n (the accumulator moves it)
+            ZK_HIP(hipEventRecord(lease.w->ev, s));
+            if (verify_proof_decode_b(d + o_rec, n, dQ, d + o_v + n, s) || verify_g2_replicate((const G2Affine *)(d + k_g2), n, dQ, s)) return ZKG_ERROR;
+            if (seam_each_bit_table(vk, npl, s2, built)) return ZKG_ERROR;
+            ZK_HIP(hipStreamWaitEvent(s2, lease.w->ev, 0));
+            if (verify_zklaim_ic_each((const G1Affine *)(d + k_ic0), vk.bits.as<G1Affine>(), d + o_pub, npl, n, dP + n, dP + n, dP + 2 * n, s2)) return ZKG_ERROR;
+            ZK_HIP(hipEventRecord(lease.w->ev2, s2));
+            ZK_HIP(hipStreamWaitEvent(s, lease.w->ev2, 0));
+            if (verify_miller(dP, dQ, nullptr, 3 * n, d + o_M, s) ||
+                verify_final_exp_check(d + o_M, n, 3, d + o_ws, d + k_ab, d + o_v, nullptr, s)) return ZKG_ERROR;
+            back.assign(4 * n, 0xFF);
+            ZK_HIP(hipMemcpyAsync(back.data(), d + o_v, 4 * n, hipMemcpyDeviceToHost, s));
+            ZK_HIP(hipStreamSynchronize(s));
+            for (size_t t = 0; t < n; ++t) {
+                if (back[n + t] == 1 && back[2 * n + t] == 1 && back[3 * n + t] == 1) { verdicts[pos[lo + t]] = back[t]; ++on_device; }
+                else own[pos[lo + t]] = 1;                                  // a point that did not decode: the single verifier says why
+            }
+            ++rounds;
+        }
+    }
+    std::vector<size_t> decide_alone;
+    for (size_t i = 0; i < count; ++i) if (own[i] == 1) decide_alone.push_back(i);
+    host_parallel_for((int)decide_alone.size(), [&](int t) {
+        int v;
+        try { v = verify_ctx_alone(ctxs[decide_alone[t]]); } catch (...) { v = 2; }
+        verdicts[decide_alone[t]] = (uint8_t)v;
+    });
+    for (size_t i = 0; i < count; ++i) rc[i] = verdicts[i] == 0 ? 0 : 1;
+    t_seam_each_stats[0] = on_device; t_seam_each_stats[1] = decide_alone.size(); t_seam_each_stats[2] = rounds; t_seam_each_stats[3] = built;
+    return ZKG_OK;
+}
+}  // extern "C"
+// compat.hip's entry: arguments checked, the seam's device bound; rc[i] is written for every i
+int seam_verify_each(const zklaim_ctx *const *ctxs, size_t count, int *rc) { return seam_verify_each_impl(ctxs, count, rc); }
+void seam_verify_each_stats_clear() { for (size_t i = 0; i < 4; ++i) t_seam_each_stats[i] = 0; }
+extern "C" {
+void zkg_zklaim_verify_each_stats(size_t out[4]) { if (out) for (int i = 0; i < 4; ++i) out[i] = t_seam_each_stats[i]; }
+
+// test hook of the accumulator (include/zkg.h)
+static int zklaim_ic_each_impl(const uint64_t *ic0, const uint64_t *ic, const zklaim_ctx *const *ctxs, size_t count, int where, uint64_t *out) {
+    if (where != 1 && where != 2) { set_error("zkg_zklaim_ic_each: where is 1 (GPU) or 2 (the device code on the host)"); return ZKG_ERROR; }
+    if (where == 1 && initialised_device() < 0) { set_error("zkg_zklaim_ic_each: zkg_init not called (no GPU: the kernel has no CPU path)"); return ZKG_ERROR; }
+    if (!ic0 || !ic || !ctxs || !count || !out) { set_error("zkg_zklaim_ic_each: bad argument"); return ZKG_ERROR; }
+    size_t first = 0;
+    while (first < count && !ctxs[first]) ++first;
+    const uint32_t npl = first < count ? payloads_walked(ctxs[first], 4096) : 0;
+    if (!npl || npl > 4096 || count > ((size_t)1 << 20)) { set_error("zkg_zklaim_ic_each: payload or context count out of range"); return ZKG_ERROR; }
+    for (size_t i = 0; i < count; ++i)
+        if (!ctxs[i] || payloads_walked(ctxs[i], npl) != npl) { set_error("zkg_zklaim_ic_each: a null context or another payload count"); return ZKG_ERROR; }
+    const uint32_t l = zv_input_count(npl);
+    std::vector<G1Affine> key(1 + (size_t)l);                               // IC_0, then the l points
+    memcpy(&key[0], ic0, 64); memcpy(&key[1], ic, 64 * (size_t)l);
+    for (const G1Affine &p : key)
+        if (!limbs_below(p.x.v, FqParams::P) || !limbs_below(p.y.v, FqParams::P) || !pairing::on_curve_g1(p)) { set_error("zkg_zklaim_ic_each: a point is not on the curve"); return ZKG_ERROR; }
+    const size_t pub = count * npl * ZV_REC;
+    std::vector<uint8_t> host(pub);
+    for (size_t i = 0; i < count; ++i) pack_public_records(ctxs[i], npl, host.data() + i * npl * ZV_REC);
+    std::vector<G1Affine> res(count);
+    if (where == 2) zklaim_ic_each_device_code_on_host(key[0], key.data() + 1, host.data(), npl, count, res.data());
+    else {
+        const size_t o_key = 0, o_T = align16(64 * key.size()), o_tmp = o_T + 64 * zklaim_bit_table_entries(npl), o_pub = align16(o_tmp + zklaim_bit_table_tmp_bytes(npl)),
+                     o_out = align16(o_pub + pub), total = o_out + 64 * count + 16;
+        WorkspaceLease lease;
+        if (!(lease.w = verify_workspace_acquire()) || lease.w->buf.reserve(total)) return ZKG_ERROR;
+        uint8_t *d = lease.w->buf.as<uint8_t>(); hipStream_t s = lease.w->s;
+        ZK_HIP(hipMemcpyAsync(d + o_key, key.data(), 64 * key.size(), hipMemcpyHostToDevice, s));
+        ZK_HIP(hipMemcpyAsync(d + o_pub, host.data(), pub, hipMemcpyHostToDevice, s));
+        if (verify_zklaim_bit_table((const G1Affine *)(d + o_key) + 1, npl, d + o_tmp, (G1Affine *)(d + o_T), s) ||
+            verify_zklaim_ic_each((const G1Affine *)(d + o_key), (const G1Affine *)(d + o_T), d + o_pub, npl, count, (G1Affine *)(d + o_out), nullptr, nullptr, s)) return ZKG_ERROR;
+        ZK_HIP(hipMemcpyAsync(res.data(), d + o_out, 64 * count, hipMemcpyDeviceToHost, s));
+        ZK_HIP(hipStreamSynchronize(s));
+    }
+    memcpy(out, res.data(), 64 * count);
+    return ZKG_OK;
+}
+int zkg_zklaim_ic_each(const uint64_t *ic0, const uint64_t *ic, const zklaim_ctx *const *ctxs, size_t count, int where, uint64_t *out) {
+    return c_boundary("zkg_zklaim_ic_each", ZKG_ERROR, [&] { return zklaim_ic_each_impl(ic0, ic, ctxs, count, where, out); });
+}
 
 // ---- test hooks of the device front end
 static int proof_decode_gpu_impl(const uint8_t *proofs, size_t count, uint64_t *A, uint64_t *B, uint64_t *C, uint8_t *ok) {

@@ -18,6 +18,10 @@
 //                         produce and a flag byte per item (the single verifier's acceptance rule and coords_canonical, bit for bit)
 //   k_zklaim_input_sums   s_k = sum over the entering positions of a range of weight_p * x_pk, the public inputs x_pk assembled from the
 //                         payloads' public bytes (zklaim_public.hip.hpp); a block per (element, slice), k_fr_fold adds the slices
+// and the accumulator of the seam's per-proof entry (zkg_zklaim_verify_each), which works from the same public records:
+//   k_zklaim_bit_chain, k_zklaim_bit_affine   per key, once: T[s] = 2^(s mod 253) IC_(s / 253) for every string bit s, affine
+//   k_zklaim_ic_each      -(IC_0 + sum_k x_ik IC_k) per item as the sum of T over the string's set bits: a wavefront per item, the lanes
+//                         stride over the string's bytes, an LDS tree adds the lanes; no doubling, no Fr
 #include "common.hpp"
 #include "pairing.hip.hpp"
 #include "final_exp.hip.hpp"
@@ -260,9 +264,114 @@ __global__ __launch_bounds__(VB) void k_fr_fold(const Fr *part, uint32_t l, uint
     out[k] = acc.normalized();
 }
 
+// ---- the seam's per-proof entry (zkg_zklaim_verify_each): -(IC_0 + sum_k x_ik IC_k) from the payloads' public records.  An input map is
+// a bit string and element k holds its bits [253 k, 253 k + 253), so the sum is the sum of T[s] = 2^(s mod 253) IC_(s / 253) over the
+// string's set bits s: a table per key, indexed by the string bit, and per item nothing but mixed additions.  The bodies are ZK_HD: the
+// hook's where = 2 runs them on the host (zklaim_ic_each_device_code_on_host).
+// the doubling chain of one element: tmp[b] = 2^b p, b < 253 (infinity stays infinity)
+ZK_HD void zv_bit_table_chain(const G1Affine &p, G1 *tmp) {
+    G1 a = G1::from_affine(p);
+#pragma unroll 1
+    for (uint32_t b = 0; b < ZV_FR_CAPACITY; ++b) { tmp[b] = a.normalized(); a = a.dbl(); }
+}
+// the stored form of a chain value: affine and canonical, all-zero for infinity (an inversion of its own: the entries are lanes)
+ZK_HD G1Affine zv_bit_table_entry(const G1 &t) { return t.to_affine().normalized(); }
+// what lane `lane` of an item's wavefront adds up: the table entries of the set bits of the string bytes lane, lane + VB, ..
+// (zv_string_byte reverses a byte's bits, so bit j of its value is string bit 8 B + j).  madd is complete: an entry that meets the running
+// sum itself, its negative or infinity comes out right.
+ZK_HD G1 zv_ic_lane_sum(const G1Affine *T, const uint8_t *rec, uint32_t npl, uint32_t lane) {
+    G1 sum = G1::inf();
+#pragma unroll 1
+    for (uint32_t B = lane; B < ZV_STRING_BYTES * npl; B += VB) {
+        uint32_t v = zv_string_byte(rec, npl, B);
+#pragma unroll 1
+        while (v) {
+            const uint32_t j = (uint32_t)__builtin_ctz(v);
+            v &= v - 1u;
+            sum.madd(T[8u * B + j]);
+        }
+    }
+    return sum;
+}
+// -(ic0 + the lanes' sum), affine and canonical (infinity: all-zero)
+ZK_HD G1Affine zv_ic_finish(const G1Affine &ic0, const G1 &lanes_sum) {
+    G1 acc = G1::from_affine(ic0);
+    acc.add(lanes_sum);
+    return acc.neg().to_affine().normalized();
+}
+
+// lane k: the chain of element k into tmp + 253 k (tmp: 253 l XYZZ points)
+__global__ __launch_bounds__(VB) void k_zklaim_bit_chain(uint32_t l, const G1Affine *ic, G1 *tmp) {
+    const uint32_t k = blockIdx.x * VB + threadIdx.x;
+    if (k < l) zv_bit_table_chain(ic[k], tmp + (size_t)ZV_FR_CAPACITY * k);
+}
+// lane s: T[s] for the string bits a payload can set, s < entries <= 253 l
+__global__ __launch_bounds__(VB) void k_zklaim_bit_affine(size_t entries, const G1 *tmp, G1Affine *T) {
+    const size_t s = (size_t)blockIdx.x * VB + threadIdx.x;
+    if (s < entries) T[s] = zv_bit_table_entry(tmp[s]);
+}
+// out[i] = -(ic0 + sum_k x_ik IC_k) for the item whose npl public records lie at pub + i * npl * ZV_REC.  One wavefront per item
+// (gridDim.x == n): the lanes' sums, an LDS tree over the lanes, lane 0 finishes.  c_in != null: the last lane also stores
+// c_neg[i] = -c_in[i] (the proof's C behind the sums; c_in may be `out`: the lane reads before the first barrier, lane 0 writes after the last)
+__global__ __launch_bounds__(VB) void k_zklaim_ic_each(size_t n, uint32_t npl, const G1Affine *ic0, const G1Affine *T, const uint8_t *pub, G1Affine *out,
+                                                       const G1Affine *c_in, G1Affine *c_neg) {
+    __shared__ G1 sh[VB];
+    const size_t i = blockIdx.x;
+    if (c_in && threadIdx.x == VB - 1 && i < n) {
+        const G1Affine c = c_in[i];
+        c_neg[i] = c.is_inf() ? G1Affine::inf() : c.neg().normalized();
+    }
+    sh[threadIdx.x] = zv_ic_lane_sum(T, pub + i * npl * ZV_REC, npl, threadIdx.x);
+    __syncthreads();
+#pragma unroll 1
+    for (int s = VB / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) { G1 a = sh[threadIdx.x]; a.add(sh[threadIdx.x + s]); sh[threadIdx.x] = a; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && i < n) out[i] = zv_ic_finish(*ic0, sh[0]);
+}
+
 unsigned blocks_for(size_t n) { return (unsigned)((n + VB - 1) / VB); }
 
 }  // namespace
+
+size_t zklaim_bit_table_entries(uint32_t npl) { return (size_t)ZV_STRING_BYTES * 8 * npl; }
+size_t zklaim_bit_table_tmp_bytes(uint32_t npl) { return (size_t)ZV_FR_CAPACITY * zv_input_count(npl) * sizeof(G1); }
+// d_ic: the l = zv_input_count(npl) points of the key, dense (infinity where the key has none); d_tmp: zklaim_bit_table_tmp_bytes(npl);
+// d_T: zklaim_bit_table_entries(npl) affine points
+int verify_zklaim_bit_table(const G1Affine *d_ic, uint32_t npl, void *d_tmp, G1Affine *d_T, hipStream_t s) {
+    const uint32_t l = zv_input_count(npl);
+    const size_t entries = zklaim_bit_table_entries(npl);
+    if (!l) return ZKG_OK;
+    hipLaunchKernelGGL(k_zklaim_bit_chain, dim3(blocks_for(l)), dim3(VB), 0, s, l, d_ic, (G1 *)d_tmp);
+    ZK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_zklaim_bit_affine, dim3(blocks_for(entries)), dim3(VB), 0, s, entries, (const G1 *)d_tmp, d_T);
+    ZK_HIP(hipGetLastError());
+    return ZKG_OK;
+}
+// d_out[i] = -(ic0 + sum_k x_ik IC_k), i < n, from d_pub's n x npl public records; d_c (optional): d_negc[i] = -d_c[i]
+int verify_zklaim_ic_each(const G1Affine *d_ic0, const G1Affine *d_T, const uint8_t *d_pub, uint32_t npl, size_t n, G1Affine *d_out,
+                          const G1Affine *d_c, G1Affine *d_negc, hipStream_t s) {
+    if (!n) return ZKG_OK;
+    hipLaunchKernelGGL(k_zklaim_ic_each, dim3((unsigned)n), dim3(VB), 0, s, n, npl, d_ic0, d_T, d_pub, d_out, d_c, d_negc);
+    ZK_HIP(hipGetLastError());
+    return ZKG_OK;
+}
+// the same text on the host (zkg_zklaim_ic_each, where = 2): the table, then per item the VB lane sums, the tree in the kernel's order, the finish
+void zklaim_ic_each_device_code_on_host(const G1Affine &ic0, const G1Affine *ic, const uint8_t *pub, uint32_t npl, size_t n, G1Affine *out) {
+    const uint32_t l = zv_input_count(npl);
+    std::vector<G1> tmp((size_t)ZV_FR_CAPACITY * l);
+    for (uint32_t k = 0; k < l; ++k) zv_bit_table_chain(ic[k], tmp.data() + (size_t)ZV_FR_CAPACITY * k);
+    std::vector<G1Affine> T(zklaim_bit_table_entries(npl));
+    for (size_t s = 0; s < T.size(); ++s) T[s] = zv_bit_table_entry(tmp[s]);
+    std::vector<G1> sh(VB);
+    for (size_t i = 0; i < n; ++i) {
+        for (int t = 0; t < VB; ++t) sh[t] = zv_ic_lane_sum(T.data(), pub + i * npl * ZV_REC, npl, (uint32_t)t);
+        for (int s = VB / 2; s > 0; s >>= 1)
+            for (int t = 0; t < s; ++t) { G1 a = sh[t]; a.add(sh[t + s]); sh[t] = a; }
+        out[i] = zv_ic_finish(ic0, sh[0]);
+    }
+}
 
 MillerConsts miller_consts() {
     static const MillerConsts k = [] {
