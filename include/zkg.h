@@ -552,7 +552,18 @@ int zkg_point_compress(const uint64_t *g1, const uint64_t *g2, const uint32_t *i
  *      Fq only, ops 10-14: the same arithmetic on the 9 x 29-bit representation of the bucket-accumulation kernel (csrc/fq29.hip.hpp),
  *      entered and left through its conversions: 10 mul, 11 add, 12 sub, 13 a if a != b else 0 (its zero test), 14 the composite
  *      (b-a)(a-b) - (b-a)^2 - 2ab with unnormalised intermediate sums, as the mixed addition chains them, 15 the inverse of 3a
- *      (safegcd divsteps on 30-bit limbs, f29::inverse: what the table levels and fixed-base batches normalise through; 0 -> 0).               */
+ *      (safegcd divsteps on 30-bit limbs, f29::inverse: what the table levels and fixed-base batches normalise through; 0 -> 0).
+ *      The lazy range of the 32-bit layer, all three fields.  On the device a value is any representative in [0, 2p) (Fq2: per component), and
+ *      NO input of any op is normalised before the operation, so a caller may pass limbs anywhere below 2p.
+ *      8 dbl(a), fully reduced like ops 0-7.
+ *      RAW stores (the result leaves WITHOUT normalized(): the limbs are the operator's own, in [0, 2p)):
+ *      20 mul, 21 add, 22 sub, 26 negate, 27 square, 28 dbl  (ops 0, 1, 2, 6, 7, 8 plus 20).
+ *      40  ((a*b) - a) * (a + b)
+ *      41  x <- a; 8 times: x <- (x + x) - b
+ *      42  M = a.sqr().dbl() + a.sqr();  M.sqr() - (a*b).dbl()          (the shape XYZZ::dbl_inl builds)
+ *      with no normalisation between the steps of 40-42.
+ *      Predicates, the integer 0 or 1 in 32-bit limb 0 of the result (all other limbs 0):  30 a.is_zero(), 31 a == b
+ *      (Fq2: both components take part).  b is read by ops 0-2, 20-22, 31 and 40-42.                                                       */
 int zkg_field_op(int field, int op, const uint64_t *a, const uint64_t *b, size_t n, uint64_t *out);
 
 /* known-answer hook for the NTT's 29-bit Fr arithmetic (csrc/fr29.hip.hpp: Fr as nine 29-bit limbs, R' = 2^261, lazy limb-wise sums).
@@ -611,6 +622,24 @@ int zkg_fq12_op(int op, const uint32_t *a, const uint32_t *b, size_t n, int wher
 int zkg_g1_add_quad29(const uint64_t *a_jac, const uint64_t *b_jac, size_t n, int chain, uint64_t *out_jac);
 /* the same for the pair form the bucket reduction uses since round 4 (xyzz29_add_pair: lane 0 of a pair holds (X, ZZ), lane 1 (Y, ZZZ)) */
 int zkg_g1_add_pair29(const uint64_t *a_jac, const uint64_t *b_jac, size_t n, int chain, uint64_t *out_jac);
+
+/* known-answer hook for the 32-bit device group law (csrc/curve.hip.hpp as the device compiles it: lazy values in [0, 2p), zero as 0 or p):
+ * element-wise ON THE GPU, host pointers.  group 0 = G1 over Fq, 1 = G2 over Fq2.  Inputs are RAW records of 32-bit limbs exactly as the
+ * device structs lay them out — XYZZ<F> = x, y, zz, zzz and Affine<F> = x, y, each coordinate 8 (Fq) or 16 (Fq2: c0 then c1) little-endian
+ * limbs of Montgomery form — and nothing is normalised on the way in, so a caller can place any representative below 2p in any coordinate,
+ * ZZ != 1 included; infinity is ZZ == 0 (XYZZ) and x == y == 0 (affine), in either representative of zero.  No input is range-checked.
+ * Outputs are XYZZ<F>::normalized() (op 5: Affine<F>::normalized()).
+ *   op 0  madd        a.madd(b)                 a XYZZ, b affine
+ *      1  add         a.add_inl(b)              a, b XYZZ
+ *      2  add_quad    xyzz_add_quad<F>(a, b, lane & 3): four lanes per element hold identical copies; out holds all FOUR lanes' results,
+ *                     4 n XYZZ records, element i's at 4 i .. 4 i + 3 (they must be equal)
+ *      3  dbl         a.dbl_inl()               a XYZZ
+ *      4  dbl_affine  XYZZ::dbl_affine_inl(a)   a affine (no infinity check there: the callers make it)
+ *      5  to_affine   a.to_affine()             a XYZZ, out affine
+ *      6  mul         a.mul(k, 8)               a XYZZ, k eight raw 32-bit limbs per element (any 256-bit value)
+ * chain (ops 0-2 only, 0 .. 64; otherwise 0): x <- a + b, then `chain` rounds of x <- 2x + b with 2x = x.add_inl(x) (op 2: xyzz_add_quad(x, x)),
+ * which takes the doubling branch, and + b the op itself.  b is read by ops 0-2, k by op 6.  n at most 2^20. */
+int zkg_curve_op(int group, int op, const uint32_t *a, const uint32_t *b, const uint32_t *k, size_t n, int chain, uint32_t *out);
 
 /* kernel-only timing hooks for bench.py (HIP events on the stream the kernels run on): average device ms per launch of the dominant kernel
  * since the last reset.  Every fourth call of an MSM entry point is timed, with all of its launches (the event records cost the stream they

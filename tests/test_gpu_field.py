@@ -1,6 +1,8 @@
 """GPU known-answer test of the device field arithmetic: the generated v_mad_u64_u32 / v_addc streams
 of zklaim_amd/csrc/mont_asm.inc, run on the GPU through zkg_field_op, against the definition-level vectors of tests/golden/field.json
-(plain Python integers) and, on random operands including the edges of the lazy [0, 2p) range, against the CPU oracle.
+(plain Python integers) and, on random operands and a few edge values, against the CPU oracle.  Every operand here is CANONICAL (it enters
+through op 4, to_mont().normalized()): the lazy range [p, 2p), both representatives of zero and the limb edges of the streams are the
+subject of tests/test_gpu_fp32.py, the 32-bit group law on such operands that of tests/test_gpu_curve32.py.
 Ops 10-15 and the 29-bit additions here are the canonical-input smoke of csrc/fq29.hip.hpp: they enter through to29, so every operand is
 digits below 1.01 q.  The bounds of that representation (lazy limbs, every representative the invariants admit, the exceptional cases of
 the mixed addition) are tested on raw limbs in tests/test_gpu_fq29.py."""

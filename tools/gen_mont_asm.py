@@ -422,48 +422,85 @@ def selftest_f29():
     print("selftest ok: 29-bit product / squaring streams (single and interleaved pairs) == a*b*2^-261 mod q, no column overflow")
 
 
-def simulate(ins_list, a, b):
-    """Interprets the generated stream on Python ints (one lane).  Returns the 8 result limbs."""
+def decode(ins_list):
+    """Decodes the generated product stream once (the text of every instruction into register slots and operand kinds) and returns
+    run(a, b): the stream interpreted on Python ints (one lane), the 8 result limbs as one integer.  A register read before it was written
+    is an error, except the halves of a 64-bit pair (the first multiply-add of a column reads them as zero)."""
     import re
-    reg = {}
     M32 = 0xFFFFFFFF
+    slot = {}
 
-    def val(tok):
+    def r(tok):
+        return slot.setdefault(tok, len(slot))
+
+    def src(tok):
         tok = tok.strip()
         if tok.startswith("0x"):
-            return int(tok, 16)
+            return (0, int(tok, 16))
         if tok.isdigit():
-            return int(tok)
+            return (0, int(tok))
         m = re.fullmatch(r"v\[(\d+):(\d+)\]", tok)
         if m:
-            return reg.get(f"v{m.group(1)}", 0) | (reg.get(f"v{m.group(2)}", 0) << 32)
-        return reg[tok]
+            return (2, r(f"v{m.group(1)}"), r(f"v{m.group(2)}"))
+        return (1, r(tok))
 
-    for i in range(8):
-        reg[f"%{11 + i}"] = (a >> (32 * i)) & M32
-        reg[f"%{19 + i}"] = (b >> (32 * i)) & M32
+    MOV, MAD, ADDC, MULLO = range(4)
+    prog = []
     for ins in ins_list:
         op, rest = ins.text.split(" ", 1)
         args = [x.strip() for x in re.split(r",\s*(?![^\[]*\])", rest)]
         if op == "s_mov_b32" or op == "v_mov_b32":
-            reg[args[0]] = val(args[1]) & M32
+            prog.append((MOV, r(args[0]), src(args[1])))
         elif op == "v_mad_u64_u32":
-            r = val(args[2]) * val(args[3]) + val(args[4])
             m = re.fullmatch(r"v\[(\d+):(\d+)\]", args[0])
-            reg[f"v{m.group(1)}"] = r & M32; reg[f"v{m.group(2)}"] = (r >> 32) & M32
-            reg[args[1]] = r >> 64
-            assert reg[args[1]] in (0, 1)
+            prog.append((MAD, r(f"v{m.group(1)}"), r(f"v{m.group(2)}"), r(args[1]), src(args[2]), src(args[3]), src(args[4])))
         elif op == "v_addc_co_u32_e64":
-            r = val(args[2]) + val(args[3]) + val(args[4])
-            assert r <= M32, "ex overflow"
-            reg[args[0]] = r & M32; reg[args[1]] = r >> 32
+            prog.append((ADDC, r(args[0]), r(args[1]), src(args[2]), src(args[3]), src(args[4])))
         elif op == "v_mul_lo_u32":
-            reg[args[0]] = (val(args[1]) * val(args[2])) & M32
+            prog.append((MULLO, r(args[0]), src(args[1]), src(args[2])))
         elif op == "s_nop":
             pass
         else:
             raise ValueError(op)
-    return sum(reg[f"%{j}"] << (32 * j) for j in range(8))
+    ins_a = [r(f"%{11 + i}") for i in range(8)]; ins_b = [r(f"%{19 + i}") for i in range(8)]; outs = [r(f"%{j}") for j in range(8)]
+    nslots = len(slot)
+
+    def run(a, b):
+        reg = [None] * nslots
+
+        def val(s):
+            if s[0] == 0:
+                return s[1]
+            if s[0] == 1:
+                return reg[s[1]] + 0                  # None (never written): TypeError
+            return (reg[s[1]] or 0) | ((reg[s[2]] or 0) << 32)
+
+        for i in range(8):
+            reg[ins_a[i]] = (a >> (32 * i)) & M32
+            reg[ins_b[i]] = (b >> (32 * i)) & M32
+        for t in prog:
+            k = t[0]
+            if k == MAD:
+                x = val(t[4]) * val(t[5]) + val(t[6])
+                reg[t[1]] = x & M32; reg[t[2]] = (x >> 32) & M32
+                reg[t[3]] = x >> 64
+                assert reg[t[3]] in (0, 1)
+            elif k == ADDC:
+                x = val(t[3]) + val(t[4]) + val(t[5])
+                assert x <= M32, "ex overflow"
+                reg[t[1]] = x & M32; reg[t[2]] = x >> 32
+            elif k == MOV:
+                reg[t[1]] = val(t[2]) & M32
+            else:
+                reg[t[1]] = (val(t[2]) * val(t[3])) & M32
+        return sum(reg[j] << (32 * i) for i, j in enumerate(outs))
+
+    return run
+
+
+def simulate(ins_list, a, b):
+    """Interprets the generated stream on Python ints (one lane).  Returns the 8 result limbs."""
+    return decode(ins_list)(a, b)
 
 
 def selftest():

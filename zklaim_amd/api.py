@@ -34,6 +34,7 @@ DECLARED_SYMBOLS = [
     "zkg_groth16_verify_each", "zkg_verify_each_stats", "zkg_verify_each_set_chunk", "zkg_pairing_each", "zkg_final_exp",
     "zkg_fq12_op", "zkg_point_decompress", "zkg_point_compress",
     "zkg_zklaim_verify_each", "zkg_zklaim_verify_each_stats", "zkg_zklaim_ic_each",
+    "zkg_curve_op",
 ]
 # the reference's own seam, exported with its original names (zklaim.h:257-259)
 COMPAT_SYMBOLS = ["libsnark_trusted_setup", "libsnark_prove", "libsnark_verify"]
@@ -127,7 +128,10 @@ def field_op(field, op, a, b=None):
     """element-wise device arithmetic (zkg_field_op): field 0 Fq, 1 Fr, 2 Fq2; op 0 mul 1 add 2 sub 3 inv 4 to_mont 5 from_mont 6 neg 7 sqr;
     Fq only: 10-15 the 29-bit representation of the accumulation kernel (mul, add, sub, zero test, composite, inverse of 3a) entered through
     to29 on canonical values: a smoke of that code on digits below 1.01 q.  Its lazy bounds are tested on raw limbs through fq29_op
-    (tests/test_gpu_fq29.py)."""
+    (tests/test_gpu_fq29.py).
+    The lazy range of the 32-bit layer (no input is normalised: any representative below 2p may be passed): 8 dbl; raw stores 20 mul 21 add
+    22 sub 26 neg 27 sqr 28 dbl; predicates (0 or 1 in the low word) 30 is_zero 31 ==; raw chains 40 ((ab) - a)(a + b), 41 x <- a then eight
+    times x <- (x + x) - b, 42 M = 3 a^2, M^2 - 2ab (tests/test_gpu_fp32.py)."""
     a = _u64(a); limbs = 8 if field == 2 else 4
     out = np.zeros_like(a)
     bb = None if b is None else _u64(b)
@@ -181,6 +185,38 @@ def g1_add_pair29(a_jac, b_jac, chain=0):
     a = _u64(a_jac); b = _u64(b_jac); out = np.zeros_like(a)
     _check(lib().zkg_g1_add_pair29(_p(a), _p(b), C.c_size_t(a.size // 12), int(chain), _p(out)), "zkg_g1_add_pair29")
     return out.reshape(-1, 12)
+
+
+CURVE_OPS = {"madd": 0, "add": 1, "add_quad": 2, "dbl": 3, "dbl_affine": 4, "to_affine": 5, "mul": 6}          # name -> op of zkg_curve_op
+
+
+def curve_op(group, name, a, b=None, k=None, chain=0):
+    """the 32-bit device group law on raw records (zkg_curve_op): group 0 G1, 1 G2; a, b (n, coordinates, w) uint32 with w = 8 (G1) or 16 (G2)
+    limbs per coordinate, XYZZ records of 4 coordinates and affine ones of 2 (b of madd, a of dbl_affine); k (n, 8) uint32 scalars for mul.
+    Returns (n, 4, w), for to_affine (n, 2, w), for add_quad (n, 4 lanes, 4, w)."""
+    op = CURVE_OPS[name]; w = 16 if group else 8
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    need_a = 2 if name == "dbl_affine" else 4
+    if a.ndim != 3 or a.shape[1:] != (need_a, w):
+        raise ZkgError(f"curve_op {name}: a must be (n, {need_a}, {w}), got {a.shape}")
+    n = a.shape[0]
+    if name in ("madd", "add", "add_quad"):
+        need_b = 2 if name == "madd" else 4
+        b = np.ascontiguousarray(b, dtype=np.uint32)
+        if b.shape != (n, need_b, w):
+            raise ZkgError(f"curve_op {name}: b must be ({n}, {need_b}, {w}), got {b.shape}")
+    else:
+        b = None
+    if name == "mul":
+        k = np.ascontiguousarray(k, dtype=np.uint32)
+        if k.shape != (n, 8):
+            raise ZkgError(f"curve_op mul: k must be ({n}, 8), got {k.shape}")
+    else:
+        k = None
+    shape = (n, 2, w) if name == "to_affine" else (n, 4, 4, w) if name == "add_quad" else (n, 4, w)
+    out = np.zeros(shape, np.uint32)
+    _check(lib().zkg_curve_op(int(group), int(op), _p(a), _p(b), _p(k), C.c_size_t(n), int(chain), _p(out)), "zkg_curve_op")
+    return out
 
 
 # ---- NTT (libfqfft basic_radix2_domain FFT/iFFT/cosetFFT/icosetFFT) -------------------------------

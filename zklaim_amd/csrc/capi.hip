@@ -198,8 +198,24 @@ template <class F> ZK_D F field_apply(int op, const F &x, const F &y) {
     switch (op) {
     case 0: return x * y;   case 1: return x + y;   case 2: return x - y;   case 3: return x.inverse();
     case 6: return x.neg(); case 7: return x.sqr();
+    case 8: return x.dbl();
     default: return x;
     }
+}
+// ops 20-28 and 40-42: the stores stay RAW (no normalized()), so the representative an operator leaves in [0, 2p) is what the caller reads
+template <class F> ZK_D F field_apply_raw(int op, const F &x, const F &y) {
+    switch (op) {
+    case 20: return x * y;   case 21: return x + y;   case 22: return x - y;
+    case 26: return x.neg(); case 27: return x.sqr(); case 28: return x.dbl();
+    case 40: return ((x * y) - x) * (x + y);
+    case 41: { F t = x; for (int k = 0; k < 8; ++k) t = (t + t) - y; return t; }
+    default: { F xx = x.sqr(), M = xx.dbl() + xx; return M.sqr() - (x * y).dbl(); }         // 42: the shape dbl_inl builds
+    }
+}
+template <class F> ZK_D F field_flag(bool f) {
+    F r = F::zero();
+    if constexpr (sizeof(F) == sizeof(Fq)) r.v[0] = f ? 1u : 0u; else r.c0.v[0] = f ? 1u : 0u;
+    return r;
 }
 template <class F> __global__ __launch_bounds__(64) void k_field_op(int op, const F *a, const F *b, size_t n, F *out) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -226,6 +242,12 @@ template <class F> __global__ __launch_bounds__(64) void k_field_op(int op, cons
             if (op == 13 && f29::is_zero_mod_p(f29::norm(f29::sub(xa, f29::S2_1, yb)))) o = Fq::zero();                          // zero test: out = 0 iff a == b
             out[i] = o; return;
         }
+    }
+    if (op >= 20) {
+        if (op == 30) out[i] = field_flag<F>(x.is_zero());
+        else if (op == 31) out[i] = field_flag<F>(x == y);
+        else out[i] = field_apply_raw(op, x, y);
+        return;
     }
     out[i] = field_apply(op, x, y).normalized();
 }
@@ -470,6 +492,69 @@ int dev_range_refused(const void *d, size_t bytes, size_t align, int device, con
     const uintptr_t lo = reinterpret_cast<uintptr_t>(base), at_d = reinterpret_cast<uintptr_t>(d);
     if (at_d < lo || at_d - lo > size || bytes > size - (at_d - lo)) return refuse("runs past the end of its allocation");
     return ZKG_OK;
+}
+// ---- the 32-bit device group law of curve.hip.hpp, element-wise (the known-answer hook behind zkg_curve_op): RAW records in, exactly as the
+//      device structs lay them out and with no load_norm or normalized() before the operation, so a caller can place any representative
+//      below 2p in any coordinate (ZZ != 1, infinity as ZZ = p, the affine infinity as x = y = p).  Results leave through normalized().
+enum { CURVE_MADD, CURVE_ADD, CURVE_ADD_QUAD, CURVE_DBL, CURVE_DBL_AFFINE, CURVE_TO_AFFINE, CURVE_MUL, CURVE_OPS };
+template <class F, int OP> __global__ __launch_bounds__(64) void k_curve_op(const void *a, const void *b, const uint32_t *k, size_t n, int chain, void *out) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t i = OP == CURVE_ADD_QUAD ? t >> 2 : t;                       // the quad form: four lanes per element, identical copies
+    if (i >= n) return;
+    if constexpr (OP == CURVE_MADD) {
+        XYZZ<F> x = ((const XYZZ<F> *)a)[i]; const Affine<F> y = ((const Affine<F> *)b)[i];
+        x.madd(y);
+        for (int c = 0; c < chain; ++c) { const XYZZ<F> z = x; x.add_inl(z); x.madd(y); }
+        ((XYZZ<F> *)out)[i] = x.normalized();
+    } else if constexpr (OP == CURVE_ADD) {
+        XYZZ<F> x = ((const XYZZ<F> *)a)[i]; const XYZZ<F> y = ((const XYZZ<F> *)b)[i];
+        x.add_inl(y);
+        for (int c = 0; c < chain; ++c) { const XYZZ<F> z = x; x.add_inl(z); x.add_inl(y); }
+        ((XYZZ<F> *)out)[i] = x.normalized();
+    } else if constexpr (OP == CURVE_ADD_QUAD) {
+        const uint32_t q = threadIdx.x & 3;
+        XYZZ<F> x = ((const XYZZ<F> *)a)[i]; const XYZZ<F> y = ((const XYZZ<F> *)b)[i];
+        xyzz_add_quad<F>(x, y, q);
+        for (int c = 0; c < chain; ++c) { const XYZZ<F> z = x; xyzz_add_quad<F>(x, z, q); xyzz_add_quad<F>(x, y, q); }
+        ((XYZZ<F> *)out)[4 * i + q] = x.normalized();                         // every lane's copy: the caller checks that the four agree
+    } else if constexpr (OP == CURVE_DBL) {
+        ((XYZZ<F> *)out)[i] = ((const XYZZ<F> *)a)[i].dbl_inl().normalized();
+    } else if constexpr (OP == CURVE_DBL_AFFINE) {
+        ((XYZZ<F> *)out)[i] = XYZZ<F>::dbl_affine_inl(((const Affine<F> *)a)[i]).normalized();
+    } else if constexpr (OP == CURVE_TO_AFFINE) {
+        ((Affine<F> *)out)[i] = ((const XYZZ<F> *)a)[i].to_affine().normalized();
+    } else {
+        uint32_t s[8];
+        for (int j = 0; j < 8; ++j) s[j] = k[8 * i + j];
+        ((XYZZ<F> *)out)[i] = ((const XYZZ<F> *)a)[i].mul(s, 8).normalized();
+    }
+}
+template <class F, int OP> static int curve_op_run(const uint32_t *a, const uint32_t *b, const uint32_t *k, size_t n, int chain, uint32_t *out) {
+    const size_t a_bytes = n * (OP == CURVE_DBL_AFFINE ? sizeof(Affine<F>) : sizeof(XYZZ<F>));
+    const size_t b_bytes = OP == CURVE_MADD ? n * sizeof(Affine<F>) : OP == CURVE_ADD || OP == CURVE_ADD_QUAD ? n * sizeof(XYZZ<F>) : 0;
+    const size_t k_bytes = OP == CURVE_MUL ? n * 8 * sizeof(uint32_t) : 0;
+    const size_t out_bytes = OP == CURVE_TO_AFFINE ? n * sizeof(Affine<F>) : (OP == CURVE_ADD_QUAD ? 4 : 1) * n * sizeof(XYZZ<F>);
+    const size_t lanes = OP == CURVE_ADD_QUAD ? 4 * n : n;
+    ScopedDevBuf da, db, dk, dout;
+    if (da.reserve(a_bytes) || dout.reserve(out_bytes) || (b_bytes && db.reserve(b_bytes)) || (k_bytes && dk.reserve(k_bytes))) return ZKG_ERROR;
+    ZK_HIP(hipMemcpy(da.p, a, a_bytes, hipMemcpyHostToDevice));
+    if (b_bytes) ZK_HIP(hipMemcpy(db.p, b, b_bytes, hipMemcpyHostToDevice));
+    if (k_bytes) ZK_HIP(hipMemcpy(dk.p, k, k_bytes, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL((k_curve_op<F, OP>), dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, nullptr, (const void *)da.p, (const void *)db.p, dk.as<uint32_t>(), n, chain, dout.p);
+    if (hipGetLastError() != hipSuccess) { set_error("zkg_curve_op: launch failed"); return ZKG_ERROR; }
+    ZK_HIP(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
+    return ZKG_OK;
+}
+template <class F> static int curve_op_group(int op, const uint32_t *a, const uint32_t *b, const uint32_t *k, size_t n, int chain, uint32_t *out) {
+    switch (op) {
+    case CURVE_MADD: return curve_op_run<F, CURVE_MADD>(a, b, k, n, chain, out);
+    case CURVE_ADD: return curve_op_run<F, CURVE_ADD>(a, b, k, n, chain, out);
+    case CURVE_ADD_QUAD: return curve_op_run<F, CURVE_ADD_QUAD>(a, b, k, n, chain, out);
+    case CURVE_DBL: return curve_op_run<F, CURVE_DBL>(a, b, k, n, chain, out);
+    case CURVE_DBL_AFFINE: return curve_op_run<F, CURVE_DBL_AFFINE>(a, b, k, n, chain, out);
+    case CURVE_TO_AFFINE: return curve_op_run<F, CURVE_TO_AFFINE>(a, b, k, n, chain, out);
+    default: return curve_op_run<F, CURVE_MUL>(a, b, k, n, chain, out);
+    }
 }
 static void kernels_configure() { (void)ntt_configure(); (void)msm_configure(); }
 
@@ -805,6 +890,15 @@ int zkg_g2_sum(const uint64_t *points_jac, size_t count, uint64_t out_jac[24]) {
     return ZKG_OK;
 }
 
+int zkg_curve_op(int group, int op, const uint32_t *a, const uint32_t *b, const uint32_t *k, size_t n, int chain, uint32_t *out) {
+    REQUIRE_INIT();
+    const bool binary = op == CURVE_MADD || op == CURVE_ADD || op == CURVE_ADD_QUAD;
+    if (group < 0 || group > 1 || op < 0 || op >= CURVE_OPS || !a || !out || (binary && !b) || (op == CURVE_MUL && !k) || n > ((size_t)1 << 20) ||
+        chain < 0 || chain > 64 || (chain && !binary)) { set_error("zkg_curve_op: bad argument"); return ZKG_ERROR; }
+    if (!n) return ZKG_OK;
+    return group == 0 ? curve_op_group<Fq>(op, a, b, k, n, chain, out) : curve_op_group<Fq2>(op, a, b, k, n, chain, out);
+}
+
 int zkg_g1_fixed_base_dev(const uint64_t base[8], const void *d_scalars, size_t n, void *d_out_affine, void *stream) {
     REQUIRE_INIT();
     G1Affine b; memcpy(&b, base, 64);
@@ -818,7 +912,8 @@ int zkg_g2_fixed_base_dev(const uint64_t base[16], const void *d_scalars, size_t
 
 int zkg_field_op(int field, int op, const uint64_t *a, const uint64_t *b, size_t n, uint64_t *out) {
     REQUIRE_INIT();
-    const bool binary = (op >= 0 && op <= 2) || (op >= 10 && op <= 14 && field == 0), known = binary || op == 3 || op == 6 || op == 7 || (op == 15 && field == 0) || ((op == 4 || op == 5) && field != 2);
+    const bool binary = (op >= 0 && op <= 2) || (op >= 10 && op <= 14 && field == 0) || (op >= 20 && op <= 22) || op == 31 || (op >= 40 && op <= 42);
+    const bool known = binary || op == 3 || (op >= 6 && op <= 8) || (op == 15 && field == 0) || ((op == 4 || op == 5) && field != 2) || (op >= 26 && op <= 28) || op == 30;
     if (!known || field < 0 || field > 2 || !a || !out || (binary && !b)) { set_error("zkg_field_op: bad argument"); return ZKG_ERROR; }
     if (!n) return ZKG_OK;
     if (field == 0) return field_op_run<Fq>(op, a, binary ? b : nullptr, n, out);
