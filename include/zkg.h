@@ -113,6 +113,44 @@ int zkg_evaluation_domain_size(size_t min_size, size_t *m, int *is_step);
 int zkg_ntt_domain(uint64_t *a, size_t m, int inverse, int coset);
 int zkg_ntt_domain_dev(void *d_a, size_t m, int inverse, int coset, void *stream);
 
+/* ---- One evaluation domain as a handle: many transforms per call and the Lagrange coefficients, on the caller's stream.
+ *      zkg_domain_new(m): m as zkg_ntt_domain takes it (2^k, k <= 28, or 2^a + 2^b; m >= 2).  The handle lives on the calling thread's device,
+ *      which must be the zkg_init device (the twiddle and coset tables are the process-wide ones zkg_ntt* use; they are built here if they
+ *      are not there yet).  NULL on failure, with zkg_last_error set.  zkg_domain_free waits for the handle's pending work; NULL is accepted.
+ *      zkg_domain_size: m (0 for NULL).
+ *      zkg_domain_ntt_async: `count` in-place transforms.  Vector i is m Fr elements, Montgomery, at d_a + i * stride * 32 bytes, stride >= m,
+ *      the base aligned to 16 bytes; what lies between m and the stride is never read or written.  inverse / coset as in zkg_ntt_domain.
+ *      Once the work has run every vector holds exactly what zkg_ntt_domain_dev writes for that vector alone, bit for bit (the same kernels,
+ *      with the vectors of a group in grid.y).  The vectors are cut into groups of at most zkg_domain_batch_max, one launch sequence each;
+ *      the default is min(65535, 1 GiB / (m * 40 bytes)), at least 1.
+ *      Ordering: the kernels are queued on `stream` (NULL: the null stream) behind everything already there, and the call does not wait on
+ *      the host: synchronise `stream` before the host reads the result.  A handle serves its calls in call order whatever streams they name:
+ *      each call leaves the handle's event behind its last kernel (that launch carries it as its completion), and a later call on another
+ *      stream makes that stream wait for it first — this is what keeps two streams out of the handle's one scratch buffer.  The handle owns that inter-pass scratch (40 bytes per element of a
+ *      group, packed whatever the stride); it only grows.  A call that needs more of it waits for the handle's event, reallocates and counts
+ *      one host wait; a call at a group size the handle has served neither waits nor allocates.
+ *      Refused with ZKG_ERROR before any launch, nothing written: a null handle or pointer; stride < m; more than 2^24 vectors or a stride
+ *      above 2^32 elements; a calling thread whose current device is not the handle's; a pointer that hipPointerGetAttributes does not
+ *      report as device memory of that device (pinned, managed and unregistered host memory are all refused), that is misaligned, or whose
+ *      range runs past the end of its allocation where hipMemGetAddressRange knows it.  count == 0 is ZKG_OK and touches nothing.
+ *      zkg_domain_lagrange_async: libfqfft evaluate_all_lagrange_polynomials(t) into d_u (DEVICE, m Fr) and, where d_z is not NULL,
+ *      compute_vanishing_polynomial(t) into d_z (DEVICE, one Fr): fully reduced Montgomery limbs, the values the key generator's host loop
+ *      computes, from one kernel (Montgomery's trick per lane over a run of consecutive elements).  t: Montgomery Fr in HOST memory, read
+ *      during the call.  Z(t) is computed on the host first: for a domain point (Z(t) = 0) the call is ZKG_ERROR before any launch.
+ *      Ordering and refusals as above; the call makes no host wait.                                                                       */
+typedef struct zkg_domain zkg_domain;
+zkg_domain *zkg_domain_new(size_t m);
+void   zkg_domain_free(zkg_domain *d);
+size_t zkg_domain_size(const zkg_domain *d);
+size_t zkg_domain_batch_max(const zkg_domain *d);   /* vectors one launch sequence takes; >= 1, 0 for NULL */
+void   zkg_domain_set_batch_max(zkg_domain *d, size_t k);   /* test hook: k vectors per launch sequence from now on; 0 restores the default, a larger k is clamped to it */
+int zkg_domain_ntt_async(zkg_domain *d, void *d_a, size_t stride /* Fr elements between vectors, >= m */, size_t count,
+                         int inverse, int coset, void *stream);
+int zkg_domain_lagrange_async(zkg_domain *d, const uint64_t t[4], void *d_u, void *d_z, void *stream);
+/* test hook: the calling thread's last zkg_domain_ntt_async — out[0] vectors enqueued, out[1] launch groups, out[2] host waits the entry
+ * made.  Counters, not clocks.                                                                                                           */
+void zkg_domain_stats(size_t out[3]);
+
 /* ---- MSM: libff::multi_exp<G1,Fr,multi_exp_method_BDLO12> and
  *      multi_exp_with_mixed_addition (A/H/L queries), and the G2 half of
  *      kc_multi_exp_with_mixed_addition (B query); reached from snark.cpp:126.

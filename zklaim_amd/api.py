@@ -35,6 +35,8 @@ DECLARED_SYMBOLS = [
     "zkg_fq12_op", "zkg_point_decompress", "zkg_point_compress",
     "zkg_zklaim_verify_each", "zkg_zklaim_verify_each_stats", "zkg_zklaim_ic_each",
     "zkg_curve_op",
+    "zkg_domain_new", "zkg_domain_free", "zkg_domain_size", "zkg_domain_batch_max", "zkg_domain_set_batch_max", "zkg_domain_ntt_async",
+    "zkg_domain_lagrange_async", "zkg_domain_stats",
 ]
 # the reference's own seam, exported with its original names (zklaim.h:257-259)
 COMPAT_SYMBOLS = ["libsnark_trusted_setup", "libsnark_prove", "libsnark_verify"]
@@ -254,6 +256,60 @@ def evaluation_domain_size(min_size):
 
 def ntt_dev(d_ptr, logn, inverse=False, coset=False, stream=0):
     _check(lib().zkg_ntt_dev(_vp(d_ptr), C.c_uint(logn), int(inverse), int(coset), _vp(stream)), "zkg_ntt_dev")
+
+
+class Domain:
+    """zkg_domain: the evaluation domain of size m (2^k or 2^a + 2^b) as a handle — batched transforms and the Lagrange coefficients on
+    device memory, queued on the caller's stream without a wait on the host"""
+
+    def __init__(self, m):
+        L = lib()
+        L.zkg_domain_new.restype = C.c_void_p
+        L.zkg_domain_new.argtypes = [C.c_size_t]
+        L.zkg_domain_free.argtypes = [C.c_void_p]
+        for name in ("zkg_domain_size", "zkg_domain_batch_max"):
+            getattr(L, name).restype = C.c_size_t
+            getattr(L, name).argtypes = [C.c_void_p]
+        L.zkg_domain_set_batch_max.argtypes = [C.c_void_p, C.c_size_t]
+        L.zkg_domain_ntt_async.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
+        L.zkg_domain_lagrange_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._h = L.zkg_domain_new(C.c_size_t(m))
+        if not self._h:
+            raise ZkgError("zkg_domain_new failed: " + L.zkg_last_error().decode())
+        self.m = m
+
+    def ntt_async(self, d_ptr, count=1, stride=None, inverse=False, coset=False, stream=0):
+        """zkg_domain_ntt_async: `count` in-place transforms of m Fr each, `stride` elements apart (default m), at the device address d_ptr.
+        Returns without waiting: synchronise `stream` before reading the result on the host."""
+        _check(lib().zkg_domain_ntt_async(C.c_void_p(self._h), _vp(d_ptr), C.c_size_t(self.m if stride is None else stride), C.c_size_t(count),
+                                          int(inverse), int(coset), _vp(stream)), "zkg_domain_ntt_async")
+
+    def lagrange_async(self, t, d_u_ptr, d_z_ptr=0, stream=0):
+        """zkg_domain_lagrange_async: t (4 Montgomery limbs, host) -> evaluate_all_lagrange_polynomials(t) at the device address d_u_ptr
+        (m Fr) and, if d_z_ptr is given, Z(t) there (one Fr)"""
+        t = _u64(t).reshape(4)
+        _check(lib().zkg_domain_lagrange_async(C.c_void_p(self._h), _p(t), _vp(d_u_ptr), _vp(d_z_ptr), _vp(stream)), "zkg_domain_lagrange_async")
+
+    def batch_max(self):
+        return int(lib().zkg_domain_batch_max(C.c_void_p(self._h)))
+
+    def set_batch_max(self, k):
+        """test hook: k vectors per launch sequence from now on (0: the default; a larger k is clamped to it)"""
+        lib().zkg_domain_set_batch_max(C.c_void_p(self._h), C.c_size_t(k))
+
+    def size(self):
+        return int(lib().zkg_domain_size(C.c_void_p(self._h)))
+
+    def free(self):
+        if self._h:
+            lib().zkg_domain_free(C.c_void_p(self._h)); self._h = None
+
+
+def domain_stats():
+    """(vectors, launch groups, host waits) of the calling thread's last Domain.ntt_async"""
+    out = (C.c_size_t * 3)()
+    lib().zkg_domain_stats(out)
+    return tuple(int(v) for v in out)
 
 
 # ---- MSM (libff multi_exp / multi_exp_with_mixed_addition) -----------------------------------------

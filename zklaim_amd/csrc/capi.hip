@@ -493,6 +493,20 @@ int dev_range_refused(const void *d, size_t bytes, size_t align, int device, con
     if (at_d < lo || at_d - lo > size || bytes > size - (at_d - lo)) return refuse("runs past the end of its allocation");
     return ZKG_OK;
 }
+// the rules the *_async entries share (zkg_msm_g1_resident_async, zkg_domain_*_async): the caller is on the handle's device (`made`: "the
+// bases were uploaded on"), and `count` vectors of n elements lie `stride` elements apart
+static int wrong_device_refused(const char *who, int device, const char *made) {
+    int cur = -1;
+    if (hipGetDevice(&cur) == hipSuccess && cur == device) return ZKG_OK;
+    (void)hipGetLastError();
+    set_error(std::string(who) + ": the calling thread's device is not the one " + made);
+    return ZKG_ERROR;
+}
+static int async_vectors_refused(const char *who, size_t n, const char *n_name, size_t stride, size_t count, int device, const char *made) {
+    if (stride < n) { set_error(std::string(who) + ": stride must be at least " + n_name); return ZKG_ERROR; }
+    if (count > ZKG_MSM_ASYNC_MAX_COUNT || stride > ZKG_MSM_ASYNC_MAX_STRIDE) { set_error(std::string(who) + ": at most 2^24 vectors, at most 2^32 elements apart"); return ZKG_ERROR; }
+    return wrong_device_refused(who, device, made);
+}
 // ---- the 32-bit device group law of curve.hip.hpp, element-wise (the known-answer hook behind zkg_curve_op): RAW records in, exactly as the
 //      device structs lay them out and with no load_norm or normalized() before the operation, so a caller can place any representative
 //      below 2p in any coordinate (ZZ != 1, infinity as ZZ = p, the affine infinity as x = y = p).  Results leave through normalized().
@@ -666,6 +680,126 @@ int zkg_ntt_domain(uint64_t *a, size_t m, int inverse, int coset) {
     return rc;
 }
 
+// ---- zkg_domain: one evaluation domain as a handle — batched transforms and the Lagrange coefficients, queued on the caller's stream with no
+//      wait on the host (include/zkg.h).  The twiddle and coset tables are the shared ones of ntt_domain / step_domain; the handle owns the
+//      inter-pass scratch of its batches (packed: m records per vector of a group, however far apart the vectors lie) and one event.
+static constexpr size_t DOMAIN_WORKSPACE_CAP = (size_t)1 << 30;          // the scratch of one launch group stays below this (one vector is always taken)
+static constexpr size_t DOMAIN_MAX_GROUP = 65535;                        // grid.y
+struct zkg_domain {
+    DomainShape sh; int device = 0; std::mutex mu;
+    DevBuf scratch;
+    hipEvent_t ev = nullptr; bool pending = false; hipStream_t last = nullptr;   // behind the last call's last kernel, on the stream it named
+    size_t bmax_default = 1, bmax = 1;
+};
+static thread_local size_t t_domain_stats[3];
+// A handle serves its calls in call order whatever streams they name: a call on another stream than the last one's waits (on the device) for
+// the last call's event before anything of its own — that is what keeps two streams out of the one scratch buffer.
+static int domain_order_behind(zkg_domain *d, hipStream_t s) {
+    if (d->pending && s != d->last) ZK_HIP(hipStreamWaitEvent(s, d->ev, 0));
+    return ZKG_OK;
+}
+// The event of a call: its last launch carries d->ev as its completion (ZK_LAUNCH_DONE, ntt.hip).  Behind a lone transform that costs 2.0 us of
+// device time where a hipEventRecord behind the kernel costs 2.9 and no event nothing (profiles/ntt_batch_time.json, "event_cost"); a
+// device-scope release (hipEventReleaseToDevice) changes neither.  domain_mark records it the plain way where a call failed after it had
+// enqueued something.
+static void domain_marked(zkg_domain *d, hipStream_t s) { d->pending = true; d->last = s; }
+static int domain_mark(zkg_domain *d, hipStream_t s) {
+    ZK_HIP(hipEventRecord(d->ev, s));
+    domain_marked(d, s);
+    return ZKG_OK;
+}
+static zkg_domain *domain_new_impl(size_t m) {
+    if (g_device < 0) { set_error("zkg_init not called"); return nullptr; }
+    DomainShape sh;
+    if (m < 2 || !domain_shape_of(m, sh)) { set_error("zkg_domain_new: m is neither 2^k (k <= 28) nor 2^a + 2^b (get_evaluation_domain would not return it)"); return nullptr; }
+    if (wrong_device_refused("zkg_domain_new", g_device, "zkg_init selected (the domain tables live there)")) return nullptr;
+    std::unique_ptr<zkg_domain> d(new zkg_domain());
+    d->sh = sh; d->device = g_device;
+    d->bmax_default = d->bmax = std::max<size_t>(1, std::min(DOMAIN_MAX_GROUP, DOMAIN_WORKSPACE_CAP / (m * NTT_SCRATCH_BYTES)));
+    // the tables are built here, on the null stream, and waited for: no later call finds them missing or half made
+    const bool tables = sh.step ? step_domain(m, nullptr) != nullptr : ntt_domain(sh.log_m, nullptr) != nullptr;
+    if (!tables || !hip_ok(hipStreamSynchronize(nullptr), "hipStreamSynchronize", __FILE__, __LINE__) ||
+        !hip_ok(hipEventCreateWithFlags(&d->ev, hipEventDisableTiming), "hipEventCreate", __FILE__, __LINE__)) return nullptr;
+    return d.release();
+}
+static int domain_ntt_async_impl(zkg_domain *d, void *d_a, size_t stride, size_t count, int inverse, int coset, void *stream) {
+    static const char *who = "zkg_domain_ntt_async";
+    for (size_t &v : t_domain_stats) v = 0;
+    if (count == 0) return ZKG_OK;                                      // nothing to do, nothing touched
+    REQUIRE_INIT();
+    if (!d || !d_a) { set_error(std::string(who) + ": bad argument (null handle or pointer)"); return ZKG_ERROR; }
+    const size_t m = d->sh.m;
+    if (async_vectors_refused(who, m, "m", stride, count, d->device, "the handle was made on") ||
+        dev_range_refused(d_a, ((count - 1) * stride + m) * 32, 16, d->device, who, "d_a", "handle")) return ZKG_ERROR;
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk(d->mu);                              // held for the enqueue only
+    NttDomain *nd = nullptr; StepDomain *sd = nullptr;                  // looked up per call (a map find): zkg_shutdown releases them under a live handle
+    if (d->sh.step) sd = step_domain(m, s); else nd = ntt_domain(d->sh.log_m, s);
+    if (!nd && !sd) return ZKG_ERROR;
+    size_t waits = 0, groups = 0, done = 0;
+    // the scratch of the call's largest group.  Growing it frees it: earlier calls may still be in it, so the handle's event is waited for first
+    const size_t need = std::min(d->bmax, count) * m * NTT_SCRATCH_BYTES;
+    if (need > d->scratch.cap) {
+        if (d->pending) ZK_HIP(hipEventSynchronize(d->ev));
+        if (d->scratch.reserve(need)) return ZKG_ERROR;
+        ++waits;
+    }
+    if (domain_order_behind(d, s)) return ZKG_ERROR;
+    Fr *a = (Fr *)d_a;
+    int rc = ZKG_OK;
+    while (done < count && rc == ZKG_OK) {
+        const size_t g = std::min(d->bmax, count - done);
+        Fr *ag = a + done * stride;
+        const hipEvent_t ev = done + g == count ? d->ev : nullptr;      // the call's last group ends in the handle's event
+        rc = sd ? step_ntt_run(sd, ag, inverse != 0, coset != 0, s, d->scratch.as<Fr>(), (unsigned)g, stride, m, ev)
+                : ntt_run(nd, ag, inverse, coset, s, d->scratch.as<Fr>(), (unsigned)g, stride, m, ev);
+        if (rc == ZKG_OK) { done += g; ++groups; }
+    }
+    t_domain_stats[0] = done; t_domain_stats[1] = groups; t_domain_stats[2] = waits;
+    if (rc == ZKG_OK) { domain_marked(d, s); return ZKG_OK; }
+    (void)domain_mark(d, s);                                            // a failure: the groups enqueued before it still run
+    return ZKG_ERROR;
+}
+static int domain_lagrange_async_impl(zkg_domain *d, const uint64_t t[4], void *d_u, void *d_z, void *stream) {
+    static const char *who = "zkg_domain_lagrange_async";
+    REQUIRE_INIT();
+    if (!d || !t || !d_u) { set_error(std::string(who) + ": bad argument (null handle or pointer)"); return ZKG_ERROR; }
+    if (wrong_device_refused(who, d->device, "the handle was made on") || dev_range_refused(d_u, d->sh.m * 32, 16, d->device, who, "d_u", "handle") ||
+        (d_z && dev_range_refused(d_z, 32, 16, d->device, who, "d_z", "handle"))) return ZKG_ERROR;
+    Fr tf; memcpy(tf.v, t, 32);                                         // read now: the caller may reuse t on return
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk(d->mu);
+    if (domain_order_behind(d, s) || domain_lagrange_dev(d->sh, tf, (Fr *)d_u, (Fr *)d_z, s, d->ev)) return ZKG_ERROR;
+    domain_marked(d, s);
+    return ZKG_OK;
+}
+zkg_domain *zkg_domain_new(size_t m) { return c_boundary<zkg_domain *>("zkg_domain_new", nullptr, [&] { return domain_new_impl(m); }); }
+void zkg_domain_free(zkg_domain *d) {
+    if (!d) return;
+    c_boundary("zkg_domain_free", 0, [&] {
+        int cur = 0; (void)hipGetDevice(&cur);
+        if (cur != d->device) (void)hipSetDevice(d->device);           // the scratch and the event live on the handle's device
+        if (d->ev) { if (d->pending) (void)hipEventSynchronize(d->ev); (void)hipEventDestroy(d->ev); }
+        d->scratch.release();
+        if (cur != d->device) (void)hipSetDevice(cur);
+        delete d;
+        return 0;
+    });
+}
+size_t zkg_domain_size(const zkg_domain *d) { return d ? d->sh.m : 0; }
+size_t zkg_domain_batch_max(const zkg_domain *d) { return d ? d->bmax : 0; }
+void zkg_domain_set_batch_max(zkg_domain *d, size_t k) {
+    if (!d) return;
+    c_boundary("zkg_domain_set_batch_max", 0, [&] { std::lock_guard<std::mutex> lk(d->mu); d->bmax = (k == 0 || k > d->bmax_default) ? d->bmax_default : k; return 0; });
+}
+int zkg_domain_ntt_async(zkg_domain *d, void *d_a, size_t stride, size_t count, int inverse, int coset, void *stream) {
+    return c_boundary("zkg_domain_ntt_async", ZKG_ERROR, [&] { return domain_ntt_async_impl(d, d_a, stride, count, inverse, coset, stream); });
+}
+int zkg_domain_lagrange_async(zkg_domain *d, const uint64_t t[4], void *d_u, void *d_z, void *stream) {
+    return c_boundary("zkg_domain_lagrange_async", ZKG_ERROR, [&] { return domain_lagrange_async_impl(d, t, d_u, d_z, stream); });
+}
+void zkg_domain_stats(size_t out[3]) { if (out) for (int i = 0; i < 3; ++i) out[i] = t_domain_stats[i]; }
+
 int zkg_msm_g1_dev(const void *d_bases, const void *d_scalars, size_t n, int scalars_mont, uint64_t out_jac[12], void *stream) {
     REQUIRE_INIT();
     G1 r;
@@ -758,10 +892,7 @@ int zkg_msm_g1_resident_async(zkg_msm_bases *h, const void *d_scalars, size_t n,
     if (count == 0) return ZKG_OK;                                      // nothing to do, nothing touched
     REQUIRE_INIT();
     if (!h || !d_scalars || !d_out_jac || n != h->table.n) { set_error(std::string(who) + ": bad argument (n must be the handle's point count)"); return ZKG_ERROR; }
-    if (stride < n) { set_error(std::string(who) + ": stride must be at least n"); return ZKG_ERROR; }
-    if (count > ZKG_MSM_ASYNC_MAX_COUNT || stride > ZKG_MSM_ASYNC_MAX_STRIDE) { set_error(std::string(who) + ": at most 2^24 vectors, at most 2^32 elements apart"); return ZKG_ERROR; }
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != h->device) { (void)hipGetLastError(); set_error(std::string(who) + ": the calling thread's device is not the one the bases were uploaded on"); return ZKG_ERROR; }
+    if (async_vectors_refused(who, n, "n", stride, count, h->device, "the bases were uploaded on")) return ZKG_ERROR;
     if (dev_range_refused(d_scalars, ((count - 1) * stride + n) * 32, 16, h->device, who, "d_scalars", "handle") ||
         dev_range_refused(d_out_jac, count * 96, 8, h->device, who, "d_out_jac", "handle")) return ZKG_ERROR;
     const size_t bmax = zkg_msm_g1_resident_batch_max(h);

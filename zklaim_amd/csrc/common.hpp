@@ -88,14 +88,17 @@ struct NttDomain {
 NttDomain *ntt_domain(unsigned logn, hipStream_t s);     // cached per size
 // mode: inverse / coset as in zkg_ntt.  extra_post (device, N Fr, optional) replaces the default
 // post table: the prover fuses iFFT's 1/N with the following cosetFFT's g^i through it.
-int ntt_run(NttDomain *d, Fr *d_a, int inverse, int coset, hipStream_t s);
+int ntt_run(NttDomain *d, Fr *d_a, int inverse, int coset, hipStream_t s, Fr *scratch = nullptr, unsigned batch = 1, size_t batch_stride = 0,
+            size_t scratch_stride = 0, hipEvent_t done = nullptr);      // the batch arguments of ntt_run_ex (below)
 // batch > 1: `batch` vectors, batch_stride elements apart (0 = N: back to back) in d_a and in `scratch` (which must then be given),
 // one launch per pass
 // pre29 / post29: the 29-bit twins of a caller's own pre / post table (ntt_table29); without them such a call takes the 32-bit pass.
-// A caller's scratch holds 40 bytes per element (NTT_SCRATCH_BYTES).
+// A caller's scratch holds 40 bytes per element (NTT_SCRATCH_BYTES).  scratch_stride (0 = batch_stride): elements between the vectors' areas in
+// `scratch`, for vectors that lie further apart than their scratch has to.  done (optional): an event that completes with the transform's
+// last kernel, carried by that launch itself (cheaper on the device than a record behind it).
 static constexpr size_t NTT_SCRATCH_BYTES = 40;
 int ntt_run_ex(NttDomain *d, Fr *d_a, bool inverse, const Fr *pre, const Fr *post, const Fr *post_scalar, hipStream_t s, Fr *scratch = nullptr,
-               unsigned batch = 1, size_t batch_stride = 0, const void *pre29 = nullptr, const void *post29 = nullptr);
+               unsigned batch = 1, size_t batch_stride = 0, const void *pre29 = nullptr, const void *post29 = nullptr, size_t scratch_stride = 0, hipEvent_t done = nullptr);
 int ntt_table29(DevBuf &out, const Fr *d_in, size_t n, hipStream_t s);       // a table in libff's form -> its 29-bit records
 
 // libfqfft get_evaluation_domain(min_size) for min_size <= 2^28: basic_radix2_domain (m = 2^k) or step_radix2_domain (m = big + small,
@@ -106,6 +109,9 @@ bool domain_shape_of(size_t m, DomainShape &d);           // m must be a size th
 Fr fr_root_of_unity_pow2(unsigned logn);                  // libff::get_root_of_unity(2^logn)
 // evaluate_all_lagrange_polynomials(t) and compute_vanishing_polynomial(t) of the domain (host, one batched inversion)
 int domain_lagrange(const DomainShape &d, const Fr &t, std::vector<Fr> &u, Fr &Zt);
+// the same values from one kernel queued on s (k_lagrange): d_u (device, m Fr) and, if given, d_z (device, one Fr), canonical limbs.  Z(t) is
+// computed on the host first: ZKG_ERROR before any launch when t is a domain point.  No host wait once the domain's tables exist.
+int domain_lagrange_dev(const DomainShape &d, const Fr &t, Fr *d_u, Fr *d_z, hipStream_t s, hipEvent_t done = nullptr);   // done: as in ntt_run_ex
 
 // step_radix2_domain on the device: FFT = fold (mod x^big - 1 | x -> omega x, mod x^small - 1) + one radix-2 transform of each size
 struct StepDomain {
@@ -121,8 +127,9 @@ struct StepDomain {
     void release();
 };
 StepDomain *step_domain(size_t m, hipStream_t s);         // cached per size
-// a: batch vectors of m elements, batch_stride apart; scratch: same shape
-int step_ntt_run(StepDomain *d, Fr *d_a, bool inverse, bool coset, hipStream_t s, Fr *scratch, unsigned batch = 1, size_t batch_stride = 0);
+// a: batch vectors of m elements, batch_stride apart; scratch: same shape, or scratch_stride (>= m) elements of 40 bytes apart when given
+int step_ntt_run(StepDomain *d, Fr *d_a, bool inverse, bool coset, hipStream_t s, Fr *scratch, unsigned batch = 1, size_t batch_stride = 0,
+                 size_t scratch_stride = 0, hipEvent_t done = nullptr);
 int powers_table(Fr *d_out, size_t n, const Fr &base, const Fr &scale, hipStream_t s);   // out[i] = scale * base^i
 void ntt_release_all();
 int ntt_configure();

@@ -15,6 +15,7 @@
 #include "common.hpp"
 #include "fr29.hip.hpp"
 #include "../../include/zkg.h"
+#include <hip/hip_ext.h>
 #include <algorithm>
 #include <cstdlib>
 #include <map>
@@ -34,6 +35,15 @@ struct NttPassArgs {
     uint32_t n_log, s0, R, cw_log, first, has_post_scalar;
     size_t src_batch_stride, dst_batch_stride;      // elements between the vectors of a batch (blockIdx.y)
 };
+
+// A launch whose completion is the event `done` (null: a plain launch).  The event rides on the kernel's own completion signal: 2.0 us of
+// device time behind a lone transform, where a hipEventRecord behind the kernel, a packet of its own, costs 2.9 (profiles/ntt_batch_time.json,
+// "event_cost").  zkg_domain marks the last kernel of a call this way.
+#define ZK_LAUNCH_DONE(done, kernel, grid, block, lds, s, ...)                                                                      \
+    do {                                                                                                                            \
+        if (done) hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)(lds), s, nullptr, done, 0, __VA_ARGS__);                    \
+        else hipLaunchKernelGGL(kernel, grid, block, lds, s, __VA_ARGS__);                                                          \
+    } while (0)
 
 ZK_D uint32_t bitrev(uint32_t x, uint32_t bits) { return bits ? (__brev(x) >> (32 - bits)) : 0; }
 
@@ -357,7 +367,7 @@ void ntt_release_all() {
 }
 
 int ntt_run_ex(NttDomain *d, Fr *d_a, bool inverse, const Fr *pre, const Fr *post, const Fr *post_scalar, hipStream_t s, Fr *scratch, unsigned batch, size_t batch_stride,
-               const void *pre29, const void *post29) {
+               const void *pre29, const void *post29, size_t scratch_stride, hipEvent_t done) {
     const unsigned n = d->logn;
     if (n == 0) return ZKG_OK;                 // N = 1: every variant is the identity (g^0 = 1, 1/N = 1)
     if (batch > 1 && !scratch) { set_error("ntt: a batched transform needs its own scratch"); return ZKG_ERROR; }
@@ -383,6 +393,7 @@ int ntt_run_ex(NttDomain *d, Fr *d_a, bool inverse, const Fr *pre, const Fr *pos
     unsigned s0 = 0;
     for (unsigned p = 0; p < npass; ++p) {
         unsigned R = base + (p < extra ? 1 : 0);
+        const hipEvent_t ev = (p == npass - 1) ? done : nullptr;      // the transform's last launch carries the caller's event
         NttPassArgs A;
         A.first = (p == 0);
         A.src = (p == 0) ? d_a : tmp;
@@ -393,7 +404,9 @@ int ntt_run_ex(NttDomain *d, Fr *d_a, bool inverse, const Fr *pre, const Fr *pos
         A.has_post_scalar = (p == npass - 1 && post_scalar && !post) ? 1 : 0;
         A.post_scalar = A.has_post_scalar ? *post_scalar : Fr::zero();
         A.n_log = n; A.s0 = s0; A.R = R;
-        A.src_batch_stride = A.dst_batch_stride = batch_stride ? batch_stride : N;     // vectors and their scratch share one layout
+        // vectors and their scratch share one layout, unless the caller packs the scratch (scratch_stride: zkg_domain's vectors may lie far apart)
+        const size_t vec_stride = batch_stride ? batch_stride : N, tmp_stride = scratch_stride ? scratch_stride : vec_stride;
+        A.src_batch_stride = (p == 0) ? vec_stride : tmp_stride; A.dst_batch_stride = (p == npass - 1) ? vec_stride : tmp_stride;
         unsigned cols_log = n - R;                                   // columns in total
         const unsigned room = (unsigned)NTT_TILE_LOG > R ? (unsigned)NTT_TILE_LOG - R : 0u;   // (a forced tile smaller than 2^R rows: one column per tile)
         A.cw_log = cols_log < room ? cols_log : room;
@@ -430,21 +443,21 @@ int ntt_run_ex(NttDomain *d, Fr *d_a, bool inverse, const Fr *pre, const Fr *pos
             static const int radix_force = getenv("ZKG_NTT_RADIX2") ? (atoi(getenv("ZKG_NTT_RADIX2")) ? 2 : 4) : 0;          // A/B switch
             if (radix_force ? radix_force == 4 : large) {
                 const unsigned threads4 = (unsigned)std::min<size_t>(256, std::max<size_t>(64, rows * CW / 4));             // one thread per four rows of a column
-                hipLaunchKernelGGL(k_ntt_pass29_r4, dim3((unsigned)tiles, batch), dim3(threads4), rows * (CW + pad29) * sizeof(Rec29), s, B);
+                ZK_LAUNCH_DONE(ev, k_ntt_pass29_r4, dim3((unsigned)tiles, batch), dim3(threads4), rows * (CW + pad29) * sizeof(Rec29), s, B);
             } else
-            hipLaunchKernelGGL(k_ntt_pass29, dim3((unsigned)tiles, batch), dim3(threads), rows * (CW + pad29) * sizeof(Rec29), s, B);
+            ZK_LAUNCH_DONE(ev, k_ntt_pass29, dim3((unsigned)tiles, batch), dim3(threads), rows * (CW + pad29) * sizeof(Rec29), s, B);
         } else
-        hipLaunchKernelGGL(k_ntt_pass, dim3((unsigned)tiles, batch), dim3(threads), lds, s, A);
+        ZK_LAUNCH_DONE(ev, k_ntt_pass, dim3((unsigned)tiles, batch), dim3(threads), lds, s, A);
         if (hipGetLastError() != hipSuccess) { set_error("ntt pass launch failed"); return ZKG_ERROR; }
         s0 += R;
     }
     return ZKG_OK;
 }
 
-int ntt_run(NttDomain *d, Fr *d_a, int inverse, int coset, hipStream_t s) {
-    if (!inverse) return ntt_run_ex(d, d_a, false, coset ? d->coset_pre.as<Fr>() : nullptr, nullptr, nullptr, s);
-    if (coset) return ntt_run_ex(d, d_a, true, nullptr, d->icoset_post.as<Fr>(), nullptr, s);
-    return ntt_run_ex(d, d_a, true, nullptr, nullptr, &d->n_inv, s);
+int ntt_run(NttDomain *d, Fr *d_a, int inverse, int coset, hipStream_t s, Fr *scratch, unsigned batch, size_t batch_stride, size_t scratch_stride, hipEvent_t done) {
+    if (!inverse) return ntt_run_ex(d, d_a, false, coset ? d->coset_pre.as<Fr>() : nullptr, nullptr, nullptr, s, scratch, batch, batch_stride, nullptr, nullptr, scratch_stride, done);
+    if (coset) return ntt_run_ex(d, d_a, true, nullptr, d->icoset_post.as<Fr>(), nullptr, s, scratch, batch, batch_stride, nullptr, nullptr, scratch_stride, done);
+    return ntt_run_ex(d, d_a, true, nullptr, nullptr, &d->n_inv, s, scratch, batch, batch_stride, nullptr, nullptr, scratch_stride, done);
 }
 
 
@@ -499,32 +512,43 @@ template <class Fn> static void chunked(size_t n, Fn f) {
     if (chunks <= 1) { f((size_t)0, n); return; }
     host_parallel_for(chunks, [&](int c) { f(n * (size_t)c / chunks, n * (size_t)(c + 1) / chunks); });
 }
+// the constants of those forms for one t (a handful of squarings on the host), shared by the host loops and the device kernel.  basic: num =
+// Z(t), bf = m, the rest unused
+struct LagrangeConsts { Fr Zt, num, bf, omega_s, tp, L1num, L1s; };
+static LagrangeConsts lagrange_consts(const DomainShape &d, const Fr &t) {
+    LagrangeConsts c;
+    c.omega_s = c.tp = c.L1num = c.L1s = Fr::zero();
+    if (!d.step) { c.Zt = c.num = t.pow_u64(d.m) - Fr::one(); c.bf = Fr::from_u64(d.m); return c; }
+    const Fr omega = fr_root_of_unity_pow2(d.log_m);
+    c.omega_s = omega.pow_u64(d.small);
+    const Fr Zb = t.pow_u64(d.big) - Fr::one(), L0 = t.pow_u64(d.small) - c.omega_s;
+    c.Zt = c.num = Zb * L0; c.bf = Fr::from_u64(d.big);
+    c.tp = t * omega.inverse();
+    const Fr Zs = c.tp.pow_u64(d.small) - Fr::one();
+    c.L1num = Zb * Zs; c.L1s = (omega.pow_u64(d.big) - Fr::one()) * Fr::from_u64(d.small);
+    return c;
+}
 int domain_lagrange(const DomainShape &d, const Fr &t, std::vector<Fr> &u, Fr &Zt) {
     const size_t m = d.m;
     u.assign(m, Fr::zero());
     std::vector<Fr> den(m);
+    const LagrangeConsts K = lagrange_consts(d, t);
+    Zt = K.Zt;
     if (!d.step) {
-        Fr omega = fr_root_of_unity_pow2(d.log_m), wi = Fr::one(), mf = Fr::from_u64(m);
-        Zt = t.pow_u64(m) - Fr::one();
-        (void)wi;
+        const Fr omega = fr_root_of_unity_pow2(d.log_m), mf = K.bf;
         chunked(m, [&](size_t lo, size_t hi) {                                             // each chunk restarts the running power at omega^lo
             Fr w = omega.pow_u64(lo);
             for (size_t i = lo; i < hi; ++i) { u[i] = Zt * w; den[i] = mf * (t - w); w = w * omega; }
         });
     } else {
         const size_t big = d.big, small = d.small;
-        Fr omega = fr_root_of_unity_pow2(d.log_m), wb = omega.sqr(), ws = fr_root_of_unity_pow2(ceil_log2(small));
-        Fr omega_s = omega.pow_u64(small), Zb = t.pow_u64(big) - Fr::one(), L0 = t.pow_u64(small) - omega_s;
-        Zt = Zb * L0;
-        Fr wbs = wb.pow_u64(small), wi = Fr::one(), elt = Fr::one(), bf = Fr::from_u64(big), num = Zb * L0;
-        (void)wi; (void)elt;
+        const Fr omega = fr_root_of_unity_pow2(d.log_m), wb = omega.sqr(), ws = fr_root_of_unity_pow2(ceil_log2(small));
+        const Fr omega_s = K.omega_s, wbs = wb.pow_u64(small), bf = K.bf, num = K.num;
         chunked(big, [&](size_t lo, size_t hi) {
             Fr w = wb.pow_u64(lo), e = wbs.pow_u64(lo);
             for (size_t i = lo; i < hi; ++i) { u[i] = num * w; den[i] = bf * (t - w) * (e - omega_s); w = w * wb; e = e * wbs; }
         });
-        Fr tp = t * omega.inverse(), Zs = tp.pow_u64(small) - Fr::one(), sf = Fr::from_u64(small);
-        Fr L1num = Zb * Zs, L1den = omega.pow_u64(big) - Fr::one();
-        const Fr L1s = L1den * sf;
+        const Fr tp = K.tp, L1num = K.L1num, L1s = K.L1s;
         chunked(small, [&](size_t lo, size_t hi) {
             Fr w = ws.pow_u64(lo);
             for (size_t i = lo; i < hi; ++i) { u[big + i] = L1num * w; den[big + i] = L1s * (tp - w); w = w * ws; }
@@ -532,6 +556,73 @@ int domain_lagrange(const DomainShape &d, const Fr &t, std::vector<Fr> &u, Fr &Z
     }
     if (batch_invert(den)) { set_error("domain_lagrange: t is a domain point"); return ZKG_ERROR; }
     chunked(m, [&](size_t lo, size_t hi) { for (size_t i = lo; i < hi; ++i) u[i] = u[i] * den[i]; });
+    return ZKG_OK;
+}
+
+// ---- the same closed forms on the device (zkg_domain_lagrange_async).  The powers come from the twiddle tables the domains hold: a table of
+//      order n has the first n / 2 powers, and root^(i + n/2) = -root^i.  Montgomery's trick per lane: a lane owns a run of `run` consecutive
+//      elements, leaves the prefix products of their denominators in u (its own elements: nobody else reads them), inverts the run's product once
+//      (Fermat, about 380 products, a dependent chain) and sweeps back, recomputing each denominator (two or three products and a table read) instead of
+//      holding the run in registers, so the run length is a launch argument and costs no registers.
+struct LagrangeArgs {
+    Fr *u, *z;                                  // z: optional, receives Z(t)
+    const Fr *tw_big, *tw_small;                // powers of the root of order big (i < big / 2), of order small
+    size_t m, big, small;                       // basic: big = m, small = 0
+    uint32_t run;
+    Fr t, Zt, num, bf, omega_s, tp, L1num, L1s;
+};
+ZK_D Fr root_pow(const Fr *tw, size_t n, size_t i) {                         // root^i, i < n, root of order n (a power of two)
+    const size_t half = n >> 1;
+    if (i < half || half == 0) return tw[i];                                  // (n = 1: the table's one entry is 1)
+    return tw[i - half].neg();
+}
+ZK_D void lagrange_terms(const LagrangeArgs &A, size_t i, Fr &num, Fr &den) {
+    if (i < A.big) {
+        const Fr w = root_pow(A.tw_big, A.big, i);
+        num = A.num * w; den = A.bf * (A.t - w);
+        if (A.small) den = den * (root_pow(A.tw_big, A.big, (i * A.small) & (A.big - 1)) - A.omega_s);
+    } else {
+        const Fr w = root_pow(A.tw_small, A.small, i - A.big);
+        num = A.L1num * w; den = A.L1s * (A.tp - w);
+    }
+}
+static constexpr int LAGRANGE_THREADS = 64;
+__global__ __launch_bounds__(LAGRANGE_THREADS) void k_lagrange(LagrangeArgs A) {
+    const size_t lane = (size_t)blockIdx.x * blockDim.x + threadIdx.x, lo = lane * A.run;
+    if (lane == 0 && A.z) *A.z = A.Zt;
+    if (lo >= A.m) return;
+    const size_t hi = lo + A.run < A.m ? lo + A.run : A.m;
+    Fr acc = Fr::one(), num, den;
+    for (size_t i = lo; i < hi; ++i) { lagrange_terms(A, i, num, den); A.u[i] = acc; acc = acc * den; }
+    Fr inv = acc.inverse();                                                   // no denominator is zero: the host refuses t with Z(t) = 0
+    for (size_t i = hi; i-- > lo;) {
+        lagrange_terms(A, i, num, den);
+        const Fr di = inv * A.u[i];
+        inv = inv * den;
+        A.u[i] = (num * di).normalized();
+    }
+}
+// Run length, measured at m = 2^20 (profiles/ntt_batch_time.json, tools/ntt_batch_time.py): see DESIGN section 4.  ZKG_LAGRANGE_RUN: tuning aid.
+static constexpr uint32_t LAGRANGE_RUN = 16;
+int domain_lagrange_dev(const DomainShape &sh, const Fr &t, Fr *d_u, Fr *d_z, hipStream_t s, hipEvent_t done) {
+    const LagrangeConsts K = lagrange_consts(sh, t);
+    if (K.Zt.is_zero()) { set_error("domain_lagrange: t is a domain point"); return ZKG_ERROR; }
+    static const uint32_t run_force = getenv("ZKG_LAGRANGE_RUN") ? (uint32_t)atoi(getenv("ZKG_LAGRANGE_RUN")) : 0;
+    LagrangeArgs A;
+    A.u = d_u; A.z = d_z; A.m = sh.m; A.run = run_force ? run_force : LAGRANGE_RUN;
+    A.t = t; A.Zt = K.Zt; A.num = K.num; A.bf = K.bf; A.omega_s = K.omega_s; A.tp = K.tp; A.L1num = K.L1num; A.L1s = K.L1s;
+    if (!sh.step) {
+        NttDomain *d = ntt_domain(sh.log_m, s);
+        if (!d) return ZKG_ERROR;
+        A.tw_big = d->tw_fwd.as<Fr>(); A.tw_small = nullptr; A.big = sh.m; A.small = 0;
+    } else {
+        StepDomain *d = step_domain(sh.m, s);
+        if (!d) return ZKG_ERROR;
+        A.tw_big = d->dbig->tw_fwd.as<Fr>(); A.tw_small = d->dsmall->tw_fwd.as<Fr>(); A.big = sh.big; A.small = sh.small;
+    }
+    const size_t lanes = (sh.m + A.run - 1) / A.run;
+    ZK_LAUNCH_DONE(done, k_lagrange, dim3((unsigned)((lanes + LAGRANGE_THREADS - 1) / LAGRANGE_THREADS)), dim3(LAGRANGE_THREADS), 0, s, A);
+    if (hipGetLastError() != hipSuccess) { set_error("lagrange launch failed"); return ZKG_ERROR; }
     return ZKG_OK;
 }
 
@@ -676,8 +767,9 @@ StepDomain *step_domain(size_t m, hipStream_t s) {
     return d;
 }
 
-int step_ntt_run(StepDomain *d, Fr *a, bool inverse, bool coset, hipStream_t s, Fr *scratch, unsigned batch, size_t batch_stride) {
+int step_ntt_run(StepDomain *d, Fr *a, bool inverse, bool coset, hipStream_t s, Fr *scratch, unsigned batch, size_t batch_stride, size_t scratch_stride, hipEvent_t done) {
     const size_t big = d->shape.big, small = d->shape.small, stride = batch_stride ? batch_stride : d->shape.m;
+    const size_t sstride = scratch_stride ? scratch_stride : stride;       // elements between the vectors' scratch areas (at least m)
     if (!scratch) { set_error("step ntt: scratch required"); return ZKG_ERROR; }
     StepArgs A;
     A.a = a; A.w = d->w.as<Fr>(); A.winv_half = d->winv_half.as<Fr>(); A.big = big; A.small = small; A.stride = stride;
@@ -688,16 +780,17 @@ int step_ntt_run(StepDomain *d, Fr *a, bool inverse, bool coset, hipStream_t s, 
     Fr *part = scratch;                                        // big / STEP_J elements per vector: the transforms' scratch is idle around them
     if (!inverse) {
         A.g = coset ? d->g_pow.as<Fr>() : nullptr;
-        if (chunked) { hipLaunchKernelGGL(k_step_fold_chunk, grid_ch, dim3(256), 0, s, A, part, stride); hipLaunchKernelGGL(k_step_fold_finish, grid, dim3(256), 0, s, A, part, stride); }
+        if (chunked) { hipLaunchKernelGGL(k_step_fold_chunk, grid_ch, dim3(256), 0, s, A, part, sstride); hipLaunchKernelGGL(k_step_fold_finish, grid, dim3(256), 0, s, A, part, sstride); }
         else hipLaunchKernelGGL(k_step_fold, grid, dim3(256), 0, s, A);
-        if (ntt_run_ex(d->dbig, a, false, nullptr, nullptr, nullptr, s, scratch, batch, stride)) return ZKG_ERROR;
-        if (ntt_run_ex(d->dsmall, a + big, false, nullptr, nullptr, nullptr, s, scratch + big, batch, stride)) return ZKG_ERROR;
+        // `done` goes with the last launch: the small transform's, or the big one's when small = 1 (a transform of one element launches nothing)
+        if (ntt_run_ex(d->dbig, a, false, nullptr, nullptr, nullptr, s, scratch, batch, stride, nullptr, nullptr, sstride, d->dsmall->logn ? nullptr : done)) return ZKG_ERROR;
+        if (ntt_run_ex(d->dsmall, a + big, false, nullptr, nullptr, nullptr, s, scratch + big, batch, stride, nullptr, nullptr, sstride, done)) return ZKG_ERROR;
     } else {
-        if (ntt_run_ex(d->dbig, a, true, nullptr, nullptr, &d->big_inv, s, scratch, batch, stride)) return ZKG_ERROR;
-        if (ntt_run_ex(d->dsmall, a + big, true, nullptr, nullptr, &d->small_inv, s, scratch + big, batch, stride)) return ZKG_ERROR;
+        if (ntt_run_ex(d->dbig, a, true, nullptr, nullptr, &d->big_inv, s, scratch, batch, stride, nullptr, nullptr, sstride)) return ZKG_ERROR;
+        if (ntt_run_ex(d->dsmall, a + big, true, nullptr, nullptr, &d->small_inv, s, scratch + big, batch, stride, nullptr, nullptr, sstride)) return ZKG_ERROR;
         A.g = coset ? d->ginv_pow.as<Fr>() : nullptr;
-        if (chunked) { hipLaunchKernelGGL(k_step_unfold_chunk, grid_ch, dim3(256), 0, s, A, part, stride); hipLaunchKernelGGL(k_step_unfold_finish, grid, dim3(256), 0, s, A, part, stride); }
-        else hipLaunchKernelGGL(k_step_unfold, grid, dim3(256), 0, s, A);
+        if (chunked) { hipLaunchKernelGGL(k_step_unfold_chunk, grid_ch, dim3(256), 0, s, A, part, sstride); ZK_LAUNCH_DONE(done, k_step_unfold_finish, grid, dim3(256), 0, s, A, (const Fr *)part, sstride); }
+        else ZK_LAUNCH_DONE(done, k_step_unfold, grid, dim3(256), 0, s, A);
     }
     if (hipGetLastError() != hipSuccess) { set_error("step ntt launch failed"); return ZKG_ERROR; }
     return ZKG_OK;
