@@ -214,7 +214,7 @@ void zkg_msm_g1_bases_free(zkg_msm_bases *bases);
 int zkg_msm_g1_resident_async(zkg_msm_bases *bases, const void *d_scalars, size_t n, size_t stride /* Fr elements between vectors, >= n */, size_t count,
                               int scalars_mont, void *d_out_jac /* count x 12 limbs, DEVICE */, void *stream);
 size_t zkg_msm_g1_resident_batch_max(const zkg_msm_bases *bases);   /* vectors one launch takes: what the sort's index space and bucket scan allow, at most 16 (the batched prover's largest launch; the workspace grows with it); >= 1, 0 for NULL */
-/* test hook: the calling thread's last zkg_msm_g1_resident_async — out[0] vectors enqueued, out[1] launch groups, out[2] host waits the
+/* test hook: the calling thread's last zkg_msm_g1_resident_async or zkg_msm_g2_resident_async — out[0] vectors enqueued, out[1] launch groups, out[2] host waits the
  * entry made (one per buffer it had to grow: a stream drain and an allocation; 0 where nothing grew).  Counters, not clocks.                                  */
 void zkg_msm_resident_async_stats(size_t out[3]);
 /* test hook: the epilogue kernel alone, on chunk records the caller makes up.  records_jac (HOST): vectors x cpw x slots normalised points
@@ -222,6 +222,38 @@ void zkg_msm_resident_async_stats(size_t out[3]);
  * U = T + 8 A.  out_jac (HOST): per vector V = sum U_ch + 2^chunk_log * sum ch * P_ch + sum P_ch, normalised.  This reaches geometries a
  * handle does not produce at test sizes (three slots, more chunks than the kernel has lanes).  Synchronous.                               */
 int zkg_msm_combine_gpu(const uint64_t *records_jac, size_t cpw, int slots /* 2|3 */, int chunk_log, size_t vectors, uint64_t *out_jac);
+/* The same for a fixed G2 base set (a Groth16 B query): per-window tables of n affine G2 points read from DEVICE memory (the layout
+ * zkg_msm_g2_dev takes: 16 limbs per point, all-zero = infinity), window size table_window_bits(n) — 8, 12 or 16 bits; at 16 bits 16 levels
+ * of 128 bytes per point.  1 <= n < 2^25; NULL with zkg_last_error set for a bad argument or a failed allocation.  No subgroup or on-curve
+ * check is made, as for G1.  The contract of every entry is its G1 sibling's above:
+ * zkg_msm_g2_resident: sum scalars[i] * P_i for n DEVICE scalars (n = the handle's point count), the same normalised 24 limbs as
+ * zkg_msm_g2_dev over the same bases, bit for bit.  Calls on one handle take turns, run on the handle's own stream behind everything queued
+ * on `stream` at the time of the call, and the call returns when the point is in out_jac.
+ * zkg_msm_g2_resident_async: `count` vectors, vector i at d_scalars + i * stride * 32 bytes (stride >= n, 16-byte aligned; what lies between
+ * n and the stride is never read), point i at d_out_jac + i * 24 limbs, normalised exactly as zkg_msm_g2_resident returns it: X | Y | one,
+ * or (0, one, 0) for infinity, with one = (Montgomery one, 0).  The vectors are cut into groups of at most zkg_msm_g2_resident_batch_max; a
+ * group shares one sort, accumulation, fold and reduction, and a one-workgroup kernel per point (k_msm_combine_g2) sums the reduction's chunk
+ * records and normalises on the device.  The call records an event behind its last kernel and makes `stream` wait for it; it makes no
+ * host wait at a group size the handle has served before.  A buffer that must grow is freed only after the handle's stream has drained, and
+ * each such drain is counted (zkg_msm_resident_async_stats); zkg_msm_g2_resident beside pending asynchronous calls takes the same care;
+ * zkg_msm_g2_bases_free waits for the handle's stream and may be called from any device.
+ * Refused with ZKG_ERROR before any launch, nothing written: a null argument; n other than the handle's point count; stride < n; more than
+ * 2^24 vectors or a stride above 2^32 elements; a calling thread on another device; d_scalars or d_out_jac that is not device memory of the
+ * handle's device, is misaligned (16 / 8 bytes) or runs past its allocation.  count == 0 is ZKG_OK and touches nothing.                    */
+typedef struct zkg_msm_g2_bases zkg_msm_g2_bases;
+zkg_msm_g2_bases *zkg_msm_g2_bases_upload(const void *d_bases /* DEVICE, n x 16 limbs affine Montgomery, all-zero = infinity */, size_t n);
+void   zkg_msm_g2_bases_free(zkg_msm_g2_bases *bases);
+int    zkg_msm_g2_resident(zkg_msm_g2_bases *bases, const void *d_scalars, size_t n, int scalars_mont, uint64_t out_jac[24], void *stream);
+int    zkg_msm_g2_resident_async(zkg_msm_g2_bases *bases, const void *d_scalars, size_t n, size_t stride, size_t count,
+                                 int scalars_mont, void *d_out_jac /* count x 24 limbs, DEVICE */, void *stream);
+/* vectors one launch takes: the largest p <= 16 (MSM_MULTI_MAX_VECTORS, the batched prover's largest launch) that the sort's index space and
+ * bucket scan allow AND whose bucket workspace, p x windows x 2^(c-1) buckets of 256 bytes (an XYZZ<Fq2>, four times G1's), stays at or under
+ * 1 GiB: 8 at 16-bit windows (128 MiB per vector), 16 below.  >= 1, 0 for NULL.                                                            */
+size_t zkg_msm_g2_resident_batch_max(const zkg_msm_g2_bases *bases);
+/* test hook: the G2 epilogue kernel alone.  records_jac (HOST): vectors x cpw x 2 normalised G2 points (24 limbs, infinity allowed) in order
+ * vector, chunk, (P, U); out_jac (HOST): per vector V = sum U_ch + 2^chunk_log * sum ch * P_ch + sum P_ch, normalised.  Bounds as
+ * zkg_msm_combine_gpu: 1 <= cpw <= 2^16, 0 <= chunk_log <= 24, 1 <= vectors <= 1024.  Synchronous.                                         */
+int    zkg_msm_combine_g2_gpu(const uint64_t *records_jac, size_t cpw, int chunk_log, size_t vectors, uint64_t *out_jac);
 /* Window-sharded variant for multi-GPU runs where every GPU holds every base: the partial
  * sum over the Pippenger windows first_window, first_window + window_stride, ... only, each
  * already weighted by 2^(c w) — the partials of ranks g = 0..G-1 (first_window = g,

@@ -37,6 +37,8 @@ DECLARED_SYMBOLS = [
     "zkg_curve_op",
     "zkg_domain_new", "zkg_domain_free", "zkg_domain_size", "zkg_domain_batch_max", "zkg_domain_set_batch_max", "zkg_domain_ntt_async",
     "zkg_domain_lagrange_async", "zkg_domain_stats",
+    "zkg_msm_g2_bases_upload", "zkg_msm_g2_bases_free", "zkg_msm_g2_resident", "zkg_msm_g2_resident_async", "zkg_msm_g2_resident_batch_max",
+    "zkg_msm_combine_g2_gpu",
 ]
 # the reference's own seam, exported with its original names (zklaim.h:257-259)
 COMPAT_SYMBOLS = ["libsnark_trusted_setup", "libsnark_prove", "libsnark_verify"]
@@ -437,6 +439,56 @@ def msm_combine_gpu(records_jac, cpw, slots, chunk_log, vectors=1):
     out = np.zeros((vectors, 12), np.uint64)
     lib().zkg_msm_combine_gpu.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_void_p]
     _check(lib().zkg_msm_combine_gpu(_p(rec), C.c_size_t(cpw), int(slots), int(chunk_log), C.c_size_t(vectors), _p(out)), "zkg_msm_combine_gpu")
+    return out
+
+
+class ResidentBasesG2:
+    """zkg_msm_g2_bases_upload / zkg_msm_g2_resident: fixed G2 bases (device pointer, n affine points of 16 limbs) kept with their per-window tables"""
+
+    def __init__(self, d_bases, n):
+        lib().zkg_msm_g2_bases_upload.restype = C.c_void_p
+        lib().zkg_msm_g2_bases_upload.argtypes = [C.c_void_p, C.c_size_t]
+        self._h = lib().zkg_msm_g2_bases_upload(_vp(d_bases), C.c_size_t(n))
+        if not self._h:
+            raise ZkgError("zkg_msm_g2_bases_upload failed: " + last_error())
+        self.n = n
+
+    def msm(self, d_scalars, scalars_mont=False, stream=0):
+        """`stream`: the HIP stream whose queued work produced d_scalars (0 = the null stream); the job is ordered behind it"""
+        out = np.zeros(24, np.uint64)
+        lib().zkg_msm_g2_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
+        _check(lib().zkg_msm_g2_resident(C.c_void_p(self._h), _vp(d_scalars), C.c_size_t(self.n), SCALARS_MONT if scalars_mont else 0, _p(out), _vp(stream)), "zkg_msm_g2_resident")
+        return out
+
+    def msm_async(self, d_scalars_ptr, d_out_ptr, count=1, stride=None, scalars_mont=False, stream=0):
+        """zkg_msm_g2_resident_async: `count` vectors of n Fr, `stride` elements apart (default n), at the device address d_scalars_ptr; the
+        normalised points (24 limbs each) are written to the device address d_out_ptr by work that `stream` is made to wait for.  Returns
+        without waiting: synchronise `stream` before reading the points on the host."""
+        lib().zkg_msm_g2_resident_async.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
+        _check(lib().zkg_msm_g2_resident_async(C.c_void_p(self._h), _vp(d_scalars_ptr), C.c_size_t(self.n), C.c_size_t(self.n if stride is None else stride),
+                                               C.c_size_t(count), SCALARS_MONT if scalars_mont else 0, _vp(d_out_ptr), _vp(stream)), "zkg_msm_g2_resident_async")
+
+    def batch_max(self):
+        """zkg_msm_g2_resident_batch_max: scalar vectors that share one launch sequence on this handle"""
+        lib().zkg_msm_g2_resident_batch_max.restype = C.c_size_t
+        lib().zkg_msm_g2_resident_batch_max.argtypes = [C.c_void_p]
+        return int(lib().zkg_msm_g2_resident_batch_max(C.c_void_p(self._h)))
+
+    def free(self):
+        if self._h:
+            lib().zkg_msm_g2_bases_free.argtypes = [C.c_void_p]
+            lib().zkg_msm_g2_bases_free(C.c_void_p(self._h)); self._h = None
+
+
+def msm_combine_g2_gpu(records_jac, cpw, chunk_log, vectors=1):
+    """zkg_msm_combine_g2_gpu: the G2 MSM's device epilogue alone.  records_jac: vectors x cpw x 2 normalised G2 points (24 limbs) in the order
+    vector, chunk, (P, U); returns (vectors, 24) normalised points."""
+    rec = _u64(records_jac)
+    if rec.size != vectors * cpw * 2 * 24:
+        raise ZkgError("msm_combine_g2_gpu: records_jac must hold vectors x cpw x 2 points of 24 limbs")
+    out = np.zeros((vectors, 24), np.uint64)
+    lib().zkg_msm_combine_g2_gpu.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p]
+    _check(lib().zkg_msm_combine_g2_gpu(_p(rec), C.c_size_t(cpw), int(chunk_log), C.c_size_t(vectors), _p(out)), "zkg_msm_combine_g2_gpu")
     return out
 
 

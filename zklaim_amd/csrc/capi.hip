@@ -928,6 +928,114 @@ int zkg_msm_combine_gpu(const uint64_t *records_jac, size_t cpw, int slots, int 
     REQUIRE_INIT();
     return msm_combine_records(records_jac, cpw, slots, chunk_log, vectors, out_jac);
 }
+// ---- the same for G2 (a Groth16 B query): a table built by window_table_build_g2, no 29-bit records, the device epilogue k_msm_combine_g2
+struct zkg_msm_g2_bases { WindowTable table; MsmJob *job = nullptr; std::mutex mu; int device = 0; hipEvent_t ev_in = nullptr, ev_out = nullptr; };
+static constexpr size_t G2_RESIDENT_BUCKET_CAP = (size_t)1 << 30;       // one group's bucket workspace (zkg_msm_g2_resident_batch_max)
+static void g2_bases_free_impl(zkg_msm_g2_bases *h) {
+    int cur = 0; (void)hipGetDevice(&cur);
+    if (cur != h->device) (void)hipSetDevice(h->device);               // the handle's memory, stream and events live on the device it was made on
+    if (h->job) { (void)hipStreamSynchronize(msm_job_stream(h->job)); msm_job_destroy(h->job); }
+    if (h->ev_in) (void)hipEventDestroy(h->ev_in);
+    if (h->ev_out) (void)hipEventDestroy(h->ev_out);
+    h->table.release();
+    if (cur != h->device) (void)hipSetDevice(cur);
+    delete h;
+}
+static zkg_msm_g2_bases *g2_bases_upload_impl(const void *d_bases, size_t n) {
+    if (g_device < 0) { set_error("zkg_init not called"); return nullptr; }
+    if (!d_bases || n == 0 || n >= ((size_t)1 << 25)) { set_error("zkg_msm_g2_bases_upload: bad argument (1 <= n < 2^25)"); return nullptr; }
+    zkg_msm_g2_bases *h = new (std::nothrow) zkg_msm_g2_bases();
+    if (!h) { set_error("zkg_msm_g2_bases_upload: out of memory"); return nullptr; }
+    (void)hipGetDevice(&h->device);
+    h->job = msm_job_create(nullptr, true);
+    const bool ok = h->job != nullptr && hip_ok(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming), "hipEventCreate", __FILE__, __LINE__) &&
+                    hip_ok(hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming), "hipEventCreate", __FILE__, __LINE__) &&
+                    window_table_build_g2(h->table, (const G2Affine *)d_bases, n, table_window_bits(n), nullptr) == 0 && hip_ok(hipDeviceSynchronize(), "sync", __FILE__, __LINE__);
+    if (!ok) { g2_bases_free_impl(h); return nullptr; }
+    msm_job_set_window(h->job, h->table.c);                             // (rows are not merged: msm_job_set_row_merge stays at 1)
+    return h;
+}
+static MsmBases g2_table_set(const zkg_msm_g2_bases *h) { MsmBases b; b.p = h->table.buf.p; b.g2 = true; b.level_stride = h->table.n; return b; }
+static int g2_resident_impl(zkg_msm_g2_bases *h, const void *d_scalars, size_t n, int scalars_mont, uint64_t out_jac[24], void *stream) {
+    static const char *who = "zkg_msm_g2_resident";
+    REQUIRE_INIT();
+    if (!h || !d_scalars || !out_jac || n != h->table.n) { set_error(std::string(who) + ": bad argument (n must be the handle's point count)"); return ZKG_ERROR; }
+    if (wrong_device_refused(who, h->device, "the bases were uploaded on")) return ZKG_ERROR;
+    std::lock_guard<std::mutex> lk(h->mu);                              // the handle owns one job: calls take turns
+    ZK_HIP(hipEventRecord(h->ev_in, (hipStream_t)stream));              // behind whatever the caller queued on `stream`
+    ZK_HIP(hipStreamWaitEvent(msm_job_stream(h->job), h->ev_in, 0));
+    const MsmBases b = g2_table_set(h);
+    G2 r;
+    msm_job_set_device_finish(h->job, false);
+    int rc;
+    {   // asynchronous calls may still be running on the handle's stream: a buffer this launch has to grow is freed only after they have drained
+        ReserveGuard guard(msm_job_stream(h->job));
+        rc = msm_job_launch(h->job, &b, 1, (const uint32_t *)d_scalars, n, (scalars_mont & ZKG_SCALARS_MONT) != 0, nullptr);
+    }
+    if (rc || msm_job_finish(h->job, nullptr, &r)) return ZKG_ERROR;
+    store_norm(out_jac, r);
+    return ZKG_OK;
+}
+static size_t g2_resident_batch_max_impl(const zkg_msm_g2_bases *h) {
+    size_t p = std::min<size_t>(MSM_MULTI_MAX_VECTORS, std::max<size_t>(1, G2_RESIDENT_BUCKET_CAP / msm_table_bucket_bytes(h->table.c, true)));
+    while (p > 1 && !msm_multi_supported(h->table.n, h->table.c, (uint32_t)p)) --p;
+    return p;
+}
+static int g2_resident_async_impl(zkg_msm_g2_bases *h, const void *d_scalars, size_t n, size_t stride, size_t count, int scalars_mont, void *d_out_jac, void *stream) {
+    static const char *who = "zkg_msm_g2_resident_async";
+    for (size_t &v : t_resident_async_stats) v = 0;
+    if (count == 0) return ZKG_OK;                                      // nothing to do, nothing touched
+    REQUIRE_INIT();
+    if (!h || !d_scalars || !d_out_jac || n != h->table.n) { set_error(std::string(who) + ": bad argument (n must be the handle's point count)"); return ZKG_ERROR; }
+    if (async_vectors_refused(who, n, "n", stride, count, h->device, "the bases were uploaded on")) return ZKG_ERROR;
+    if (dev_range_refused(d_scalars, ((count - 1) * stride + n) * 32, 16, h->device, who, "d_scalars", "handle") ||
+        dev_range_refused(d_out_jac, count * 192, 8, h->device, who, "d_out_jac", "handle")) return ZKG_ERROR;
+    const size_t bmax = g2_resident_batch_max_impl(h);
+    const bool mont = (scalars_mont & ZKG_SCALARS_MONT) != 0;
+    const uint32_t *sc = (const uint32_t *)d_scalars; uint64_t *out = (uint64_t *)d_out_jac;
+    std::lock_guard<std::mutex> lk(h->mu);                              // held for the enqueue only: calls on one handle run in call order on its stream
+    hipStream_t js = msm_job_stream(h->job);
+    ZK_HIP(hipEventRecord(h->ev_in, (hipStream_t)stream));              // behind the work that writes d_scalars (nothing is enqueued yet)
+    ZK_HIP(hipStreamWaitEvent(js, h->ev_in, 0));
+    const MsmBases b = g2_table_set(h);
+    msm_job_set_device_finish(h->job, true);
+    int rc = ZKG_OK;
+    size_t groups = 0, waits = 0, done = 0;
+    while (done < count && rc == ZKG_OK) {
+        const size_t g = std::min(bmax, count - done);
+        ReserveGuard guard(js);                                         // a reserve that has to grow drains the handle's stream first, and is counted (as for G1)
+        const uint32_t *sg = sc + done * stride * 8;
+        rc = g > 1 ? msm_job_launch_multi(h->job, &b, 1, sg, n, stride * 8, (uint32_t)g, mont) : msm_job_launch(h->job, &b, 1, sg, n, mont, nullptr);
+        if (rc == ZKG_OK) rc = msm_job_finish_dev(h->job, out + done * 24);
+        waits += guard.drains;
+        if (rc == ZKG_OK) { done += g; ++groups; }
+    }
+    // whatever the caller queues on `stream` after this call sees the points — after a failure too: the groups enqueued before it still write theirs
+    const bool ordered = hip_ok(hipEventRecord(h->ev_out, js), "hipEventRecord", __FILE__, __LINE__) &&
+                         hip_ok(hipStreamWaitEvent((hipStream_t)stream, h->ev_out, 0), "hipStreamWaitEvent", __FILE__, __LINE__);
+    t_resident_async_stats[0] = done; t_resident_async_stats[1] = groups; t_resident_async_stats[2] = waits;
+    return rc == ZKG_OK && ordered ? ZKG_OK : ZKG_ERROR;
+}
+zkg_msm_g2_bases *zkg_msm_g2_bases_upload(const void *d_bases, size_t n) {
+    return c_boundary<zkg_msm_g2_bases *>("zkg_msm_g2_bases_upload", nullptr, [&] { return g2_bases_upload_impl(d_bases, n); });
+}
+void zkg_msm_g2_bases_free(zkg_msm_g2_bases *h) {
+    if (!h) return;
+    c_boundary("zkg_msm_g2_bases_free", 0, [&] { g2_bases_free_impl(h); return 0; });
+}
+int zkg_msm_g2_resident(zkg_msm_g2_bases *h, const void *d_scalars, size_t n, int scalars_mont, uint64_t out_jac[24], void *stream) {
+    return c_boundary("zkg_msm_g2_resident", ZKG_ERROR, [&] { return g2_resident_impl(h, d_scalars, n, scalars_mont, out_jac, stream); });
+}
+int zkg_msm_g2_resident_async(zkg_msm_g2_bases *h, const void *d_scalars, size_t n, size_t stride, size_t count, int scalars_mont, void *d_out_jac, void *stream) {
+    return c_boundary("zkg_msm_g2_resident_async", ZKG_ERROR, [&] { return g2_resident_async_impl(h, d_scalars, n, stride, count, scalars_mont, d_out_jac, stream); });
+}
+size_t zkg_msm_g2_resident_batch_max(const zkg_msm_g2_bases *h) {
+    if (!h) return 0;
+    return c_boundary<size_t>("zkg_msm_g2_resident_batch_max", 0, [&] { return g2_resident_batch_max_impl(h); });
+}
+int zkg_msm_combine_g2_gpu(const uint64_t *records_jac, size_t cpw, int chunk_log, size_t vectors, uint64_t *out_jac) {
+    return c_boundary("zkg_msm_combine_g2_gpu", ZKG_ERROR, [&]() -> int { REQUIRE_INIT(); return msm_combine_records_g2(records_jac, cpw, chunk_log, vectors, out_jac); });
+}
 int zkg_msm_g2_dev(const void *d_bases, const void *d_scalars, size_t n, int scalars_mont, uint64_t out_jac[24], void *stream) {
     REQUIRE_INIT();
     G2 r;

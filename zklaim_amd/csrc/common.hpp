@@ -173,12 +173,15 @@ static constexpr uint32_t MSM_MULTI_MAX_VECTORS = 16;       // the largest `coun
 static constexpr size_t ZKG_MSM_ASYNC_MAX_COUNT = (size_t)1 << 24, ZKG_MSM_ASYNC_MAX_STRIDE = (size_t)1 << 32;   // zkg_msm_g1_resident_async: vectors per call, elements between vectors
 int msm_job_launch_multi(MsmJob *job, const MsmBases *sets, int nsets, const uint32_t *d_scalars, size_t n, size_t scalar_stride, uint32_t count, bool scalars_mont);
 int msm_job_finish_multi(MsmJob *job, G1 *out_g1, G2 *out_g2);
-// The asynchronous end of a TABLE launch of G1 sets.  msm_job_set_device_finish(job, true) before the launch: its chunk records are not copied
-// to the host.  msm_job_finish_dev then queues the epilogue kernel (k_msm_combine) on the job's stream and returns without synchronising:
-// d_out (device, 12 limbs per point, normalised as store_norm writes them) gets point (p * sets + k) for vector p and the k-th set.
+// The asynchronous end of a TABLE launch of G1 sets, or of G2 sets (not both).  msm_job_set_device_finish(job, true) before the launch: its chunk
+// records are not copied to the host.  msm_job_finish_dev then queues the epilogue kernel (k_msm_combine, k_msm_combine_g2) on the job's stream and
+// returns without synchronising: d_out (device, 12 limbs per G1 point, 24 per G2 point, normalised as store_norm writes them) gets point
+// (p * sets + k) for vector p and the k-th set.
 void msm_job_set_device_finish(MsmJob *j, bool on);
 int msm_job_finish_dev(MsmJob *job, uint64_t *d_out);
 int msm_combine_records(const uint64_t *records_jac, size_t cpw, int slots, int chunk_log, size_t vectors, uint64_t *out_jac);   // zkg_msm_combine_gpu
+int msm_combine_records_g2(const uint64_t *records_jac, size_t cpw, int chunk_log, size_t vectors, uint64_t *out_jac);           // zkg_msm_combine_g2_gpu
+size_t msm_table_bucket_bytes(int c, bool g2);             // bucket workspace of ONE scalar vector of a table launch at window size c (every window's set)
 // the multi_exp_with_mixed_addition split of a witness z = [1 | w] (n1 elements, Montgomery): tags (0 zero, 1 one, 2 other), the
 // indices of the others and their count; and the flat sum of the bases tagged one (result lands in pinned host memory)
 // d_count: two words, [0] the number of listed elements, [1] set to 1 when a listed element has no entry in d_subset_pos (optional: position of

@@ -28,7 +28,8 @@
 //                      scan + tree reduction across the workgroup; every addition is shared by a DPP quad
 //   8. host            per-window chunk combine and the c-doublings Horner across windows
 //   8'. k_msm_combine  the same combine on the device for a table launch (no Horner there): the points stay in device memory and the job
-//                      ends without a host synchronisation (msm_job_finish_dev, zkg_msm_g1_resident_async)
+//                      ends without a host synchronisation (msm_job_finish_dev, zkg_msm_g1_resident_async); k_msm_combine_g2 is its G2 form
+//                      (zkg_msm_g2_resident_async)
 // Zero scalars are dropped in step 1 and scalars equal to one simply land in bucket (window 0, digit 1),
 // a "heavy" bucket: the effect of libff's multi_exp_with_mixed_addition prefilter without a special case.
 //
@@ -1686,6 +1687,68 @@ __global__ __launch_bounds__(256) void k_jac_to_records(const uint32_t *jac, siz
 }
 static size_t combine_lds_bytes(uint32_t cpw) { uint32_t n = 1; while (n < cpw && n < (uint32_t)COMBINE_THREADS) n <<= 1; return n * sizeof(LdsPoint<Fq>); }
 
+// ---- 8''. the G2 form of that epilogue (a device-finish launch of G2 table sets: zkg_msm_g2_resident_async).  k_bucket_reduce<Fq2, ...> writes
+//      two slots per chunk, (P, U), so V = sum U_ch + 2^chunk_log sum ch P_ch + sum P_ch and there is no A term.  Same lane plan as above on
+//      COMBINE_G2_THREADS = 128 lanes: an LdsPoint<Fq2> is 272 B, so 128 of them are 34 KiB — inside the 64 KiB a kernel gets without asking,
+//      where 256 lanes would need 68 KiB and a raised limit — and two wavefronts leave each the whole register file.  A lane takes 2^l
+//      consecutive chunks from cpw = 129 on (a lone vector at 16-bit windows reduces to 512 chunks: l = 2).
+//      A point is 64 registers, so the live set is kept at three points plus one addition's temporaries: S is scanned in place (it IS Q), lane 0
+//      adds Q_0 = sum P to its U BEFORE the doublings and drops it, Q then becomes the weighted term itself (2^l Q, + T0 — T0 dies here — then
+//      chunk_log doublings) and is added to U.  Sums in a group commute and the point leaves normalised, so the order changes no bit of it.
+static constexpr int COMBINE_G2_THREADS = 128;
+ZK_D void store_norm_dev(uint32_t *out /* 48 words */, const XYZZ<Fq2> &v) {
+    Fq2 X = Fq2::zero(), Y = Fq2::one(), Z = Fq2::zero();
+    if (!v.is_inf()) { const Affine<Fq2> a = v.to_affine().normalized(); X = a.x; Y = a.y; Z = Fq2::one(); }
+    for (int i = 0; i < 8; ++i) {
+        out[i] = X.c0.v[i]; out[8 + i] = X.c1.v[i]; out[16 + i] = Y.c0.v[i]; out[24 + i] = Y.c1.v[i]; out[32 + i] = Z.c0.v[i]; out[40 + i] = Z.c1.v[i];
+    }
+}
+__global__ __launch_bounds__(COMBINE_G2_THREADS) void k_msm_combine_g2(const XYZZ<Fq2> *red, uint32_t cpw, int chunk_log, size_t set_stride, uint32_t *out) {
+    extern __shared__ unsigned char red_smem[];
+    LdsPoint<Fq2> *sh = reinterpret_cast<LdsPoint<Fq2> *>(red_smem);          // n points
+    const uint32_t t = threadIdx.x, w = blockIdx.x, set = blockIdx.y;
+    uint32_t n = 1; while (n < cpw && n < (uint32_t)COMBINE_G2_THREADS) n <<= 1;
+    int l_log = 0; while (((uint64_t)n << l_log) < cpw) ++l_log;
+    const XYZZ<Fq2> *rec = red + (size_t)set * set_stride + (size_t)2 * w * cpw;
+    const uint64_t first = (uint64_t)t << l_log, end = first + ((uint64_t)1 << l_log) < cpw ? first + ((uint64_t)1 << l_log) : cpw;
+    XYZZ<Fq2> U = XYZZ<Fq2>::inf(), Q = XYZZ<Fq2>::inf(), T0 = XYZZ<Fq2>::inf();
+    for (uint64_t ch = end; ch > first; --ch) {                              // chunks end - 1 ... first (none for a lane behind the last chunk); Q = S here
+        const XYZZ<Fq2> *r = rec + (size_t)2 * (ch - 1);
+        Q.add(r[0]); U.add(r[1]);
+        if (ch - 1 > first) T0.add(Q);
+    }
+    for (uint32_t d = 1; d < n; d <<= 1) {                                   // inclusive suffix scan of S over the lanes, in place
+        if (t < n) sh[t] = Q;
+        __syncthreads();
+        if (t + d < n) Q.add(sh[t + d]);
+        __syncthreads();
+    }
+    if (t == 0) { U.add(Q); Q = XYZZ<Fq2>::inf(); }                          // Q_0 = sum_ch P_ch; lane 0 has no weighted term of the scan
+    for (int i = 0; i < l_log; ++i) Q = Q.dbl();
+    Q.add(T0);
+    for (int i = 0; i < chunk_log; ++i) Q = Q.dbl();                         // * buckets per chunk (infinity stays infinity)
+    U.add(Q);
+    if (t < n) sh[t] = U;
+    __syncthreads();
+    lds_tree_reduce<Fq2>(sh, n, t, COMBINE_G2_THREADS, [] { __syncthreads(); });
+    if (t == 0) store_norm_dev(out + 48 * ((size_t)w * gridDim.y + set), sh[0]);
+}
+__global__ __launch_bounds__(64) void k_msm_store_inf_g2(uint32_t *out, uint32_t count) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) store_norm_dev(out + 48 * (size_t)i, XYZZ<Fq2>::inf());
+}
+__global__ __launch_bounds__(256) void k_jac_to_records_g2(const uint32_t *jac, size_t count, XYZZ<Fq2> *rec) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    Fq2 X, Y, Z;
+    for (int k = 0; k < 8; ++k) {
+        X.c0.v[k] = jac[48 * i + k]; X.c1.v[k] = jac[48 * i + 8 + k]; Y.c0.v[k] = jac[48 * i + 16 + k]; Y.c1.v[k] = jac[48 * i + 24 + k];
+        Z.c0.v[k] = jac[48 * i + 32 + k]; Z.c1.v[k] = jac[48 * i + 40 + k];
+    }
+    rec[i] = Z.is_zero() ? XYZZ<Fq2>::inf() : XYZZ<Fq2>{X, Y, Fq2::one(), Fq2::one()};
+}
+static size_t combine_g2_lds_bytes(uint32_t cpw) { uint32_t n = 1; while (n < cpw && n < (uint32_t)COMBINE_G2_THREADS) n <<= 1; return n * sizeof(LdsPoint<Fq2>); }
+
 static int sort_digits(MsmJob *job, const uint32_t *d_scalars, bool mont, const uint32_t *d_gather) {
     const MsmGeom g0 = job->g; const size_t n0 = job->n;                        // as the scalars see them (k_digits)
     if (job->merge > 1) { job->g.W /= job->merge; job->g.Wt = job->g.W; job->n *= job->merge; }     // rows of the digit array read `merge` at a time from here on
@@ -1915,12 +1978,23 @@ void msm_job_set_device_finish(MsmJob *j, bool on) { if (j) j->dev_finish = on; 
 // The device epilogue of a launch made under msm_job_set_device_finish: nothing is copied back and nothing is waited for.  k_msm_combine goes
 // onto the job's stream behind the reduction with the launch's geometry by value, and writes the points of the launch's G1 table sets where
 // msm_job_finish / msm_job_finish_multi would return them — d_out[(p * sets + k) * 12 limbs], normalised as store_norm does.
+// A launch whose sets are all G2 table sets ends the same way through k_msm_combine_g2, 24 limbs per point; a launch of both fields is refused.
 int msm_job_finish_dev(MsmJob *job, uint64_t *d_out) {
-    const MsmGroup &gr = job->group[0];
-    if (!job->dev_finish || job->group[1].nsets || gr.nsets < 1) { set_error("msm_job_finish_dev: a device-finish launch of G1 sets only"); return ZKG_ERROR; }
+    const bool g2 = job->group[0].nsets == 0;
+    const MsmGroup &gr = job->group[g2 ? 1 : 0];
+    if (!job->dev_finish || (job->group[0].nsets && job->group[1].nsets) || gr.nsets < 1) { set_error("msm_job_finish_dev: a device-finish launch of G1 sets only, or of G2 sets only"); return ZKG_ERROR; }
     const uint32_t vectors = job->multi > 1 ? job->multi : 1;
     uint32_t *out = reinterpret_cast<uint32_t *>(d_out);
-    if (job->empty) {
+    if (g2) {
+        if (job->empty) {
+            const uint32_t count = vectors * (uint32_t)gr.nsets;
+            hipLaunchKernelGGL(k_msm_store_inf_g2, dim3((count + 63) / 64), dim3(64), 0, job->stream, out, count);
+        } else {
+            if (!gr.table || gr.red_windows != vectors || gr.red_slots != 2) { set_error("msm_job_finish_dev: table sets only (a plain set's windows need the Horner doublings)"); return ZKG_ERROR; }
+            hipLaunchKernelGGL(k_msm_combine_g2, dim3(vectors, (unsigned)gr.nsets), dim3(COMBINE_G2_THREADS), combine_g2_lds_bytes(gr.cpw), job->stream,
+                               gr.red_out.as<XYZZ<Fq2>>(), gr.cpw, gr.chunk_log, gr.red_stride, out);
+        }
+    } else if (job->empty) {
         const uint32_t count = vectors * (uint32_t)gr.nsets;
         hipLaunchKernelGGL(k_msm_store_inf, dim3((count + 63) / 64), dim3(64), 0, job->stream, out, count);
     } else {
@@ -1947,6 +2021,27 @@ int msm_combine_records(const uint64_t *records_jac, size_t cpw, int slots, int 
     if (hipGetLastError() != hipSuccess) { set_error("msm combine launch failed"); return ZKG_ERROR; }
     ZK_HIP(hipMemcpy(out_jac, out.p, vectors * 96, hipMemcpyDeviceToHost));     // (waits for the null stream)
     return ZKG_OK;
+}
+// zkg_msm_combine_g2_gpu: k_msm_combine_g2 alone.  records_jac: vectors x cpw x 2 normalised G2 points of 24 limbs, in order vector, chunk, (P, U)
+int msm_combine_records_g2(const uint64_t *records_jac, size_t cpw, int chunk_log, size_t vectors, uint64_t *out_jac) {
+    if (!records_jac || !out_jac || cpw < 1 || cpw > ((size_t)1 << 16) || chunk_log < 0 || chunk_log > 24 || vectors < 1 || vectors > 1024) {
+        set_error("zkg_msm_combine_g2_gpu: bad argument (1 <= cpw <= 2^16, 0 <= chunk_log <= 24, 1 <= vectors <= 1024)"); return ZKG_ERROR;
+    }
+    const size_t count = vectors * cpw * 2;
+    ScopedDevBuf in, rec, out;
+    if (in.reserve(count * 192) || rec.reserve(count * sizeof(XYZZ<Fq2>)) || out.reserve(vectors * 192)) return ZKG_ERROR;
+    ZK_HIP(hipMemcpy(in.p, records_jac, count * 192, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_jac_to_records_g2, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, nullptr, in.as<uint32_t>(), count, rec.as<XYZZ<Fq2>>());
+    hipLaunchKernelGGL(k_msm_combine_g2, dim3((unsigned)vectors, 1), dim3(COMBINE_G2_THREADS), combine_g2_lds_bytes((uint32_t)cpw), nullptr,
+                       rec.as<XYZZ<Fq2>>(), (uint32_t)cpw, chunk_log, (size_t)0, out.as<uint32_t>());
+    if (hipGetLastError() != hipSuccess) { set_error("msm combine launch failed"); return ZKG_ERROR; }
+    ZK_HIP(hipMemcpy(out_jac, out.p, vectors * 192, hipMemcpyDeviceToHost));    // (waits for the null stream)
+    return ZKG_OK;
+}
+// what one scalar vector of a table launch asks of the bucket workspace (launch_accumulate: every window's bucket set, before the fold)
+size_t msm_table_bucket_bytes(int c, bool g2) {
+    const MsmGeom g = pick_geom(1, c);
+    return (size_t)g.W * g.B * (g2 ? std::max(sizeof(XYZZ<Fq2>), sizeof(Bucket29)) : std::max(sizeof(XYZZ<Fq>), sizeof(Bucket29)));
 }
 
 
