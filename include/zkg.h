@@ -151,6 +151,49 @@ int zkg_domain_lagrange_async(zkg_domain *d, const uint64_t t[4], void *d_u, voi
  * made.  Counters, not clocks.                                                                                                           */
 void zkg_domain_stats(size_t out[3]);
 
+/* ---- r1cs_to_qap_witness_map on device-resident witnesses, as a handle on a constraint system alone (no proving key): three mat-vecs, three
+ *      iFFT, three cosetFFT, (A.B - C)/Z on the coset and the icosetFFT, for many witnesses per call, on the caller's stream.
+ *      zkg_qap_new(cs): the CSR matrices in HOST memory, copied to the device; the domain is get_evaluation_domain(C + l + 1).  The handle lives
+ *      on the zkg_init device, which must be the calling thread's; the domain tables are built as zkg_domain_new builds them, with the fused
+ *      g^i / m table of a radix-2 domain and the list of the rows above 24 terms (one wavefront per row).  NULL, with zkg_last_error set: no
+ *      zkg_init; a null CSR; num_constraints == 0 or num_variables == 0; num_inputs > num_variables; C + l + 1 with no radix-2 or step domain;
+ *      a row pointer that does not start at 0 or decreases; a column index above num_variables (checked here, on the host, once: the kernels
+ *      index z by it).  The system is taken as given: there is no swap_AB_if_beneficial (H does not depend on the swap).
+ *      zkg_qap_free waits for the handle's pending work; NULL is accepted; callable from any device.
+ *      zkg_qap_domain_size: m.  zkg_qap_num_variables: n.  Both 0 for NULL.
+ *      zkg_qap_witness_h_async: witness i is n Fr, Montgomery, at d_witnesses + i * stride * 32 bytes, stride >= n — the layout
+ *      zkg_groth16_prove_dev takes.  It is read in place: the constant z[0] = 1 is supplied by the kernel, and what lies between n and the stride
+ *      is never read.  coefficients_for_H of witness i, m + 1 Fr, goes to d_h + i * h_stride * 32 bytes, h_stride >= m + 1: the limbs
+ *      zkg_qap_witness_h writes for a host copy of that witness on a key over the same system, bit for bit, coefficients_for_H[m] = 0 included;
+ *      what lies between m + 1 and h_stride is never written.  d_unsat (DEVICE, `count` 32-bit words, or NULL): every word is written — 0 for
+ *      a satisfied witness, 1 where some row has <A,z><B,z> != <C,z> (the pb.is_satisfied() gate).  H is written for such a witness all the same
+ *      (the map is defined on it) and the other witnesses of the call are not affected.
+ *      The witnesses are cut into groups of at most zkg_qap_batch_max, one launch sequence each (mat-vec with the witness in grid.y, the seven
+ *      transforms as batches of 3 g and g vectors, the pointwise step writing into d_h, the icosetFFT in place there).  A group's workspace is
+ *      3 m Fr of aA | aB | aC plus the transforms' 40 bytes per element, 216 m bytes per witness; the default group is
+ *      max(1, min(65535 / 3, 1 GiB / (m * 216 bytes))) — 65535 / 3 because grid.y of the batched transforms carries 3 g vectors.
+ *      Ordering is zkg_domain's: the kernels are queued on `stream` behind everything already there and the call makes no host wait; a handle
+ *      serves its calls in call order whatever streams they name (one workspace: each call leaves the handle's event in its last launch, and a
+ *      later call on another stream makes that stream wait for it first).  The workspace only grows; a call that needs more of it waits for
+ *      the handle's event, reallocates and counts one host wait; a call at a group size the handle has served neither waits nor allocates.
+ *      Refused with ZKG_ERROR before any launch, nothing written: a null handle or pointer (d_unsat may be NULL); stride < n or
+ *      h_stride < m + 1; more than 2^24 witnesses or a stride above 2^32 elements; a calling thread on another device than the handle's; a
+ *      pointer that is not device memory of that device, is misaligned (16 bytes; 4 for d_unsat) or runs past the end of its allocation
+ *      (zkg_domain_ntt_async's rules); ranges of d_witnesses, d_h and d_unsat that overlap.  count == 0 is ZKG_OK and touches nothing.       */
+typedef struct zkg_qap zkg_qap;
+zkg_qap *zkg_qap_new(const zkg_r1cs *cs);
+void     zkg_qap_free(zkg_qap *q);
+size_t   zkg_qap_domain_size(const zkg_qap *q);
+uint32_t zkg_qap_num_variables(const zkg_qap *q);
+size_t   zkg_qap_batch_max(const zkg_qap *q);     /* witnesses one launch sequence takes; >= 1, 0 for NULL */
+void     zkg_qap_set_batch_max(zkg_qap *q, size_t k);   /* test hook: k witnesses per launch sequence from now on; 0 restores the default, a larger k is clamped to it */
+int      zkg_qap_witness_h_async(zkg_qap *q, const void *d_witnesses, size_t stride /* Fr elements between witnesses, >= n */, size_t count,
+                                 void *d_h, size_t h_stride /* Fr elements between outputs, >= m + 1 */, uint32_t *d_unsat /* DEVICE, count words, or NULL */,
+                                 void *stream);
+/* test hook: the calling thread's last zkg_qap_witness_h_async — out[0] witnesses enqueued, out[1] launch groups, out[2] host waits the entry
+ * made.  Counters, not clocks.                                                                                                           */
+void     zkg_qap_stats(size_t out[3]);
+
 /* ---- MSM: libff::multi_exp<G1,Fr,multi_exp_method_BDLO12> and
  *      multi_exp_with_mixed_addition (A/H/L queries), and the G2 half of
  *      kc_multi_exp_with_mixed_addition (B query); reached from snark.cpp:126.

@@ -39,6 +39,8 @@ DECLARED_SYMBOLS = [
     "zkg_domain_lagrange_async", "zkg_domain_stats",
     "zkg_msm_g2_bases_upload", "zkg_msm_g2_bases_free", "zkg_msm_g2_resident", "zkg_msm_g2_resident_async", "zkg_msm_g2_resident_batch_max",
     "zkg_msm_combine_g2_gpu",
+    "zkg_qap_new", "zkg_qap_free", "zkg_qap_domain_size", "zkg_qap_num_variables", "zkg_qap_batch_max", "zkg_qap_set_batch_max",
+    "zkg_qap_witness_h_async", "zkg_qap_stats",
 ]
 # the reference's own seam, exported with its original names (zklaim.h:257-259)
 COMPAT_SYMBOLS = ["libsnark_trusted_setup", "libsnark_prove", "libsnark_verify"]
@@ -311,6 +313,59 @@ def domain_stats():
     """(vectors, launch groups, host waits) of the calling thread's last Domain.ntt_async"""
     out = (C.c_size_t * 3)()
     lib().zkg_domain_stats(out)
+    return tuple(int(v) for v in out)
+
+
+class Qap:
+    """zkg_qap: r1cs_to_qap_witness_map on device-resident witnesses as a handle on a constraint system alone (cs: make_r1cs's struct, host
+    CSR, copied to the device) — coefficients_for_H of many witnesses per call, queued on the caller's stream without a wait on the host"""
+
+    def __init__(self, cs):
+        L = lib()
+        L.zkg_qap_new.restype = C.c_void_p
+        L.zkg_qap_new.argtypes = [C.c_void_p]
+        L.zkg_qap_free.argtypes = [C.c_void_p]
+        for name in ("zkg_qap_domain_size", "zkg_qap_batch_max"):
+            getattr(L, name).restype = C.c_size_t
+            getattr(L, name).argtypes = [C.c_void_p]
+        L.zkg_qap_num_variables.restype = C.c_uint32
+        L.zkg_qap_num_variables.argtypes = [C.c_void_p]
+        L.zkg_qap_set_batch_max.argtypes = [C.c_void_p, C.c_size_t]
+        L.zkg_qap_witness_h_async.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        self._h = L.zkg_qap_new(C.byref(cs))
+        if not self._h:
+            raise ZkgError("zkg_qap_new failed: " + L.zkg_last_error().decode())
+        self.m, self.n = self.domain_size(), self.num_variables()
+
+    def witness_h_async(self, d_w_ptr, count, stride, d_h_ptr, h_stride, d_unsat_ptr=0, stream=0):
+        """zkg_qap_witness_h_async: `count` witnesses of n Montgomery Fr, `stride` elements apart at the device address d_w_ptr, read in place ->
+        coefficients_for_H (m + 1 Fr each, `h_stride` apart) at d_h_ptr and, if d_unsat_ptr is given, one 32-bit word per witness there (1: the
+        witness violates the system).  Returns without waiting: synchronise `stream` before reading the result on the host."""
+        _check(lib().zkg_qap_witness_h_async(C.c_void_p(self._h), _vp(d_w_ptr), C.c_size_t(stride), C.c_size_t(count), _vp(d_h_ptr), C.c_size_t(h_stride),
+                                             _vp(d_unsat_ptr), _vp(stream)), "zkg_qap_witness_h_async")
+
+    def domain_size(self):
+        return int(lib().zkg_qap_domain_size(C.c_void_p(self._h)))
+
+    def num_variables(self):
+        return int(lib().zkg_qap_num_variables(C.c_void_p(self._h)))
+
+    def batch_max(self):
+        return int(lib().zkg_qap_batch_max(C.c_void_p(self._h)))
+
+    def set_batch_max(self, k):
+        """test hook: k witnesses per launch sequence from now on (0: the default; a larger k is clamped to it)"""
+        lib().zkg_qap_set_batch_max(C.c_void_p(self._h), C.c_size_t(k))
+
+    def free(self):
+        if self._h:
+            lib().zkg_qap_free(C.c_void_p(self._h)); self._h = None
+
+
+def qap_stats():
+    """(witnesses, launch groups, host waits) of the calling thread's last Qap.witness_h_async"""
+    out = (C.c_size_t * 3)()
+    lib().zkg_qap_stats(out)
     return tuple(int(v) for v in out)
 
 

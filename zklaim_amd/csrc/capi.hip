@@ -495,14 +495,14 @@ int dev_range_refused(const void *d, size_t bytes, size_t align, int device, con
 }
 // the rules the *_async entries share (zkg_msm_g1_resident_async, zkg_domain_*_async): the caller is on the handle's device (`made`: "the
 // bases were uploaded on"), and `count` vectors of n elements lie `stride` elements apart
-static int wrong_device_refused(const char *who, int device, const char *made) {
+int wrong_device_refused(const char *who, int device, const char *made) {
     int cur = -1;
     if (hipGetDevice(&cur) == hipSuccess && cur == device) return ZKG_OK;
     (void)hipGetLastError();
     set_error(std::string(who) + ": the calling thread's device is not the one " + made);
     return ZKG_ERROR;
 }
-static int async_vectors_refused(const char *who, size_t n, const char *n_name, size_t stride, size_t count, int device, const char *made) {
+int async_vectors_refused(const char *who, size_t n, const char *n_name, size_t stride, size_t count, int device, const char *made) {
     if (stride < n) { set_error(std::string(who) + ": stride must be at least " + n_name); return ZKG_ERROR; }
     if (count > ZKG_MSM_ASYNC_MAX_COUNT || stride > ZKG_MSM_ASYNC_MAX_STRIDE) { set_error(std::string(who) + ": at most 2^24 vectors, at most 2^32 elements apart"); return ZKG_ERROR; }
     return wrong_device_refused(who, device, made);

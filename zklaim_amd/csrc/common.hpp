@@ -255,6 +255,10 @@ void verify_keys_release_all();                          // zkg_shutdown: the pr
 int initialised_device();                                // the device zkg_init selected, -1 before (capi.hip)
 // ZKG_ERROR (message "<who>: <what> ...") unless d is `bytes` of device memory of `device`, aligned to `align` (capi.hip); owner: "key", "handle"
 int dev_range_refused(const void *d, size_t bytes, size_t align, int device, const char *who, const char *what, const char *owner);
+// the rules the *_async entries share (capi.hip): the calling thread is on `device` ("<who>: the calling thread's device is not the one <made>");
+// `count` vectors of n elements lie `stride` elements apart, within ZKG_MSM_ASYNC_MAX_COUNT / _STRIDE
+int wrong_device_refused(const char *who, int device, const char *made);
+int async_vectors_refused(const char *who, size_t n, const char *n_name, size_t stride, size_t count, int device, const char *made);
 // the per-proof verifier (zkg_groth16_verify_each, zkg_pairing_each, zkg_final_exp)
 int verify_ic_each(const G1Affine *d_ic0, const G1Affine *d_ic, uint32_t nidx, const void *d_x, size_t n, G1Affine *d_out, hipStream_t s);
 int verify_g2_replicate(const G2Affine *d_key2, size_t n, G2Affine *d_Q, hipStream_t s);     // d_Q[n + i] = key2[0], d_Q[2 n + i] = key2[1]
