@@ -193,6 +193,33 @@ int      zkg_qap_witness_h_async(zkg_qap *q, const void *d_witnesses, size_t str
 /* test hook: the calling thread's last zkg_qap_witness_h_async — out[0] witnesses enqueued, out[1] launch groups, out[2] host waits the entry
  * made.  Counters, not clocks.                                                                                                           */
 void     zkg_qap_stats(size_t out[3]);
+/* ---- the other half of the QAP reduction on the same handle: r1cs_to_qap_instance_map_with_evaluation, the QAP polynomials at a point t.
+ *      With u = evaluate_all_lagrange_polynomials(t) on the handle's domain: At[j] = sum_i u[i] A[i][j] (+ u[C + j] for j <= l, the
+ *      input-consistency rows), Bt[j] = sum_i u[i] B[i][j], Ct[j] = sum_i u[i] C[i][j], j = 0 .. n with column 0 the constant — for the system as
+ *      the handle holds it (no swap_AB_if_beneficial).  t: 4 limbs in HOST memory, Montgomery, read during the call.  Vector k of At | Bt | Ct,
+ *      n + 1 Fr, goes to d_abc + k * stride * 32 bytes, stride >= n + 1; d_z (or NULL) receives Z(t).  Everything written is a fully reduced
+ *      Montgomery element; a column no row touches is exactly zero; what lies between n + 1 and the stride is never written.
+ *      It is a transposed sparse mat-vec, so the handle needs its matrices by columns.  That index — per matrix n + 2 column pointers and, per
+ *      entry, the row and the position of its coefficient in the row-major values the handle already holds (the 32-byte values are not copied)
+ *      — is built on the device by the FIRST instance call of a handle, which waits for it once on the host (zkg_qap_instance_stats counts
+ *      both); zkg_qap_new and handles used for H alone pay nothing.  It is made with atomics (degree count, exclusive scan, scatter through
+ *      per-column cursors), so the order of the entries inside a column differs from build to build; the sums are exact in Fr and every result
+ *      is reduced to [0, r) on the way out, so the output does not depend on that order.
+ *      A call queues: the Lagrange kernel (u into the handle's workspace, m Fr), one lane per column over the three matrices (the u[C + j] term
+ *      added there), and — when some column has more than LONG_COLUMN = 24 terms — one wavefront per segment of such a column (lanes stride
+ *      over the terms, shuffle reduction; a column is cut into segments of 2048 terms, zklaim's constant column in B holds a term of every
+ *      bitness row) and a closing launch that sums a column's partial sums, one wavefront per column.  Ordering, the event and the grow-only
+ *      workspace are zkg_qap_witness_h_async's: instance and H calls on one handle run in call order whatever streams they name.
+ *      Refused with ZKG_ERROR before any launch, nothing written: a null handle, t or d_abc; stride < n + 1 or above 2^32; a calling thread on
+ *      another device than the handle's; d_abc or d_z that is not device memory of that device, is not 16-byte aligned or runs past the end of
+ *      its allocation; d_z inside d_abc's range; a t with Z(t) = 0 (a point of the domain).                                                  */
+int      zkg_qap_instance_async(zkg_qap *q, const uint64_t t[4] /* HOST, Montgomery */, void *d_abc /* DEVICE: At | Bt | Ct */,
+                                size_t stride /* Fr elements between the three vectors, >= n + 1 */, void *d_z /* DEVICE, one Fr, or NULL */, void *stream);
+/* test hook: long columns are cut into segments of k terms from the next instance call on (which rebuilds the segment list behind the handle's
+ * pending work and counts one host wait); 0 restores the default 2048, k below 64 is taken as 64, above 2^20 as 2^20                        */
+void     zkg_qap_set_column_segment(zkg_qap *q, size_t k);
+/* test hook: the calling thread's last zkg_qap_instance_async — out[0] column indexes built (1 on a handle's first call), out[1] host waits */
+void     zkg_qap_instance_stats(size_t out[2]);
 
 /* ---- MSM: libff::multi_exp<G1,Fr,multi_exp_method_BDLO12> and
  *      multi_exp_with_mixed_addition (A/H/L queries), and the G2 half of
@@ -511,6 +538,11 @@ size_t zkg_zklaim_input_map(const struct zklaim_ctx *ctx, uint64_t *out, size_t 
  *      zkg_groth16_verify replaces r1cs_gg_ppzksnark_verifier_strong_IC (snark.cpp:62): 0 valid, 1 invalid, 2 malformed.   */
 typedef struct zkg_keypair zkg_keypair;
 zkg_keypair *zkg_groth16_setup(const zkg_r1cs *cs, const uint64_t *trapdoor);
+/* The same keypair, byte for byte under the same trapdoor (pk arrays, swap flag, pk and vk blobs), with no scalar vector on the host: after the
+ * swap decision a zkg_qap handle over the stored system runs zkg_qap_instance_async at t, t^i Z(t) / delta comes from the powers kernel, the
+ * (beta At + alpha Bt + Ct) / gamma and / delta combinations from one kernel, and the fixed-base batches read those device buffers.  NULL with
+ * zkg_last_error set: no zkg_init, a system zkg_qap_new refuses, a trapdoor whose t lies on the evaluation domain.                            */
+zkg_keypair *zkg_groth16_setup_dev(const zkg_r1cs *cs, const uint64_t *trapdoor /* as zkg_groth16_setup; NULL = random */);
 void zkg_keypair_free(zkg_keypair *kp);
 const zkg_pk *zkg_keypair_pk(const zkg_keypair *kp);               /* flat arrays, valid until zkg_keypair_free              */
 int zkg_keypair_swapped(const zkg_keypair *kp);                    /* 1 if swap_AB_if_beneficial exchanged A and B          */

@@ -41,6 +41,7 @@ DECLARED_SYMBOLS = [
     "zkg_msm_combine_g2_gpu",
     "zkg_qap_new", "zkg_qap_free", "zkg_qap_domain_size", "zkg_qap_num_variables", "zkg_qap_batch_max", "zkg_qap_set_batch_max",
     "zkg_qap_witness_h_async", "zkg_qap_stats",
+    "zkg_qap_instance_async", "zkg_qap_set_column_segment", "zkg_qap_instance_stats", "zkg_groth16_setup_dev",
 ]
 # the reference's own seam, exported with its original names (zklaim.h:257-259)
 COMPAT_SYMBOLS = ["libsnark_trusted_setup", "libsnark_prove", "libsnark_verify"]
@@ -332,6 +333,8 @@ class Qap:
         L.zkg_qap_num_variables.argtypes = [C.c_void_p]
         L.zkg_qap_set_batch_max.argtypes = [C.c_void_p, C.c_size_t]
         L.zkg_qap_witness_h_async.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.zkg_qap_instance_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.zkg_qap_set_column_segment.argtypes = [C.c_void_p, C.c_size_t]
         self._h = L.zkg_qap_new(C.byref(cs))
         if not self._h:
             raise ZkgError("zkg_qap_new failed: " + L.zkg_last_error().decode())
@@ -343,6 +346,20 @@ class Qap:
         witness violates the system).  Returns without waiting: synchronise `stream` before reading the result on the host."""
         _check(lib().zkg_qap_witness_h_async(C.c_void_p(self._h), _vp(d_w_ptr), C.c_size_t(stride), C.c_size_t(count), _vp(d_h_ptr), C.c_size_t(h_stride),
                                              _vp(d_unsat_ptr), _vp(stream)), "zkg_qap_witness_h_async")
+
+    def instance_async(self, t, d_abc_ptr, stride=None, d_z_ptr=0, stream=0):
+        """zkg_qap_instance_async: the QAP polynomials at t (4 Montgomery limbs, host) -> At | Bt | Ct, n + 1 Montgomery Fr each, `stride`
+        elements apart (default n + 1) at the device address d_abc_ptr and, if d_z_ptr is given, Z(t) there.  The first call on a handle builds
+        the column index and waits for it; later calls return without waiting: synchronise `stream` before reading the result on the host."""
+        tt = None if t is None else _u64(t).reshape(-1)
+        if tt is not None and tt.size != 4:
+            raise ZkgError("zkg_qap_instance_async: t is 4 limbs")
+        _check(lib().zkg_qap_instance_async(C.c_void_p(self._h), _p(tt), _vp(d_abc_ptr), C.c_size_t(self.n + 1 if stride is None else stride), _vp(d_z_ptr),
+                                            _vp(stream)), "zkg_qap_instance_async")
+
+    def set_column_segment(self, k):
+        """test hook: long columns are cut into segments of k terms from the next instance call on (0: the default)"""
+        lib().zkg_qap_set_column_segment(C.c_void_p(self._h), C.c_size_t(k))
 
     def domain_size(self):
         return int(lib().zkg_qap_domain_size(C.c_void_p(self._h)))
@@ -366,6 +383,13 @@ def qap_stats():
     """(witnesses, launch groups, host waits) of the calling thread's last Qap.witness_h_async"""
     out = (C.c_size_t * 3)()
     lib().zkg_qap_stats(out)
+    return tuple(int(v) for v in out)
+
+
+def qap_instance_stats():
+    """(column indexes built, host waits) of the calling thread's last Qap.instance_async"""
+    out = (C.c_size_t * 2)()
+    lib().zkg_qap_instance_stats(out)
     return tuple(int(v) for v in out)
 
 
@@ -849,7 +873,8 @@ def zklaim_input_map(ctx):
 
 # ---- key generation / verification (r1cs_gg_ppzksnark_generator, r1cs_gg_ppzksnark_verifier_strong_IC) ------------------
 class Keypair:
-    def __init__(self, r1cs, trapdoor=None):
+    def __init__(self, r1cs, trapdoor=None, dev=False):
+        """dev: zkg_groth16_setup_dev, the generator whose scalars never leave the device (the same keypair byte for byte)"""
         L = lib()
         L.zkg_groth16_setup.restype = C.c_void_p
         L.zkg_groth16_setup.argtypes = [C.c_void_p, C.c_void_p]
@@ -859,9 +884,13 @@ class Keypair:
         for f in (L.zkg_keypair_pk_blob, L.zkg_keypair_vk_blob):
             f.restype = C.c_size_t; f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         td = None if trapdoor is None else _u64(trapdoor)
-        self._h = L.zkg_groth16_setup(C.byref(r1cs), _p(td))
+        entry = "zkg_groth16_setup_dev" if dev else "zkg_groth16_setup"
+        if dev:
+            L.zkg_groth16_setup_dev.restype = C.c_void_p
+            L.zkg_groth16_setup_dev.argtypes = [C.c_void_p, C.c_void_p]
+        self._h = getattr(L, entry)(C.byref(r1cs), _p(td))
         if not self._h:
-            raise ZkgError("zkg_groth16_setup failed: " + L.zkg_last_error().decode())
+            raise ZkgError(entry + " failed: " + L.zkg_last_error().decode())
         self.pk = L.zkg_keypair_pk(self._h).contents
         self.swapped = bool(L.zkg_keypair_swapped(self._h))
 

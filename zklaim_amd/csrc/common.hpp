@@ -109,6 +109,7 @@ bool domain_shape_of(size_t m, DomainShape &d);           // m must be a size th
 Fr fr_root_of_unity_pow2(unsigned logn);                  // libff::get_root_of_unity(2^logn)
 // evaluate_all_lagrange_polynomials(t) and compute_vanishing_polynomial(t) of the domain (host, one batched inversion)
 int domain_lagrange(const DomainShape &d, const Fr &t, std::vector<Fr> &u, Fr &Zt);
+Fr domain_vanishing_at(const DomainShape &d, const Fr &t);    // Z(t) alone, as both of them compute it (host)
 // the same values from one kernel queued on s (k_lagrange): d_u (device, m Fr) and, if given, d_z (device, one Fr), canonical limbs.  Z(t) is
 // computed on the host first: ZKG_ERROR before any launch when t is a domain point.  No host wait once the domain's tables exist.
 int domain_lagrange_dev(const DomainShape &d, const Fr &t, Fr *d_u, Fr *d_z, hipStream_t s, hipEvent_t done = nullptr);   // done: as in ntt_run_ex

@@ -528,6 +528,7 @@ static LagrangeConsts lagrange_consts(const DomainShape &d, const Fr &t) {
     c.L1num = Zb * Zs; c.L1s = (omega.pow_u64(d.big) - Fr::one()) * Fr::from_u64(d.small);
     return c;
 }
+Fr domain_vanishing_at(const DomainShape &d, const Fr &t) { return lagrange_consts(d, t).Zt; }
 int domain_lagrange(const DomainShape &d, const Fr &t, std::vector<Fr> &u, Fr &Zt) {
     const size_t m = d.m;
     u.assign(m, Fr::zero());

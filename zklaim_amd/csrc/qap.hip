@@ -6,6 +6,7 @@
 // workspace, the pointwise step writes into the caller's buffer and the closing icosetFFT runs there in place.  Everything is queued on the
 // caller's stream; nothing waits on the host.  The row kernels share their device functions with the prover's (r1cs.hip.hpp), the transforms
 // are the prover's batched runners (ntt_run_ex, step_ntt_run) with 3 g vectors per launch: a witness's H has the limbs zkg_qap_witness_h gives.
+// The same handle evaluates the QAP at a point (zkg_qap_instance_async, r1cs_to_qap_instance_map_with_evaluation): see "the instance map" below.
 #include "common.hpp"
 #include "r1cs.hip.hpp"
 #include "../../include/zkg.h"
@@ -74,7 +75,118 @@ __global__ __launch_bounds__(256) void k_qap_pointwise_step(const Fr *aABC, size
     out[i] = ((aA[i] * aA[m + i] - aA[2 * m + i]) * zi).normalized();
 }
 
-static constexpr size_t QAP_WORKSPACE_CAP = (size_t)1 << 30;                    // one launch group's workspace stays at or under this (one witness is always taken)
+// ---- the instance map (zkg_qap_instance_async): At | Bt | Ct = the columns of A, B, C against u = the Lagrange coefficients at t, a transposed
+//      sparse mat-vec.  The handle holds the matrices by rows (CSR); the column-major index below is built from them on the device, once, by the
+//      first instance call: per matrix n + 2 column pointers and, per entry, (row, position of the coefficient in the CSR val) — the 32-byte
+//      values are not copied.  Degree count with atomics, exclusive scan, scatter through per-column cursors: the order of the entries inside a
+//      column is whatever the atomics give, and the sums, exact in Fr and fully reduced on the way out, do not depend on it.
+static constexpr uint32_t LONG_COLUMN = 24;          // columns above this many terms go one wavefront per segment (include/zkg.h names the number)
+static constexpr uint32_t COLUMN_SEGMENT = 2048;     // terms per segment of such a column: 32 per lane
+static constexpr uint32_t COLUMN_SEGMENT_MIN = 64;   // zkg_qap_set_column_segment: one term per lane at the least
+struct ColSeg { uint32_t key /* matrix << 30 | column */, lo, hi /* entries [lo, hi) of the matrix's index */, nseg /* on a column's first segment: how many it has; else 0 */; };
+struct QapCsc { const uint32_t *a_cp; const uint2 *a_ent; const Fr *a_val; const uint32_t *b_cp; const uint2 *b_ent; const Fr *b_val; const uint32_t *c_cp; const uint2 *c_ent; const Fr *c_val; };
+template <class T> ZK_D T pick3(uint32_t k, T a, T b, T c) { return k == 0 ? a : k == 1 ? b : c; }
+
+// one lane per row of matrix blockIdx.y: the degree of every column it touches
+__global__ __launch_bounds__(256) void k_col_count(QapCsr M, uint32_t C, uint32_t *cnt_a, uint32_t *cnt_b, uint32_t *cnt_c) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, k = blockIdx.y;
+    if (i >= C) return;
+    const uint32_t *rp = pick3(k, M.a_rp, M.b_rp, M.c_rp), *col = pick3(k, M.a_col, M.b_col, M.c_col);
+    uint32_t *cnt = pick3(k, cnt_a, cnt_b, cnt_c);
+    for (uint32_t e = rp[i]; e < rp[i + 1]; ++e) atomicAdd(cnt + col[e], 1u);
+}
+// one workgroup per matrix: cnt[0, cols) -> its exclusive prefix sums, in place and into the cursors, and the total at cnt[cols].  Every lane
+// owns a run of consecutive columns; the 1024 run sums are scanned in LDS
+__global__ __launch_bounds__(1024) void k_col_scan(uint32_t *cnt_a, uint32_t *cnt_b, uint32_t *cnt_c, uint32_t *cur, size_t cols) {
+    __shared__ uint32_t sums[1024];
+    const uint32_t tid = threadIdx.x, k = blockIdx.x;
+    uint32_t *cnt = pick3(k, cnt_a, cnt_b, cnt_c);
+    cur += k * cols;
+    const size_t per = (cols + 1023) / 1024, lo = std::min((size_t)tid * per, cols), hi = std::min(lo + per, cols);
+    uint32_t own = 0;
+    for (size_t j = lo; j < hi; ++j) own += cnt[j];
+    sums[tid] = own;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024; d <<= 1) {
+        const uint32_t v = tid >= d ? sums[tid - d] : 0;
+        __syncthreads();
+        sums[tid] += v;
+        __syncthreads();
+    }
+    uint32_t run = sums[tid] - own;
+    for (size_t j = lo; j < hi; ++j) { const uint32_t c = cnt[j]; cnt[j] = run; cur[j] = run; run += c; }
+    if (tid == 1023) cnt[cols] = sums[1023];
+}
+// the rows again: every entry takes the next place of its column
+__global__ __launch_bounds__(256) void k_col_scatter(QapCsr M, uint32_t C, uint32_t *cur, size_t cols, uint2 *ent_a, uint2 *ent_b, uint2 *ent_c) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, k = blockIdx.y;
+    if (i >= C) return;
+    const uint32_t *rp = pick3(k, M.a_rp, M.b_rp, M.c_rp), *col = pick3(k, M.a_col, M.b_col, M.c_col);
+    uint2 *ent = pick3(k, ent_a, ent_b, ent_c);
+    cur += k * cols;
+    for (uint32_t e = rp[i]; e < rp[i + 1]; ++e) ent[atomicAdd(cur + col[e], 1u)] = make_uint2(i, e);
+}
+// the list of the long columns' segments: a column above LONG_COLUMN terms takes ceil(degree / seg) consecutive entries (`counter` hands them
+// out: the list's order is the atomics' too).  Entry e's partial sum is partial e, a column's partials lie side by side.
+__global__ __launch_bounds__(256) void k_col_segments(const uint32_t *cp_a, const uint32_t *cp_b, const uint32_t *cp_c, size_t cols, uint32_t seg, ColSeg *list, uint32_t cap, uint32_t *counter) {
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; const uint32_t k = blockIdx.y;
+    if (j >= cols) return;
+    const uint32_t *cp = pick3(k, cp_a, cp_b, cp_c);
+    const uint32_t lo = cp[j], hi = cp[j + 1];
+    if (hi - lo <= LONG_COLUMN) return;
+    const uint32_t nseg = (hi - lo + seg - 1) / seg, base = atomicAdd(counter, nseg);
+    for (uint32_t s = 0; s < nseg && base + s < cap; ++s)
+        list[base + s] = ColSeg{(k << 30) | (uint32_t)j, lo + s * seg, std::min(lo + (s + 1) * seg, hi), s == 0 ? nseg : 0u};
+}
+
+ZK_D Fr wave_sum(Fr acc) {                            // the shuffle reduction of r1cs_long_entry: every lane ends with the wavefront's sum
+    for (int d = 32; d >= 1; d >>= 1) {
+        Fr o;
+        for (int j = 0; j < 8; ++j) o.v[j] = __shfl_xor(acc.v[j], d, 64);
+        acc += o;
+    }
+    return acc;
+}
+// one lane per column of matrix blockIdx.y (vector k at abc + k * stride); the columns above LONG_COLUMN terms are k_qap_columns_close's.  The
+// input-consistency rows C .. C + l of A (one term each, u[C + j] into column j) are added here, not by a pass of their own.
+__global__ __launch_bounds__(256) void k_qap_columns(QapCsc M, const Fr *u, size_t cols, uint32_t C, uint32_t l, Fr *abc, size_t stride) {
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; const uint32_t k = blockIdx.y;
+    if (j >= cols) return;
+    const uint32_t *cp = pick3(k, M.a_cp, M.b_cp, M.c_cp); const uint2 *ent = pick3(k, M.a_ent, M.b_ent, M.c_ent); const Fr *val = pick3(k, M.a_val, M.b_val, M.c_val);
+    const uint32_t lo = cp[j], hi = cp[j + 1];
+    if (hi - lo > LONG_COLUMN) return;
+    Fr acc = (k == 0 && j <= l) ? u[C + j] : Fr::zero();
+    for (uint32_t e = lo; e < hi; ++e) { const uint2 t = ent[e]; acc += val[t.y] * u[t.x]; }
+    abc[k * stride + j] = acc.normalized();
+}
+// one wavefront per segment: lanes stride over its terms
+__global__ __launch_bounds__(256) void k_qap_columns_long(const ColSeg *list, uint32_t n_seg, QapCsc M, const Fr *u, Fr *part) {
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+    if (wave >= n_seg) return;
+    const ColSeg g = list[wave]; const uint32_t k = g.key >> 30;
+    const uint2 *ent = pick3(k, M.a_ent, M.b_ent, M.c_ent); const Fr *val = pick3(k, M.a_val, M.b_val, M.c_val);
+    Fr acc = Fr::zero();
+    for (uint32_t e = g.lo + lane; e < g.hi; e += 64) { const uint2 t = ent[e]; acc += val[t.y] * u[t.x]; }
+    acc = wave_sum(acc);
+    if (lane == 0) part[wave] = acc.normalized();
+}
+// the closing launch: one wavefront per long column (the list entry of its first segment) sums the column's partials, so no chain grows with
+// the column; the entries of later segments have nothing to do
+__global__ __launch_bounds__(256) void k_qap_columns_close(const ColSeg *list, uint32_t n_seg, const Fr *part, const Fr *u, uint32_t C, uint32_t l, Fr *abc, size_t stride) {
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+    if (wave >= n_seg) return;
+    const ColSeg g = list[wave];
+    if (!g.nseg) return;
+    Fr acc = Fr::zero();
+    for (uint32_t s = lane; s < g.nseg; s += 64) acc += part[wave + s];
+    acc = wave_sum(acc);
+    const uint32_t k = g.key >> 30, j = g.key & 0x3fffffffu;
+    if (lane != 0) return;
+    if (k == 0 && j <= l) acc += u[C + j];
+    abc[k * stride + j] = acc.normalized();
+}
+
+static constexpr size_t QAP_WORKSPACE_CAP = (size_t)1 << 30;                   // one launch group's workspace stays at or under this (one witness is always taken)
 static constexpr size_t QAP_BYTES_PER_ELEMENT = 3 * sizeof(Fr) + 3 * NTT_SCRATCH_BYTES;   // aA | aB | aC and the scratch of their three transforms: 216
 static constexpr size_t QAP_MAX_GROUP = 65535 / 3;                              // grid.y of the batched transforms carries 3 g vectors
 
@@ -92,10 +204,18 @@ struct zkg_qap {
     DevBuf ws;                                      // a group's aA | aB | aC (3 g m Fr), then the transforms' scratch (3 g m records of 40 bytes)
     hipEvent_t ev = nullptr; bool pending = false; hipStream_t last = nullptr;   // behind the last call's last kernel, on the stream it named
     size_t bmax_default = 1, bmax = 1;
-    void release() { for (DevBuf *b : {&rp[0], &rp[1], &rp[2], &col[0], &col[1], &col[2], &val[0], &val[1], &val[2], &long_rows, &coset_over_m, &coset_over_m29, &ws}) b->release(); }
+    // the instance map's column index, made by the first zkg_qap_instance_async: column pointers (n + 2) and (row, position in val) per entry
+    size_t nnz[3] = {0, 0, 0};
+    DevBuf cp[3], ent[3], seg_list, seg_counter; bool indexed = false;
+    uint32_t seg_len = COLUMN_SEGMENT, seg_built = 0, n_seg = 0;   // the list holds n_seg segments of at most seg_built terms
+    void release() {
+        for (DevBuf *b : {&rp[0], &rp[1], &rp[2], &col[0], &col[1], &col[2], &val[0], &val[1], &val[2], &long_rows, &coset_over_m, &coset_over_m29, &ws,
+                          &cp[0], &cp[1], &cp[2], &ent[0], &ent[1], &ent[2], &seg_list, &seg_counter}) b->release();
+    }
 };
 
 static thread_local size_t t_qap_stats[3];
+static thread_local size_t t_qap_instance_stats[2];
 
 static int qap_upload(DevBuf &d, const void *src, size_t bytes) {
     if (d.reserve(bytes ? bytes : 16)) return ZKG_ERROR;
@@ -144,6 +264,7 @@ static zkg_qap *qap_new_impl(const zkg_r1cs *cs) {
     q->bmax_default = q->bmax = std::max<size_t>(1, std::min(QAP_MAX_GROUP, QAP_WORKSPACE_CAP / (m * QAP_BYTES_PER_ELEMENT)));
     for (uint32_t mtx = 0; mtx < 3; ++mtx) {
         const size_t nnz = rps[mtx][C];
+        q->nnz[mtx] = nnz;
         if (qap_upload(q->rp[mtx], rps[mtx], ((size_t)C + 1) * 4) || qap_upload(q->col[mtx], cols[mtx], nnz * 4) || qap_upload(q->val[mtx], vals[mtx], nnz * 32)) return nullptr;
     }
     q->n_long = (uint32_t)lr.size();
@@ -243,6 +364,89 @@ static int qap_witness_h_async_impl(zkg_qap *q, const void *d_witnesses, size_t 
     return ZKG_ERROR;
 }
 
+// The column index and the segment list, on s, under the handle's mutex.  The first call builds both and waits for them once (the list's length
+// comes back with that wait); a call after zkg_qap_set_column_segment rebuilds the list alone, behind the handle's pending work (which reads it).
+static int qap_index(zkg_qap *q, hipStream_t s, size_t &builds, size_t &waits) {
+    static const char *who = "zkg_qap_instance_async";
+    if (q->indexed && q->seg_built == q->seg_len) return ZKG_OK;
+    const size_t cols = (size_t)q->n + 1; const uint32_t C = q->C;
+    const QapCsr M = {q->rp[0].as<uint32_t>(), q->col[0].as<uint32_t>(), q->val[0].as<Fr>(), q->rp[1].as<uint32_t>(), q->col[1].as<uint32_t>(), q->val[1].as<Fr>(),
+                      q->rp[2].as<uint32_t>(), q->col[2].as<uint32_t>(), q->val[2].as<Fr>()};
+    ScopedDevBuf cur;                                                   // the scatter's cursors: gone after the wait below
+    const bool build = !q->indexed;
+    if (build) {
+        if (cur.reserve(3 * cols * 4) || q->seg_counter.reserve(4)) return ZKG_ERROR;
+        for (int k = 0; k < 3; ++k) {
+            if (q->cp[k].reserve((cols + 1) * 4) || q->ent[k].reserve(std::max<size_t>(q->nnz[k], 1) * sizeof(uint2))) return ZKG_ERROR;
+            ZK_HIP(hipMemsetAsync(q->cp[k].p, 0, (cols + 1) * 4, s));
+        }
+        const dim3 rows((C + 255) / 256, 3);
+        hipLaunchKernelGGL(k_col_count, rows, dim3(256), 0, s, M, C, q->cp[0].as<uint32_t>(), q->cp[1].as<uint32_t>(), q->cp[2].as<uint32_t>());
+        hipLaunchKernelGGL(k_col_scan, dim3(3), dim3(1024), 0, s, q->cp[0].as<uint32_t>(), q->cp[1].as<uint32_t>(), q->cp[2].as<uint32_t>(), cur.as<uint32_t>(), cols);
+        hipLaunchKernelGGL(k_col_scatter, rows, dim3(256), 0, s, M, C, cur.as<uint32_t>(), cols, q->ent[0].as<uint2>(), q->ent[1].as<uint2>(), q->ent[2].as<uint2>());
+    } else if (q->pending) {
+        ZK_HIP(hipEventSynchronize(q->ev));
+    }
+    // a long column has more than LONG_COLUMN terms and ceil(degree / seg) <= degree / seg + 1 segments
+    size_t cap = 0;
+    for (int k = 0; k < 3; ++k) cap += q->nnz[k] / (LONG_COLUMN + 1) + q->nnz[k] / q->seg_len;
+    if (cap >= ((size_t)1 << 31)) { set_error(std::string(who) + ": too many column segments"); return ZKG_ERROR; }
+    uint32_t n_seg = 0;
+    if (q->seg_list.reserve(std::max<size_t>(cap, 1) * sizeof(ColSeg))) return ZKG_ERROR;
+    ZK_HIP(hipMemsetAsync(q->seg_counter.p, 0, 4, s));
+    hipLaunchKernelGGL(k_col_segments, dim3((unsigned)((cols + 255) / 256), 3), dim3(256), 0, s, q->cp[0].as<uint32_t>(), q->cp[1].as<uint32_t>(), q->cp[2].as<uint32_t>(), cols,
+                       q->seg_len, q->seg_list.as<ColSeg>(), (uint32_t)cap, q->seg_counter.as<uint32_t>());
+    if (hipGetLastError() != hipSuccess) { set_error(std::string(who) + ": kernel launch failed"); (void)hipStreamSynchronize(s); return ZKG_ERROR; }
+    const bool landed = hip_ok(hipMemcpyAsync(&n_seg, q->seg_counter.p, 4, hipMemcpyDeviceToHost, s), "D2H", __FILE__, __LINE__);
+    if (!hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize", __FILE__, __LINE__) || !landed) return ZKG_ERROR;   // the cursors are freed behind this
+    ++waits;
+    if (n_seg > cap) { set_error(std::string(who) + ": the segment list overran its bound"); return ZKG_ERROR; }
+    if (build) { q->indexed = true; ++builds; }
+    q->n_seg = n_seg; q->seg_built = q->seg_len;
+    return ZKG_OK;
+}
+static int qap_instance_async_impl(zkg_qap *q, const uint64_t *t, void *d_abc, size_t stride, void *d_z, void *stream) {
+    static const char *who = "zkg_qap_instance_async";
+    for (size_t &v : t_qap_instance_stats) v = 0;
+    if (initialised_device() < 0) { set_error("zkg_init not called"); return ZKG_ERROR; }
+    if (!q || !t || !d_abc) { set_error(std::string(who) + ": bad argument (null handle or pointer)"); return ZKG_ERROR; }
+    const size_t cols = (size_t)q->n + 1, m = q->sh.m;
+    if (cols >= ((size_t)1 << 30)) { set_error(std::string(who) + ": too many variables"); return ZKG_ERROR; }
+    if (async_vectors_refused(who, cols, "n + 1", stride, 3, q->device, "the handle was made on")) return ZKG_ERROR;
+    const size_t abc_bytes = (2 * stride + cols) * 32;
+    if (dev_range_refused(d_abc, abc_bytes, 16, q->device, who, "d_abc", "handle") || (d_z && dev_range_refused(d_z, 32, 16, q->device, who, "d_z", "handle"))) return ZKG_ERROR;
+    if (d_z && ranges_overlap(d_abc, abc_bytes, d_z, 32)) { set_error(std::string(who) + ": the output ranges overlap"); return ZKG_ERROR; }
+    Fr tf; memcpy(tf.v, t, 32);                                         // read now: the caller may reuse t on return
+    if (domain_vanishing_at(q->sh, tf).is_zero()) { set_error(std::string(who) + ": t is a domain point (Z(t) = 0)"); return ZKG_ERROR; }
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk(q->mu);                              // held for the enqueue (and the first call's one wait)
+    size_t builds = 0, waits = 0;
+    auto leave = [&](int rc) { t_qap_instance_stats[0] = builds; t_qap_instance_stats[1] = waits; return rc; };
+    if (qap_index(q, s, builds, waits)) return leave(ZKG_ERROR);
+    // u (m Fr), then the segments' partial sums, in the workspace the H calls use: grown and ordered by their rules
+    const size_t need = (m + q->n_seg) * sizeof(Fr);
+    if (need > q->ws.cap) {
+        if (q->pending && !hip_ok(hipEventSynchronize(q->ev), "hipEventSynchronize", __FILE__, __LINE__)) return leave(ZKG_ERROR);
+        if (q->ws.reserve(need)) return leave(ZKG_ERROR);
+        ++waits;
+    }
+    if (q->pending && s != q->last && !hip_ok(hipStreamWaitEvent(s, q->ev, 0), "hipStreamWaitEvent", __FILE__, __LINE__)) return leave(ZKG_ERROR);
+    Fr *u = q->ws.as<Fr>(), *part = u + m, *abc = (Fr *)d_abc;
+    if (domain_lagrange_dev(q->sh, tf, u, (Fr *)d_z, s)) return leave(ZKG_ERROR);
+    const QapCsc M = {q->cp[0].as<uint32_t>(), q->ent[0].as<uint2>(), q->val[0].as<Fr>(), q->cp[1].as<uint32_t>(), q->ent[1].as<uint2>(), q->val[1].as<Fr>(),
+                      q->cp[2].as<uint32_t>(), q->ent[2].as<uint2>(), q->val[2].as<Fr>()};
+    hipLaunchKernelGGL(k_qap_columns, dim3((unsigned)((cols + 255) / 256), 3), dim3(256), 0, s, M, (const Fr *)u, cols, q->C, q->l, abc, stride);
+    if (q->n_seg) {
+        const dim3 waves((q->n_seg + 3) / 4);
+        hipLaunchKernelGGL(k_qap_columns_long, waves, dim3(256), 0, s, q->seg_list.as<ColSeg>(), q->n_seg, M, (const Fr *)u, part);
+        hipLaunchKernelGGL(k_qap_columns_close, waves, dim3(256), 0, s, q->seg_list.as<ColSeg>(), q->n_seg, (const Fr *)part, (const Fr *)u, q->C, q->l, abc, stride);
+    }
+    const bool launched = hipGetLastError() == hipSuccess;
+    if (hipEventRecord(q->ev, s) == hipSuccess) { q->pending = true; q->last = s; }      // whatever was enqueued still runs
+    if (!launched) { set_error(std::string(who) + ": kernel launch failed"); return leave(ZKG_ERROR); }
+    return leave(ZKG_OK);
+}
+
 extern "C" {
 
 zkg_qap *zkg_qap_new(const zkg_r1cs *cs) { return c_boundary<zkg_qap *>("zkg_qap_new", nullptr, [&] { return qap_new_impl(cs); }); }
@@ -261,5 +465,17 @@ int zkg_qap_witness_h_async(zkg_qap *q, const void *d_witnesses, size_t stride, 
     return c_boundary("zkg_qap_witness_h_async", ZKG_ERROR, [&] { return qap_witness_h_async_impl(q, d_witnesses, stride, count, d_h, h_stride, d_unsat, stream); });
 }
 void zkg_qap_stats(size_t out[3]) { if (out) for (int i = 0; i < 3; ++i) out[i] = t_qap_stats[i]; }
+int zkg_qap_instance_async(zkg_qap *q, const uint64_t t[4], void *d_abc, size_t stride, void *d_z, void *stream) {
+    return c_boundary("zkg_qap_instance_async", ZKG_ERROR, [&] { return qap_instance_async_impl(q, t, d_abc, stride, d_z, stream); });
+}
+void zkg_qap_set_column_segment(zkg_qap *q, size_t k) {
+    if (!q) return;
+    c_boundary("zkg_qap_set_column_segment", 0, [&] {
+        std::lock_guard<std::mutex> lk(q->mu);
+        q->seg_len = k == 0 ? COLUMN_SEGMENT : (uint32_t)std::min<size_t>(std::max<size_t>(k, COLUMN_SEGMENT_MIN), (size_t)1 << 20);
+        return 0;
+    });
+}
+void zkg_qap_instance_stats(size_t out[2]) { if (out) for (int i = 0; i < 2; ++i) out[i] = t_qap_instance_stats[i]; }
 
 }  // extern "C"

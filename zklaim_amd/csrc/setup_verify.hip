@@ -71,21 +71,32 @@ void copy_csr(std::vector<uint32_t> &rp, std::vector<uint32_t> &col, std::vector
     val.assign(s_val, s_val + 4 * nnz);
 }
 
+// the scalars of one fixed-base batch: a host vector (uploaded by the batch), or n Montgomery Fr that already lie on the device
+// (zkg_groth16_setup_dev: computed there by work queued on the null stream, which is where the batches run)
+struct Scalars {
+    const std::vector<Fr> *host = nullptr; const Fr *dev = nullptr; size_t n = 0;
+    Scalars(const std::vector<Fr> &v) : host(&v), n(v.size()) {}
+    Scalars(const Fr *d, size_t count) : dev(d), n(count) {}
+    size_t size() const { return n; }
+};
+
 template <class A, class FN>
-int batch_points(FN fixed_base_fn, const A &base, const std::vector<Fr> &scalars, std::vector<A> &out) {
+int batch_points(FN fixed_base_fn, const A &base, const Scalars &scalars, std::vector<A> &out) {
     size_t n = scalars.size();
     out.resize(n);
     if (!n) return ZKG_OK;
     static_assert(sizeof(Fr) == 32, "Fr is the 32-byte Montgomery element the kernel reads");
     DevBuf d_s, d_o;
-    if (d_s.reserve(n * 32) || d_o.reserve(n * sizeof(A))) return ZKG_ERROR;
+    if ((scalars.host && d_s.reserve(n * 32)) || d_o.reserve(n * sizeof(A))) return ZKG_ERROR;
     int rc = ZKG_ERROR;                                    // Montgomery scalars go up as they are: the kernel converts (no host pass)
-    if (hip_ok(hipMemcpy(d_s.p, scalars.data(), n * 32, hipMemcpyHostToDevice), "H2D", __FILE__, __LINE__) &&
-        fixed_base_fn(base, d_s.as<uint32_t>(), n, d_o.as<A>(), nullptr, true) == ZKG_OK &&
+    if ((!scalars.host || hip_ok(hipMemcpy(d_s.p, scalars.host->data(), n * 32, hipMemcpyHostToDevice), "H2D", __FILE__, __LINE__)) &&
+        fixed_base_fn(base, scalars.host ? d_s.as<uint32_t>() : reinterpret_cast<const uint32_t *>(scalars.dev), n, d_o.as<A>(), nullptr, true) == ZKG_OK &&
         hip_ok(hipMemcpy(out.data(), d_o.p, n * sizeof(A), hipMemcpyDeviceToHost), "D2H", __FILE__, __LINE__)) rc = ZKG_OK;
     d_s.release(); d_o.release();
     return rc;
 }
+template <class A, class FN>
+int batch_points(FN fixed_base_fn, const A &base, const std::vector<Fr> &scalars, std::vector<A> &out) { return batch_points(fixed_base_fn, base, Scalars(scalars), out); }
 
 // the same batch with its result left on the device
 template <class A, class FN>
@@ -108,6 +119,15 @@ G2Affine g2_generator() {
 }
 void fr_limbs(const Fr &x, uint32_t out[8]) { Fr c = x.from_mont(); memcpy(out, c.v, 32); }
 
+// zkg_groth16_setup_dev: out[j] = (beta At[j] + alpha Bt[j] + Ct[j]) * (j <= l ? 1 / gamma : 1 / delta) over At | Bt | Ct, `stride` elements
+// apart — the IC scalars, then the L query's, back to back
+__global__ __launch_bounds__(256) void k_setup_abc_scalars(const Fr *abc, size_t stride, size_t cols, uint32_t l, Fr alpha, Fr beta, Fr ginv, Fr dinv, Fr *out) {
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= cols) return;
+    const Fr v = beta * abc[j] + alpha * abc[stride + j] + abc[2 * stride + j];
+    out[j] = (v * (j <= l ? ginv : dinv)).normalized();
+}
+
 }  // namespace
 
 extern "C" {
@@ -119,7 +139,8 @@ extern "C" {
 // begins (kp holds the constraint system it will store) — the seam starts writing the pk blob's constraint rows there; before_delete()
 // runs before a failing generator deletes kp (whatever after_csr started must have let go of it).
 static zkg_keypair *groth16_setup_impl(const zkg_r1cs *cs, const uint64_t *trapdoor, OwnedCsr *owned, const std::function<void()> &under_gpu, bool keep_on_device = false,
-                                       const std::function<void(zkg_keypair *)> &after_csr = nullptr, const std::function<void()> &before_delete = nullptr) {
+                                       const std::function<void(zkg_keypair *)> &after_csr = nullptr, const std::function<void()> &before_delete = nullptr,
+                                       bool dev_scalars = false) {
     if (!cs || (!owned && (!cs->a_rowptr || !cs->b_rowptr || !cs->c_rowptr))) { set_error("zkg_groth16_setup: null constraint system"); return nullptr; }
     zkg_keypair *kp = new zkg_keypair();
     static const bool dbg = getenv("ZKG_DEBUG_TIMING") != nullptr;
@@ -154,12 +175,36 @@ static zkg_keypair *groth16_setup_impl(const zkg_r1cs *cs, const uint64_t *trapd
     if (trapdoor) { t = fr_from_canonical(trapdoor); alpha = fr_from_canonical(trapdoor + 4); beta = fr_from_canonical(trapdoor + 8); gamma = fr_from_canonical(trapdoor + 12); delta = fr_from_canonical(trapdoor + 16); }
     else { t = random_fr(); alpha = random_fr(); beta = random_fr(); gamma = random_fr(); delta = random_fr(); }
     lap("copy + swap");
+    std::vector<Fr> At, Bt, Ct, Hs, Ls, ICs;                               // the scalars on the host ...
+    ScopedDevBuf d_scalars;                                                // ... or (dev_scalars) on the device: At | Bt | Ct | t^i Z(t) / delta | IC, L
+    if (dev_scalars) {
+        // ---- zkg_groth16_setup_dev: the instance map on a zkg_qap handle over the system as it is stored (swapped or not), H's scalars from
+        //      powers_table, IC's and L's from one kernel — all queued on the null stream, where the fixed-base batches follow them
+        if (keep_on_device) { set_error("zkg_groth16_setup_dev: no device-resident key"); return drop(); }
+        zkg_r1cs view; memset(&view, 0, sizeof(view));
+        view.num_variables = kp->n; view.num_inputs = kp->l; view.num_constraints = kp->C;
+        view.a_rowptr = kp->rp[0].data(); view.a_col = kp->col[0].data(); view.a_val = kp->val[0].data();
+        view.b_rowptr = kp->rp[1].data(); view.b_col = kp->col[1].data(); view.b_val = kp->val[1].data();
+        view.c_rowptr = kp->rp[2].data(); view.c_col = kp->col[2].data(); view.c_val = kp->val[2].data();
+        std::unique_ptr<zkg_qap, void (*)(zkg_qap *)> qap(zkg_qap_new(&view), zkg_qap_free);
+        if (!qap) return drop();
+        lap("qap handle");
+        if (d_scalars.reserve((4 * (n + 1) + (m - 1)) * sizeof(Fr))) return drop();
+        Fr *d_abc = d_scalars.as<Fr>(), *d_h = d_abc + 3 * (n + 1), *d_icl = d_h + (m - 1);
+        if (zkg_qap_instance_async(qap.get(), reinterpret_cast<const uint64_t *>(t.v), d_abc, n + 1, nullptr, nullptr)) return drop();   // refuses a t on the domain
+        const Fr dinv = delta.inverse(), ginv = gamma.inverse(), zd = domain_vanishing_at(shape, t) * dinv;
+        if (powers_table(d_h, m - 1, t, zd, nullptr)) { set_error("zkg_groth16_setup_dev: kernel launch failed"); return drop(); }   // t^i Z(t) / delta
+        hipLaunchKernelGGL(k_setup_abc_scalars, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, nullptr, (const Fr *)d_abc, n + 1, n + 1, (uint32_t)l, alpha, beta, ginv, dinv, d_icl);
+        if (hipGetLastError() != hipSuccess) { set_error("zkg_groth16_setup_dev: kernel launch failed"); return drop(); }
+        if (dbg) (void)hipStreamSynchronize(nullptr);                      // the lap then holds the kernels, not their enqueue
+        lap("qap instance + scalars (device)");
+    } else {
     // ---- Lagrange coefficients u_i = L_i(t) and Z(t) on the chosen domain (closed forms, one batched inversion)
     Fr Zt; std::vector<Fr> u;
     if (domain_lagrange(shape, t, u, Zt)) return drop();
     lap("lagrange");
     // ---- QAP polynomials at t (r1cs_to_qap_instance_map_with_evaluation)
-    std::vector<Fr> At(n + 1, Fr::zero()), Bt(n + 1, Fr::zero()), Ct(n + 1, Fr::zero());
+    At.assign(n + 1, Fr::zero()); Bt.assign(n + 1, Fr::zero()); Ct.assign(n + 1, Fr::zero());
     for (size_t i = 0; i <= l; ++i) At[i] = u[C + i];
     std::vector<Fr> *dst[3] = {&At, &Bt, &Ct};
     host_parallel_for(3, [&](int k) {                                       // the three matrices accumulate into separate vectors
@@ -172,7 +217,7 @@ static zkg_keypair *groth16_setup_impl(const zkg_r1cs *cs, const uint64_t *trapd
             }
     });
     Fr dinv = delta.inverse(), ginv = gamma.inverse();
-    std::vector<Fr> Hs(m - 1), Ls(n - l), ICs(l + 1);
+    Hs.resize(m - 1); Ls.resize(n - l); ICs.resize(l + 1);
     auto chunked = [&](size_t count, const std::function<void(size_t, size_t)> &f) {           // [0, count) in chunks on the host pool
         const int chunks = (int)std::min<size_t>(64, (count + 8191) / 8192);
         if (chunks <= 1) { f(0, count); return; }
@@ -189,6 +234,12 @@ static zkg_keypair *groth16_setup_impl(const zkg_r1cs *cs, const uint64_t *trapd
         }
     });
     lap("qap evaluation + scalars");
+    }
+    // one batch's scalars from either side: the host vector, or `count` elements at `offset` of the device buffer (the layout above)
+    auto scalars_of = [&](const std::vector<Fr> &host, size_t offset, size_t count) { return dev_scalars ? Scalars(d_scalars.as<Fr>() + offset, count) : Scalars(host); };
+    const size_t h_at = 3 * (n + 1), icl_at = h_at + (m - 1);
+    const Scalars sAt = scalars_of(At, 0, n + 1), sBt = scalars_of(Bt, n + 1, n + 1), sHs = scalars_of(Hs, h_at, m - 1), sICs = scalars_of(ICs, icl_at, l + 1),
+                  sLs = scalars_of(Ls, icl_at + l + 1, n - l);
     // ---- scalars -> points (GPU fixed-base batches).  The host pool is free from here on: what after_csr starts (the seam: the pk blob's
     //      constraint rows) shares it with nothing but the short page pre-faulting below (started earlier it made the Lagrange and QAP
     //      loops above run inline on this thread: 37 -> 90 ms)
@@ -212,13 +263,13 @@ static zkg_keypair *groth16_setup_impl(const zkg_r1cs *cs, const uint64_t *trapd
         if (!okd) return drop();
     } else {
     if (!no_prefault) host_parallel_for(5, [&](int i) {
-        if (i == 0) kp->B_g2.resize(Bt.size()); else if (i == 1) kp->A_query.resize(At.size()); else if (i == 2) kp->B_g1.resize(Bt.size());
-        else if (i == 3) kp->H_query.resize(Hs.size()); else kp->L_query.resize(Ls.size());
+        if (i == 0) kp->B_g2.resize(sBt.size()); else if (i == 1) kp->A_query.resize(sAt.size()); else if (i == 2) kp->B_g1.resize(sBt.size());
+        else if (i == 3) kp->H_query.resize(sHs.size()); else kp->L_query.resize(sLs.size());
     });
     bool ok = batch_points<G1Affine>(fixed_base_g1, g1, {alpha, beta, delta}, small1) == 0 && batch_points<G2Affine>(fixed_base_g2, g2, {beta, delta, gamma}, small2) == 0 &&
-              batch_points<G1Affine>(fixed_base_g1, g1, At, kp->A_query) == 0 && batch_points<G1Affine>(fixed_base_g1, g1, Bt, kp->B_g1) == 0 &&
-              batch_points<G2Affine>(fixed_base_g2, g2, Bt, kp->B_g2) == 0 && batch_points<G1Affine>(fixed_base_g1, g1, Hs, kp->H_query) == 0 &&
-              batch_points<G1Affine>(fixed_base_g1, g1, Ls, kp->L_query) == 0 && batch_points<G1Affine>(fixed_base_g1, g1, ICs, kp->IC) == 0;
+              batch_points<G1Affine>(fixed_base_g1, g1, sAt, kp->A_query) == 0 && batch_points<G1Affine>(fixed_base_g1, g1, sBt, kp->B_g1) == 0 &&
+              batch_points<G2Affine>(fixed_base_g2, g2, sBt, kp->B_g2) == 0 && batch_points<G1Affine>(fixed_base_g1, g1, sHs, kp->H_query) == 0 &&
+              batch_points<G1Affine>(fixed_base_g1, g1, sLs, kp->L_query) == 0 && batch_points<G1Affine>(fixed_base_g1, g1, sICs, kp->IC) == 0;
     if (!ok) return drop();
     }
     kp->alpha_g1 = small1[0]; kp->beta_g1 = small1[1]; kp->delta_g1 = small1[2];
@@ -243,6 +294,13 @@ static zkg_keypair *groth16_setup_impl(const zkg_r1cs *cs, const uint64_t *trapd
 }
 zkg_keypair *zkg_groth16_setup(const zkg_r1cs *cs, const uint64_t *trapdoor /* 5 x 4 canonical limbs: t, alpha, beta, gamma, delta; NULL = random */) {
     return groth16_setup_impl(cs, trapdoor, nullptr, nullptr);
+}
+// the same keypair with every scalar computed on the device (zkg_qap_instance_async, powers_table, k_setup_abc_scalars): no scalar vector on the host
+zkg_keypair *zkg_groth16_setup_dev(const zkg_r1cs *cs, const uint64_t *trapdoor) {
+    return c_boundary<zkg_keypair *>("zkg_groth16_setup_dev", nullptr, [&]() -> zkg_keypair * {
+        if (initialised_device() < 0) { set_error("zkg_init not called"); return nullptr; }
+        return groth16_setup_impl(cs, trapdoor, nullptr, nullptr, false, nullptr, nullptr, true);
+    });
 }
 
 void zkg_keypair_free(zkg_keypair *kp) { delete kp; }
