@@ -302,7 +302,7 @@ int zkg_msm_combine_gpu(const uint64_t *records_jac, size_t cpw, int slots /* 2|
  * zkg_msm_g2_resident_async: `count` vectors, vector i at d_scalars + i * stride * 32 bytes (stride >= n, 16-byte aligned; what lies between
  * n and the stride is never read), point i at d_out_jac + i * 24 limbs, normalised exactly as zkg_msm_g2_resident returns it: X | Y | one,
  * or (0, one, 0) for infinity, with one = (Montgomery one, 0).  The vectors are cut into groups of at most zkg_msm_g2_resident_batch_max; a
- * group shares one sort, accumulation, fold and reduction, and a one-workgroup kernel per point (k_msm_combine_g2) sums the reduction's chunk
+ * group shares one sort, accumulation, fold and reduction, and a one-workgroup kernel per point (k_msm_combine) sums the reduction's chunk
  * records and normalises on the device.  The call records an event behind its last kernel and makes `stream` wait for it; it makes no
  * host wait at a group size the handle has served before.  A buffer that must grow is freed only after the handle's stream has drained, and
  * each such drain is counted (zkg_msm_resident_async_stats); zkg_msm_g2_resident beside pending asynchronous calls takes the same care;

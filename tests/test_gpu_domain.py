@@ -121,6 +121,31 @@ def test_calls_follow_their_stream_and_each_other_across_streams(zkg, oracle, do
         torch.cuda.synchronize()
 
 
+def test_a_call_on_a_second_stream_that_grows_the_scratch_waits_once(zkg, oracle):
+    """m = 8, a fresh handle: one vector on one stream, then three on another — a larger group, so the scratch the first call may still be in
+    is freed and made anew behind one host wait.  Both calls give what they give alone on one stream"""
+    import torch
+    m = 8
+    vecs, want = reference(oracle, m)
+    dom = zkg.Domain(m)
+    try:
+        s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+        d1, d3 = _dev(vecs[0]), _dev(np.stack(vecs))
+        torch.cuda.synchronize()
+        dom.ntt_async(d1.data_ptr(), count=1, stream=s1.cuda_stream)
+        dom.ntt_async(d3.data_ptr(), count=3, stream=s2.cuda_stream)
+        assert zkg.domain_stats() == (3, 1, 1)
+        s2.synchronize()
+        got1, got3 = _host(d1), _host(d3)
+        torch.cuda.synchronize()
+        alone = _run(dom, [0, 1, 2], vecs, m, (0, 0))
+        assert zkg.domain_stats() == (3, 1, 0)
+        assert np.array_equal(got1, alone[0]) and np.array_equal(got3, alone)
+        assert np.array_equal(got3, np.stack(want[(0, 0)]))
+    finally:
+        dom.free()
+
+
 def test_counters_groups_and_the_empty_batch(zkg, oracle):
     """on a fresh handle the first call at a group size may wait (it allocates the scratch); the same call again does not; the groups are
     ceil(count / batch_max); an empty batch is ZKG_OK and touches nothing"""

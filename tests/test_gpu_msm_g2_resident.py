@@ -1,5 +1,5 @@
 """GPU parity: zkg_msm_g2_resident / zkg_msm_g2_resident_async (fixed G2 bases kept with their per-window tables; batched, the points left in
-device memory by the one-workgroup epilogue kernel k_msm_combine_g2) against zkg_msm_g2_dev on the plain bases and the oracle, bit for bit on
+device memory by the one-workgroup epilogue kernel k_msm_combine<Fq2, 128>) against zkg_msm_g2_dev on the plain bases and the oracle, bit for bit on
 the normalised point; the stream-order contract, the refusals, and the epilogue kernel alone (zkg_msm_combine_g2_gpu) against the chunk-sum
 formula in integers and one oracle scalar multiplication."""
 import numpy as np
@@ -319,10 +319,10 @@ def _combine_case(zkg, oracle, multiples, mult, cpw, chunk_log, vectors):
 
 @pytest.mark.parametrize("vectors", [1, 3])
 @pytest.mark.parametrize("chunk_log", [0, 5])
-@pytest.mark.parametrize("cpw", [1, 2, 16, 17, 64, 129, 257, 600])
+@pytest.mark.parametrize("cpw", [1, 2, 16, 17, 64, 128, 129, 257, 600])
 def test_the_epilogue_kernel_matches_the_chunk_sum_formula(zkg, oracle, multiples, cpw, chunk_log, vectors):
-    """cpw up to 64: one chunk per lane at 1 ... 64 of the kernel's 128 lanes; 129, 257 and 600: two, four and eight chunks per lane (more
-    chunks than the kernel has lanes).  Records are multiples -40 ... 40 of the generator with about one in six at infinity."""
+    """cpw up to 128: one chunk per lane at 1 ... 128 of the kernel's 128 lanes (128: the last such shape); 129, 257 and 600: two, four and
+    eight chunks per lane (more chunks than the kernel has lanes).  Records are multiples -40 ... 40 of the generator with about one in six at infinity."""
     rng = np.random.default_rng(1000 * cpw + 10 * chunk_log + vectors)
     mult = rng.integers(-40, 41, (vectors, cpw, 2))
     mult[rng.integers(0, 6, mult.shape) == 0] = 0

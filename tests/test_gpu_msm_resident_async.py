@@ -298,9 +298,10 @@ def _combine_case(zkg, oracle, mult, cpw, slots, chunk_log, vectors):
 @pytest.mark.parametrize("vectors", [1, 3])
 @pytest.mark.parametrize("chunk_log", [0, 5])
 @pytest.mark.parametrize("slots", [2, 3])
-@pytest.mark.parametrize("cpw", [1, 2, 16, 17, 64, 257, 600])
+@pytest.mark.parametrize("cpw", [1, 2, 16, 17, 64, 128, 129, 256, 257, 600])
 def test_the_epilogue_kernel_matches_the_chunk_sum_formula(zkg, oracle, cpw, slots, chunk_log, vectors):
-    """cpw up to 64: one chunk per lane at 1 ... 64 lanes; 257 and 600: two and four chunks per lane (more chunks than the kernel has lanes).
+    """cpw up to 256: one chunk per lane at 1 ... 256 lanes (128 | 129: the step from 128 lanes to 256; 256: the last one-chunk-per-lane
+    shape); 257 and 600: two and four chunks per lane (more chunks than the kernel has lanes).
     Records are multiples -40 ... 40 of the generator with about one in six at infinity."""
     rng = np.random.default_rng(1000 * cpw + 100 * slots + 10 * chunk_log + vectors)
     mult = rng.integers(-40, 41, (vectors, cpw, slots))
@@ -324,3 +325,22 @@ def test_the_epilogue_kernel_on_equal_and_cancelling_records(zkg, oracle):
     mult = np.zeros((2, 17, 3), dtype=object); mult[1, 16, 2] = 1
     got = _combine_case(zkg, oracle, mult, 17, 3, 0, 2)
     assert np.array_equal(got[0], INF) and not np.array_equal(got[1], INF)
+
+
+@pytest.mark.parametrize("live", ["P and T", "A"])
+def test_the_A_term_is_neither_lost_nor_counted_twice(zkg, oracle, live):
+    """three-slot records at cpw 17 (a 32-lane workgroup with lanes behind the last chunk): the kernel finishes 8 A behind its chunk loop,
+    before the scan.  Every A at infinity: the point is the two-slot one.  Only A live: the point is 8 sum A."""
+    cpw, cl = 17, 5
+    rng = np.random.default_rng(317)
+    mult = rng.integers(1, 41, (2, cpw, 3))
+    if live == "A":
+        mult[:, :, :2] = 0
+        got = _combine_case(zkg, oracle, mult, cpw, 3, cl, 2)
+        for v in range(2):
+            total = 8 * int(mult[v, :, 2].sum())
+            assert np.array_equal(got[v], oracle.g1_scalar_mul(oracle.g1_generator(), np.array(limbs(total % R), np.uint64)))
+    else:
+        mult[:, :, 2] = 0
+        got = _combine_case(zkg, oracle, mult, cpw, 3, cl, 2)
+        assert np.array_equal(got, _combine_case(zkg, oracle, mult[:, :, :2], cpw, 2, cl, 2))

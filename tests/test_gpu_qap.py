@@ -313,6 +313,34 @@ def test_two_calls_on_two_streams_follow_each_other(zkg, systems):
     torch.cuda.synchronize()
 
 
+def test_a_call_on_a_second_stream_that_grows_the_workspace_waits_once(zkg, oracle):
+    """a fresh handle: one witness on one stream, then two on another — a larger group, so the workspace the first call may still be in is
+    freed and made anew behind one host wait.  Both calls give what they give alone on one stream, and the oracle's H"""
+    import torch
+    from qap_instance_systems import log10_system
+    s = System(zkg, oracle, *log10_system())
+    try:
+        n, m = s.n, s.m
+        names = [0, ("bad", 0)]
+        s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+        src1, src2 = _dev(s.witness(0)), _dev(np.stack([s.witness(k) for k in names]))
+        d_h1 = torch.full((1, m + 1, 4), FILL, dtype=torch.int64, device="cuda"); d_h2 = torch.full((2, m + 1, 4), FILL, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        s.qap.witness_h_async(src1.data_ptr(), 1, n, d_h1.data_ptr(), m + 1, 0, s1.cuda_stream)
+        s.qap.witness_h_async(src2.data_ptr(), 2, n, d_h2.data_ptr(), m + 1, 0, s2.cuda_stream)
+        assert zkg.qap_stats() == (2, 1, 1)
+        s2.synchronize()
+        got1, got2 = _host(d_h1).reshape(1, m + 1, 4), _host(d_h2).reshape(2, m + 1, 4)
+        torch.cuda.synchronize()
+        alone, _, stats = s.run(names)
+        assert stats == (2, 1, 0)
+        assert np.array_equal(got1[0], alone[0]) and np.array_equal(got2, alone)
+        for i, name in enumerate(names):
+            assert np.array_equal(got2[i], s.want(name)), name
+    finally:
+        s.qap.free()
+
+
 def test_refusals_write_nothing(zkg, systems):
     import torch
     s = systems("log10")

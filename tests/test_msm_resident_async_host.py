@@ -18,6 +18,7 @@ def _lib():
     L.zkg_msm_g1_resident_async.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
     L.zkg_msm_g1_resident_batch_max.restype = C.c_size_t
     L.zkg_msm_g1_resident_batch_max.argtypes = [C.c_void_p]
+    L.zkg_msm_g2_resident_async.argtypes = L.zkg_msm_g1_resident_async.argtypes
     return zklaim_amd, L
 
 
@@ -55,3 +56,46 @@ def test_a_null_handle_takes_no_vectors_and_an_empty_batch_is_ok():
     assert L.zkg_msm_g1_resident_async(None, None, 0, 0, 0, 0, out.ctypes.data, None) == zkg.OK
     assert (out == 0xA5A5A5A5A5A5A5A5).all()
     assert zkg.msm_resident_async_stats() == (0, 0, 0)
+
+
+def test_upload_returns_null_with_a_message_before_zkg_init_for_a_null_pointer_and_for_no_points():
+    import torch
+    zkg, L = _lib()
+    L.zkg_msm_g1_bases_upload.restype = C.c_void_p
+    L.zkg_msm_g1_bases_upload.argtypes = [C.c_void_p, C.c_size_t]
+    points = np.zeros(8, np.uint64)
+    cases = [(None, 1), (points.ctypes.data, 0)]
+    if not torch.cuda.is_available():
+        cases.append((points.ctypes.data, 1))                            # nothing wrong but the missing zkg_init (which no machine without a GPU can make)
+    for d_bases, n in cases:
+        assert L.zkg_msm_g2_resident_async(None, points.ctypes.data, 1, 1, 1, 0, points.ctypes.data, None) == zkg.ERROR   # another entry's message first
+        assert "zkg_msm_g1_bases_upload" not in L.zkg_last_error().decode()
+        assert L.zkg_msm_g1_bases_upload(d_bases, n) is None
+        msg = L.zkg_last_error().decode()
+        # (before zkg_init that is what is missing, whatever the arguments; after it the entry names itself)
+        assert "zkg_init" in msg or "zkg_msm_g1_bases_upload" in msg, msg
+        if not torch.cuda.is_available():
+            assert "zkg_init" in msg
+    assert (points == 0).all()
+
+
+def test_the_synchronous_call_on_a_null_handle_is_an_error_with_a_message_and_writes_nothing():
+    zkg, L = _lib()
+    L.zkg_msm_g1_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
+    scalars = np.zeros(4, np.uint64); out = np.full(12, 0xA5A5A5A5A5A5A5A5, np.uint64)
+    assert L.zkg_msm_g1_resident(None, scalars.ctypes.data, 1, 0, out.ctypes.data, None) == zkg.ERROR
+    msg = L.zkg_last_error().decode()
+    assert "zkg_init" in msg or "zkg_msm_g1_resident" in msg, msg
+    assert (out == 0xA5A5A5A5A5A5A5A5).all()
+
+
+def test_the_epilogue_hook_is_an_error_without_a_gpu():
+    import torch
+    zkg, L = _lib()
+    if torch.cuda.is_available():
+        return                                                          # (with a GPU the hook is tests/test_gpu_msm_resident_async.py's business)
+    L.zkg_msm_combine_gpu.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_void_p]
+    rec = np.zeros(2 * 12, np.uint64); out = np.full(12, 0xA5A5A5A5A5A5A5A5, np.uint64)
+    assert L.zkg_msm_combine_gpu(rec.ctypes.data, 1, 2, 0, 1, out.ctypes.data) == zkg.ERROR
+    assert L.zkg_last_error().decode()
+    assert (out == 0xA5A5A5A5A5A5A5A5).all()

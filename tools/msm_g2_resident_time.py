@@ -4,7 +4,7 @@
   (b) resident  a loop of `count` zkg_msm_g2_resident calls on the handle's per-window tables (zkg_msm_g2_bases_upload), each returning its
                 point to the host
   (c) async     ONE zkg_msm_g2_resident_async call over the `count` vectors (groups of zkg_msm_g2_resident_batch_max share a sort, an
-                accumulation, a fold and a reduction; the epilogue is k_msm_combine_g2 on the device), then ONE stream synchronisation
+                accumulation, a fold and a reduction; the epilogue is k_msm_combine on the device), then ONE stream synchronisation
 for n = 2^15 and 2^18 points and count = 1, 4 and the handle's batch_max (--logs, --counts; 0 stands for batch_max).  Host clock around the
 calls, scalars resident and everything allocated outside the clock; one warm-up of each leg, then --reps repetitions with the legs
 alternated; min / median / max per leg, in ms for all `count` vectors.  The points of the three legs are compared.  The figures are reported,

@@ -464,42 +464,57 @@ def msm_g1_host_scalars(d_bases, scalars_host_ptr, n, scalars_mont=False, stream
     return out
 
 
-class ResidentBases:
-    """zkg_msm_g1_bases_upload / zkg_msm_g1_resident: fixed G1 bases (device pointer, n affine points) kept with their per-window tables"""
+class _ResidentBases:
+    """zkg_msm_<group>_bases_upload / _resident / _resident_async / _resident_batch_max / _bases_free behind one class: _PREFIX is the entries'
+    common prefix (zkg_msm_g1, zkg_msm_g2), _LIMBS the 64-bit limbs of a normalised point (12, 24)"""
+    _PREFIX = None
+    _LIMBS = 0
+
+    def _fn(self, suffix, argtypes, restype=C.c_int):
+        fn = getattr(lib(), self._PREFIX + suffix)
+        fn.argtypes = argtypes; fn.restype = restype
+        return fn
 
     def __init__(self, d_bases, n):
-        lib().zkg_msm_g1_bases_upload.restype = C.c_void_p
-        lib().zkg_msm_g1_bases_upload.argtypes = [C.c_void_p, C.c_size_t]
-        self._h = lib().zkg_msm_g1_bases_upload(_vp(d_bases), C.c_size_t(n))
+        self._h = self._fn("_bases_upload", [C.c_void_p, C.c_size_t], C.c_void_p)(_vp(d_bases), C.c_size_t(n))
         if not self._h:
-            raise ZkgError("zkg_msm_g1_bases_upload failed: " + last_error())
+            raise ZkgError(self._PREFIX + "_bases_upload failed: " + last_error())
         self.n = n
 
     def msm(self, d_scalars, scalars_mont=False, stream=0):
         """`stream`: the HIP stream whose queued work produced d_scalars (0 = the null stream); the job is ordered behind it"""
-        out = np.zeros(12, np.uint64)
-        lib().zkg_msm_g1_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
-        _check(lib().zkg_msm_g1_resident(C.c_void_p(self._h), _vp(d_scalars), C.c_size_t(self.n), SCALARS_MONT if scalars_mont else 0, _p(out), _vp(stream)), "zkg_msm_g1_resident")
+        out = np.zeros(self._LIMBS, np.uint64)
+        fn = self._fn("_resident", [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p])
+        _check(fn(C.c_void_p(self._h), _vp(d_scalars), C.c_size_t(self.n), SCALARS_MONT if scalars_mont else 0, _p(out), _vp(stream)), self._PREFIX + "_resident")
         return out
 
     def msm_async(self, d_scalars_ptr, d_out_ptr, count=1, stride=None, scalars_mont=False, stream=0):
-        """zkg_msm_g1_resident_async: `count` vectors of n Fr, `stride` elements apart (default n), at the device address d_scalars_ptr; the
-        normalised points (12 limbs each) are written to the device address d_out_ptr by work that `stream` is made to wait for.  Returns
-        without waiting: synchronise `stream` before reading the points on the host."""
-        lib().zkg_msm_g1_resident_async.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
-        _check(lib().zkg_msm_g1_resident_async(C.c_void_p(self._h), _vp(d_scalars_ptr), C.c_size_t(self.n), C.c_size_t(self.n if stride is None else stride),
-                                               C.c_size_t(count), SCALARS_MONT if scalars_mont else 0, _vp(d_out_ptr), _vp(stream)), "zkg_msm_g1_resident_async")
+        """zkg_msm_g1_resident_async / zkg_msm_g2_resident_async: `count` vectors of n Fr, `stride` elements apart (default n), at the device
+        address d_scalars_ptr; the normalised points (12 limbs each for G1, 24 for G2) are written to the device address d_out_ptr by work that
+        `stream` is made to wait for.  Returns without waiting: synchronise `stream` before reading the points on the host."""
+        fn = self._fn("_resident_async", [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p])
+        _check(fn(C.c_void_p(self._h), _vp(d_scalars_ptr), C.c_size_t(self.n), C.c_size_t(self.n if stride is None else stride),
+                  C.c_size_t(count), SCALARS_MONT if scalars_mont else 0, _vp(d_out_ptr), _vp(stream)), self._PREFIX + "_resident_async")
 
     def batch_max(self):
-        """zkg_msm_g1_resident_batch_max: scalar vectors that share one launch sequence on this handle"""
-        lib().zkg_msm_g1_resident_batch_max.restype = C.c_size_t
-        lib().zkg_msm_g1_resident_batch_max.argtypes = [C.c_void_p]
-        return int(lib().zkg_msm_g1_resident_batch_max(C.c_void_p(self._h)))
+        """zkg_msm_g1_resident_batch_max / zkg_msm_g2_resident_batch_max: scalar vectors that share one launch sequence on this handle"""
+        return int(self._fn("_resident_batch_max", [C.c_void_p], C.c_size_t)(C.c_void_p(self._h)))
 
     def free(self):
         if self._h:
-            lib().zkg_msm_g1_bases_free.argtypes = [C.c_void_p]
-            lib().zkg_msm_g1_bases_free(C.c_void_p(self._h)); self._h = None
+            self._fn("_bases_free", [C.c_void_p], None)(C.c_void_p(self._h)); self._h = None
+
+
+class ResidentBases(_ResidentBases):
+    """zkg_msm_g1_bases_upload / zkg_msm_g1_resident: fixed G1 bases (device pointer, n affine points) kept with their per-window tables"""
+    _PREFIX = "zkg_msm_g1"
+    _LIMBS = 12
+
+
+class ResidentBasesG2(_ResidentBases):
+    """zkg_msm_g2_bases_upload / zkg_msm_g2_resident: fixed G2 bases (device pointer, n affine points of 16 limbs) kept with their per-window tables"""
+    _PREFIX = "zkg_msm_g2"
+    _LIMBS = 24
 
 
 def msm_resident_async_stats():
@@ -509,66 +524,27 @@ def msm_resident_async_stats():
     return tuple(int(v) for v in out)
 
 
-def msm_combine_gpu(records_jac, cpw, slots, chunk_log, vectors=1):
-    """zkg_msm_combine_gpu: the MSM's device epilogue alone.  records_jac: vectors x cpw x slots normalised G1 points (12 limbs) in the order
-    vector, chunk, slot; returns (vectors, 12) normalised points."""
+def _msm_combine(name, limbs, records_jac, cpw, slots, chunk_log, vectors, slot_args):
     rec = _u64(records_jac)
-    if rec.size != vectors * cpw * slots * 12:
-        raise ZkgError("msm_combine_gpu: records_jac must hold vectors x cpw x slots points of 12 limbs")
-    out = np.zeros((vectors, 12), np.uint64)
-    lib().zkg_msm_combine_gpu.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_void_p]
-    _check(lib().zkg_msm_combine_gpu(_p(rec), C.c_size_t(cpw), int(slots), int(chunk_log), C.c_size_t(vectors), _p(out)), "zkg_msm_combine_gpu")
+    if rec.size != vectors * cpw * slots * limbs:
+        raise ZkgError("%s: records_jac must hold vectors x cpw x %s points of %d limbs" % (name, "slots" if slot_args else slots, limbs))
+    out = np.zeros((vectors, limbs), np.uint64)
+    fn = getattr(lib(), "zkg_" + name)
+    fn.argtypes = [C.c_void_p, C.c_size_t] + [C.c_int] * len(slot_args) + [C.c_int, C.c_size_t, C.c_void_p]
+    _check(fn(_p(rec), C.c_size_t(cpw), *slot_args, int(chunk_log), C.c_size_t(vectors), _p(out)), "zkg_" + name)
     return out
 
 
-class ResidentBasesG2:
-    """zkg_msm_g2_bases_upload / zkg_msm_g2_resident: fixed G2 bases (device pointer, n affine points of 16 limbs) kept with their per-window tables"""
-
-    def __init__(self, d_bases, n):
-        lib().zkg_msm_g2_bases_upload.restype = C.c_void_p
-        lib().zkg_msm_g2_bases_upload.argtypes = [C.c_void_p, C.c_size_t]
-        self._h = lib().zkg_msm_g2_bases_upload(_vp(d_bases), C.c_size_t(n))
-        if not self._h:
-            raise ZkgError("zkg_msm_g2_bases_upload failed: " + last_error())
-        self.n = n
-
-    def msm(self, d_scalars, scalars_mont=False, stream=0):
-        """`stream`: the HIP stream whose queued work produced d_scalars (0 = the null stream); the job is ordered behind it"""
-        out = np.zeros(24, np.uint64)
-        lib().zkg_msm_g2_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
-        _check(lib().zkg_msm_g2_resident(C.c_void_p(self._h), _vp(d_scalars), C.c_size_t(self.n), SCALARS_MONT if scalars_mont else 0, _p(out), _vp(stream)), "zkg_msm_g2_resident")
-        return out
-
-    def msm_async(self, d_scalars_ptr, d_out_ptr, count=1, stride=None, scalars_mont=False, stream=0):
-        """zkg_msm_g2_resident_async: `count` vectors of n Fr, `stride` elements apart (default n), at the device address d_scalars_ptr; the
-        normalised points (24 limbs each) are written to the device address d_out_ptr by work that `stream` is made to wait for.  Returns
-        without waiting: synchronise `stream` before reading the points on the host."""
-        lib().zkg_msm_g2_resident_async.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
-        _check(lib().zkg_msm_g2_resident_async(C.c_void_p(self._h), _vp(d_scalars_ptr), C.c_size_t(self.n), C.c_size_t(self.n if stride is None else stride),
-                                               C.c_size_t(count), SCALARS_MONT if scalars_mont else 0, _vp(d_out_ptr), _vp(stream)), "zkg_msm_g2_resident_async")
-
-    def batch_max(self):
-        """zkg_msm_g2_resident_batch_max: scalar vectors that share one launch sequence on this handle"""
-        lib().zkg_msm_g2_resident_batch_max.restype = C.c_size_t
-        lib().zkg_msm_g2_resident_batch_max.argtypes = [C.c_void_p]
-        return int(lib().zkg_msm_g2_resident_batch_max(C.c_void_p(self._h)))
-
-    def free(self):
-        if self._h:
-            lib().zkg_msm_g2_bases_free.argtypes = [C.c_void_p]
-            lib().zkg_msm_g2_bases_free(C.c_void_p(self._h)); self._h = None
+def msm_combine_gpu(records_jac, cpw, slots, chunk_log, vectors=1):
+    """zkg_msm_combine_gpu: the MSM's device epilogue alone.  records_jac: vectors x cpw x slots normalised G1 points (12 limbs) in the order
+    vector, chunk, slot; returns (vectors, 12) normalised points."""
+    return _msm_combine("msm_combine_gpu", 12, records_jac, cpw, slots, chunk_log, vectors, [int(slots)])
 
 
 def msm_combine_g2_gpu(records_jac, cpw, chunk_log, vectors=1):
     """zkg_msm_combine_g2_gpu: the G2 MSM's device epilogue alone.  records_jac: vectors x cpw x 2 normalised G2 points (24 limbs) in the order
     vector, chunk, (P, U); returns (vectors, 24) normalised points."""
-    rec = _u64(records_jac)
-    if rec.size != vectors * cpw * 2 * 24:
-        raise ZkgError("msm_combine_g2_gpu: records_jac must hold vectors x cpw x 2 points of 24 limbs")
-    out = np.zeros((vectors, 24), np.uint64)
-    lib().zkg_msm_combine_g2_gpu.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p]
-    _check(lib().zkg_msm_combine_g2_gpu(_p(rec), C.c_size_t(cpw), int(chunk_log), C.c_size_t(vectors), _p(out)), "zkg_msm_combine_g2_gpu")
-    return out
+    return _msm_combine("msm_combine_g2_gpu", 24, records_jac, cpw, 2, chunk_log, vectors, [])
 
 
 def msm_g1_windows_dev(d_bases, d_scalars, n, first_window, window_stride, scalars_mont=False, stream=0):

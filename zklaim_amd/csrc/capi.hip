@@ -41,6 +41,18 @@ int DevBuf::reserve(size_t bytes) {
 }
 void DevBuf::release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 
+int HandleOrder::create() { ZK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); return ZKG_OK; }
+int HandleOrder::order_behind(hipStream_t s) { if (pending && s != last) ZK_HIP(hipStreamWaitEvent(s, ev, 0)); return ZKG_OK; }
+int HandleOrder::wait_host() { if (pending) ZK_HIP(hipEventSynchronize(ev)); return ZKG_OK; }
+int HandleOrder::grow(DevBuf &ws, size_t need, size_t &waits) {
+    if (need <= ws.cap) return ZKG_OK;
+    if (wait_host() || ws.reserve(need)) return ZKG_ERROR;               // earlier calls may still be in it
+    ++waits;
+    return ZKG_OK;
+}
+void HandleOrder::record(hipStream_t s) { if (hipEventRecord(ev, s) == hipSuccess) carried(s); }
+void HandleOrder::destroy() { if (ev) { if (pending) (void)hipEventSynchronize(ev); (void)hipEventDestroy(ev); ev = nullptr; pending = false; } }
+
 KernelTimer g_dominant_timer;
 bool crit_priority_for(int part, unsigned log_m) {
     static const int parts = getenv("ZKG_CRIT_PRIO_PARTS") ? atoi(getenv("ZKG_CRIT_PRIO_PARTS")) : 7;
@@ -688,26 +700,10 @@ static constexpr size_t DOMAIN_MAX_GROUP = 65535;                        // grid
 struct zkg_domain {
     DomainShape sh; int device = 0; std::mutex mu;
     DevBuf scratch;
-    hipEvent_t ev = nullptr; bool pending = false; hipStream_t last = nullptr;   // behind the last call's last kernel, on the stream it named
+    HandleOrder order;                                                  // its calls run in call order whatever streams they name (common.hpp)
     size_t bmax_default = 1, bmax = 1;
 };
 static thread_local size_t t_domain_stats[3];
-// A handle serves its calls in call order whatever streams they name: a call on another stream than the last one's waits (on the device) for
-// the last call's event before anything of its own — that is what keeps two streams out of the one scratch buffer.
-static int domain_order_behind(zkg_domain *d, hipStream_t s) {
-    if (d->pending && s != d->last) ZK_HIP(hipStreamWaitEvent(s, d->ev, 0));
-    return ZKG_OK;
-}
-// The event of a call: its last launch carries d->ev as its completion (ZK_LAUNCH_DONE, ntt.hip).  Behind a lone transform that costs 2.0 us of
-// device time where a hipEventRecord behind the kernel costs 2.9 and no event nothing (profiles/ntt_batch_time.json, "event_cost"); a
-// device-scope release (hipEventReleaseToDevice) changes neither.  domain_mark records it the plain way where a call failed after it had
-// enqueued something.
-static void domain_marked(zkg_domain *d, hipStream_t s) { d->pending = true; d->last = s; }
-static int domain_mark(zkg_domain *d, hipStream_t s) {
-    ZK_HIP(hipEventRecord(d->ev, s));
-    domain_marked(d, s);
-    return ZKG_OK;
-}
 static zkg_domain *domain_new_impl(size_t m) {
     if (g_device < 0) { set_error("zkg_init not called"); return nullptr; }
     DomainShape sh;
@@ -718,8 +714,7 @@ static zkg_domain *domain_new_impl(size_t m) {
     d->bmax_default = d->bmax = std::max<size_t>(1, std::min(DOMAIN_MAX_GROUP, DOMAIN_WORKSPACE_CAP / (m * NTT_SCRATCH_BYTES)));
     // the tables are built here, on the null stream, and waited for: no later call finds them missing or half made
     const bool tables = sh.step ? step_domain(m, nullptr) != nullptr : ntt_domain(sh.log_m, nullptr) != nullptr;
-    if (!tables || !hip_ok(hipStreamSynchronize(nullptr), "hipStreamSynchronize", __FILE__, __LINE__) ||
-        !hip_ok(hipEventCreateWithFlags(&d->ev, hipEventDisableTiming), "hipEventCreate", __FILE__, __LINE__)) return nullptr;
+    if (!tables || !hip_ok(hipStreamSynchronize(nullptr), "hipStreamSynchronize", __FILE__, __LINE__) || d->order.create()) return nullptr;
     return d.release();
 }
 static int domain_ntt_async_impl(zkg_domain *d, void *d_a, size_t stride, size_t count, int inverse, int coset, void *stream) {
@@ -739,25 +734,20 @@ static int domain_ntt_async_impl(zkg_domain *d, void *d_a, size_t stride, size_t
     size_t waits = 0, groups = 0, done = 0;
     // the scratch of the call's largest group.  Growing it frees it: earlier calls may still be in it, so the handle's event is waited for first
     const size_t need = std::min(d->bmax, count) * m * NTT_SCRATCH_BYTES;
-    if (need > d->scratch.cap) {
-        if (d->pending) ZK_HIP(hipEventSynchronize(d->ev));
-        if (d->scratch.reserve(need)) return ZKG_ERROR;
-        ++waits;
-    }
-    if (domain_order_behind(d, s)) return ZKG_ERROR;
+    if (d->order.grow(d->scratch, need, waits) || d->order.order_behind(s)) return ZKG_ERROR;
     Fr *a = (Fr *)d_a;
     int rc = ZKG_OK;
     while (done < count && rc == ZKG_OK) {
         const size_t g = std::min(d->bmax, count - done);
         Fr *ag = a + done * stride;
-        const hipEvent_t ev = done + g == count ? d->ev : nullptr;      // the call's last group ends in the handle's event
+        const hipEvent_t ev = done + g == count ? d->order.ev : nullptr;     // the call's last group ends in the handle's event
         rc = sd ? step_ntt_run(sd, ag, inverse != 0, coset != 0, s, d->scratch.as<Fr>(), (unsigned)g, stride, m, ev)
                 : ntt_run(nd, ag, inverse, coset, s, d->scratch.as<Fr>(), (unsigned)g, stride, m, ev);
         if (rc == ZKG_OK) { done += g; ++groups; }
     }
     t_domain_stats[0] = done; t_domain_stats[1] = groups; t_domain_stats[2] = waits;
-    if (rc == ZKG_OK) { domain_marked(d, s); return ZKG_OK; }
-    (void)domain_mark(d, s);                                            // a failure: the groups enqueued before it still run
+    if (rc == ZKG_OK) { d->order.carried(s); return ZKG_OK; }
+    d->order.record(s);                                                 // a failure: the groups enqueued before it still run
     return ZKG_ERROR;
 }
 static int domain_lagrange_async_impl(zkg_domain *d, const uint64_t t[4], void *d_u, void *d_z, void *stream) {
@@ -769,8 +759,8 @@ static int domain_lagrange_async_impl(zkg_domain *d, const uint64_t t[4], void *
     Fr tf; memcpy(tf.v, t, 32);                                         // read now: the caller may reuse t on return
     hipStream_t s = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(d->mu);
-    if (domain_order_behind(d, s) || domain_lagrange_dev(d->sh, tf, (Fr *)d_u, (Fr *)d_z, s, d->ev)) return ZKG_ERROR;
-    domain_marked(d, s);
+    if (d->order.order_behind(s) || domain_lagrange_dev(d->sh, tf, (Fr *)d_u, (Fr *)d_z, s, d->order.ev)) return ZKG_ERROR;
+    d->order.carried(s);
     return ZKG_OK;
 }
 zkg_domain *zkg_domain_new(size_t m) { return c_boundary<zkg_domain *>("zkg_domain_new", nullptr, [&] { return domain_new_impl(m); }); }
@@ -779,7 +769,7 @@ void zkg_domain_free(zkg_domain *d) {
     c_boundary("zkg_domain_free", 0, [&] {
         int cur = 0; (void)hipGetDevice(&cur);
         if (cur != d->device) (void)hipSetDevice(d->device);           // the scratch and the event live on the handle's device
-        if (d->ev) { if (d->pending) (void)hipEventSynchronize(d->ev); (void)hipEventDestroy(d->ev); }
+        d->order.destroy();
         d->scratch.release();
         if (cur != d->device) (void)hipSetDevice(cur);
         delete d;
@@ -790,7 +780,7 @@ size_t zkg_domain_size(const zkg_domain *d) { return d ? d->sh.m : 0; }
 size_t zkg_domain_batch_max(const zkg_domain *d) { return d ? d->bmax : 0; }
 void zkg_domain_set_batch_max(zkg_domain *d, size_t k) {
     if (!d) return;
-    c_boundary("zkg_domain_set_batch_max", 0, [&] { std::lock_guard<std::mutex> lk(d->mu); d->bmax = (k == 0 || k > d->bmax_default) ? d->bmax_default : k; return 0; });
+    c_boundary("zkg_domain_set_batch_max", 0, [&] { std::lock_guard<std::mutex> lk(d->mu); d->bmax = clamp_batch_max(k, d->bmax_default); return 0; });
 }
 int zkg_domain_ntt_async(zkg_domain *d, void *d_a, size_t stride, size_t count, int inverse, int coset, void *stream) {
     return c_boundary("zkg_domain_ntt_async", ZKG_ERROR, [&] { return domain_ntt_async_impl(d, d_a, stride, count, inverse, coset, stream); });
@@ -825,84 +815,99 @@ int zkg_msm_g1_windows_dev(const void *d_bases, const void *d_scalars, size_t n,
     store_norm(out_jac, r);
     return ZKG_OK;
 }
-// ---- fixed bases kept resident with their per-window tables (what the prover's H query gets): include/zkg.h
-struct zkg_msm_bases { WindowTable table; MsmJob *job = nullptr; std::mutex mu; int device = 0; hipEvent_t ev_in = nullptr, ev_out = nullptr; };
-zkg_msm_bases *zkg_msm_g1_bases_upload(const void *d_bases, size_t n) {
-    if (g_device < 0) { set_error("zkg_init not called"); return nullptr; }
-    if (!d_bases || n == 0 || n >= ((size_t)1 << 27)) { set_error("zkg_msm_g1_bases_upload: bad argument"); return nullptr; }
-    zkg_msm_bases *h = new (std::nothrow) zkg_msm_bases();
-    if (!h) return nullptr;
-    (void)hipGetDevice(&h->device);
-    h->job = msm_job_create(nullptr, true);
-    bool ok = h->job != nullptr && hip_ok(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming), "hipEventCreate", __FILE__, __LINE__) &&
-              hip_ok(hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming), "hipEventCreate", __FILE__, __LINE__) && window_table_build_g1(h->table, (const G1Affine *)d_bases, n, table_window_bits(n), nullptr) == 0 && window_table_records29(h->table, nullptr) == 0 &&
-              hip_ok(hipDeviceSynchronize(), "sync", __FILE__, __LINE__);
-    if (!ok) { zkg_msm_g1_bases_free(h); return nullptr; }
-    msm_job_set_window(h->job, h->table.c); msm_job_set_row_merge(h->job, n >= 49152 ? 2u : 1u);
-    return h;
-}
-void zkg_msm_g1_bases_free(zkg_msm_bases *h) {
-    if (!h) return;
+// ---- fixed bases kept resident with their per-window tables (what the prover's H query gets; a Groth16 B query for G2): include/zkg.h.
+//      One implementation for both groups.  A handle owns its table, one job on a stream of its own, and the two events that tie that stream
+//      to the caller's.  The groups differ in what MsmResidentG1 / MsmResidentG2 say and in two places marked below: G1 also builds the 29-bit
+//      records and merges rows, G2 caps a group by its bucket workspace.
+struct MsmResident { WindowTable table; MsmJob *job = nullptr; std::mutex mu; int device = 0; hipEvent_t ev_in = nullptr, ev_out = nullptr; };
+struct zkg_msm_bases : MsmResident {};
+struct zkg_msm_g2_bases : MsmResident {};
+struct MsmResidentG1 { using Handle = zkg_msm_bases; using Point = G1; static constexpr bool g2 = false; static constexpr size_t limbs = 12; static constexpr unsigned n_log = 27; static constexpr const char *prefix = "zkg_msm_g1"; };
+struct MsmResidentG2 { using Handle = zkg_msm_g2_bases; using Point = G2; static constexpr bool g2 = true; static constexpr size_t limbs = 24; static constexpr unsigned n_log = 25; static constexpr const char *prefix = "zkg_msm_g2"; };
+static constexpr size_t G2_RESIDENT_BUCKET_CAP = (size_t)1 << 30;       // one group's bucket workspace (zkg_msm_g2_resident_batch_max)
+
+extern "C++" {                                                          // (templates: this file's entries sit in one extern "C" block)
+static void resident_free(MsmResident *h) {
     int cur = 0; (void)hipGetDevice(&cur);
-    if (cur != h->device) (void)hipSetDevice(h->device);               // the handle's memory, stream and event live on the device it was made on
+    if (cur != h->device) (void)hipSetDevice(h->device);               // the handle's memory, stream and events live on the device it was made on
     if (h->job) { (void)hipStreamSynchronize(msm_job_stream(h->job)); msm_job_destroy(h->job); }
     if (h->ev_in) (void)hipEventDestroy(h->ev_in);
     if (h->ev_out) (void)hipEventDestroy(h->ev_out);
     h->table.release();
     if (cur != h->device) (void)hipSetDevice(cur);
-    delete h;
 }
-int zkg_msm_g1_resident(zkg_msm_bases *h, const void *d_scalars, size_t n, int scalars_mont, uint64_t out_jac[12], void *stream) {
+template <class G> static typename G::Handle *resident_upload(const void *d_bases, size_t n) {
+    const std::string who = std::string(G::prefix) + "_bases_upload";
+    if (g_device < 0) { set_error("zkg_init not called"); return nullptr; }
+    if (!d_bases || n == 0 || n >= ((size_t)1 << G::n_log)) { set_error(who + ": bad argument (1 <= n < 2^" + std::to_string(G::n_log) + ")"); return nullptr; }
+    typename G::Handle *h = new (std::nothrow) typename G::Handle();
+    if (!h) { set_error(who + ": out of memory"); return nullptr; }
+    (void)hipGetDevice(&h->device);
+    h->job = msm_job_create(nullptr, true);
+    bool ok = h->job != nullptr && hip_ok(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming), "hipEventCreate", __FILE__, __LINE__) &&
+              hip_ok(hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming), "hipEventCreate", __FILE__, __LINE__);
+    if constexpr (G::g2) ok = ok && window_table_build_g2(h->table, (const G2Affine *)d_bases, n, table_window_bits(n), nullptr) == 0;
+    else ok = ok && window_table_build_g1(h->table, (const G1Affine *)d_bases, n, table_window_bits(n), nullptr) == 0 && window_table_records29(h->table, nullptr) == 0;
+    if (!ok || !hip_ok(hipDeviceSynchronize(), "sync", __FILE__, __LINE__)) { resident_free(h); delete h; return nullptr; }   // (the failing step has set the message)
+    msm_job_set_window(h->job, h->table.c);
+    if constexpr (!G::g2) msm_job_set_row_merge(h->job, n >= 49152 ? 2u : 1u);  // (G2 rows are not merged: the job's default, 1)
+    return h;
+}
+// the handle's table as a launch's one base set (rec29 is null where no 29-bit records were built: G2)
+static MsmBases resident_table_set(const MsmResident *h) { MsmBases b; b.p = h->table.buf.p; b.g2 = h->table.g2; b.level_stride = h->table.n; b.p29 = h->table.rec29.p; return b; }
+template <class G> static int resident_sync(MsmResident *h, const void *d_scalars, size_t n, int scalars_mont, uint64_t *out_jac, void *stream) {
+    const std::string who = std::string(G::prefix) + "_resident";
     REQUIRE_INIT();
-    if (!h || !d_scalars || !out_jac || n != h->table.n) { set_error("zkg_msm_g1_resident: bad argument (n must be the handle's point count)"); return ZKG_ERROR; }
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != h->device) { set_error("zkg_msm_g1_resident: the calling thread's device is not the one the bases were uploaded on"); return ZKG_ERROR; }
+    if (!h || !d_scalars || !out_jac || n != h->table.n) { set_error(who + ": bad argument (n must be the handle's point count)"); return ZKG_ERROR; }
+    if (wrong_device_refused(who.c_str(), h->device, "the bases were uploaded on")) return ZKG_ERROR;
     std::lock_guard<std::mutex> lk(h->mu);                              // the handle owns one job: calls take turns
     // the job runs on the handle's own (non-blocking) stream: order it behind whatever the caller queued on `stream` (the work that
     // produces d_scalars).  The call returns after the result has landed, so nothing of it is left running for the caller to order after.
     ZK_HIP(hipEventRecord(h->ev_in, (hipStream_t)stream));
     ZK_HIP(hipStreamWaitEvent(msm_job_stream(h->job), h->ev_in, 0));
-    MsmBases b; b.p = h->table.buf.p; b.g2 = false; b.level_stride = h->table.n; b.p29 = h->table.rec29.p;
-    G1 r;
+    const MsmBases b = resident_table_set(h);
+    typename G::Point r;
     msm_job_set_device_finish(h->job, false);
     int rc;
     {   // asynchronous calls may still be running on the handle's stream: a buffer this launch has to grow is freed only after they have drained
         ReserveGuard guard(msm_job_stream(h->job));
         rc = msm_job_launch(h->job, &b, 1, (const uint32_t *)d_scalars, n, (scalars_mont & ZKG_SCALARS_MONT) != 0, nullptr);
     }
-    if (rc || msm_job_finish(h->job, &r, nullptr)) return ZKG_ERROR;
+    if constexpr (G::g2) rc = rc || msm_job_finish(h->job, nullptr, &r); else rc = rc || msm_job_finish(h->job, &r, nullptr);
+    if (rc) return ZKG_ERROR;
     store_norm(out_jac, r);
     return ZKG_OK;
 }
-// ---- zkg_msm_g1_resident_async: the same multi-exponentiation for `count` scalar vectors, the points left in DEVICE memory, no host wait.
+// ---- zkg_msm_g1_resident_async, zkg_msm_g2_resident_async: the same multi-exponentiation for `count` scalar vectors, the points left in
+//      DEVICE memory, no host wait.
 static thread_local size_t t_resident_async_stats[3];
 // Vectors per launch: what msm_multi_supported allows (the sort's 32-bit index space and its 2^22-bucket scan), and never more than
 // MSM_MULTI_MAX_VECTORS, the largest batch the prover runs through msm_job_launch_multi — the workspace grows linearly with the group (at 2^12-bit
 // windows of 5000 points 128 vectors would ask for 0.6 GB of buckets for a 0.6 MB scalar batch) and nothing above that size is exercised.
-size_t zkg_msm_g1_resident_batch_max(const zkg_msm_bases *h) {
-    if (!h) return 0;
+// G2, whose buckets are twice the size, also keeps one group's bucket workspace below G2_RESIDENT_BUCKET_CAP.
+template <class G> static size_t resident_batch_max(const MsmResident *h) {
     size_t p = MSM_MULTI_MAX_VECTORS;
+    if constexpr (G::g2) p = std::min<size_t>(p, std::max<size_t>(1, G2_RESIDENT_BUCKET_CAP / msm_table_bucket_bytes(h->table.c, true)));
     while (p > 1 && !msm_multi_supported(h->table.n, h->table.c, (uint32_t)p)) --p;
     return p;
 }
-void zkg_msm_resident_async_stats(size_t out[3]) { if (out) for (int i = 0; i < 3; ++i) out[i] = t_resident_async_stats[i]; }
-int zkg_msm_g1_resident_async(zkg_msm_bases *h, const void *d_scalars, size_t n, size_t stride, size_t count, int scalars_mont, void *d_out_jac, void *stream) {
-    static const char *who = "zkg_msm_g1_resident_async";
+template <class G> static int resident_async(MsmResident *h, const void *d_scalars, size_t n, size_t stride, size_t count, int scalars_mont, void *d_out_jac, void *stream) {
+    const std::string who_s = std::string(G::prefix) + "_resident_async"; const char *who = who_s.c_str();
     for (size_t &v : t_resident_async_stats) v = 0;
     if (count == 0) return ZKG_OK;                                      // nothing to do, nothing touched
     REQUIRE_INIT();
-    if (!h || !d_scalars || !d_out_jac || n != h->table.n) { set_error(std::string(who) + ": bad argument (n must be the handle's point count)"); return ZKG_ERROR; }
+    if (!h || !d_scalars || !d_out_jac || n != h->table.n) { set_error(who_s + ": bad argument (n must be the handle's point count)"); return ZKG_ERROR; }
     if (async_vectors_refused(who, n, "n", stride, count, h->device, "the bases were uploaded on")) return ZKG_ERROR;
     if (dev_range_refused(d_scalars, ((count - 1) * stride + n) * 32, 16, h->device, who, "d_scalars", "handle") ||
-        dev_range_refused(d_out_jac, count * 96, 8, h->device, who, "d_out_jac", "handle")) return ZKG_ERROR;
-    const size_t bmax = zkg_msm_g1_resident_batch_max(h);
+        dev_range_refused(d_out_jac, count * G::limbs * 8, 8, h->device, who, "d_out_jac", "handle")) return ZKG_ERROR;
+    const size_t bmax = resident_batch_max<G>(h);
     const bool mont = (scalars_mont & ZKG_SCALARS_MONT) != 0;
     const uint32_t *sc = (const uint32_t *)d_scalars; uint64_t *out = (uint64_t *)d_out_jac;
     std::lock_guard<std::mutex> lk(h->mu);                              // held for the enqueue only: calls on one handle run in call order on its stream
     hipStream_t js = msm_job_stream(h->job);
     ZK_HIP(hipEventRecord(h->ev_in, (hipStream_t)stream));              // behind the work that writes d_scalars (nothing is enqueued yet)
     ZK_HIP(hipStreamWaitEvent(js, h->ev_in, 0));
-    MsmBases b; b.p = h->table.buf.p; b.g2 = false; b.level_stride = h->table.n; b.p29 = h->table.rec29.p;
+    const MsmBases b = resident_table_set(h);
     msm_job_set_device_finish(h->job, true);
     int rc = ZKG_OK;
     size_t groups = 0, waits = 0, done = 0;
@@ -914,7 +919,7 @@ int zkg_msm_g1_resident_async(zkg_msm_bases *h, const void *d_scalars, size_t n,
         ReserveGuard guard(js);
         const uint32_t *sg = sc + done * stride * 8;
         rc = g > 1 ? msm_job_launch_multi(h->job, &b, 1, sg, n, stride * 8, (uint32_t)g, mont) : msm_job_launch(h->job, &b, 1, sg, n, mont, nullptr);
-        if (rc == ZKG_OK) rc = msm_job_finish_dev(h->job, out + done * 12);
+        if (rc == ZKG_OK) rc = msm_job_finish_dev(h->job, out + done * G::limbs);
         waits += guard.drains;
         if (rc == ZKG_OK) { done += g; ++groups; }
     }
@@ -924,117 +929,33 @@ int zkg_msm_g1_resident_async(zkg_msm_bases *h, const void *d_scalars, size_t n,
     t_resident_async_stats[0] = done; t_resident_async_stats[1] = groups; t_resident_async_stats[2] = waits;
     return rc == ZKG_OK && ordered ? ZKG_OK : ZKG_ERROR;
 }
+}  // extern "C++"
+void zkg_msm_resident_async_stats(size_t out[3]) { if (out) for (int i = 0; i < 3; ++i) out[i] = t_resident_async_stats[i]; }
+// the twelve entries: five per group and the two hooks that run the device epilogue (k_msm_combine, msm.hip) alone
+#define ZKG_RESIDENT_ENTRIES(NAME, G)                                                                                                                       \
+    G::Handle *NAME##_bases_upload(const void *d_bases, size_t n) {                                                                                         \
+        return c_boundary<G::Handle *>(#NAME "_bases_upload", nullptr, [&] { return resident_upload<G>(d_bases, n); });                                    \
+    }                                                                                                                                                       \
+    void NAME##_bases_free(G::Handle *h) {                                                                                                                  \
+        if (h) c_boundary(#NAME "_bases_free", 0, [&] { resident_free(h); delete h; return 0; });                                                           \
+    }                                                                                                                                                       \
+    int NAME##_resident(G::Handle *h, const void *d_scalars, size_t n, int scalars_mont, uint64_t *out_jac, void *stream) {                                \
+        return c_boundary(#NAME "_resident", ZKG_ERROR, [&] { return resident_sync<G>(h, d_scalars, n, scalars_mont, out_jac, stream); });                  \
+    }                                                                                                                                                       \
+    int NAME##_resident_async(G::Handle *h, const void *d_scalars, size_t n, size_t stride, size_t count, int scalars_mont, void *d_out_jac, void *stream) { \
+        return c_boundary(#NAME "_resident_async", ZKG_ERROR, [&] { return resident_async<G>(h, d_scalars, n, stride, count, scalars_mont, d_out_jac, stream); }); \
+    }                                                                                                                                                       \
+    size_t NAME##_resident_batch_max(const G::Handle *h) {                                                                                                  \
+        return h ? c_boundary<size_t>(#NAME "_resident_batch_max", 0, [&] { return resident_batch_max<G>(h); }) : 0;                                        \
+    }
+ZKG_RESIDENT_ENTRIES(zkg_msm_g1, MsmResidentG1)
+ZKG_RESIDENT_ENTRIES(zkg_msm_g2, MsmResidentG2)
+#undef ZKG_RESIDENT_ENTRIES
 int zkg_msm_combine_gpu(const uint64_t *records_jac, size_t cpw, int slots, int chunk_log, size_t vectors, uint64_t *out_jac) {
-    REQUIRE_INIT();
-    return msm_combine_records(records_jac, cpw, slots, chunk_log, vectors, out_jac);
-}
-// ---- the same for G2 (a Groth16 B query): a table built by window_table_build_g2, no 29-bit records, the device epilogue k_msm_combine_g2
-struct zkg_msm_g2_bases { WindowTable table; MsmJob *job = nullptr; std::mutex mu; int device = 0; hipEvent_t ev_in = nullptr, ev_out = nullptr; };
-static constexpr size_t G2_RESIDENT_BUCKET_CAP = (size_t)1 << 30;       // one group's bucket workspace (zkg_msm_g2_resident_batch_max)
-static void g2_bases_free_impl(zkg_msm_g2_bases *h) {
-    int cur = 0; (void)hipGetDevice(&cur);
-    if (cur != h->device) (void)hipSetDevice(h->device);               // the handle's memory, stream and events live on the device it was made on
-    if (h->job) { (void)hipStreamSynchronize(msm_job_stream(h->job)); msm_job_destroy(h->job); }
-    if (h->ev_in) (void)hipEventDestroy(h->ev_in);
-    if (h->ev_out) (void)hipEventDestroy(h->ev_out);
-    h->table.release();
-    if (cur != h->device) (void)hipSetDevice(cur);
-    delete h;
-}
-static zkg_msm_g2_bases *g2_bases_upload_impl(const void *d_bases, size_t n) {
-    if (g_device < 0) { set_error("zkg_init not called"); return nullptr; }
-    if (!d_bases || n == 0 || n >= ((size_t)1 << 25)) { set_error("zkg_msm_g2_bases_upload: bad argument (1 <= n < 2^25)"); return nullptr; }
-    zkg_msm_g2_bases *h = new (std::nothrow) zkg_msm_g2_bases();
-    if (!h) { set_error("zkg_msm_g2_bases_upload: out of memory"); return nullptr; }
-    (void)hipGetDevice(&h->device);
-    h->job = msm_job_create(nullptr, true);
-    const bool ok = h->job != nullptr && hip_ok(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming), "hipEventCreate", __FILE__, __LINE__) &&
-                    hip_ok(hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming), "hipEventCreate", __FILE__, __LINE__) &&
-                    window_table_build_g2(h->table, (const G2Affine *)d_bases, n, table_window_bits(n), nullptr) == 0 && hip_ok(hipDeviceSynchronize(), "sync", __FILE__, __LINE__);
-    if (!ok) { g2_bases_free_impl(h); return nullptr; }
-    msm_job_set_window(h->job, h->table.c);                             // (rows are not merged: msm_job_set_row_merge stays at 1)
-    return h;
-}
-static MsmBases g2_table_set(const zkg_msm_g2_bases *h) { MsmBases b; b.p = h->table.buf.p; b.g2 = true; b.level_stride = h->table.n; return b; }
-static int g2_resident_impl(zkg_msm_g2_bases *h, const void *d_scalars, size_t n, int scalars_mont, uint64_t out_jac[24], void *stream) {
-    static const char *who = "zkg_msm_g2_resident";
-    REQUIRE_INIT();
-    if (!h || !d_scalars || !out_jac || n != h->table.n) { set_error(std::string(who) + ": bad argument (n must be the handle's point count)"); return ZKG_ERROR; }
-    if (wrong_device_refused(who, h->device, "the bases were uploaded on")) return ZKG_ERROR;
-    std::lock_guard<std::mutex> lk(h->mu);                              // the handle owns one job: calls take turns
-    ZK_HIP(hipEventRecord(h->ev_in, (hipStream_t)stream));              // behind whatever the caller queued on `stream`
-    ZK_HIP(hipStreamWaitEvent(msm_job_stream(h->job), h->ev_in, 0));
-    const MsmBases b = g2_table_set(h);
-    G2 r;
-    msm_job_set_device_finish(h->job, false);
-    int rc;
-    {   // asynchronous calls may still be running on the handle's stream: a buffer this launch has to grow is freed only after they have drained
-        ReserveGuard guard(msm_job_stream(h->job));
-        rc = msm_job_launch(h->job, &b, 1, (const uint32_t *)d_scalars, n, (scalars_mont & ZKG_SCALARS_MONT) != 0, nullptr);
-    }
-    if (rc || msm_job_finish(h->job, nullptr, &r)) return ZKG_ERROR;
-    store_norm(out_jac, r);
-    return ZKG_OK;
-}
-static size_t g2_resident_batch_max_impl(const zkg_msm_g2_bases *h) {
-    size_t p = std::min<size_t>(MSM_MULTI_MAX_VECTORS, std::max<size_t>(1, G2_RESIDENT_BUCKET_CAP / msm_table_bucket_bytes(h->table.c, true)));
-    while (p > 1 && !msm_multi_supported(h->table.n, h->table.c, (uint32_t)p)) --p;
-    return p;
-}
-static int g2_resident_async_impl(zkg_msm_g2_bases *h, const void *d_scalars, size_t n, size_t stride, size_t count, int scalars_mont, void *d_out_jac, void *stream) {
-    static const char *who = "zkg_msm_g2_resident_async";
-    for (size_t &v : t_resident_async_stats) v = 0;
-    if (count == 0) return ZKG_OK;                                      // nothing to do, nothing touched
-    REQUIRE_INIT();
-    if (!h || !d_scalars || !d_out_jac || n != h->table.n) { set_error(std::string(who) + ": bad argument (n must be the handle's point count)"); return ZKG_ERROR; }
-    if (async_vectors_refused(who, n, "n", stride, count, h->device, "the bases were uploaded on")) return ZKG_ERROR;
-    if (dev_range_refused(d_scalars, ((count - 1) * stride + n) * 32, 16, h->device, who, "d_scalars", "handle") ||
-        dev_range_refused(d_out_jac, count * 192, 8, h->device, who, "d_out_jac", "handle")) return ZKG_ERROR;
-    const size_t bmax = g2_resident_batch_max_impl(h);
-    const bool mont = (scalars_mont & ZKG_SCALARS_MONT) != 0;
-    const uint32_t *sc = (const uint32_t *)d_scalars; uint64_t *out = (uint64_t *)d_out_jac;
-    std::lock_guard<std::mutex> lk(h->mu);                              // held for the enqueue only: calls on one handle run in call order on its stream
-    hipStream_t js = msm_job_stream(h->job);
-    ZK_HIP(hipEventRecord(h->ev_in, (hipStream_t)stream));              // behind the work that writes d_scalars (nothing is enqueued yet)
-    ZK_HIP(hipStreamWaitEvent(js, h->ev_in, 0));
-    const MsmBases b = g2_table_set(h);
-    msm_job_set_device_finish(h->job, true);
-    int rc = ZKG_OK;
-    size_t groups = 0, waits = 0, done = 0;
-    while (done < count && rc == ZKG_OK) {
-        const size_t g = std::min(bmax, count - done);
-        ReserveGuard guard(js);                                         // a reserve that has to grow drains the handle's stream first, and is counted (as for G1)
-        const uint32_t *sg = sc + done * stride * 8;
-        rc = g > 1 ? msm_job_launch_multi(h->job, &b, 1, sg, n, stride * 8, (uint32_t)g, mont) : msm_job_launch(h->job, &b, 1, sg, n, mont, nullptr);
-        if (rc == ZKG_OK) rc = msm_job_finish_dev(h->job, out + done * 24);
-        waits += guard.drains;
-        if (rc == ZKG_OK) { done += g; ++groups; }
-    }
-    // whatever the caller queues on `stream` after this call sees the points — after a failure too: the groups enqueued before it still write theirs
-    const bool ordered = hip_ok(hipEventRecord(h->ev_out, js), "hipEventRecord", __FILE__, __LINE__) &&
-                         hip_ok(hipStreamWaitEvent((hipStream_t)stream, h->ev_out, 0), "hipStreamWaitEvent", __FILE__, __LINE__);
-    t_resident_async_stats[0] = done; t_resident_async_stats[1] = groups; t_resident_async_stats[2] = waits;
-    return rc == ZKG_OK && ordered ? ZKG_OK : ZKG_ERROR;
-}
-zkg_msm_g2_bases *zkg_msm_g2_bases_upload(const void *d_bases, size_t n) {
-    return c_boundary<zkg_msm_g2_bases *>("zkg_msm_g2_bases_upload", nullptr, [&] { return g2_bases_upload_impl(d_bases, n); });
-}
-void zkg_msm_g2_bases_free(zkg_msm_g2_bases *h) {
-    if (!h) return;
-    c_boundary("zkg_msm_g2_bases_free", 0, [&] { g2_bases_free_impl(h); return 0; });
-}
-int zkg_msm_g2_resident(zkg_msm_g2_bases *h, const void *d_scalars, size_t n, int scalars_mont, uint64_t out_jac[24], void *stream) {
-    return c_boundary("zkg_msm_g2_resident", ZKG_ERROR, [&] { return g2_resident_impl(h, d_scalars, n, scalars_mont, out_jac, stream); });
-}
-int zkg_msm_g2_resident_async(zkg_msm_g2_bases *h, const void *d_scalars, size_t n, size_t stride, size_t count, int scalars_mont, void *d_out_jac, void *stream) {
-    return c_boundary("zkg_msm_g2_resident_async", ZKG_ERROR, [&] { return g2_resident_async_impl(h, d_scalars, n, stride, count, scalars_mont, d_out_jac, stream); });
-}
-size_t zkg_msm_g2_resident_batch_max(const zkg_msm_g2_bases *h) {
-    if (!h) return 0;
-    return c_boundary<size_t>("zkg_msm_g2_resident_batch_max", 0, [&] { return g2_resident_batch_max_impl(h); });
+    return c_boundary("zkg_msm_combine_gpu", ZKG_ERROR, [&]() -> int { REQUIRE_INIT(); return msm_combine_records(false, records_jac, cpw, slots, chunk_log, vectors, out_jac); });
 }
 int zkg_msm_combine_g2_gpu(const uint64_t *records_jac, size_t cpw, int chunk_log, size_t vectors, uint64_t *out_jac) {
-    return c_boundary("zkg_msm_combine_g2_gpu", ZKG_ERROR, [&]() -> int { REQUIRE_INIT(); return msm_combine_records_g2(records_jac, cpw, chunk_log, vectors, out_jac); });
+    return c_boundary("zkg_msm_combine_g2_gpu", ZKG_ERROR, [&]() -> int { REQUIRE_INIT(); return msm_combine_records(true, records_jac, cpw, 2, chunk_log, vectors, out_jac); });
 }
 int zkg_msm_g2_dev(const void *d_bases, const void *d_scalars, size_t n, int scalars_mont, uint64_t out_jac[24], void *stream) {
     REQUIRE_INIT();

@@ -48,6 +48,26 @@ struct ScopedDevBuf : DevBuf {
     ~ScopedDevBuf() { release(); }
 };
 
+// The call order of a handle that queues its work on the caller's streams and owns one workspace (zkg_domain, zkg_qap): its calls run in call
+// order whatever streams they name.  One event completes with the last call's last kernel; a call on another stream than that one's waits for
+// it on the device before anything of its own — that is what keeps two streams out of the one workspace — and the host waits for it before the
+// workspace is freed.  Used under the handle's mutex (capi.hip).
+struct HandleOrder {
+    hipEvent_t ev = nullptr; bool pending = false; hipStream_t last = nullptr;
+    int create();
+    int order_behind(hipStream_t s);                          // s waits (on the device) for the last call, unless that was on s itself
+    int wait_host();                                          // the host waits for the last call
+    int grow(DevBuf &ws, size_t need, size_t &waits);         // ws to `need` bytes: growing frees it, so wait_host first; counted in waits
+    // The event of a call: its last launch carries ev as its completion (ZK_LAUNCH_DONE, ntt.hip).  Behind a lone transform that costs 2.0 us of
+    // device time where a hipEventRecord behind the kernel costs 2.9 and no event nothing (profiles/ntt_batch_time.json, "event_cost"); a
+    // device-scope release (hipEventReleaseToDevice) changes neither.  record() is the plain way, for a call that failed after it had enqueued
+    // something (that still runs) or whose last launch cannot carry it.
+    void carried(hipStream_t s) { pending = true; last = s; }
+    void record(hipStream_t s);
+    void destroy();                                           // wait_host, then the event goes (on the handle's device)
+};
+inline size_t clamp_batch_max(size_t k, size_t dflt) { return k == 0 || k > dflt ? dflt : k; }   // zkg_*_set_batch_max: 0 or too many = the default
+
 // HIP-event timing of the dominant kernel (bench.py's roofline.achieved), on the launch stream
 struct KernelTimer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pairs; size_t used = 0; bool enabled = true, pending = false;
@@ -175,13 +195,12 @@ static constexpr size_t ZKG_MSM_ASYNC_MAX_COUNT = (size_t)1 << 24, ZKG_MSM_ASYNC
 int msm_job_launch_multi(MsmJob *job, const MsmBases *sets, int nsets, const uint32_t *d_scalars, size_t n, size_t scalar_stride, uint32_t count, bool scalars_mont);
 int msm_job_finish_multi(MsmJob *job, G1 *out_g1, G2 *out_g2);
 // The asynchronous end of a TABLE launch of G1 sets, or of G2 sets (not both).  msm_job_set_device_finish(job, true) before the launch: its chunk
-// records are not copied to the host.  msm_job_finish_dev then queues the epilogue kernel (k_msm_combine, k_msm_combine_g2) on the job's stream and
+// records are not copied to the host.  msm_job_finish_dev then queues the epilogue kernel (k_msm_combine) on the job's stream and
 // returns without synchronising: d_out (device, 12 limbs per G1 point, 24 per G2 point, normalised as store_norm writes them) gets point
 // (p * sets + k) for vector p and the k-th set.
 void msm_job_set_device_finish(MsmJob *j, bool on);
 int msm_job_finish_dev(MsmJob *job, uint64_t *d_out);
-int msm_combine_records(const uint64_t *records_jac, size_t cpw, int slots, int chunk_log, size_t vectors, uint64_t *out_jac);   // zkg_msm_combine_gpu
-int msm_combine_records_g2(const uint64_t *records_jac, size_t cpw, int chunk_log, size_t vectors, uint64_t *out_jac);           // zkg_msm_combine_g2_gpu
+int msm_combine_records(bool g2, const uint64_t *records_jac, size_t cpw, int slots, int chunk_log, size_t vectors, uint64_t *out_jac);   // zkg_msm_combine_gpu, zkg_msm_combine_g2_gpu (slots 2)
 size_t msm_table_bucket_bytes(int c, bool g2);             // bucket workspace of ONE scalar vector of a table launch at window size c (every window's set)
 // the multi_exp_with_mixed_addition split of a witness z = [1 | w] (n1 elements, Montgomery): tags (0 zero, 1 one, 2 other), the
 // indices of the others and their count; and the flat sum of the bases tagged one (result lands in pinned host memory)

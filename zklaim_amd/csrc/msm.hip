@@ -28,8 +28,8 @@
 //                      scan + tree reduction across the workgroup; every addition is shared by a DPP quad
 //   8. host            per-window chunk combine and the c-doublings Horner across windows
 //   8'. k_msm_combine  the same combine on the device for a table launch (no Horner there): the points stay in device memory and the job
-//                      ends without a host synchronisation (msm_job_finish_dev, zkg_msm_g1_resident_async); k_msm_combine_g2 is its G2 form
-//                      (zkg_msm_g2_resident_async)
+//                      ends without a host synchronisation (msm_job_finish_dev; zkg_msm_g1_resident_async at <Fq, 256>,
+//                      zkg_msm_g2_resident_async at <Fq2, 128>)
 // Zero scalars are dropped in step 1 and scalars equal to one simply land in bucket (window 0, digit 1),
 // a "heavy" bucket: the effect of libff's multi_exp_with_mixed_addition prefilter without a special case.
 //
@@ -1624,98 +1624,61 @@ static XYZZ<F> host_combine(const MsmJob *job, const MsmGroup &gr, int set, int 
     return xyzz_times_pow2(acc, g.c * g.w0);
 }
 
-// ---- 8'. the same epilogue on the device for a TABLE launch of G1 sets (msm_job_finish_dev): host_combine's window(w), no Horner.
+// ---- 8'. the same epilogue on the device for a TABLE launch of G1 sets, or of G2 sets (msm_job_finish_dev): host_combine's window(w), no Horner.
 //      One workgroup per output point (blockIdx.x = the window of the reduction, i.e. the scalar vector of a multi launch; blockIdx.y = set).
-//      Lanes own chunks: n = the power of two that covers cpw (COMBINE_THREADS at the most) lanes take 2^l consecutive chunks each — one chunk
-//      in every geometry a table produces (cpw <= 256) — and sum them as host_combine's walk does (S = sum P, T0 = sum (ch - first) P, U, A).
-//      sum_ch ch P_ch = 2^l sum_{t >= 1} Q_t + sum_t T0_t with Q the inclusive suffix scan of S over the lanes (Hillis-Steele through LDS, as
-//      k_bucket_reduce's), so every lane weighs its own term — 2^chunk_log (2^l Q_t + T0_t), chunk_log + l doublings side by side — adds it to
-//      its U (+ 8 A), lane 0 adds Q_0 = sum P, and ONE tree (lds_tree_reduce) sums the lanes.  Chain: log2 n + 3 additions, chunk_log + l
-//      doublings, log2 n tree levels, one inversion.  Lane 0 stores the point as store_norm does: X | Y | one, or (0, one, 0) for infinity.
-static constexpr int COMBINE_THREADS = 256;
-ZK_D void store_norm_dev(uint32_t *out /* 24 words */, const XYZZ<Fq> &v) {
-    Fq X = Fq::zero(), Y = Fq::one(), Z = Fq::zero();
-    if (!v.is_inf()) { const Affine<Fq> a = v.to_affine().normalized(); X = a.x; Y = a.y; Z = Fq::one(); }
-    for (int i = 0; i < 8; ++i) { out[i] = X.v[i]; out[8 + i] = Y.v[i]; out[16 + i] = Z.v[i]; }
+//      A chunk's record is (P, U) — V = sum U_ch + 2^chunk_log sum ch P_ch + sum P_ch — or, from k_bucket_reduce29l (G1 only), (P, T, A) with
+//      U = T + 8 A: `slots` says which.
+//      Lanes own chunks: n = the power of two that covers cpw (THREADS at the most) lanes take 2^l consecutive chunks each and sum them as
+//      host_combine's walk does (S = sum P, T0 = sum (ch - first) P, U, A).  sum_ch ch P_ch = 2^l sum_{t >= 1} Q_t + sum_t T0_t with Q the
+//      inclusive suffix scan of S over the lanes (Hillis-Steele through LDS, as k_bucket_reduce's), so every lane weighs its own term —
+//      2^chunk_log (2^l Q_t + T0_t), chunk_log + l doublings side by side — adds it to its U, lane 0 adds Q_0 = sum P, and ONE tree
+//      (lds_tree_reduce) sums the lanes.  Chain: log2 n + 3 additions, chunk_log + l doublings, log2 n tree levels, one inversion.  Lane 0 stores
+//      the point as store_norm does: X | Y | one, or (0, one, 0) for infinity.
+//      G1 runs 256 lanes: one chunk per lane in every geometry a table produces (cpw <= 256).  G2 runs 128: an LdsPoint<Fq2> is 272 B, so 128
+//      of them are 34 KiB — inside the 64 KiB a kernel gets without asking, where 256 lanes would need 68 KiB and a raised limit — and two
+//      wavefronts leave each the whole register file; a lane takes 2^l consecutive chunks from cpw = 129 on (a lone vector at 16-bit windows
+//      reduces to 512 chunks: l = 2).
+//      A G2 point is 64 registers, so the live set is kept at three points plus one addition's temporaries: S is scanned in place (it IS Q), the
+//      A term is finished (8 A added to U) straight behind the chunk loop and is dead before the scan, lane 0 adds Q_0 = sum P to its U BEFORE
+//      the doublings and drops it, Q then becomes the weighted term itself (2^l Q, + T0 — T0 dies here — then chunk_log doublings) and is added
+//      to U.  Sums in a group commute and the point leaves normalised, so the order changes no bit of it.
+template <class F> constexpr int COMBINE_THREADS = 256;
+template <> constexpr int COMBINE_THREADS<Fq2> = 128;
+template <class F> constexpr int COMBINE_MAX_SLOTS = 3;                        // (P, T, A) records are k_bucket_reduce29l's: G1 only
+template <> constexpr int COMBINE_MAX_SLOTS<Fq2> = 2;
+template <class F> constexpr int POINT_WORDS = 3 * sizeof(F) / 4;              // a normalised point in the ABI's form: 24 words (G1), 48 (G2)
+template <class F> static __host__ __device__ uint32_t combine_lanes(uint32_t cpw) { uint32_t n = 1; while (n < cpw && n < (uint32_t)COMBINE_THREADS<F>) n <<= 1; return n; }
+template <class F> static size_t combine_lds_bytes(uint32_t cpw) { return combine_lanes<F>(cpw) * sizeof(LdsPoint<F>); }
+// the limbs of a field element as the ABI lays them out: 8 words, c0 | c1 for Fq2
+ZK_D void store_limbs(uint32_t *out, const Fq &a) { for (int i = 0; i < 8; ++i) out[i] = a.v[i]; }
+ZK_D void store_limbs(uint32_t *out, const Fq2 &a) { store_limbs(out, a.c0); store_limbs(out + 8, a.c1); }
+ZK_D void load_limbs(Fq &a, const uint32_t *in) { for (int i = 0; i < 8; ++i) a.v[i] = in[i]; }
+ZK_D void load_limbs(Fq2 &a, const uint32_t *in) { load_limbs(a.c0, in); load_limbs(a.c1, in + 8); }
+template <class F> ZK_D void store_norm_dev(uint32_t *out /* POINT_WORDS<F> */, const XYZZ<F> &v) {
+    F X = F::zero(), Y = F::one(), Z = F::zero();
+    if (!v.is_inf()) { const Affine<F> a = v.to_affine().normalized(); X = a.x; Y = a.y; Z = F::one(); }
+    store_limbs(out, X); store_limbs(out + sizeof(F) / 4, Y); store_limbs(out + 2 * (sizeof(F) / 4), Z);
 }
-__global__ __launch_bounds__(COMBINE_THREADS) void k_msm_combine(const XYZZ<Fq> *red, uint32_t cpw, int slots, int chunk_log, size_t set_stride, uint32_t *out) {
+template <class F, int THREADS>
+__global__ __launch_bounds__(THREADS) void k_msm_combine(const XYZZ<F> *red, uint32_t cpw, int slots, int chunk_log, size_t set_stride, uint32_t *out) {
     extern __shared__ unsigned char red_smem[];
-    LdsPoint<Fq> *sh = reinterpret_cast<LdsPoint<Fq> *>(red_smem);            // n points
+    LdsPoint<F> *sh = reinterpret_cast<LdsPoint<F> *>(red_smem);              // n points
     const uint32_t t = threadIdx.x, w = blockIdx.x, set = blockIdx.y;
-    uint32_t n = 1; while (n < cpw && n < (uint32_t)COMBINE_THREADS) n <<= 1;
+    const uint32_t n = combine_lanes<F>(cpw);
     int l_log = 0; while (((uint64_t)n << l_log) < cpw) ++l_log;
-    const XYZZ<Fq> *rec = red + (size_t)set * set_stride + (size_t)slots * w * cpw;
+    const XYZZ<F> *rec = red + (size_t)set * set_stride + (size_t)slots * w * cpw;
     const uint64_t first = (uint64_t)t << l_log, end = first + ((uint64_t)1 << l_log) < cpw ? first + ((uint64_t)1 << l_log) : cpw;
-    XYZZ<Fq> U = XYZZ<Fq>::inf(), S = XYZZ<Fq>::inf(), T0 = XYZZ<Fq>::inf(), A = XYZZ<Fq>::inf();
-    for (uint64_t ch = end; ch > first; --ch) {                              // chunks end - 1 ... first (none for a lane behind the last chunk)
-        const XYZZ<Fq> *r = rec + (size_t)slots * (ch - 1);
-        S.add(r[0]); U.add(r[1]);
-        if (slots == 3) A.add(r[2]);
-        if (ch - 1 > first) T0.add(S);
-    }
-    XYZZ<Fq> Q = S;
-    for (uint32_t d = 1; d < n; d <<= 1) {
-        if (t < n) sh[t] = Q;
-        __syncthreads();
-        if (t + d < n) Q.add(sh[t + d]);
-        __syncthreads();
-    }
-    XYZZ<Fq> Wt = t >= 1 ? Q : XYZZ<Fq>::inf();
-    for (int i = 0; i < l_log; ++i) Wt = Wt.dbl();
-    Wt.add(T0);
-    for (int i = 0; i < chunk_log; ++i) Wt = Wt.dbl();                       // * buckets per chunk (dbl() returns infinity as it is: lanes whose term is infinity idle through the loop, where host_combine skips it)
-    if (slots == 3) { for (int i = 0; i < 3; ++i) A = A.dbl(); U.add(A); }    // U = T + 8 A (k_bucket_reduce29l)
-    U.add(Wt);
-    if (t == 0) U.add(Q);                                                    // Q_0 = sum_ch P_ch
-    if (t < n) sh[t] = U;
-    __syncthreads();
-    lds_tree_reduce<Fq>(sh, n, t, COMBINE_THREADS, [] { __syncthreads(); });
-    if (t == 0) store_norm_dev(out + 24 * ((size_t)w * gridDim.y + set), sh[0]);
-}
-// an empty job's points (no window owned): the infinity encoding
-__global__ __launch_bounds__(64) void k_msm_store_inf(uint32_t *out, uint32_t count) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) store_norm_dev(out + 24 * (size_t)i, XYZZ<Fq>::inf());
-}
-// the test hook's records: normalised Jacobian points (X | Y | Z, Z = one or zero) -> the reduction's record form
-__global__ __launch_bounds__(256) void k_jac_to_records(const uint32_t *jac, size_t count, XYZZ<Fq> *rec) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    Fq X, Y, Z;
-    for (int k = 0; k < 8; ++k) { X.v[k] = jac[24 * i + k]; Y.v[k] = jac[24 * i + 8 + k]; Z.v[k] = jac[24 * i + 16 + k]; }
-    rec[i] = Z.is_zero() ? XYZZ<Fq>::inf() : XYZZ<Fq>{X, Y, Fq::one(), Fq::one()};
-}
-static size_t combine_lds_bytes(uint32_t cpw) { uint32_t n = 1; while (n < cpw && n < (uint32_t)COMBINE_THREADS) n <<= 1; return n * sizeof(LdsPoint<Fq>); }
-
-// ---- 8''. the G2 form of that epilogue (a device-finish launch of G2 table sets: zkg_msm_g2_resident_async).  k_bucket_reduce<Fq2, ...> writes
-//      two slots per chunk, (P, U), so V = sum U_ch + 2^chunk_log sum ch P_ch + sum P_ch and there is no A term.  Same lane plan as above on
-//      COMBINE_G2_THREADS = 128 lanes: an LdsPoint<Fq2> is 272 B, so 128 of them are 34 KiB — inside the 64 KiB a kernel gets without asking,
-//      where 256 lanes would need 68 KiB and a raised limit — and two wavefronts leave each the whole register file.  A lane takes 2^l
-//      consecutive chunks from cpw = 129 on (a lone vector at 16-bit windows reduces to 512 chunks: l = 2).
-//      A point is 64 registers, so the live set is kept at three points plus one addition's temporaries: S is scanned in place (it IS Q), lane 0
-//      adds Q_0 = sum P to its U BEFORE the doublings and drops it, Q then becomes the weighted term itself (2^l Q, + T0 — T0 dies here — then
-//      chunk_log doublings) and is added to U.  Sums in a group commute and the point leaves normalised, so the order changes no bit of it.
-static constexpr int COMBINE_G2_THREADS = 128;
-ZK_D void store_norm_dev(uint32_t *out /* 48 words */, const XYZZ<Fq2> &v) {
-    Fq2 X = Fq2::zero(), Y = Fq2::one(), Z = Fq2::zero();
-    if (!v.is_inf()) { const Affine<Fq2> a = v.to_affine().normalized(); X = a.x; Y = a.y; Z = Fq2::one(); }
-    for (int i = 0; i < 8; ++i) {
-        out[i] = X.c0.v[i]; out[8 + i] = X.c1.v[i]; out[16 + i] = Y.c0.v[i]; out[24 + i] = Y.c1.v[i]; out[32 + i] = Z.c0.v[i]; out[40 + i] = Z.c1.v[i];
-    }
-}
-__global__ __launch_bounds__(COMBINE_G2_THREADS) void k_msm_combine_g2(const XYZZ<Fq2> *red, uint32_t cpw, int chunk_log, size_t set_stride, uint32_t *out) {
-    extern __shared__ unsigned char red_smem[];
-    LdsPoint<Fq2> *sh = reinterpret_cast<LdsPoint<Fq2> *>(red_smem);          // n points
-    const uint32_t t = threadIdx.x, w = blockIdx.x, set = blockIdx.y;
-    uint32_t n = 1; while (n < cpw && n < (uint32_t)COMBINE_G2_THREADS) n <<= 1;
-    int l_log = 0; while (((uint64_t)n << l_log) < cpw) ++l_log;
-    const XYZZ<Fq2> *rec = red + (size_t)set * set_stride + (size_t)2 * w * cpw;
-    const uint64_t first = (uint64_t)t << l_log, end = first + ((uint64_t)1 << l_log) < cpw ? first + ((uint64_t)1 << l_log) : cpw;
-    XYZZ<Fq2> U = XYZZ<Fq2>::inf(), Q = XYZZ<Fq2>::inf(), T0 = XYZZ<Fq2>::inf();
-    for (uint64_t ch = end; ch > first; --ch) {                              // chunks end - 1 ... first (none for a lane behind the last chunk); Q = S here
-        const XYZZ<Fq2> *r = rec + (size_t)2 * (ch - 1);
-        Q.add(r[0]); U.add(r[1]);
-        if (ch - 1 > first) T0.add(Q);
+    XYZZ<F> U = XYZZ<F>::inf(), Q = XYZZ<F>::inf(), T0 = XYZZ<F>::inf();
+    {
+        const bool has_a = COMBINE_MAX_SLOTS<F> == 3 && slots == 3;            // (no G2 reduction writes an A: that instantiation carries no code for it)
+        XYZZ<F> A = XYZZ<F>::inf();
+        for (uint64_t ch = end; ch > first; --ch) {                          // chunks end - 1 ... first (none for a lane behind the last chunk); Q = S here
+            const XYZZ<F> *r = rec + (size_t)slots * (ch - 1);
+            Q.add(r[0]); U.add(r[1]);
+            if (has_a) A.add(r[2]);
+            if (ch - 1 > first) T0.add(Q);
+        }
+        if (has_a) { for (int i = 0; i < 3; ++i) A = A.dbl(); U.add(A); }      // U = T + 8 A (k_bucket_reduce29l)
     }
     for (uint32_t d = 1; d < n; d <<= 1) {                                   // inclusive suffix scan of S over the lanes, in place
         if (t < n) sh[t] = Q;
@@ -1723,31 +1686,33 @@ __global__ __launch_bounds__(COMBINE_G2_THREADS) void k_msm_combine_g2(const XYZ
         if (t + d < n) Q.add(sh[t + d]);
         __syncthreads();
     }
-    if (t == 0) { U.add(Q); Q = XYZZ<Fq2>::inf(); }                          // Q_0 = sum_ch P_ch; lane 0 has no weighted term of the scan
+    if (t == 0) { U.add(Q); Q = XYZZ<F>::inf(); }                            // Q_0 = sum_ch P_ch; lane 0 has no weighted term of the scan
     for (int i = 0; i < l_log; ++i) Q = Q.dbl();
     Q.add(T0);
-    for (int i = 0; i < chunk_log; ++i) Q = Q.dbl();                         // * buckets per chunk (infinity stays infinity)
+    for (int i = 0; i < chunk_log; ++i) Q = Q.dbl();                         // * buckets per chunk (dbl() returns infinity as it is: lanes whose term is infinity idle through the loop, where host_combine skips it)
     U.add(Q);
     if (t < n) sh[t] = U;
     __syncthreads();
-    lds_tree_reduce<Fq2>(sh, n, t, COMBINE_G2_THREADS, [] { __syncthreads(); });
-    if (t == 0) store_norm_dev(out + 48 * ((size_t)w * gridDim.y + set), sh[0]);
+    lds_tree_reduce<F>(sh, n, t, THREADS, [] { __syncthreads(); });
+    if (t == 0) store_norm_dev<F>(out + POINT_WORDS<F> * ((size_t)w * gridDim.y + set), sh[0]);
 }
-__global__ __launch_bounds__(64) void k_msm_store_inf_g2(uint32_t *out, uint32_t count) {
+template <class F> static void launch_combine(dim3 grid, hipStream_t s, const XYZZ<F> *red, uint32_t cpw, int slots, int chunk_log, size_t set_stride, uint32_t *out) {
+    hipLaunchKernelGGL((k_msm_combine<F, COMBINE_THREADS<F>>), grid, dim3(COMBINE_THREADS<F>), combine_lds_bytes<F>(cpw), s, red, cpw, slots, chunk_log, set_stride, out);
+}
+// an empty job's points (no window owned): the infinity encoding
+template <class F> __global__ __launch_bounds__(64) void k_msm_store_inf(uint32_t *out, uint32_t count) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) store_norm_dev(out + 48 * (size_t)i, XYZZ<Fq2>::inf());
+    if (i < count) store_norm_dev(out + POINT_WORDS<F> * (size_t)i, XYZZ<F>::inf());
 }
-__global__ __launch_bounds__(256) void k_jac_to_records_g2(const uint32_t *jac, size_t count, XYZZ<Fq2> *rec) {
+// the test hooks' records: normalised Jacobian points (X | Y | Z, Z = one or zero) -> the reduction's record form
+template <class F> __global__ __launch_bounds__(256) void k_jac_to_records(const uint32_t *jac, size_t count, XYZZ<F> *rec) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
-    Fq2 X, Y, Z;
-    for (int k = 0; k < 8; ++k) {
-        X.c0.v[k] = jac[48 * i + k]; X.c1.v[k] = jac[48 * i + 8 + k]; Y.c0.v[k] = jac[48 * i + 16 + k]; Y.c1.v[k] = jac[48 * i + 24 + k];
-        Z.c0.v[k] = jac[48 * i + 32 + k]; Z.c1.v[k] = jac[48 * i + 40 + k];
-    }
-    rec[i] = Z.is_zero() ? XYZZ<Fq2>::inf() : XYZZ<Fq2>{X, Y, Fq2::one(), Fq2::one()};
+    const uint32_t *in = jac + POINT_WORDS<F> * i;
+    F X, Y, Z;
+    load_limbs(X, in); load_limbs(Y, in + sizeof(F) / 4); load_limbs(Z, in + 2 * (sizeof(F) / 4));
+    rec[i] = Z.is_zero() ? XYZZ<F>::inf() : XYZZ<F>{X, Y, F::one(), F::one()};
 }
-static size_t combine_g2_lds_bytes(uint32_t cpw) { uint32_t n = 1; while (n < cpw && n < (uint32_t)COMBINE_G2_THREADS) n <<= 1; return n * sizeof(LdsPoint<Fq2>); }
 
 static int sort_digits(MsmJob *job, const uint32_t *d_scalars, bool mont, const uint32_t *d_gather) {
     const MsmGeom g0 = job->g; const size_t n0 = job->n;                        // as the scalars see them (k_digits)
@@ -1976,67 +1941,51 @@ int msm_job_finish(MsmJob *job, G1 *out_g1, G2 *out_g2) {
 
 void msm_job_set_device_finish(MsmJob *j, bool on) { if (j) j->dev_finish = on; }
 // The device epilogue of a launch made under msm_job_set_device_finish: nothing is copied back and nothing is waited for.  k_msm_combine goes
-// onto the job's stream behind the reduction with the launch's geometry by value, and writes the points of the launch's G1 table sets where
-// msm_job_finish / msm_job_finish_multi would return them — d_out[(p * sets + k) * 12 limbs], normalised as store_norm does.
-// A launch whose sets are all G2 table sets ends the same way through k_msm_combine_g2, 24 limbs per point; a launch of both fields is refused.
+// onto the job's stream behind the reduction with the launch's geometry by value, and writes the points of the launch's table sets where
+// msm_job_finish / msm_job_finish_multi would return them — d_out[(p * sets + k) * 12 limbs] for G1 sets, 24 limbs for G2 sets, normalised as
+// store_norm does.  The sets of a launch are all of one group: a launch of both is refused.
+template <class F> static int finish_dev(MsmJob *job, const MsmGroup &gr, uint32_t *out) {
+    const uint32_t vectors = job->multi > 1 ? job->multi : 1;
+    if (job->empty) {
+        const uint32_t count = vectors * (uint32_t)gr.nsets;
+        hipLaunchKernelGGL(k_msm_store_inf<F>, dim3((count + 63) / 64), dim3(64), 0, job->stream, out, count);
+    } else {
+        if (!gr.table || gr.red_windows != vectors || gr.red_slots > COMBINE_MAX_SLOTS<F>) { set_error("msm_job_finish_dev: table sets only (a plain set's windows need the Horner doublings)"); return ZKG_ERROR; }
+        launch_combine<F>(dim3(vectors, (unsigned)gr.nsets), job->stream, gr.red_out.as<XYZZ<F>>(), gr.cpw, gr.red_slots, gr.chunk_log, gr.red_stride, out);
+    }
+    if (hipGetLastError() != hipSuccess) { set_error("msm combine launch failed"); return ZKG_ERROR; }
+    return ZKG_OK;
+}
 int msm_job_finish_dev(MsmJob *job, uint64_t *d_out) {
     const bool g2 = job->group[0].nsets == 0;
     const MsmGroup &gr = job->group[g2 ? 1 : 0];
     if (!job->dev_finish || (job->group[0].nsets && job->group[1].nsets) || gr.nsets < 1) { set_error("msm_job_finish_dev: a device-finish launch of G1 sets only, or of G2 sets only"); return ZKG_ERROR; }
-    const uint32_t vectors = job->multi > 1 ? job->multi : 1;
     uint32_t *out = reinterpret_cast<uint32_t *>(d_out);
-    if (g2) {
-        if (job->empty) {
-            const uint32_t count = vectors * (uint32_t)gr.nsets;
-            hipLaunchKernelGGL(k_msm_store_inf_g2, dim3((count + 63) / 64), dim3(64), 0, job->stream, out, count);
-        } else {
-            if (!gr.table || gr.red_windows != vectors || gr.red_slots != 2) { set_error("msm_job_finish_dev: table sets only (a plain set's windows need the Horner doublings)"); return ZKG_ERROR; }
-            hipLaunchKernelGGL(k_msm_combine_g2, dim3(vectors, (unsigned)gr.nsets), dim3(COMBINE_G2_THREADS), combine_g2_lds_bytes(gr.cpw), job->stream,
-                               gr.red_out.as<XYZZ<Fq2>>(), gr.cpw, gr.chunk_log, gr.red_stride, out);
-        }
-    } else if (job->empty) {
-        const uint32_t count = vectors * (uint32_t)gr.nsets;
-        hipLaunchKernelGGL(k_msm_store_inf, dim3((count + 63) / 64), dim3(64), 0, job->stream, out, count);
-    } else {
-        if (!gr.table || gr.red_windows != vectors) { set_error("msm_job_finish_dev: table sets only (a plain set's windows need the Horner doublings)"); return ZKG_ERROR; }
-        hipLaunchKernelGGL(k_msm_combine, dim3(vectors, (unsigned)gr.nsets), dim3(COMBINE_THREADS), combine_lds_bytes(gr.cpw), job->stream,
-                           gr.red_out.as<XYZZ<Fq>>(), gr.cpw, gr.red_slots, gr.chunk_log, gr.red_stride, out);
-    }
-    if (hipGetLastError() != hipSuccess) { set_error("msm combine launch failed"); return ZKG_ERROR; }
-    return ZKG_OK;
+    return g2 ? finish_dev<Fq2>(job, gr, out) : finish_dev<Fq>(job, gr, out);
 }
-// zkg_msm_combine_gpu: k_msm_combine alone on records the caller makes up.  records_jac: vectors x cpw x slots normalised points in the
-// reduction's order (vector, chunk, slot); out_jac: one normalised point per vector.  Host pointers; synchronous.
-int msm_combine_records(const uint64_t *records_jac, size_t cpw, int slots, int chunk_log, size_t vectors, uint64_t *out_jac) {
-    if (!records_jac || !out_jac || cpw < 1 || cpw > ((size_t)1 << 16) || (slots != 2 && slots != 3) || chunk_log < 0 || chunk_log > 24 || vectors < 1 || vectors > 1024) {
-        set_error("zkg_msm_combine_gpu: bad argument (1 <= cpw <= 2^16, slots 2 or 3, 0 <= chunk_log <= 24, 1 <= vectors <= 1024)"); return ZKG_ERROR;
-    }
+// zkg_msm_combine_gpu, zkg_msm_combine_g2_gpu: k_msm_combine alone on records the caller makes up.  records_jac: vectors x cpw x slots
+// normalised points (12 limbs, 24 for G2) in the reduction's order (vector, chunk, slot); out_jac: one normalised point per vector.  Host
+// pointers; synchronous.
+template <class F> static int combine_records(const uint64_t *records_jac, size_t cpw, int slots, int chunk_log, size_t vectors, uint64_t *out_jac) {
+    constexpr size_t point_bytes = POINT_WORDS<F> * 4;
     const size_t count = vectors * cpw * (size_t)slots;
     ScopedDevBuf in, rec, out;
-    if (in.reserve(count * 96) || rec.reserve(count * sizeof(XYZZ<Fq>)) || out.reserve(vectors * 96)) return ZKG_ERROR;
-    ZK_HIP(hipMemcpy(in.p, records_jac, count * 96, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_jac_to_records, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, nullptr, in.as<uint32_t>(), count, rec.as<XYZZ<Fq>>());
-    hipLaunchKernelGGL(k_msm_combine, dim3((unsigned)vectors, 1), dim3(COMBINE_THREADS), combine_lds_bytes((uint32_t)cpw), nullptr,
-                       rec.as<XYZZ<Fq>>(), (uint32_t)cpw, slots, chunk_log, (size_t)0, out.as<uint32_t>());
+    if (in.reserve(count * point_bytes) || rec.reserve(count * sizeof(XYZZ<F>)) || out.reserve(vectors * point_bytes)) return ZKG_ERROR;
+    ZK_HIP(hipMemcpy(in.p, records_jac, count * point_bytes, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_jac_to_records<F>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, nullptr, in.as<uint32_t>(), count, rec.as<XYZZ<F>>());
+    launch_combine<F>(dim3((unsigned)vectors, 1), nullptr, rec.as<XYZZ<F>>(), (uint32_t)cpw, slots, chunk_log, (size_t)0, out.as<uint32_t>());
     if (hipGetLastError() != hipSuccess) { set_error("msm combine launch failed"); return ZKG_ERROR; }
-    ZK_HIP(hipMemcpy(out_jac, out.p, vectors * 96, hipMemcpyDeviceToHost));     // (waits for the null stream)
+    ZK_HIP(hipMemcpy(out_jac, out.p, vectors * point_bytes, hipMemcpyDeviceToHost));     // (waits for the null stream)
     return ZKG_OK;
 }
-// zkg_msm_combine_g2_gpu: k_msm_combine_g2 alone.  records_jac: vectors x cpw x 2 normalised G2 points of 24 limbs, in order vector, chunk, (P, U)
-int msm_combine_records_g2(const uint64_t *records_jac, size_t cpw, int chunk_log, size_t vectors, uint64_t *out_jac) {
-    if (!records_jac || !out_jac || cpw < 1 || cpw > ((size_t)1 << 16) || chunk_log < 0 || chunk_log > 24 || vectors < 1 || vectors > 1024) {
-        set_error("zkg_msm_combine_g2_gpu: bad argument (1 <= cpw <= 2^16, 0 <= chunk_log <= 24, 1 <= vectors <= 1024)"); return ZKG_ERROR;
+int msm_combine_records(bool g2, const uint64_t *records_jac, size_t cpw, int slots, int chunk_log, size_t vectors, uint64_t *out_jac) {
+    const bool args = records_jac && out_jac && cpw >= 1 && cpw <= ((size_t)1 << 16) && chunk_log >= 0 && chunk_log <= 24 && vectors >= 1 && vectors <= 1024;
+    if (g2) {
+        if (!args || slots != 2) { set_error("zkg_msm_combine_g2_gpu: bad argument (1 <= cpw <= 2^16, 0 <= chunk_log <= 24, 1 <= vectors <= 1024)"); return ZKG_ERROR; }
+        return combine_records<Fq2>(records_jac, cpw, slots, chunk_log, vectors, out_jac);
     }
-    const size_t count = vectors * cpw * 2;
-    ScopedDevBuf in, rec, out;
-    if (in.reserve(count * 192) || rec.reserve(count * sizeof(XYZZ<Fq2>)) || out.reserve(vectors * 192)) return ZKG_ERROR;
-    ZK_HIP(hipMemcpy(in.p, records_jac, count * 192, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_jac_to_records_g2, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, nullptr, in.as<uint32_t>(), count, rec.as<XYZZ<Fq2>>());
-    hipLaunchKernelGGL(k_msm_combine_g2, dim3((unsigned)vectors, 1), dim3(COMBINE_G2_THREADS), combine_g2_lds_bytes((uint32_t)cpw), nullptr,
-                       rec.as<XYZZ<Fq2>>(), (uint32_t)cpw, chunk_log, (size_t)0, out.as<uint32_t>());
-    if (hipGetLastError() != hipSuccess) { set_error("msm combine launch failed"); return ZKG_ERROR; }
-    ZK_HIP(hipMemcpy(out_jac, out.p, vectors * 192, hipMemcpyDeviceToHost));    // (waits for the null stream)
-    return ZKG_OK;
+    if (!args || (slots != 2 && slots != 3)) { set_error("zkg_msm_combine_gpu: bad argument (1 <= cpw <= 2^16, slots 2 or 3, 0 <= chunk_log <= 24, 1 <= vectors <= 1024)"); return ZKG_ERROR; }
+    return combine_records<Fq>(records_jac, cpw, slots, chunk_log, vectors, out_jac);
 }
 // what one scalar vector of a table launch asks of the bucket workspace (launch_accumulate: every window's bucket set, before the fold)
 size_t msm_table_bucket_bytes(int c, bool g2) {

@@ -202,7 +202,7 @@ struct zkg_qap {
     DevBuf coset_over_m, coset_over_m29;            // g^i / m and its 29-bit records (radix-2 domains: iFFT's scaling fused with the cosetFFT's)
     Fr z_inv_coset;                                 // 1 / (g^m - 1) (radix-2 domains)
     DevBuf ws;                                      // a group's aA | aB | aC (3 g m Fr), then the transforms' scratch (3 g m records of 40 bytes)
-    hipEvent_t ev = nullptr; bool pending = false; hipStream_t last = nullptr;   // behind the last call's last kernel, on the stream it named
+    HandleOrder order;                              // its calls run in call order whatever streams they name (common.hpp)
     size_t bmax_default = 1, bmax = 1;
     // the instance map's column index, made by the first zkg_qap_instance_async: column pointers (n + 2) and (row, position in val) per entry
     size_t nnz[3] = {0, 0, 0};
@@ -225,7 +225,7 @@ static int qap_upload(DevBuf &d, const void *src, size_t bytes) {
 static void qap_destroy(zkg_qap *q) {
     int cur = 0; (void)hipGetDevice(&cur);
     if (cur != q->device) (void)hipSetDevice(q->device);               // the buffers and the event live on the handle's device
-    if (q->ev) { if (q->pending) (void)hipEventSynchronize(q->ev); (void)hipEventDestroy(q->ev); }
+    q->order.destroy();
     q->release();
     if (cur != q->device) (void)hipSetDevice(cur);
     delete q;
@@ -280,8 +280,7 @@ static zkg_qap *qap_new_impl(const zkg_r1cs *cs) {
         if (q->coset_over_m.reserve(m * sizeof(Fr)) || powers_table(q->coset_over_m.as<Fr>(), m, g, nd->n_inv, nullptr) ||
             ntt_table29(q->coset_over_m29, q->coset_over_m.as<Fr>(), m, nullptr)) return nullptr;
     }
-    if (!hip_ok(hipStreamSynchronize(nullptr), "hipStreamSynchronize", __FILE__, __LINE__) ||
-        !hip_ok(hipEventCreateWithFlags(&q->ev, hipEventDisableTiming), "hipEventCreate", __FILE__, __LINE__)) return nullptr;
+    if (!hip_ok(hipStreamSynchronize(nullptr), "hipStreamSynchronize", __FILE__, __LINE__) || q->order.create()) return nullptr;
     return q.release();
 }
 
@@ -314,12 +313,7 @@ static int qap_witness_h_async_impl(zkg_qap *q, const void *d_witnesses, size_t 
     size_t waits = 0, groups = 0, done = 0;
     // the workspace of the call's largest group.  Growing it frees it: earlier calls may still be in it, so the handle's event is waited for first
     const size_t need = std::min(q->bmax, count) * m * QAP_BYTES_PER_ELEMENT;
-    if (need > q->ws.cap) {
-        if (q->pending) ZK_HIP(hipEventSynchronize(q->ev));
-        if (q->ws.reserve(need)) return ZKG_ERROR;
-        ++waits;
-    }
-    if (q->pending && s != q->last) ZK_HIP(hipStreamWaitEvent(s, q->ev, 0));   // call order whatever the streams: there is one workspace
+    if (q->order.grow(q->ws, need, waits) || q->order.order_behind(s)) return ZKG_ERROR;
     const QapCsr M = {q->rp[0].as<uint32_t>(), q->col[0].as<uint32_t>(), q->val[0].as<Fr>(), q->rp[1].as<uint32_t>(), q->col[1].as<uint32_t>(), q->val[1].as<Fr>(),
                       q->rp[2].as<uint32_t>(), q->col[2].as<uint32_t>(), q->val[2].as<Fr>()};
     const Fr *w = (const Fr *)d_witnesses; Fr *h = (Fr *)d_h;
@@ -332,7 +326,7 @@ static int qap_witness_h_async_impl(zkg_qap *q, const void *d_witnesses, size_t 
         Fr *aABC = q->ws.as<Fr>(), *scr = aABC + (size_t)3 * g * m;
         const Fr *wg = w + done * stride; Fr *hg = h + done * h_stride;
         uint32_t *ug = d_unsat ? d_unsat + done : nullptr;
-        const hipEvent_t ev = done + g == count ? q->ev : nullptr;      // the call's last group ends in the handle's event
+        const hipEvent_t ev = done + g == count ? q->order.ev : nullptr;     // the call's last group ends in the handle's event
         enqueued = true;
         hipLaunchKernelGGL(k_qap_eval, dim3(grid_m, g), dim3(256), 0, s, M, wg, stride, q->C, q->l, m, aABC, ug);
         if (q->n_long) {
@@ -359,8 +353,8 @@ static int qap_witness_h_async_impl(zkg_qap *q, const void *d_witnesses, size_t 
         if (rc == ZKG_OK) { done += g; ++groups; }
     }
     t_qap_stats[0] = done; t_qap_stats[1] = groups; t_qap_stats[2] = waits;
-    if (rc == ZKG_OK) { q->pending = true; q->last = s; return ZKG_OK; }
-    if (enqueued && hipEventRecord(q->ev, s) == hipSuccess) { q->pending = true; q->last = s; }   // a failure: what was enqueued before it still runs
+    if (rc == ZKG_OK) { q->order.carried(s); return ZKG_OK; }
+    if (enqueued) q->order.record(s);                                   // a failure: what was enqueued before it still runs
     return ZKG_ERROR;
 }
 
@@ -384,8 +378,8 @@ static int qap_index(zkg_qap *q, hipStream_t s, size_t &builds, size_t &waits) {
         hipLaunchKernelGGL(k_col_count, rows, dim3(256), 0, s, M, C, q->cp[0].as<uint32_t>(), q->cp[1].as<uint32_t>(), q->cp[2].as<uint32_t>());
         hipLaunchKernelGGL(k_col_scan, dim3(3), dim3(1024), 0, s, q->cp[0].as<uint32_t>(), q->cp[1].as<uint32_t>(), q->cp[2].as<uint32_t>(), cur.as<uint32_t>(), cols);
         hipLaunchKernelGGL(k_col_scatter, rows, dim3(256), 0, s, M, C, cur.as<uint32_t>(), cols, q->ent[0].as<uint2>(), q->ent[1].as<uint2>(), q->ent[2].as<uint2>());
-    } else if (q->pending) {
-        ZK_HIP(hipEventSynchronize(q->ev));
+    } else if (q->order.wait_host()) {
+        return ZKG_ERROR;
     }
     // a long column has more than LONG_COLUMN terms and ceil(degree / seg) <= degree / seg + 1 segments
     size_t cap = 0;
@@ -425,12 +419,7 @@ static int qap_instance_async_impl(zkg_qap *q, const uint64_t *t, void *d_abc, s
     if (qap_index(q, s, builds, waits)) return leave(ZKG_ERROR);
     // u (m Fr), then the segments' partial sums, in the workspace the H calls use: grown and ordered by their rules
     const size_t need = (m + q->n_seg) * sizeof(Fr);
-    if (need > q->ws.cap) {
-        if (q->pending && !hip_ok(hipEventSynchronize(q->ev), "hipEventSynchronize", __FILE__, __LINE__)) return leave(ZKG_ERROR);
-        if (q->ws.reserve(need)) return leave(ZKG_ERROR);
-        ++waits;
-    }
-    if (q->pending && s != q->last && !hip_ok(hipStreamWaitEvent(s, q->ev, 0), "hipStreamWaitEvent", __FILE__, __LINE__)) return leave(ZKG_ERROR);
+    if (q->order.grow(q->ws, need, waits) || q->order.order_behind(s)) return leave(ZKG_ERROR);
     Fr *u = q->ws.as<Fr>(), *part = u + m, *abc = (Fr *)d_abc;
     if (domain_lagrange_dev(q->sh, tf, u, (Fr *)d_z, s)) return leave(ZKG_ERROR);
     const QapCsc M = {q->cp[0].as<uint32_t>(), q->ent[0].as<uint2>(), q->val[0].as<Fr>(), q->cp[1].as<uint32_t>(), q->ent[1].as<uint2>(), q->val[1].as<Fr>(),
@@ -442,7 +431,7 @@ static int qap_instance_async_impl(zkg_qap *q, const uint64_t *t, void *d_abc, s
         hipLaunchKernelGGL(k_qap_columns_close, waves, dim3(256), 0, s, q->seg_list.as<ColSeg>(), q->n_seg, (const Fr *)part, (const Fr *)u, q->C, q->l, abc, stride);
     }
     const bool launched = hipGetLastError() == hipSuccess;
-    if (hipEventRecord(q->ev, s) == hipSuccess) { q->pending = true; q->last = s; }      // whatever was enqueued still runs
+    q->order.record(s);                                                 // whatever was enqueued still runs
     if (!launched) { set_error(std::string(who) + ": kernel launch failed"); return leave(ZKG_ERROR); }
     return leave(ZKG_OK);
 }
@@ -459,7 +448,7 @@ uint32_t zkg_qap_num_variables(const zkg_qap *q) { return q ? q->n : 0; }
 size_t zkg_qap_batch_max(const zkg_qap *q) { return q ? q->bmax : 0; }
 void zkg_qap_set_batch_max(zkg_qap *q, size_t k) {
     if (!q) return;
-    c_boundary("zkg_qap_set_batch_max", 0, [&] { std::lock_guard<std::mutex> lk(q->mu); q->bmax = (k == 0 || k > q->bmax_default) ? q->bmax_default : k; return 0; });
+    c_boundary("zkg_qap_set_batch_max", 0, [&] { std::lock_guard<std::mutex> lk(q->mu); q->bmax = clamp_batch_max(k, q->bmax_default); return 0; });
 }
 int zkg_qap_witness_h_async(zkg_qap *q, const void *d_witnesses, size_t stride, size_t count, void *d_h, size_t h_stride, uint32_t *d_unsat, void *stream) {
     return c_boundary("zkg_qap_witness_h_async", ZKG_ERROR, [&] { return qap_witness_h_async_impl(q, d_witnesses, stride, count, d_h, h_stride, d_unsat, stream); });
