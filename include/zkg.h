@@ -246,8 +246,17 @@ int zkg_msm_g2_dev(const void *d_bases, const void *d_scalars, size_t n, int sca
  * canonical limbs (or Montgomery with ZKG_SCALARS_MONT) in host memory; page-locked memory (hipHostMalloc / hipHostRegister) lets the upload
  * run under the work: from 2^19 points on the job is cut by points into four pieces whose uploads overlap the sort and accumulation of the
  * pieces before them, all accumulating into one set of buckets (pageable memory works, without the overlap).  Same point as zkg_msm_g1_dev on
- * the uploaded vector, bit for bit.  `stream` as in zkg_msm_g1_dev; the result is in out_jac when the call returns.                      */
+ * the uploaded vector, bit for bit.  `stream` as in zkg_msm_g1_dev; the result is in out_jac when the call returns.  The calling thread
+ * is busy for the length of the call: it enqueues each piece's accumulation once that piece's sort has finished.                        */
 int zkg_msm_g1_host_scalars(const void *d_bases, const uint64_t *scalars, size_t n, int scalars_mont, uint64_t out_jac[12], void *stream);
+/* test hook: what the last zkg_msm_g1_host_scalars of the process did.  The calling thread paces a piece-wise job: it enqueues an accumulation
+ * only once that piece's digit sort has finished, and reads the piece's count of heavy buckets (lists above the accumulation's threshold) from
+ * a word the sort stored in the library's pinned memory — the two heavy-bucket kernels are launched behind an accumulation only where that
+ * count is not zero.  out[0]: pieces run (1: the single-launch path); out[1]: cross-stream waits enqueued on the caller's stream (0 for a
+ * piece-wise job); then per piece k, out[2 + 2k]: the heavy-bucket count the host read (0xffffffff where it reads none: the single-launch path
+ * launches the pair blind) and out[3 + 2k]: 1 if the pair was launched.  At most n words are written; returns the words the record has
+ * (2 + 2 * pieces; 0 before the first call or for a null `out`).  Counters, not clocks.                                                      */
+int zkg_msm_host_scalars_stats(uint32_t *out, int n);
 /* Fixed bases kept resident WITH their per-window tables (level w = 2^(c w) P_i; c = 16 from 2^15 points on: 16 x the bases' memory plus the
  * same again as 29-bit records) — what the prover builds for a key's H query, offered for any fixed G1 base set (libff has no counterpart; its
  * multi_exp takes the bases as they are).  Every window's digit then weighs the same: one bucket set, one reduction, no doublings on the

@@ -42,6 +42,7 @@ DECLARED_SYMBOLS = [
     "zkg_qap_new", "zkg_qap_free", "zkg_qap_domain_size", "zkg_qap_num_variables", "zkg_qap_batch_max", "zkg_qap_set_batch_max",
     "zkg_qap_witness_h_async", "zkg_qap_stats",
     "zkg_qap_instance_async", "zkg_qap_set_column_segment", "zkg_qap_instance_stats", "zkg_groth16_setup_dev",
+    "zkg_msm_host_scalars_stats",
 ]
 # the reference's own seam, exported with its original names (zklaim.h:257-259)
 COMPAT_SYMBOLS = ["libsnark_trusted_setup", "libsnark_prove", "libsnark_verify"]
@@ -462,6 +463,19 @@ def msm_g1_host_scalars(d_bases, scalars_host_ptr, n, scalars_mont=False, stream
     lib().zkg_msm_g1_host_scalars.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
     _check(lib().zkg_msm_g1_host_scalars(_vp(d_bases), _vp(scalars_host_ptr), C.c_size_t(n), SCALARS_MONT if scalars_mont else 0, _p(out), _vp(stream)), "zkg_msm_g1_host_scalars")
     return out
+
+
+def msm_host_scalars_stats():
+    """zkg_msm_host_scalars_stats: the last msm_g1_host_scalars as a dict — pieces, stream_waits (cross-stream waits on the caller's stream),
+    heavy (per piece: the heavy-bucket count the host read, None where it read none) and pair (per piece: the heavy kernels were launched)"""
+    out = (C.c_uint32 * 18)()
+    words = lib().zkg_msm_host_scalars_stats(out, 18)
+    if words < 2:
+        return None
+    pieces = int(out[0])
+    return {"pieces": pieces, "stream_waits": int(out[1]),
+            "heavy": [None if out[2 + 2 * k] == 0xFFFFFFFF else int(out[2 + 2 * k]) for k in range(pieces)],
+            "pair": [bool(out[3 + 2 * k]) for k in range(pieces)]}
 
 
 class _ResidentBases:

@@ -805,6 +805,7 @@ int zkg_msm_g1_host_scalars(const void *d_bases, const uint64_t *scalars, size_t
     store_norm(out_jac, r);
     return ZKG_OK;
 }
+int zkg_msm_host_scalars_stats(uint32_t *out, int n) { return out && n >= 0 ? msm_host_scalars_stats(out, n) : 0; }
 int zkg_msm_g1_windows_dev(const void *d_bases, const void *d_scalars, size_t n, int scalars_mont, unsigned first_window, unsigned window_stride,
                            uint64_t out_jac[12], void *stream) {
     REQUIRE_INIT();

@@ -228,6 +228,7 @@ int ones_sum_launch_multi(OnesSum &o, const MsmBases *sets, int nsets, const uin
 int msm_g1(const G1Affine *d_bases, const uint32_t *d_scalars, size_t n, bool scalars_mont, G1 *out, hipStream_t s, bool mostly_bits = false);
 int msm_g2(const G2Affine *d_bases, const uint32_t *d_scalars, size_t n, bool scalars_mont, G2 *out, hipStream_t s, bool mostly_bits = false);
 int msm_g1_host_scalars(const G1Affine *d_bases, const uint32_t *h_scalars, size_t n, bool scalars_mont, G1 *out, hipStream_t s);   // bases resident, scalars uploaded in pieces under the work
+int msm_host_scalars_stats(uint32_t *out, int n);         // zkg_msm_host_scalars_stats: the last msm_g1_host_scalars' pieces, heavy counts, heavy launches and stream waits
 // one digit/sort pass shared by several base sets (A, B_g1, B_g2 queries use the same scalars)
 int msm_shared(const G1Affine *const *d_g1_bases, int n_g1, const G2Affine *d_g2_bases, const uint32_t *d_scalars, size_t n,
                bool scalars_mont, G1 *out_g1, G2 *out_g2, hipStream_t s, uint32_t w0 = 0, uint32_t ws = 1,   // w0, ws: window subset (see MsmGeom)

@@ -661,8 +661,11 @@ __global__ __launch_bounds__(1024) void k_class_hist(const uint32_t *counts, con
 // reserved from class_cursor, which the job's first kernel zeroes with the histogram.  The kernel runs beside an accumulation in a piece-wise
 // job, so the scan is kept off its issue slots: inside the wavefronts that hold classes (two positions per thread; a uniform 2^20-point job has
 // ~50 classes: one wavefront), their totals through LDS, and one thread's threshold for all.
+// heavy_out (may be null): a word of pinned host memory that gets the count of heavy buckets — class heavy_t + 1, the lists the accumulation
+// hands to k_heavy_parts / k_heavy_merge under the same threshold — so that a host that paces the launches knows whether that pair has work
+// (msm_g1_host_scalars).
 __global__ __launch_bounds__(1024) void k_order_place(const uint32_t *counts, const uint32_t *offsets, size_t total, const uint32_t *class_hist, uint32_t *class_cursor,
-                                                       uint32_t *order) {
+                                                       uint32_t *order, uint32_t *heavy_out) {
     sort_wave_priority();
     __shared__ uint32_t h[HEAVY_T_MAX + 2], first[HEAVY_T_MAX + 2], wave_total[16], threshold;
     const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63;
@@ -681,6 +684,7 @@ __global__ __launch_bounds__(1024) void k_order_place(const uint32_t *counts, co
             if (2 * t < nc) v0 += copy[nc - 1 - 2 * t];
             if (2 * t + 1 < nc) v1 += copy[nc - 2 - 2 * t];
         }
+        if (heavy_out && blockIdx.x == 0 && t == 0) *heavy_out = v0;      // position 0 of the reversed order: class heavy_t + 1, summed over its copies
         incl = v0 + v1;
         for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(incl, d, 64); if (lane >= d) incl += y; }
     }
@@ -1409,7 +1413,8 @@ struct MsmJob {
     // a second job that alternates with this one over the pieces of one multi-exponentiation accumulates into THIS job's buckets
     MsmJob *bucket_owner = nullptr;
     // the digit sort may run on a stream of its own (high priority: its small kernels get the compute units an accumulation frees first);
-    // ev_sorted orders the accumulation behind it, ev_acc_done the next sort of this job's buffers behind the accumulation that reads them
+    // ev_sorted orders the accumulation behind it (msm_job_launch: a wait on the stream; msm_g1_host_scalars: the calling thread waits and then
+    // enqueues), ev_acc_done the next sort of this job's buffers behind the accumulation that reads them
     hipStream_t sort_stream = nullptr; hipEvent_t ev_sorted = nullptr, ev_acc_done = nullptr;
     uint32_t w0 = 0, ws = 1;           // window subset of the next launches (window-sharded multi-GPU runs)
     bool empty = false;
@@ -1418,11 +1423,14 @@ struct MsmJob {
     uint32_t multi = 1; size_t multi_stride = 0;
     // bases resident, scalars in host memory (msm_g1_host_scalars): device copy of the scalars, the copy stream and one event per piece
     DevBuf hs_scalars; hipStream_t copy = nullptr; hipEvent_t ev_piece[8] = {nullptr};
+    // ... and eight words of pinned host memory, one per piece: the next sort's k_order_place stores its heavy-bucket count at heavy_out (null: nowhere)
+    uint32_t *heavy_words = nullptr, *heavy_out = nullptr;
+    uint32_t stream_waits = 0;         // cross-stream waits this job's launches have put on job->stream (zkg_msm_host_scalars_stats; msm_g1_host_scalars resets it)
     std::mutex mu;
 };
 
 template <class F>
-static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, const uint32_t *d_gather, bool time_it) {
+static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, const uint32_t *d_gather, bool time_it, bool heavy_pair = true /* false: the caller knows that no bucket is heavy */) {
     const MsmGeom g = job->g; const size_t n = job->n, total_buckets = (size_t)g.W * g.B; const unsigned ns = (unsigned)gr.nsets;
     // a multi launch (msm_job_launch_multi): P vectors' rows side by side, a window is P * B buckets wide and the fold leaves P bucket sets
     const uint32_t P = job->multi, BP = g.B * P, Wp = g.W / P;
@@ -1467,7 +1475,8 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
             use29 = true;
             if (sets[0].p29) rec29 = reinterpret_cast<const Rec64 *>(sets[0].p29);       // the caller made the records (a piece of a piece-wise job)
             else {
-                ZK_HIP(hipStreamWaitEvent(s, job->ev_join, 0));                          // converted beside the sort (msm_job_launch: the same conditions)
+                ZK_HIP(hipStreamWaitEvent(s, job->ev_join, 0));                          // converted beside the sort (msm_job_enqueue_sort: the same conditions)
+                ++job->stream_waits;
                 rec29 = gr.bases29.as<Rec64>();
             }
         } else if (ns == 1 && !d_gather && sets[0].p29 && !sets[0].remap && sets[0].index_sub == 0) {
@@ -1507,10 +1516,13 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
                            views, job->sorted.as<uint32_t>(), job->offsets.as<uint32_t>(), job->order.as<uint32_t>(), lanes, buckets,
                            gr.heavy_items.as<HeavyItem>(), gr.heavy_buckets.as<HeavyBucket>(), gr.heavy_counters.as<uint32_t>(), L);
     if (time_it) g_dominant_timer.end(s);
+    // (counters == 0 and both kernels return at once where no list is above the threshold: 10 ... 15 us of dispatches per accumulation all the same)
+    if (heavy_pair) {
     hipLaunchKernelGGL(k_heavy_parts<F>, dim3(HEAVY_PART_BLOCKS, ns), dim3(256), 256 * sizeof(LdsPoint<F>), s,
                        views, job->sorted.as<uint32_t>(), gr.heavy_items.as<HeavyItem>(), gr.heavy_counters.as<uint32_t>(), gr.heavy_partials.as<XYZZ<F>>(), buckets, L, (int)out29);
     hipLaunchKernelGGL(k_heavy_merge<F>, dim3(HEAVY_MERGE_BLOCKS, ns), dim3(256), 256 * sizeof(LdsPoint<F>), s,
                        gr.heavy_buckets.as<HeavyBucket>(), gr.heavy_counters.as<uint32_t>(), gr.heavy_partials.as<XYZZ<F>>(), buckets, L, (int)out29, resume);
+    }
     if (job->defer_reduce) {                                                    // a piece of a larger job: its buckets wait for the next piece
         if (hipGetLastError() != hipSuccess) { set_error("msm kernel launch failed"); return ZKG_ERROR; }
         return ZKG_OK;
@@ -1793,7 +1805,7 @@ static int sort_digits(MsmJob *job, const uint32_t *d_scalars, bool mont, const 
     hipLaunchKernelGGL(k_place, dim3(S, g.W), dim3(SORT_THREADS), g.B * 4, s, digits, n, g.B, S, slice_len, hist, offsets, job->sorted.as<uint32_t>());
     hipLaunchKernelGGL(k_class_hist, dim3((unsigned)((total + 1023) / 1024)), dim3(1024), 0, s, counts, offsets, total, chist);
     }
-    hipLaunchKernelGGL(k_order_place, dim3((unsigned)((total + 1023) / 1024)), dim3(1024), 0, s, counts, offsets, total, chist, chist + CLASS_HIST_COPIES * (HEAVY_T_MAX + 2), job->order.as<uint32_t>());
+    hipLaunchKernelGGL(k_order_place, dim3((unsigned)((total + 1023) / 1024)), dim3(1024), 0, s, counts, offsets, total, chist, chist + CLASS_HIST_COPIES * (HEAVY_T_MAX + 2), job->order.as<uint32_t>(), job->heavy_out);
     if (hipGetLastError() != hipSuccess) { set_error("msm sort launch failed"); return ZKG_ERROR; }
     return ZKG_OK;
 }
@@ -1830,13 +1842,26 @@ void msm_job_destroy(MsmJob *j) {
 static MsmJob g_default_job;          // the synchronous entry points share one job (serialised by its mutex); only it feeds the kernel timer
 static MsmJob g_piece_job;            // msm_g1_host_scalars: the second set of sort buffers its pieces alternate over (used under g_default_job's mutex)
 static hipStream_t g_sort_hi = nullptr;   // and the high-priority stream their digit sorts run on
+// what the last msm_g1_host_scalars did (zkg_msm_host_scalars_stats; written and read under g_default_job's mutex): pieces run, cross-stream
+// waits put on the caller's stream, and per piece the heavy-bucket count the host read and whether the heavy pair was launched
+struct HostScalarsStats { uint32_t pieces = 0, waits = 0, heavy[8] = {0}, pair[8] = {0}; };
+static HostScalarsStats g_hs_stats;
 
 // enqueue: one digit sort of the scalars (element d_gather[i] of d_scalars when a gather list is given), then one accumulate + reduce
 // per base set
-int msm_job_launch(MsmJob *job, const MsmBases *sets, int nsets, const uint32_t *d_scalars, size_t n, bool scalars_mont, const uint32_t *d_gather) {
-    static const bool dbg = getenv("ZKG_DEBUG_TIMING") != nullptr;
-    auto t0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char *w) { if (dbg) fprintf(stderr, "[zkg]     %-18s %8.3f ms\n", w, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count()); };
+//
+// A launch has two halves.  msm_job_enqueue_sort: the geometry, a plain G1 set's records on the side stream, the digit sort, and — where the
+// sort runs on a stream of its own — the record of ev_sorted behind it.  msm_job_enqueue_accumulate: accumulate (+ reduce) per base set on
+// job->stream.  msm_job_launch calls them back to back; a caller that takes them apart (msm_g1_host_scalars) orders the second behind
+// ev_sorted itself.  MsmLaunchSets is what the first half leaves for the second: the launch's base sets by field.
+struct MsmLaunchSets { MsmBases by_field[2][MSM_MAX_SETS]; };
+// an error return after the fork must not leave the side stream reading the caller's bases (a synchronous caller may free them next)
+static int msm_launch_failed(MsmJob *job) {
+    if (job->converted_aside) { (void)hipStreamSynchronize(job->aux); job->converted_aside = false; }
+    return ZKG_ERROR;
+}
+static int msm_job_enqueue_sort(MsmJob *job, const MsmBases *sets, int nsets, const uint32_t *d_scalars, size_t n, bool scalars_mont, const uint32_t *d_gather, MsmLaunchSets &ls) {
+    auto &by_field = ls.by_field;
     if (n >= ((size_t)1 << 31) || nsets < 0 || nsets > MSM_MAX_SETS) { set_error("msm: bad size"); return ZKG_ERROR; }
     bool any_table = false;
     for (int i = 0; i < nsets; ++i) any_table = any_table || sets[i].level_stride != 0;
@@ -1844,7 +1869,6 @@ int msm_job_launch(MsmJob *job, const MsmBases *sets, int nsets, const uint32_t 
     if (any_table && (job->w0 != 0 || job->ws != 1 || job->window_hint <= 0)) { set_error("msm: a table launch covers all windows at the table's window size"); return ZKG_ERROR; }
     job->g = pick_geom(n, job->window_hint, job->w0, job->ws); job->n = n;
     job->empty = false; job->multi = 1;
-    MsmBases by_field[2][MSM_MAX_SETS];
     for (MsmGroup &gr : job->group) gr.nsets = 0;
     job->group[0].g2 = false; job->group[1].g2 = true;
     for (int i = 0; i < nsets; ++i) { MsmGroup &gr = job->group[sets[i].g2 ? 1 : 0]; by_field[sets[i].g2 ? 1 : 0][gr.nsets] = sets[i]; gr.out_index[gr.nsets] = gr.nsets; ++gr.nsets; }
@@ -1870,19 +1894,33 @@ int msm_job_launch(MsmJob *job, const MsmBases *sets, int nsets, const uint32_t 
             job->converted_aside = true;
         }
     }
-    // an error return after the fork must not leave the side stream reading the caller's bases (a synchronous caller may free them next)
-    auto fail = [&] { if (job->converted_aside) { (void)hipStreamSynchronize(job->aux); job->converted_aside = false; } return ZKG_ERROR; };
-    if (sort_digits(job, d_scalars, scalars_mont, d_gather)) return fail();
-    if (job->sort_stream && job->sort_stream != job->stream) {                 // the accumulation (job->stream) behind the sort
-        if (hipEventRecord(job->ev_sorted, job->sort_stream) != hipSuccess || hipStreamWaitEvent(job->stream, job->ev_sorted, 0) != hipSuccess) return fail();
-    }
+    if (sort_digits(job, d_scalars, scalars_mont, d_gather)) return msm_launch_failed(job);
+    if (job->sort_stream && job->sort_stream != job->stream && hipEventRecord(job->ev_sorted, job->sort_stream) != hipSuccess) return msm_launch_failed(job);
     if (job->merge > 1) {
         for (int k = 0; k < 2; ++k) for (int i = 0; i < job->group[k].nsets; ++i) by_field[k][i].level_stride *= job->merge;
     }
-    lap("sort enqueued");
+    return ZKG_OK;
+}
+// heavy_pair == false: the caller has read the sort's heavy-bucket count (job->heavy_out) and found zero
+static int msm_job_enqueue_accumulate(MsmJob *job, MsmLaunchSets &ls, const uint32_t *d_gather, bool heavy_pair) {
+    if (job->empty) return ZKG_OK;
     const bool timed_field_g2 = job->group[0].nsets == 0;                       // the kernel timer follows the first G1 launch (G2 when there is no G1 set)
-    if (job->group[1].nsets && launch_accumulate<Fq2>(job, job->group[1], by_field[1], d_gather, job == &g_default_job && timed_field_g2)) return fail();   // G2 first: the longer chains
-    if (job->group[0].nsets && launch_accumulate<Fq>(job, job->group[0], by_field[0], d_gather, job == &g_default_job || job == &g_piece_job)) return fail();
+    if (job->group[1].nsets && launch_accumulate<Fq2>(job, job->group[1], ls.by_field[1], d_gather, job == &g_default_job && timed_field_g2, heavy_pair)) return msm_launch_failed(job);   // G2 first: the longer chains
+    if (job->group[0].nsets && launch_accumulate<Fq>(job, job->group[0], ls.by_field[0], d_gather, job == &g_default_job || job == &g_piece_job, heavy_pair)) return msm_launch_failed(job);
+    return ZKG_OK;
+}
+int msm_job_launch(MsmJob *job, const MsmBases *sets, int nsets, const uint32_t *d_scalars, size_t n, bool scalars_mont, const uint32_t *d_gather) {
+    static const bool dbg = getenv("ZKG_DEBUG_TIMING") != nullptr;
+    auto t0 = std::chrono::steady_clock::now();
+    auto lap = [&](const char *w) { if (dbg) fprintf(stderr, "[zkg]     %-18s %8.3f ms\n", w, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count()); };
+    MsmLaunchSets ls;
+    if (msm_job_enqueue_sort(job, sets, nsets, d_scalars, n, scalars_mont, d_gather, ls)) return ZKG_ERROR;
+    if (!job->empty && job->sort_stream && job->sort_stream != job->stream) {   // the accumulation (job->stream) behind the sort, on the device
+        if (hipStreamWaitEvent(job->stream, job->ev_sorted, 0) != hipSuccess) return msm_launch_failed(job);
+        ++job->stream_waits;
+    }
+    lap("sort enqueued");
+    if (msm_job_enqueue_accumulate(job, ls, d_gather, true)) return ZKG_ERROR;
     lap("accum enqueued");
     return ZKG_OK;
 }
@@ -2056,11 +2094,14 @@ int msm_g1_host_scalars(const G1Affine *d_bases, const uint32_t *h_scalars, size
     uint32_t *d_sc = J.hs_scalars.as<uint32_t>();
     J.stream = s; J.w0 = 0; J.ws = 1; J.one_pass_sort = false;
     MsmBases set; set.p = d_bases;
+    g_hs_stats = HostScalarsStats(); J.stream_waits = 0; g_piece_job.stream_waits = 0;
     if (!pieces) {                                                              // small or switched off: one upload in stream order, one launch
         ZK_HIP(hipMemcpyAsync(d_sc, h_scalars, n * 32, hipMemcpyHostToDevice, s));
         if (msm_job_launch(&J, &set, 1, d_sc, n, mont, nullptr)) return ZKG_ERROR;
+        g_hs_stats.pieces = 1; g_hs_stats.waits = J.stream_waits; g_hs_stats.heavy[0] = 0xffffffffu; g_hs_stats.pair[0] = 1;     // (the pair goes out blind: nobody reads a count)
         return msm_job_finish(&J, out, nullptr);
     }
+    if (!J.heavy_words && hipHostMalloc(reinterpret_cast<void **>(&J.heavy_words), 8 * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) { J.heavy_words = nullptr; set_error("msm: pinned words"); return ZKG_ERROR; }
     // piece boundaries: halves from the top, the lowest one split once more -> n/8, n/8, n/4, n/2 for four pieces
     size_t cut[9]; int P = max_pieces;
     cut[P] = n;
@@ -2086,7 +2127,9 @@ int msm_g1_host_scalars(const G1Affine *d_bases, const uint32_t *h_scalars, size
         int lo = 0, hi = 0; (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
         // (confining this stream to 16 ... 128 compute units with a CU mask instead was measured: 2.11 -> 4.25 ... 2.70 ms — the sort needs the chip's width)
         bool ok = hipStreamCreateWithPriority(&g_sort_hi, hipStreamNonBlocking, hi) == hipSuccess;
-        // (these events without their system-scope fence — hipEventDisableSystemFence — were measured: 1.994 against 1.998 ms, nothing; an A/B on one box)
+        // (these events without their system-scope fence — hipEventDisableSystemFence — were measured: 1.994 against 1.998 ms, nothing; an A/B on one box.
+        //  Again for ev_acc_done alone once the host paced the accumulations: 1.7512 against 1.7549 ms over five alternating runs, nothing.  ev_sorted
+        //  needs its fence in any case: the host reads the heavy word behind it.)
         for (MsmJob *w : {&J, &K}) ok = ok && hipEventCreateWithFlags(&w->ev_sorted, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&w->ev_acc_done, hipEventDisableTiming) == hipSuccess;
         if (!ok) { g_sort_hi = nullptr; set_error("msm: sort stream"); return ZKG_ERROR; }
     }
@@ -2098,32 +2141,68 @@ int msm_g1_host_scalars(const G1Affine *d_bases, const uint32_t *h_scalars, size
     ZK_HIP(hipEventRecord(J.ev_fork, s));                                     // behind whatever the caller queued (the work that made the bases), and the last call's accumulation
     ZK_HIP(hipStreamWaitEvent(J.aux, J.ev_fork, 0));
     hipLaunchKernelGGL(k_bases_to29, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, J.aux, reinterpret_cast<const Affine<Fq> *>(d_bases), n, J.group[0].bases29.as<Rec64>());
-    ZK_HIP(hipEventRecord(J.ev_join, J.aux));
-    ZK_HIP(hipStreamWaitEvent(s, J.ev_join, 0));
+    ZK_HIP(hipEventRecord(J.ev_join, J.aux));                                 // (the calling thread waits for it before the first accumulation, below)
     ZK_HIP(hipStreamWaitEvent(s_hi, J.ev_fork, 0));
     const int c = (int)pick_geom(n, J.window_hint).c;                         // every piece under the whole job's window size
     const int saved_hint = J.window_hint, saved_hint_k = K.window_hint;
     J.window_hint = c; K.window_hint = c; K.bucket_owner = &J; K.w0 = 0; K.ws = 1; K.one_pass_sort = false; K.stream = s;
-    int rc = ZKG_OK; bool started = false; bool used[2] = {false, false};
-    for (int k = 0; k < P && rc == ZKG_OK; ++k) {
-        if (cut[k + 1] == cut[k] && k + 1 < P) continue;                      // (an empty piece; the last one always runs: it carries the reduction)
-        const int which = (P - 1 - k) & 1;                                     // the last piece is the default job's: it carries the reduction and the result
-        MsmJob &W = which ? K : J;
+    // The calling thread paces the accumulations (it would only sleep in msm_job_finish otherwise): an accumulation is enqueued once the host has
+    // seen its sort finish, so the caller's stream carries kernels and one event record per piece and no cross-stream wait — such a wait in front
+    // of a kernel stood for 15 ... 23 us of idle chip even where the awaited sort had ended long before.  And the host then knows the piece's
+    // heavy-bucket count (k_order_place's word, visible once ev_sorted has completed: the event keeps its system-scope fence): the heavy pair is
+    // launched only where it has work.  Per piece: the NEXT piece's sort goes onto the sort stream first, with its waits for its upload and for the
+    // accumulation that last read its buffers on the device — two pieces back: that accumulation's ev_acc_done was recorded in the round before —
+    // then the host waits for this piece's sort, enqueues its accumulation and records ev_acc_done behind it.
+    int run[8], R = 0;
+    for (int k = 0; k < P; ++k) if (cut[k + 1] != cut[k] || k + 1 == P) run[R++] = k;      // (empty pieces are skipped; the last one always runs: it carries the reduction)
+    MsmLaunchSets ls[2];
+    int rc = ZKG_OK; bool used[2] = {false, false};
+    // pieces alternate over the two jobs by their position among the pieces that run; the last one is the default job's: it carries the reduction and the result
+    auto job_of = [&](int i) -> MsmJob & { return ((R - 1 - i) & 1) ? K : J; };
+    auto enqueue_sort = [&](int i) {
+        const int k = run[i], which = (R - 1 - i) & 1;
+        MsmJob &W = job_of(i);
         MsmBases piece = set; piece.p = reinterpret_cast<const char *>(d_bases) + cut[k] * sizeof(G1Affine);
         piece.p29 = J.group[0].bases29.as<Rec64>() + cut[k];
-        W.resume = started; W.defer_reduce = k + 1 < P; started = true;
-        W.sort_stream = s_hi;
-        // this piece's sort: after its scalars have landed, and after the accumulation that last read this job's sort buffers
-        if (hipStreamWaitEvent(s_hi, J.ev_piece[k], 0) != hipSuccess) { rc = ZKG_ERROR; break; }
-        if (used[which] && hipStreamWaitEvent(s_hi, W.ev_acc_done, 0) != hipSuccess) { rc = ZKG_ERROR; break; }
-        rc = msm_job_launch(&W, &piece, 1, d_sc + 8 * cut[k], cut[k + 1] - cut[k], mont, nullptr);
+        W.sort_stream = s_hi; W.heavy_out = J.heavy_words + i;
+        // after its scalars have landed, and after the accumulation that last read this job's sort buffers
+        if (hipStreamWaitEvent(s_hi, J.ev_piece[k], 0) != hipSuccess) return ZKG_ERROR;
+        if (used[which] && hipStreamWaitEvent(s_hi, W.ev_acc_done, 0) != hipSuccess) return ZKG_ERROR;
+        return msm_job_enqueue_sort(&W, &piece, 1, d_sc + 8 * cut[k], cut[k + 1] - cut[k], mont, nullptr, ls[which]);
+    };
+    rc = enqueue_sort(0);
+    for (int i = 0; i < R && rc == ZKG_OK; ++i) {
+        const int which = (R - 1 - i) & 1;
+        MsmJob &W = job_of(i);
+        if (i + 1 < R && (rc = enqueue_sort(i + 1)) != ZKG_OK) break;
+        if (i == 0 && hipEventSynchronize(J.ev_join) != hipSuccess) { rc = ZKG_ERROR; break; }      // the bases' records
+        uint32_t heavy = 0;
+        if (!W.empty) {
+            if (hipEventSynchronize(W.ev_sorted) != hipSuccess) { rc = ZKG_ERROR; break; }
+            heavy = *static_cast<volatile const uint32_t *>(J.heavy_words + i);
+        }
+        W.resume = i > 0; W.defer_reduce = i + 1 < R;
+        rc = msm_job_enqueue_accumulate(&W, ls[which], nullptr, heavy != 0);
         if (rc == ZKG_OK && hipEventRecord(W.ev_acc_done, s) != hipSuccess) rc = ZKG_ERROR;
         used[which] = true;
+        g_hs_stats.heavy[i] = heavy; g_hs_stats.pair[i] = heavy != 0; g_hs_stats.pieces = (uint32_t)(i + 1);
     }
-    J.resume = false; J.defer_reduce = false; J.window_hint = saved_hint; J.sort_stream = nullptr;      // (the other entry points sort on the job's own stream)
-    K.resume = false; K.defer_reduce = false; K.window_hint = saved_hint_k; K.bucket_owner = nullptr; K.sort_stream = nullptr; K.stream = nullptr;
-    if (rc != ZKG_OK) { (void)hipStreamSynchronize(J.copy); (void)hipStreamSynchronize(s_hi); (void)hipStreamSynchronize(s); return ZKG_ERROR; }
+    g_hs_stats.waits = J.stream_waits + K.stream_waits;
+    J.resume = false; J.defer_reduce = false; J.window_hint = saved_hint; J.sort_stream = nullptr; J.heavy_out = nullptr;      // (the other entry points sort on the job's own stream)
+    K.resume = false; K.defer_reduce = false; K.window_hint = saved_hint_k; K.bucket_owner = nullptr; K.sort_stream = nullptr; K.stream = nullptr; K.heavy_out = nullptr;
+    if (rc != ZKG_OK) { (void)hipStreamSynchronize(J.copy); (void)hipStreamSynchronize(J.aux); (void)hipStreamSynchronize(s_hi); (void)hipStreamSynchronize(s); return ZKG_ERROR; }
     return msm_job_finish(&J, out, nullptr);
+}
+// out: pieces | stream waits | (heavy count, pair launched) per piece — at most n words; returns the words the record has (0: no call yet)
+int msm_host_scalars_stats(uint32_t *out, int n) {
+    std::lock_guard<std::mutex> lk(g_default_job.mu);
+    const HostScalarsStats &st = g_hs_stats;
+    if (!st.pieces) return 0;
+    uint32_t rec[2 + 2 * 8] = {st.pieces, st.waits};
+    for (uint32_t k = 0; k < st.pieces; ++k) { rec[2 + 2 * k] = st.heavy[k]; rec[3 + 2 * k] = st.pair[k]; }
+    const int words = 2 + 2 * (int)st.pieces;
+    for (int i = 0; i < words && i < n; ++i) out[i] = rec[i];
+    return words;
 }
 
 int msm_g1(const G1Affine *d_bases, const uint32_t *d_scalars, size_t n, bool mont, G1 *out, hipStream_t s, bool mostly_bits) {
@@ -2355,6 +2434,7 @@ void msm_release_all() {
     }
     if (j.copy) { (void)hipStreamSynchronize(j.copy); (void)hipStreamDestroy(j.copy); j.copy = nullptr; }
     for (auto &e : j.ev_piece) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+    if (j.heavy_words) { (void)hipHostFree(j.heavy_words); j.heavy_words = nullptr; }
     if (j.ev_fork) { (void)hipEventDestroy(j.ev_fork); j.ev_fork = nullptr; }
     if (j.ev_join) { (void)hipEventDestroy(j.ev_join); j.ev_join = nullptr; }
 }
