@@ -60,6 +60,12 @@ class _Inputs:
             self._expected[key] = self.zkg.msm_g1_dev(d_bases.data_ptr(), d_sc.data_ptr(), n)
         return self._expected[key]
 
+    def oracle_uniform(self, oracle):
+        """the oracle's point for the uniform scalars at N, computed once for the tests that compare with it"""
+        if "oracle" not in self._expected:
+            self._expected["oracle"] = oracle.msm_g1(self.bases[:N], self.uniform[:N], oracle.BDLO12, oracle.num_threads())
+        return self._expected["oracle"]
+
     def pinned(self, key, sc):
         import torch
         if key not in self._pinned:
@@ -93,7 +99,7 @@ def test_uniform_scalars_launch_no_heavy_pair(inputs, oracle):
     got, exp, st = inputs.run_uniform()
     print("stats:", st)
     assert np.array_equal(got, exp)
-    assert np.array_equal(got, oracle.msm_g1(inputs.bases[:N], inputs.uniform[:N], oracle.BDLO12, oracle.num_threads()))
+    assert np.array_equal(got, inputs.oracle_uniform(oracle))
     _assert_uniform_stats(st)
 
 
@@ -133,3 +139,84 @@ def test_sizes_around_the_piece_wise_threshold(inputs):
     got, exp, st = inputs.run_uniform(N - 256)                 # the single-launch path: one piece, no count read, the pair launched as before
     assert np.array_equal(got, exp)
     assert st["pieces"] == 1 and st["heavy"] == [None] and st["pair"] == [True], st
+
+
+def test_launch_modes_do_not_leak_between_entries(inputs, oracle):
+    """What a piece-wise call sets for its launches — the sort stream and its 512-thread sort form, two wavefronts per SIMD, resumed buckets, no
+    reduction, the heavy count's address, the window size — holds for those launches alone: the resident entries that follow it on the same
+    job (a plain G1 set with its side-stream conversion, the three-wave form and the one-launch sort at 4096 points; the two-pass sort at 2^19;
+    a G2 set), the single-launch form of the entry itself and a second piece-wise call return what they returned before the first one."""
+    import torch
+    zkg = inputs.zkg
+    n_small, n_g2, n_single = 4096, 2048, N - 256
+    d_small, d_big = to_dev(inputs.uniform[:n_small]), to_dev(inputs.uniform[:N])
+    d_k = to_dev(inputs.uniform[:n_g2])
+    d_g2 = torch.empty((n_g2, 16), dtype=torch.int64, device="cuda")
+    zkg.fixed_base_g2_dev(oracle.g2_generator(), d_k.data_ptr(), n_g2, d_g2.data_ptr())
+    torch.cuda.synchronize()
+    g2_bases = d_g2.cpu().numpy().view(np.uint64)
+    sc_g2 = np.ascontiguousarray(inputs.uniform[n_g2:2 * n_g2])
+    d_sc_g2 = to_dev(sc_g2)
+
+    def entries():
+        return [zkg.msm_g1_dev(inputs.d_bases.data_ptr(), d_small.data_ptr(), n_small),
+                zkg.msm_g1_dev(inputs.d_bases.data_ptr(), d_big.data_ptr(), N),
+                zkg.msm_g2_dev(d_g2.data_ptr(), d_sc_g2.data_ptr(), n_g2)]
+
+    before = entries()
+    before_single = inputs.expected(("uniform", n_single), inputs.d_bases, inputs.uniform, n_single)
+    assert np.array_equal(before[1], inputs.expected(("uniform", N), inputs.d_bases, inputs.uniform, N))
+    assert np.array_equal(before[0], oracle.msm_g1(inputs.bases[:n_small], inputs.uniform[:n_small], oracle.BDLO12, oracle.num_threads()))
+    assert np.array_equal(before[1], inputs.oracle_uniform(oracle))
+    assert np.array_equal(before[2], oracle.msm_g2(g2_bases, sc_g2, oracle.BDLO12, oracle.num_threads()))
+
+    got, exp, st = inputs.run_uniform()                                                       # 1. piece-wise
+    print("stats:", st)
+    assert np.array_equal(got, before[1]) and np.array_equal(got, exp)
+    _assert_uniform_stats(st)
+    after = entries()                                                                         # 2. - 4.
+    for k in range(3):
+        assert np.array_equal(after[k], before[k]), k
+    got, _, st = inputs.run_uniform(n_single)                                                 # 5. the entry's single launch
+    print("stats:", st)
+    assert np.array_equal(got, before_single)
+    assert st["pieces"] == 1, st
+    got, _, st = inputs.run_uniform()                                                         # 6. piece-wise again
+    print("stats:", st)
+    assert np.array_equal(got, before[1])
+    _assert_uniform_stats(st)
+
+
+def test_release_and_recreate_in_one_process():
+    """zkg_shutdown releases everything the piece-wise step and the default job hold, and a later zkg_init starts from nothing: init, piece-wise
+    call, shutdown, init, the same call, the resident call, shutdown — in a process of its own.  The three points are equal, the second
+    piece-wise call ran four pieces without a cross-stream wait on the caller's stream, and the process ends cleanly."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = r'''
+import json, sys, numpy as np, torch
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
+import zklaim_amd as zkg
+from bench import splitmix_fr
+from gpu_util import dev_bases_g1
+n = 1 << 19
+zkg.init(0)
+d_bases, _, _ = dev_bases_g1(zkg, n, 0x9AE0)
+sc = splitmix_fr(n, 0x9AE1)
+h_sc = torch.from_numpy(sc.view(np.int64)).pin_memory()
+first = zkg.msm_g1_host_scalars(d_bases.data_ptr(), h_sc.data_ptr(), n)
+zkg.shutdown()
+zkg.init(0)
+second = zkg.msm_g1_host_scalars(d_bases.data_ptr(), h_sc.data_ptr(), n)
+st = zkg.msm_host_scalars_stats()
+d_sc = h_sc.cuda()
+third = zkg.msm_g1_dev(d_bases.data_ptr(), d_sc.data_ptr(), n)
+zkg.shutdown()
+print(json.dumps({"points": [p.tobytes().hex() for p in (first, second, third)], "stats": st}))
+'''
+    r = subprocess.run([sys.executable, "-c", code, root], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    rec = json.loads(r.stdout.strip().splitlines()[-1])
+    print("stats:", rec["stats"])
+    assert rec["points"][0] == rec["points"][1] == rec["points"][2] and any(c != "0" for c in rec["points"][0])
+    assert rec["stats"]["pieces"] == 4 and rec["stats"]["stream_waits"] == 0, rec["stats"]

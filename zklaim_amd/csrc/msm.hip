@@ -1372,7 +1372,7 @@ __global__ __launch_bounds__(256) void k_sum_partials(XYZZ<F> *partials_all, uin
 
 // ---- jobs: one MSM (or several base sets over one scalar vector) in flight on one stream ---------------------
 struct MsmGroup {                   // the base sets of one field in a launch: accumulators and the host landing zone of their chunk results
-    DevBuf buckets, folded, red_out, heavy_items, heavy_buckets, heavy_counters, heavy_partials;
+    DevBuf buckets, folded, red_out, heavy_items, heavy_buckets, heavy_partials;
     DevBuf bases29;                                    // a plain G1 set's bases as 64-byte packed 29-bit records (Rec64, k_bases_to29), rebuilt per launch
     void *host_red = nullptr; size_t host_cap = 0; bool g2 = false, table = false; int nsets = 0;
     int out_index[MSM_MAX_SETS] = {0};                 // position of each set among the launch's sets of this field
@@ -1387,16 +1387,35 @@ struct MsmGroup {                   // the base sets of one field in a launch: a
         return 0;
     }
     void release() {
-        for (DevBuf *b : {&buckets, &folded, &red_out, &heavy_items, &heavy_buckets, &heavy_counters, &heavy_partials, &bases29}) b->release();
+        for (DevBuf *b : {&buckets, &folded, &red_out, &heavy_items, &heavy_buckets, &heavy_partials, &bases29}) b->release();
         if (host_red) (void)hipHostFree(host_red);
         host_red = nullptr; host_cap = 0;
     }
 };
+// What a digit sort writes and the accumulation behind it reads: the sorted entry list with its bucket offsets and order, the sort's scratch, and
+// the heavy-list counters of the launch's two fields — the sort's first kernel clears them (ZeroList), so they go with the sort's buffers: a sort
+// that runs beside the accumulation of the launch before it (msm_g1_host_scalars) must not clear the counters that one is filling.
+struct MsmSortSpace {
+    DevBuf digits, hist, counts, offsets, scan_sums, class_hist, order, sorted, rx_tmp, rx_meta, heavy_counters[2];
+    void release() { for (DevBuf *b : {&digits, &hist, &counts, &offsets, &scan_sums, &class_hist, &order, &sorted, &rx_tmp, &rx_meta, &heavy_counters[0], &heavy_counters[1]}) b->release(); }
+};
+// What belongs to ONE launch and not to the job: passed by value through both halves of a launch, nothing of it is kept on the job.
+struct MsmLaunchMode {
+    hipStream_t sort_stream = nullptr; // the digit sort's stream (high priority: its small kernels get the compute units an accumulation frees first); null: the job's own
+    uint32_t *heavy_out = nullptr;     // where the sort's k_order_place stores its heavy-bucket count (pinned host memory); null: nowhere
+    int window = 0;                    // > 0: this launch's window size, whatever the job's hint (the pieces of one multi-exponentiation share the whole job's)
+    bool resume = false;               // the accumulation continues the buckets of the launch before it
+    bool defer_reduce = false;         // more pieces follow: no reduction, nothing copied back
+    bool heavy_pair = true;            // false: the caller has read the sort's heavy-bucket count (heavy_out) and found zero
+    bool beside = false;               // something is meant to run beside the accumulation (the next piece's sort): two wavefronts per SIMD, see launch_accumulate
+    bool timed = false;                // the launch feeds the kernel timer (the synchronous entry points' job)
+    uint32_t *stream_waits = nullptr;  // counts the cross-stream waits the launch puts on job->stream (zkg_msm_host_scalars_stats); null: not counted
+};
 struct MsmJob {
     hipStream_t stream = nullptr; bool own_stream = false;
-    DevBuf digits, hist, counts, offsets, scan_sums, class_hist, order, sorted, rx_tmp, rx_meta;
+    MsmSortSpace space;
     MsmGroup group[2];                 // [0] the G1 sets, [1] the G2 sets of the launch
-    MsmGeom g{}; size_t n = 0;
+    MsmGeom g{}; size_t n = 0;         // of the launch whose sort was enqueued last (what msm_job_finish combines)
     int window_hint = 0;               // 0: pick_geom's rule
     // Table launches: every window's digit weighs the same, so f consecutive windows can share one row of buckets — a row is then a window
     // over the f n entries (level, point) of its levels, which lie back to back in the table.  Same sorted list (rows of the digit array
@@ -1406,32 +1425,41 @@ struct MsmJob {
     // leave most of the chip idle: fork after everything queued before (the previous launch's accumulation still reads the records), join before the accumulation
     hipStream_t aux = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; bool converted_aside = false;
     bool one_pass_sort = false;        // the caller knows the digits are skewed (a prover's 0/1 witness): skip the two-pass sort's attempt
-    // piece-wise jobs (msm_g1_host_scalars): `resume` — this launch's accumulation continues the buckets of the launch before it;
-    // `defer_reduce` — more pieces follow: no reduction, nothing copied back; `c_fixed` — every piece uses the whole job's window size
-    bool resume = false, defer_reduce = false;
     bool critical = false;                        // msm_job_set_critical: the accumulate / fold / reduce kernels raise their wavefronts' issue priority
-    // a second job that alternates with this one over the pieces of one multi-exponentiation accumulates into THIS job's buckets
-    MsmJob *bucket_owner = nullptr;
-    // the digit sort may run on a stream of its own (high priority: its small kernels get the compute units an accumulation frees first);
-    // ev_sorted orders the accumulation behind it (msm_job_launch: a wait on the stream; msm_g1_host_scalars: the calling thread waits and then
-    // enqueues), ev_acc_done the next sort of this job's buffers behind the accumulation that reads them
-    hipStream_t sort_stream = nullptr; hipEvent_t ev_sorted = nullptr, ev_acc_done = nullptr;
     uint32_t w0 = 0, ws = 1;           // window subset of the next launches (window-sharded multi-GPU runs)
     bool empty = false;
     bool dev_finish = false;           // msm_job_set_device_finish: the next launches end in msm_job_finish_dev — their chunk records stay on the device
     // msm_job_launch_multi: `multi` scalar vectors, multi_stride words apart, over one table; the geometry then has W * multi rows (k_digits_multi)
     uint32_t multi = 1; size_t multi_stride = 0;
-    // bases resident, scalars in host memory (msm_g1_host_scalars): device copy of the scalars, the copy stream and one event per piece
-    DevBuf hs_scalars; hipStream_t copy = nullptr; hipEvent_t ev_piece[8] = {nullptr};
-    // ... and eight words of pinned host memory, one per piece: the next sort's k_order_place stores its heavy-bucket count at heavy_out (null: nowhere)
-    uint32_t *heavy_words = nullptr, *heavy_out = nullptr;
-    uint32_t stream_waits = 0;         // cross-stream waits this job's launches have put on job->stream (zkg_msm_host_scalars_stats; msm_g1_host_scalars resets it)
     std::mutex mu;
+    // the side stream and its two events, all three or none
+    int ensure_side() {
+        if (aux) return ZKG_OK;
+        if (hipStreamCreateWithFlags(&aux, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) == hipSuccess &&
+            hipEventCreateWithFlags(&ev_join, hipEventDisableTiming) == hipSuccess) return ZKG_OK;
+        release_side(); set_error("msm: side stream"); return ZKG_ERROR;
+    }
+    void release_side() {
+        if (aux) { (void)hipStreamSynchronize(aux); (void)hipStreamDestroy(aux); }
+        if (ev_fork) (void)hipEventDestroy(ev_fork);
+        if (ev_join) (void)hipEventDestroy(ev_join);
+        aux = nullptr; ev_fork = ev_join = nullptr;
+    }
+    // everything the job holds on the device but its own stream; the job can be used again afterwards (a later zkg_init may pick another device)
+    void release_device() {
+        space.release();
+        for (MsmGroup &gr : group) gr.release();
+        release_side();
+    }
 };
+// What msm_job_enqueue_sort leaves for msm_job_enqueue_accumulate: the launch's base sets by field (level strides in merged rows), the geometry
+// as the sorted list has it, and the workspace the sort wrote.
+struct MsmLaunchSets { MsmBases by_field[2][MSM_MAX_SETS]; MsmGeom g{}; size_t n = 0; bool empty = false; MsmSortSpace *space = nullptr; };
 
 template <class F>
-static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, const uint32_t *d_gather, bool time_it, bool heavy_pair = true /* false: the caller knows that no bucket is heavy */) {
-    const MsmGeom g = job->g; const size_t n = job->n, total_buckets = (size_t)g.W * g.B; const unsigned ns = (unsigned)gr.nsets;
+static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmLaunchSets &ls, const uint32_t *d_gather, const MsmLaunchMode &mode, bool time_it) {
+    const MsmSortSpace &sp = *ls.space; const MsmBases *sets = ls.by_field[gr.g2 ? 1 : 0];
+    const MsmGeom g = ls.g; const size_t n = ls.n, total_buckets = (size_t)g.W * g.B; const unsigned ns = (unsigned)gr.nsets;
     // a multi launch (msm_job_launch_multi): P vectors' rows side by side, a window is P * B buckets wide and the fold leaves P bucket sets
     const uint32_t P = job->multi, BP = g.B * P, Wp = g.W / P;
     hipStream_t s = job->stream;
@@ -1448,15 +1476,14 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
     const int red_l_log = force_l ? atoi(force_l) : red_buckets >= RED_LARGE_BUCKETS ? RED_L_LOG_LARGE : red_buckets > RED_SMALL_BUCKETS ? RED_L_LOG_SMALL : RED_L_LOG_TINY;
     gr.chunk_log = RG::LANES_LOG + red_l_log;
     gr.cpw = (g.B + (1u << gr.chunk_log) - 1) >> gr.chunk_log; gr.nred = (size_t)gr.red_windows * gr.cpw;
-    DevBuf &bucket_buf = job->bucket_owner ? job->bucket_owner->group[sizeof(F) != sizeof(Fq) ? 1 : 0].buckets : gr.buckets;
     gr.red_slots = 2;
     SetLayout L; L.buckets = total_buckets; L.items = max_items; L.heavy = max_heavy; L.partials = max_items; L.folded = BP; L.red_out = gr.nred * 3;      // two results per chunk, three from k_bucket_reduce29l (gr.red_slots)
     if (gr.heavy_items.reserve(ns * max_items * sizeof(HeavyItem)) || gr.heavy_buckets.reserve(ns * max_heavy * sizeof(HeavyBucket)) ||
-        gr.heavy_counters.reserve(8 * MSM_MAX_SETS) || gr.heavy_partials.reserve(ns * max_items * sizeof(XYZZ<F>)) ||
-        bucket_buf.reserve(ns * total_buckets * std::max(sizeof(XYZZ<F>), sizeof(Bucket29))) || (job->dev_finish && gr.red_out.reserve(ns * L.red_out * sizeof(XYZZ<F>))) || ((gr.red_stride = L.red_out), false) ||
+        gr.heavy_partials.reserve(ns * max_items * sizeof(XYZZ<F>)) ||
+        gr.buckets.reserve(ns * total_buckets * std::max(sizeof(XYZZ<F>), sizeof(Bucket29))) || (job->dev_finish && gr.red_out.reserve(ns * L.red_out * sizeof(XYZZ<F>))) || ((gr.red_stride = L.red_out), false) ||
         (gr.table && gr.folded.reserve(ns * (size_t)BP * std::max(sizeof(XYZZ<F>), sizeof(Bucket29)))) || (!job->dev_finish && gr.host_reserve(ns * L.red_out * sizeof(XYZZ<F>)))) return ZKG_ERROR;
-    // (gr.heavy_counters: cleared by the job's k_digits)
-    XYZZ<F> *buckets = bucket_buf.as<XYZZ<F>>();
+    XYZZ<F> *buckets = gr.buckets.as<XYZZ<F>>();
+    uint32_t *heavy_counters = sp.heavy_counters[gr.g2 ? 1 : 0].as<uint32_t>();      // (reserved and cleared by the sort's k_digits)
     ViewSet<F> views;
     for (unsigned i = 0; i < (unsigned)MSM_MAX_SETS; ++i) {
         const MsmBases &b = sets[i < ns ? i : 0];
@@ -1476,7 +1503,7 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
             if (sets[0].p29) rec29 = reinterpret_cast<const Rec64 *>(sets[0].p29);       // the caller made the records (a piece of a piece-wise job)
             else {
                 ZK_HIP(hipStreamWaitEvent(s, job->ev_join, 0));                          // converted beside the sort (msm_job_enqueue_sort: the same conditions)
-                ++job->stream_waits;
+                if (mode.stream_waits) ++*mode.stream_waits;
                 rec29 = gr.bases29.as<Rec64>();
             }
         } else if (ns == 1 && !d_gather && sets[0].p29 && !sets[0].remap && sets[0].index_sub == 0) {
@@ -1488,7 +1515,7 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
     // — where the rows are few (8 after the row merge of the large tables: a bucket's rows are added in sequence, 4 us each; a one-payload key's 22
     // rows of 2048 buckets keep the 32-bit fold, a tree over the rows: 0.75 against 0.83 ms per proof)
     const bool out29 = use29 && (stride29 == 0 ? !gr.table : (gr.table && ns == 1 && Wp <= 8));
-    const int resume = job->resume ? 1 : 0;                                     // (msm_g1_host_scalars' pieces: one plain G1 set with its records, so use29 and out29 hold)
+    const int resume = mode.resume ? 1 : 0;                                     // (msm_g1_host_scalars' pieces: one plain G1 set with its records, so use29 and out29 hold)
     if (time_it) g_dominant_timer.begin(s);
     if constexpr (sizeof(F) == sizeof(Fq)) {
         // wavefronts per SIMD: three (168 registers; the loop has no spill either way) when the launch has the chip to itself — a plain set sorted on
@@ -1497,33 +1524,29 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
         static const int waves_env = getenv("ZKG_ACC29_WAVES") ? atoi(getenv("ZKG_ACC29_WAVES")) : 0;               // tuning aid: 2 or 3 everywhere
         // (the last piece of a piece-wise job has no sort beside it; three wavefronts for it alone were measured: 1.837 against 1.850 ms over three
         //  alternating runs each, one of the three pairs the other way round — inside the runs' own spread, so it keeps the two)
-        const int waves29 = waves_env ? waves_env : (job->sort_stream || gr.table || job->bucket_owner) ? 2 : 3;
+        const int waves29 = waves_env ? waves_env : (mode.beside || gr.table) ? 2 : 3;
         auto launch29 = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, rec29, stride29, BP, job->sorted.as<uint32_t>(),
-                               job->offsets.as<uint32_t>(), job->order.as<uint32_t>(), lanes, (void *)buckets, gr.heavy_items.as<HeavyItem>(),
-                               gr.heavy_buckets.as<HeavyBucket>(), gr.heavy_counters.as<uint32_t>(), L, resume | (job->critical ? 2 : 0));
+            hipLaunchKernelGGL(kern, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, rec29, stride29, BP, sp.sorted.as<uint32_t>(),
+                               sp.offsets.as<uint32_t>(), sp.order.as<uint32_t>(), lanes, (void *)buckets, gr.heavy_items.as<HeavyItem>(),
+                               gr.heavy_buckets.as<HeavyBucket>(), heavy_counters, L, resume | (job->critical ? 2 : 0));
         };
         if (use29 && waves29 == 3) { if (out29) launch29(k_bucket_accum29<3, true>); else launch29(k_bucket_accum29<3, false>); }
         else if (use29) { if (out29) launch29(k_bucket_accum29<2, true>); else launch29(k_bucket_accum29<2, false>); }
     }
-    if (use29) {}
-    else if (plain)
-        hipLaunchKernelGGL((k_bucket_accum<F, true>), dim3((unsigned)((lanes + 255) / 256), ns), dim3(256), 0, s,
-                           views, job->sorted.as<uint32_t>(), job->offsets.as<uint32_t>(), job->order.as<uint32_t>(), lanes, buckets,
-                           gr.heavy_items.as<HeavyItem>(), gr.heavy_buckets.as<HeavyBucket>(), gr.heavy_counters.as<uint32_t>(), L);
-    else
-        hipLaunchKernelGGL((k_bucket_accum<F, false>), dim3((unsigned)((lanes + 255) / 256), ns), dim3(256), 0, s,
-                           views, job->sorted.as<uint32_t>(), job->offsets.as<uint32_t>(), job->order.as<uint32_t>(), lanes, buckets,
-                           gr.heavy_items.as<HeavyItem>(), gr.heavy_buckets.as<HeavyBucket>(), gr.heavy_counters.as<uint32_t>(), L);
+    auto launch32 = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)((lanes + 255) / 256), ns), dim3(256), 0, s, views, sp.sorted.as<uint32_t>(), sp.offsets.as<uint32_t>(), sp.order.as<uint32_t>(),
+                           lanes, buckets, gr.heavy_items.as<HeavyItem>(), gr.heavy_buckets.as<HeavyBucket>(), heavy_counters, L);
+    };
+    if (!use29) { if (plain) launch32(k_bucket_accum<F, true>); else launch32(k_bucket_accum<F, false>); }
     if (time_it) g_dominant_timer.end(s);
     // (counters == 0 and both kernels return at once where no list is above the threshold: 10 ... 15 us of dispatches per accumulation all the same)
-    if (heavy_pair) {
+    if (mode.heavy_pair) {
     hipLaunchKernelGGL(k_heavy_parts<F>, dim3(HEAVY_PART_BLOCKS, ns), dim3(256), 256 * sizeof(LdsPoint<F>), s,
-                       views, job->sorted.as<uint32_t>(), gr.heavy_items.as<HeavyItem>(), gr.heavy_counters.as<uint32_t>(), gr.heavy_partials.as<XYZZ<F>>(), buckets, L, (int)out29);
+                       views, sp.sorted.as<uint32_t>(), gr.heavy_items.as<HeavyItem>(), heavy_counters, gr.heavy_partials.as<XYZZ<F>>(), buckets, L, (int)out29);
     hipLaunchKernelGGL(k_heavy_merge<F>, dim3(HEAVY_MERGE_BLOCKS, ns), dim3(256), 256 * sizeof(LdsPoint<F>), s,
-                       gr.heavy_buckets.as<HeavyBucket>(), gr.heavy_counters.as<uint32_t>(), gr.heavy_partials.as<XYZZ<F>>(), buckets, L, (int)out29, resume);
+                       gr.heavy_buckets.as<HeavyBucket>(), heavy_counters, gr.heavy_partials.as<XYZZ<F>>(), buckets, L, (int)out29, resume);
     }
-    if (job->defer_reduce) {                                                    // a piece of a larger job: its buckets wait for the next piece
+    if (mode.defer_reduce) {                                                    // a piece of a larger job: its buckets wait for the next piece
         if (hipGetLastError() != hipSuccess) { set_error("msm kernel launch failed"); return ZKG_ERROR; }
         return ZKG_OK;
     }
@@ -1534,7 +1557,7 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
     bool folded29 = false;
     if constexpr (sizeof(F) == sizeof(Fq)) {
         if (gr.table && out29) {
-            hipLaunchKernelGGL(k_bucket_fold29, dim3((2 * BP + 255) / 256), dim3(256), 0, s, reinterpret_cast<const Bucket29 *>(buckets), job->counts.as<uint32_t>(), Wp, BP,
+            hipLaunchKernelGGL(k_bucket_fold29, dim3((2 * BP + 255) / 256), dim3(256), 0, s, reinterpret_cast<const Bucket29 *>(buckets), sp.counts.as<uint32_t>(), Wp, BP,
                                gr.folded.as<Bucket29>(), job->critical ? 1 : 0);
             red_in = gr.folded.as<XYZZ<F>>(); in_stride = L.folded; folded29 = true;
         }
@@ -1543,7 +1566,7 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
         uint32_t slots = 1; while (slots < Wp && slots < 32) slots <<= 1;                // window slots per workgroup: W rounded up to a power of two (<= 32)
         uint32_t fold_b_log = 0; while ((FOLD_THREADS >> (fold_b_log + 1)) >= slots) ++fold_b_log;
         hipLaunchKernelGGL(k_bucket_fold<F>, dim3((BP + (1u << fold_b_log) - 1) >> fold_b_log, ns), dim3(FOLD_THREADS), FOLD_THREADS * sizeof(LdsPoint<F>), s,
-                           buckets, job->counts.as<uint32_t>(), Wp, BP, fold_b_log, gr.folded.as<XYZZ<F>>(), L);
+                           buckets, sp.counts.as<uint32_t>(), Wp, BP, fold_b_log, gr.folded.as<XYZZ<F>>(), L);
         red_in = gr.folded.as<XYZZ<F>>(); in_stride = L.folded;
     }
     if constexpr (sizeof(F) == sizeof(Fq)) {
@@ -1565,15 +1588,10 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmBases *sets, co
             else launch_red(k_bucket_reduce29<RED_L_LOG_TINY, false>, RG::THREADS);
         }
     } else {
-        if (red_l_log == RED_L_LOG_LARGE)
-            hipLaunchKernelGGL((k_bucket_reduce<F, RED_L_LOG_LARGE>), dim3((unsigned)gr.nred, ns), dim3(RG::THREADS), 2 * RG::LANES * sizeof(LdsPoint<F>), s,
-                               red_in, g.B, gr.cpw, red_dst, in_stride, L.red_out);
-        else if (red_l_log == RED_L_LOG_SMALL)
-            hipLaunchKernelGGL((k_bucket_reduce<F, RED_L_LOG_SMALL>), dim3((unsigned)gr.nred, ns), dim3(RG::THREADS), 2 * RG::LANES * sizeof(LdsPoint<F>), s,
-                               red_in, g.B, gr.cpw, red_dst, in_stride, L.red_out);
-        else
-            hipLaunchKernelGGL((k_bucket_reduce<F, RED_L_LOG_TINY>), dim3((unsigned)gr.nred, ns), dim3(RG::THREADS), 2 * RG::LANES * sizeof(LdsPoint<F>), s,
-                               red_in, g.B, gr.cpw, red_dst, in_stride, L.red_out);
+        auto launch_red = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)gr.nred, ns), dim3(RG::THREADS), 2 * RG::LANES * sizeof(LdsPoint<F>), s, red_in, g.B, gr.cpw, red_dst, in_stride, L.red_out); };
+        if (red_l_log == RED_L_LOG_LARGE) launch_red(k_bucket_reduce<F, RED_L_LOG_LARGE>);
+        else if (red_l_log == RED_L_LOG_SMALL) launch_red(k_bucket_reduce<F, RED_L_LOG_SMALL>);
+        else launch_red(k_bucket_reduce<F, RED_L_LOG_TINY>);
     }
     if (hipGetLastError() != hipSuccess) { set_error("msm kernel launch failed"); return ZKG_ERROR; }
     return ZKG_OK;                                                              // (msm_job_finish_dev reads gr.red_out, host_combine gr.host_red)
@@ -1726,22 +1744,24 @@ template <class F> __global__ __launch_bounds__(256) void k_jac_to_records(const
     rec[i] = Z.is_zero() ? XYZZ<F>::inf() : XYZZ<F>{X, Y, F::one(), F::one()};
 }
 
-static int sort_digits(MsmJob *job, const uint32_t *d_scalars, bool mont, const uint32_t *d_gather) {
+// the digit sort of one launch into ls.space, on mode.sort_stream (the job's own stream when that is null); leaves the sorted list's geometry in ls
+static int sort_digits(MsmJob *job, MsmLaunchSets &ls, const uint32_t *d_scalars, bool mont, const uint32_t *d_gather, const MsmLaunchMode &mode) {
+    MsmSortSpace &sp = *ls.space;
     const MsmGeom g0 = job->g; const size_t n0 = job->n;                        // as the scalars see them (k_digits)
     if (job->merge > 1) { job->g.W /= job->merge; job->g.Wt = job->g.W; job->n *= job->merge; }     // rows of the digit array read `merge` at a time from here on
     if (job->multi > 1) { job->g.W *= job->multi; job->g.Wt = job->g.W; }                           // ... and a row per (window, vector)
-    const MsmGeom g = job->g; const size_t n = job->n;
-    hipStream_t s = job->sort_stream ? job->sort_stream : job->stream;
+    const MsmGeom g = ls.g = job->g; const size_t n = ls.n = job->n;            // ... and as the sorted list and the accumulation do
+    hipStream_t s = mode.sort_stream ? mode.sort_stream : job->stream;
     const size_t total = (size_t)g.W * g.B;
     uint32_t slice_len = (uint32_t)std::min<size_t>(65536, std::max<size_t>(4096, ((n + 15) / 16 + 1023) / 1024 * 1024));
     uint32_t S = (uint32_t)std::max<size_t>(1, (n + slice_len - 1) / slice_len);
     size_t nblk = (total + 1024 * SCAN_ITEMS - 1) / (1024 * SCAN_ITEMS);
     if (nblk > 1024) { set_error("msm: too many buckets for the block scan"); return ZKG_ERROR; }
-    if (job->digits.reserve(std::max<size_t>(1, n * g.W) * 4) || job->hist.reserve((size_t)g.W * S * g.B * 4) || job->counts.reserve(total * 4) ||
-        job->offsets.reserve((total + 1) * 4) || job->scan_sums.reserve(1024 * 4) || job->class_hist.reserve((CLASS_HIST_COPIES + 1) * (HEAVY_T_MAX + 2) * 4) ||
-        job->order.reserve(total * 4) || job->sorted.reserve(std::max<size_t>(1, n * g.W) * 4)) return ZKG_ERROR;
-    uint32_t *digits = job->digits.as<uint32_t>(), *hist = job->hist.as<uint32_t>(), *counts = job->counts.as<uint32_t>(),
-             *offsets = job->offsets.as<uint32_t>(), *sums = job->scan_sums.as<uint32_t>(), *chist = job->class_hist.as<uint32_t>();
+    if (sp.digits.reserve(std::max<size_t>(1, n * g.W) * 4) || sp.hist.reserve((size_t)g.W * S * g.B * 4) || sp.counts.reserve(total * 4) ||
+        sp.offsets.reserve((total + 1) * 4) || sp.scan_sums.reserve(1024 * 4) || sp.class_hist.reserve((CLASS_HIST_COPIES + 1) * (HEAVY_T_MAX + 2) * 4) ||
+        sp.order.reserve(total * 4) || sp.sorted.reserve(std::max<size_t>(1, n * g.W) * 4)) return ZKG_ERROR;
+    uint32_t *digits = sp.digits.as<uint32_t>(), *hist = sp.hist.as<uint32_t>(), *counts = sp.counts.as<uint32_t>(),
+             *offsets = sp.offsets.as<uint32_t>(), *sums = sp.scan_sums.as<uint32_t>(), *chist = sp.class_hist.as<uint32_t>();
     uint32_t cbits = 6;
     static const uint32_t bin_avg = getenv("ZKG_RX_AVG") ? (uint32_t)atoi(getenv("ZKG_RX_AVG")) : RX_BIN_AVG;     // tuning aid
     while (cbits < RX_MAX_CBITS && cbits + 1 < g.c - 1 && (n >> cbits) > bin_avg) ++cbits;  // bins average <= RX_BIN_AVG entries where possible, fbits >= 2
@@ -1752,14 +1772,14 @@ static int sort_digits(MsmJob *job, const uint32_t *d_scalars, bool mont, const 
         ZeroList zl{};
         int k = 0;
         zl.p[k] = chist; zl.words[k++] = (CLASS_HIST_COPIES + 1) * (HEAVY_T_MAX + 2);     // the class histogram's copies and, behind them, k_order_place's cursors
-        for (MsmGroup &gr : job->group) if (gr.nsets) {
-            if (gr.heavy_counters.reserve(8 * MSM_MAX_SETS)) return ZKG_ERROR;
-            zl.p[k] = gr.heavy_counters.as<uint32_t>(); zl.words[k++] = 2 * MSM_MAX_SETS;
+        for (int f = 0; f < 2; ++f) if (job->group[f].nsets) {
+            if (sp.heavy_counters[f].reserve(8 * MSM_MAX_SETS)) return ZKG_ERROR;
+            zl.p[k] = sp.heavy_counters[f].as<uint32_t>(); zl.words[k++] = 2 * MSM_MAX_SETS;
         }
         if (two_pass) {
             const uint32_t nbins = g.W << cbits;
-            if (job->rx_meta.reserve((2 * (size_t)nbins + g.W) * 4)) return ZKG_ERROR;       // bin counts, bin cursors, window totals
-            zl.p[k] = job->rx_meta.as<uint32_t>(); zl.words[k++] = 2 * nbins + g.W;
+            if (sp.rx_meta.reserve((2 * (size_t)nbins + g.W) * 4)) return ZKG_ERROR;       // bin counts, bin cursors, window totals
+            zl.p[k] = sp.rx_meta.as<uint32_t>(); zl.words[k++] = 2 * nbins + g.W;
         }
         const dim3 dg((unsigned)((n0 + 255) / 256));                                                     // n >= 1 (msm_job_launch)
         const bool four = !d_gather && (n0 & 3) == 0 && g0.w0 == 0 && g0.ws == 1 && g0.W == g0.Wt;      // every window stored, rows 16-byte aligned
@@ -1779,22 +1799,22 @@ static int sort_digits(MsmJob *job, const uint32_t *d_scalars, bool mont, const 
     if (two_pass) {
         // two-pass sort: 2^cbits coarse bins per window, then the remaining fbits inside LDS
         const uint32_t fbits = g.c - 1 - cbits, CB = 1u << cbits, nbins = g.W * CB, S1 = (uint32_t)((n + RX_SLICE - 1) / RX_SLICE);
-        if (job->rx_tmp.reserve(n * g.W * 4)) return ZKG_ERROR;
-        uint32_t *cnt = job->rx_meta.as<uint32_t>(), *cursor = cnt + nbins, *wtot = cursor + nbins, *tmp = job->rx_tmp.as<uint32_t>();      // (zeroed by the digits kernel)
+        if (sp.rx_tmp.reserve(n * g.W * 4)) return ZKG_ERROR;
+        uint32_t *cnt = sp.rx_meta.as<uint32_t>(), *cursor = cnt + nbins, *wtot = cursor + nbins, *tmp = sp.rx_tmp.as<uint32_t>();      // (zeroed by the digits kernel)
         const size_t fine_lds = (RX_FINE_MAX + 3 * (1u << fbits)) * 4;
         hipLaunchKernelGGL(k_rx_count, dim3(S1, g.W), dim3(1024), 0, s, digits, n, fbits, cbits, cnt, wtot);
         // (a sort on a stream of its own runs beside an accumulation: half-size workgroups fit into the registers that one leaves free)
         static const int wg_env = getenv("ZKG_SORT_WG") ? atoi(getenv("ZKG_SORT_WG")) : 0;                 // A/B switch: 512 / 1024 everywhere
-        const bool half = (wg_env ? wg_env == 512 : job->sort_stream != nullptr) && fbits <= 9;           // (k_rx_fine's scan: one fine bucket per thread)
+        const bool half = (wg_env ? wg_env == 512 : mode.sort_stream != nullptr) && fbits <= 9;           // (k_rx_fine's scan: one fine bucket per thread)
         if (half) {
             const uint32_t S2 = (uint32_t)((n + 512 * RX_PER_THREAD - 1) / (512 * RX_PER_THREAD));
             hipLaunchKernelGGL(k_rx_scatter<512>, dim3(S2, g.W), dim3(512), (512 * RX_PER_THREAD + 4 * RX_MAX_CB + 8) * 4, s, digits, n, fbits, cbits, cnt, wtot, g.W, cursor, tmp, offsets + total);
             hipLaunchKernelGGL(k_rx_fine<512>, dim3(CB, g.W), dim3(512), fine_lds, s, tmp, fbits, cbits, g.B, cnt, wtot, counts, offsets, total, chist,
-                               job->sorted.as<uint32_t>());
+                               sp.sorted.as<uint32_t>());
         } else {
             hipLaunchKernelGGL(k_rx_scatter<1024>, dim3(S1, g.W), dim3(1024), (RX_SLICE + 4 * RX_MAX_CB + 8) * 4, s, digits, n, fbits, cbits, cnt, wtot, g.W, cursor, tmp, offsets + total);
             hipLaunchKernelGGL(k_rx_fine<1024>, dim3(CB, g.W), dim3(1024), fine_lds, s, tmp, fbits, cbits, g.B, cnt, wtot, counts, offsets, total, chist,
-                               job->sorted.as<uint32_t>());
+                               sp.sorted.as<uint32_t>());
         }
     } else {                                                                                    // one pass: histogram, scans, k_place
     hipLaunchKernelGGL(k_hist, dim3(S, g.W), dim3(SORT_THREADS), g.B * 4, s, digits, n, g.B, S, slice_len, hist);
@@ -1802,10 +1822,10 @@ static int sort_digits(MsmJob *job, const uint32_t *d_scalars, bool mont, const 
     hipLaunchKernelGGL(k_scan_blocks, dim3((unsigned)nblk), dim3(1024), 0, s, counts, offsets, sums, total);
     hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, s, sums, (uint32_t)nblk, offsets + total);
     hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nblk), dim3(1024), 0, s, offsets, sums, total);
-    hipLaunchKernelGGL(k_place, dim3(S, g.W), dim3(SORT_THREADS), g.B * 4, s, digits, n, g.B, S, slice_len, hist, offsets, job->sorted.as<uint32_t>());
+    hipLaunchKernelGGL(k_place, dim3(S, g.W), dim3(SORT_THREADS), g.B * 4, s, digits, n, g.B, S, slice_len, hist, offsets, sp.sorted.as<uint32_t>());
     hipLaunchKernelGGL(k_class_hist, dim3((unsigned)((total + 1023) / 1024)), dim3(1024), 0, s, counts, offsets, total, chist);
     }
-    hipLaunchKernelGGL(k_order_place, dim3((unsigned)((total + 1023) / 1024)), dim3(1024), 0, s, counts, offsets, total, chist, chist + CLASS_HIST_COPIES * (HEAVY_T_MAX + 2), job->order.as<uint32_t>(), job->heavy_out);
+    hipLaunchKernelGGL(k_order_place, dim3((unsigned)((total + 1023) / 1024)), dim3(1024), 0, s, counts, offsets, total, chist, chist + CLASS_HIST_COPIES * (HEAVY_T_MAX + 2), sp.order.as<uint32_t>(), mode.heavy_out);
     if (hipGetLastError() != hipSuccess) { set_error("msm sort launch failed"); return ZKG_ERROR; }
     return ZKG_OK;
 }
@@ -1830,99 +1850,129 @@ void msm_job_set_window_subset(MsmJob *j, uint32_t w0, uint32_t ws) { if (j) { j
 hipStream_t msm_job_stream(MsmJob *j) { return j->stream; }
 void msm_job_destroy(MsmJob *j) {
     if (!j) return;
-    for (DevBuf *b : {&j->digits, &j->hist, &j->counts, &j->offsets, &j->scan_sums, &j->class_hist, &j->order, &j->sorted, &j->rx_tmp, &j->rx_meta}) b->release();
-    for (auto &gr : j->group) gr.release();
-    if (j->aux) { (void)hipStreamSynchronize(j->aux); (void)hipStreamDestroy(j->aux); }
-    if (j->ev_fork) (void)hipEventDestroy(j->ev_fork);
-    if (j->ev_join) (void)hipEventDestroy(j->ev_join);
+    j->release_device();
     if (j->own_stream) (void)hipStreamDestroy(j->stream);
     delete j;
 }
 
 static MsmJob g_default_job;          // the synchronous entry points share one job (serialised by its mutex); only it feeds the kernel timer
-static MsmJob g_piece_job;            // msm_g1_host_scalars: the second set of sort buffers its pieces alternate over (used under g_default_job's mutex)
-static hipStream_t g_sort_hi = nullptr;   // and the high-priority stream their digit sorts run on
-// what the last msm_g1_host_scalars did (zkg_msm_host_scalars_stats; written and read under g_default_job's mutex): pieces run, cross-stream
-// waits put on the caller's stream, and per piece the heavy-bucket count the host read and whether the heavy pair was launched
+// what the last msm_g1_host_scalars did (zkg_msm_host_scalars_stats): pieces run, cross-stream waits put on the caller's stream, and per piece
+// the heavy-bucket count the host read and whether the heavy pair was launched
 struct HostScalarsStats { uint32_t pieces = 0, waits = 0, heavy[8] = {0}, pair[8] = {0}; };
-static HostScalarsStats g_hs_stats;
+// Everything msm_g1_host_scalars keeps between calls beside the default job (used under g_default_job's mutex): the device copy of the scalars,
+// the copy stream with one event per piece, the high-priority stream the pieces' digit sorts run on, the second sort workspace — pieces
+// alternate between the default job's and this one, [0] and [1] below — and per workspace ev_sorted (the sort into it has finished: the calling
+// thread waits for it, then enqueues the accumulation) and ev_acc_done (the accumulation that read it has finished: the next sort into it waits
+// for that on the device), eight words of pinned host memory, one per piece, for the sorts' heavy-bucket counts, and the stats record.
+struct PieceStep {
+    DevBuf scalars; MsmSortSpace space;
+    hipStream_t copy = nullptr, sort = nullptr;
+    hipEvent_t ev_piece[8] = {nullptr}, ev_sorted[2] = {nullptr}, ev_acc_done[2] = {nullptr};
+    uint32_t *heavy_words = nullptr;
+    HostScalarsStats stats;
+    bool ready = false;                // streams, events and pinned words: all of them or none
+    template <class Fn> void each_event(Fn f) { for (hipEvent_t &e : ev_piece) f(e); for (hipEvent_t &e : ev_sorted) f(e); for (hipEvent_t &e : ev_acc_done) f(e); }
+    int ensure() {
+        if (ready) return ZKG_OK;
+        int lo = 0, hi = 0; (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
+        // (confining the sort stream to 16 ... 128 compute units with a CU mask instead of the priority was measured: 2.11 -> 4.25 ... 2.70 ms — the sort needs the chip's width)
+        bool ok = hipStreamCreateWithFlags(&copy, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithPriority(&sort, hipStreamNonBlocking, hi) == hipSuccess &&
+                  hipHostMalloc(reinterpret_cast<void **>(&heavy_words), 8 * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess;
+        // (ev_sorted / ev_acc_done without their system-scope fence — hipEventDisableSystemFence — were measured: 1.994 against 1.998 ms, nothing; an A/B on one box.
+        //  Again for ev_acc_done alone once the host paced the accumulations: 1.7512 against 1.7549 ms over five alternating runs, nothing.  ev_sorted
+        //  needs its fence in any case: the host reads the heavy word behind it.)
+        each_event([&](hipEvent_t &e) { ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess; });
+        if (!ok) { release(); set_error("msm: streams, events and pinned words of the piece-wise step"); return ZKG_ERROR; }
+        ready = true;
+        return ZKG_OK;
+    }
+    void release() {
+        for (hipStream_t *s : {&sort, &copy}) if (*s) { (void)hipStreamSynchronize(*s); (void)hipStreamDestroy(*s); *s = nullptr; }
+        each_event([](hipEvent_t &e) { if (e) { (void)hipEventDestroy(e); e = nullptr; } });
+        if (heavy_words) { (void)hipHostFree(heavy_words); heavy_words = nullptr; }
+        scalars.release(); space.release();
+        ready = false;
+    }
+};
+static PieceStep g_step;
 
 // enqueue: one digit sort of the scalars (element d_gather[i] of d_scalars when a gather list is given), then one accumulate + reduce
 // per base set
 //
-// A launch has two halves.  msm_job_enqueue_sort: the geometry, a plain G1 set's records on the side stream, the digit sort, and — where the
-// sort runs on a stream of its own — the record of ev_sorted behind it.  msm_job_enqueue_accumulate: accumulate (+ reduce) per base set on
-// job->stream.  msm_job_launch calls them back to back; a caller that takes them apart (msm_g1_host_scalars) orders the second behind
-// ev_sorted itself.  MsmLaunchSets is what the first half leaves for the second: the launch's base sets by field.
-struct MsmLaunchSets { MsmBases by_field[2][MSM_MAX_SETS]; };
+// A launch has two halves.  msm_job_enqueue_sort: the geometry, a plain G1 set's records on the side stream, and the digit sort into the
+// workspace it is given, on mode.sort_stream.  msm_job_enqueue_accumulate: accumulate (+ reduce) per base set on job->stream.  msm_job_launch
+// calls them back to back on one stream; a caller that takes them apart (msm_g1_host_scalars) orders the second behind the first itself.
 // an error return after the fork must not leave the side stream reading the caller's bases (a synchronous caller may free them next)
 static int msm_launch_failed(MsmJob *job) {
     if (job->converted_aside) { (void)hipStreamSynchronize(job->aux); job->converted_aside = false; }
     return ZKG_ERROR;
 }
-static int msm_job_enqueue_sort(MsmJob *job, const MsmBases *sets, int nsets, const uint32_t *d_scalars, size_t n, bool scalars_mont, const uint32_t *d_gather, MsmLaunchSets &ls) {
-    auto &by_field = ls.by_field;
+// The launch's base sets by field — ls.by_field, job->group[].nsets — and the row merge of a table launch (job->merge; ls.by_field's level strides
+// are then in merged rows).  job->g is the launch's geometry as the scalars see it.
+static void msm_job_split_sets(MsmJob *job, const MsmBases *sets, int nsets, size_t n, bool gathered, MsmLaunchSets &ls) {
+    for (MsmGroup &gr : job->group) gr.nsets = 0;
+    job->group[0].g2 = false; job->group[1].g2 = true;
+    for (int i = 0; i < nsets; ++i) { MsmGroup &gr = job->group[sets[i].g2 ? 1 : 0]; ls.by_field[sets[i].g2 ? 1 : 0][gr.nsets] = sets[i]; gr.out_index[gr.nsets] = gr.nsets; ++gr.nsets; }
+    bool merge = nsets > 0 && n > 0 && job->g.W > 0 && job->merge_hint > 1 && !gathered && job->g.W % job->merge_hint == 0 && (uint64_t)n * job->merge_hint < ((uint64_t)1 << 31);
+    for (int i = 0; i < nsets; ++i) merge = merge && sets[i].level_stride == n && sets[i].index_sub == 0 && !sets[i].remap;      // a table's levels back to back, entry i = point i
+    job->merge = merge ? job->merge_hint : 1;
+    for (int k = 0; k < 2; ++k) for (int i = 0; i < job->group[k].nsets; ++i) ls.by_field[k][i].level_stride *= job->merge;
+}
+// A plain G1 set's 29-bit records (k_bases_to29 into group[0].bases29) on the job's side stream: forked behind everything queued on job->stream
+// before (the work that made the bases; the previous launch's accumulation, which still reads the records), ev_join recorded behind it.
+static int msm_job_convert_aside(MsmJob *job, const void *bases, size_t n) {
+    if (job->ensure_side() || job->group[0].bases29.reserve(n * sizeof(Rec64))) return ZKG_ERROR;
+    ZK_HIP(hipEventRecord(job->ev_fork, job->stream));
+    ZK_HIP(hipStreamWaitEvent(job->aux, job->ev_fork, 0));
+    hipLaunchKernelGGL(k_bases_to29, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, job->aux, reinterpret_cast<const Affine<Fq> *>(bases), n, job->group[0].bases29.as<Rec64>());
+    ZK_HIP(hipEventRecord(job->ev_join, job->aux));
+    return ZKG_OK;
+}
+static int msm_job_enqueue_sort(MsmJob *job, MsmSortSpace &space, const MsmBases *sets, int nsets, const uint32_t *d_scalars, size_t n, bool scalars_mont, const uint32_t *d_gather,
+                                const MsmLaunchMode &mode, MsmLaunchSets &ls) {
     if (n >= ((size_t)1 << 31) || nsets < 0 || nsets > MSM_MAX_SETS) { set_error("msm: bad size"); return ZKG_ERROR; }
+    const int window = mode.window > 0 ? mode.window : job->window_hint;
     bool any_table = false;
     for (int i = 0; i < nsets; ++i) any_table = any_table || sets[i].level_stride != 0;
     for (int i = 0; i < nsets; ++i) if ((sets[i].level_stride != 0) != any_table) { set_error("msm: table and plain base sets cannot share a launch"); return ZKG_ERROR; }
-    if (any_table && (job->w0 != 0 || job->ws != 1 || job->window_hint <= 0)) { set_error("msm: a table launch covers all windows at the table's window size"); return ZKG_ERROR; }
-    job->g = pick_geom(n, job->window_hint, job->w0, job->ws); job->n = n;
+    if (any_table && (job->w0 != 0 || job->ws != 1 || window <= 0)) { set_error("msm: a table launch covers all windows at the table's window size"); return ZKG_ERROR; }
+    job->g = pick_geom(n, window, job->w0, job->ws); job->n = n;
     job->empty = false; job->multi = 1;
-    for (MsmGroup &gr : job->group) gr.nsets = 0;
-    job->group[0].g2 = false; job->group[1].g2 = true;
-    for (int i = 0; i < nsets; ++i) { MsmGroup &gr = job->group[sets[i].g2 ? 1 : 0]; by_field[sets[i].g2 ? 1 : 0][gr.nsets] = sets[i]; gr.out_index[gr.nsets] = gr.nsets; ++gr.nsets; }
-    if (job->g.W == 0 || n == 0) { job->empty = true; return ZKG_OK; }        // no point, or this rank owns no window: the identity
+    ls.space = &space; ls.empty = false;
+    msm_job_split_sets(job, sets, nsets, n, d_gather != nullptr, ls);
+    if (job->g.W == 0 || n == 0) { job->empty = ls.empty = true; return ZKG_OK; }        // no point, or this rank owns no window: the identity
     if ((uint64_t)n * job->g.W >= ((uint64_t)1 << 32)) { set_error("msm: n * windows exceeds the 32-bit index space of the sorted list (n < 2^28)"); return ZKG_ERROR; }
-    job->merge = 1;
-    if (any_table && job->merge_hint > 1 && !d_gather && job->g.W % job->merge_hint == 0 && (uint64_t)n * job->merge_hint < ((uint64_t)1 << 31)) {
-        bool ok = true;
-        for (int i = 0; i < nsets; ++i) ok = ok && sets[i].level_stride == n && sets[i].index_sub == 0 && !sets[i].remap;      // levels back to back, entry i = point i
-        if (ok) job->merge = job->merge_hint;
-    }
     job->converted_aside = false;
-    {
-        MsmGroup &g1 = job->group[0];
-        if (!any_table && !d_gather && g1.nsets == 1 && by_field[0][0].index_sub == 0 && !by_field[0][0].remap && !by_field[0][0].p29) {
-            if (!job->aux && (hipStreamCreateWithFlags(&job->aux, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&job->ev_fork, hipEventDisableTiming) != hipSuccess ||
-                              hipEventCreateWithFlags(&job->ev_join, hipEventDisableTiming) != hipSuccess)) { set_error("msm: side stream"); return ZKG_ERROR; }
-            if (g1.bases29.reserve(n * sizeof(Rec64))) return ZKG_ERROR;
-            ZK_HIP(hipEventRecord(job->ev_fork, job->stream));
-            ZK_HIP(hipStreamWaitEvent(job->aux, job->ev_fork, 0));
-            hipLaunchKernelGGL(k_bases_to29, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, job->aux, reinterpret_cast<const Affine<Fq> *>(by_field[0][0].p), n, g1.bases29.as<Rec64>());
-            ZK_HIP(hipEventRecord(job->ev_join, job->aux));
-            job->converted_aside = true;
-        }
+    const MsmBases &g1 = ls.by_field[0][0];
+    if (!any_table && !d_gather && job->group[0].nsets == 1 && g1.index_sub == 0 && !g1.remap && !g1.p29) {
+        if (msm_job_convert_aside(job, g1.p, n)) return ZKG_ERROR;
+        job->converted_aside = true;
     }
-    if (sort_digits(job, d_scalars, scalars_mont, d_gather)) return msm_launch_failed(job);
-    if (job->sort_stream && job->sort_stream != job->stream && hipEventRecord(job->ev_sorted, job->sort_stream) != hipSuccess) return msm_launch_failed(job);
-    if (job->merge > 1) {
-        for (int k = 0; k < 2; ++k) for (int i = 0; i < job->group[k].nsets; ++i) by_field[k][i].level_stride *= job->merge;
-    }
+    if (sort_digits(job, ls, d_scalars, scalars_mont, d_gather, mode)) return msm_launch_failed(job);
     return ZKG_OK;
 }
-// heavy_pair == false: the caller has read the sort's heavy-bucket count (job->heavy_out) and found zero
-static int msm_job_enqueue_accumulate(MsmJob *job, MsmLaunchSets &ls, const uint32_t *d_gather, bool heavy_pair) {
-    if (job->empty) return ZKG_OK;
+static int msm_job_enqueue_accumulate(MsmJob *job, const MsmLaunchSets &ls, const uint32_t *d_gather, const MsmLaunchMode &mode) {
+    if (ls.empty) return ZKG_OK;
     const bool timed_field_g2 = job->group[0].nsets == 0;                       // the kernel timer follows the first G1 launch (G2 when there is no G1 set)
-    if (job->group[1].nsets && launch_accumulate<Fq2>(job, job->group[1], ls.by_field[1], d_gather, job == &g_default_job && timed_field_g2, heavy_pair)) return msm_launch_failed(job);   // G2 first: the longer chains
-    if (job->group[0].nsets && launch_accumulate<Fq>(job, job->group[0], ls.by_field[0], d_gather, job == &g_default_job || job == &g_piece_job, heavy_pair)) return msm_launch_failed(job);
+    if (job->group[1].nsets && launch_accumulate<Fq2>(job, job->group[1], ls, d_gather, mode, mode.timed && timed_field_g2)) return msm_launch_failed(job);   // G2 first: the longer chains
+    if (job->group[0].nsets && launch_accumulate<Fq>(job, job->group[0], ls, d_gather, mode, mode.timed)) return msm_launch_failed(job);
     return ZKG_OK;
 }
-int msm_job_launch(MsmJob *job, const MsmBases *sets, int nsets, const uint32_t *d_scalars, size_t n, bool scalars_mont, const uint32_t *d_gather) {
+static int msm_job_launch_as(MsmJob *job, const MsmBases *sets, int nsets, const uint32_t *d_scalars, size_t n, bool scalars_mont, const uint32_t *d_gather, const MsmLaunchMode &mode) {
     static const bool dbg = getenv("ZKG_DEBUG_TIMING") != nullptr;
     auto t0 = std::chrono::steady_clock::now();
     auto lap = [&](const char *w) { if (dbg) fprintf(stderr, "[zkg]     %-18s %8.3f ms\n", w, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count()); };
     MsmLaunchSets ls;
-    if (msm_job_enqueue_sort(job, sets, nsets, d_scalars, n, scalars_mont, d_gather, ls)) return ZKG_ERROR;
-    if (!job->empty && job->sort_stream && job->sort_stream != job->stream) {   // the accumulation (job->stream) behind the sort, on the device
-        if (hipStreamWaitEvent(job->stream, job->ev_sorted, 0) != hipSuccess) return msm_launch_failed(job);
-        ++job->stream_waits;
-    }
+    if (msm_job_enqueue_sort(job, job->space, sets, nsets, d_scalars, n, scalars_mont, d_gather, mode, ls)) return ZKG_ERROR;
     lap("sort enqueued");
-    if (msm_job_enqueue_accumulate(job, ls, d_gather, true)) return ZKG_ERROR;
+    if (msm_job_enqueue_accumulate(job, ls, d_gather, mode)) return ZKG_ERROR;
     lap("accum enqueued");
     return ZKG_OK;
+}
+// the default mode: everything on the job's stream and in its own workspace, the chip to itself; the synchronous entry points' job feeds the kernel timer
+int msm_job_launch(MsmJob *job, const MsmBases *sets, int nsets, const uint32_t *d_scalars, size_t n, bool scalars_mont, const uint32_t *d_gather) {
+    MsmLaunchMode mode; mode.timed = job == &g_default_job;
+    return msm_job_launch_as(job, sets, nsets, d_scalars, n, scalars_mont, d_gather, mode);
 }
 // The dual of a launch over several base sets: `count` scalar vectors of n elements, scalar_stride words apart, over the SAME table sets (all
 // windows, no gather / remap / index_sub).  One digit sort, one accumulation, one fold and one reduction per field for all of them; the fold
@@ -1938,22 +1988,12 @@ int msm_job_launch_multi(MsmJob *job, const MsmBases *sets, int nsets, const uin
     if (!ok) { set_error("msm: unsupported multi launch"); return ZKG_ERROR; }
     job->g = pick_geom(n, job->window_hint); job->n = n;
     job->empty = false; job->converted_aside = false;
-    MsmBases by_field[2][MSM_MAX_SETS];
-    for (MsmGroup &gr : job->group) gr.nsets = 0;
-    job->group[0].g2 = false; job->group[1].g2 = true;
-    for (int i = 0; i < nsets; ++i) { MsmGroup &gr = job->group[sets[i].g2 ? 1 : 0]; by_field[sets[i].g2 ? 1 : 0][gr.nsets] = sets[i]; gr.out_index[gr.nsets] = gr.nsets; ++gr.nsets; }
-    job->merge = 1;
-    if (job->merge_hint > 1 && job->g.W % job->merge_hint == 0) {                                       // as msm_job_launch
-        bool m = true;
-        for (int i = 0; i < nsets; ++i) m = m && sets[i].level_stride == n;
-        if (m) job->merge = job->merge_hint;
-    }
+    MsmLaunchSets ls; ls.space = &job->space;
+    msm_job_split_sets(job, sets, nsets, n, false, ls);
     job->multi = count; job->multi_stride = scalar_stride;
-    if (sort_digits(job, d_scalars, scalars_mont, nullptr)) return ZKG_ERROR;
-    for (int k = 0; k < 2; ++k) for (int i = 0; i < job->group[k].nsets; ++i) by_field[k][i].level_stride *= job->merge;
-    if (job->group[1].nsets && launch_accumulate<Fq2>(job, job->group[1], by_field[1], nullptr, false)) return ZKG_ERROR;
-    if (job->group[0].nsets && launch_accumulate<Fq>(job, job->group[0], by_field[0], nullptr, false)) return ZKG_ERROR;
-    return ZKG_OK;
+    const MsmLaunchMode mode;                                                   // the default; a multi launch never feeds the kernel timer
+    if (sort_digits(job, ls, d_scalars, scalars_mont, nullptr, mode)) return ZKG_ERROR;
+    return msm_job_enqueue_accumulate(job, ls, nullptr, mode);
 }
 // out_g1[p * (G1 sets) + k]: vector p over the k-th G1 set of the launch; out_g2 likewise
 int msm_job_finish_multi(MsmJob *job, G1 *out_g1, G2 *out_g2) {
@@ -2066,6 +2106,19 @@ int msm_shared(const G1Affine *const *d_g1_bases, int n_g1, const G2Affine *d_g2
     return ZKG_OK;
 }
 
+// msm_g1_host_scalars' piece boundaries cut[0 .. P] (returns P): halves from the top, the lowest one split once more -> n/8, n/8, n/4, n/2 for four pieces
+static int host_scalars_cuts(size_t n, int max_pieces, size_t cut[9]) {
+    int P = max_pieces;
+    cut[P] = n;
+    for (int k = P - 1; k >= 1; --k) cut[k] = (cut[k + 1] / 2) & ~(size_t)255;
+    cut[0] = 0;
+    if (const char *e = getenv("ZKG_MSM_CUTS")) {                              // tuning aid: the piece boundaries in 64ths of n, e.g. "8,32" -> n/8, 3n/8, n/2
+        int k = 1; const char *q = e;
+        while (*q && k < 8) { const long v = strtol(q, const_cast<char **>(&q), 10); if (v <= 0 || v >= 64) break; cut[k++] = (n * (size_t)v / 64) & ~(size_t)255; if (*q == ',') ++q; }
+        if (k > 1) { P = k; cut[P] = n; for (int i = 1; i < P; ++i) if (cut[i] < cut[i - 1]) cut[i] = cut[i - 1]; }
+    }
+    return P;
+}
 // Bases resident, scalars in HOST memory: SURVEY.md section 8(d)'s step ("wall clock around the call incl. H2D of scalars; bases resident") as
 // one entry point.  The upload is 32 B x n over PCIe (0.6 ms at 2^20 points) against 1.9 ms of work that cannot start on a scalar it has not
 // seen — so the job is cut by POINTS into pieces (1/4, 1/4, 1/2 of them: a small first piece starts the chip early, and every later
@@ -2083,69 +2136,38 @@ int msm_g1_host_scalars(const G1Affine *d_bases, const uint32_t *h_scalars, size
         ZK_HIP(hipMemcpyAsync(tmp.p, h_scalars, n * 32, hipMemcpyHostToDevice, s));
         return msm_g1(d_bases, tmp.as<uint32_t>(), n, mont, out, s, false);     // (returns after the stream has drained: tmp may go)
     }
-    MsmJob &J = g_default_job;
+    MsmJob &J = g_default_job; PieceStep &T = g_step;
     std::lock_guard<std::mutex> lk(J.mu);
     g_dominant_timer.new_call();
-    if (J.hs_scalars.reserve(n * 32)) return ZKG_ERROR;
-    if (!J.copy) {
-        if (hipStreamCreateWithFlags(&J.copy, hipStreamNonBlocking) != hipSuccess) { J.copy = nullptr; set_error("msm: copy stream"); return ZKG_ERROR; }
-        for (auto &e : J.ev_piece) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { set_error("msm: event"); return ZKG_ERROR; }
-    }
-    uint32_t *d_sc = J.hs_scalars.as<uint32_t>();
+    if (T.scalars.reserve(n * 32)) return ZKG_ERROR;
+    uint32_t *d_sc = T.scalars.as<uint32_t>();
     J.stream = s; J.w0 = 0; J.ws = 1; J.one_pass_sort = false;
     MsmBases set; set.p = d_bases;
-    g_hs_stats = HostScalarsStats(); J.stream_waits = 0; g_piece_job.stream_waits = 0;
+    T.stats = HostScalarsStats();
+    MsmLaunchMode mode; mode.timed = true; mode.stream_waits = &T.stats.waits;
     if (!pieces) {                                                              // small or switched off: one upload in stream order, one launch
         ZK_HIP(hipMemcpyAsync(d_sc, h_scalars, n * 32, hipMemcpyHostToDevice, s));
-        if (msm_job_launch(&J, &set, 1, d_sc, n, mont, nullptr)) return ZKG_ERROR;
-        g_hs_stats.pieces = 1; g_hs_stats.waits = J.stream_waits; g_hs_stats.heavy[0] = 0xffffffffu; g_hs_stats.pair[0] = 1;     // (the pair goes out blind: nobody reads a count)
+        if (msm_job_launch_as(&J, &set, 1, d_sc, n, mont, nullptr, mode)) return ZKG_ERROR;
+        T.stats.pieces = 1; T.stats.heavy[0] = 0xffffffffu; T.stats.pair[0] = 1;     // (the pair goes out blind: nobody reads a count)
         return msm_job_finish(&J, out, nullptr);
     }
-    if (!J.heavy_words && hipHostMalloc(reinterpret_cast<void **>(&J.heavy_words), 8 * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) { J.heavy_words = nullptr; set_error("msm: pinned words"); return ZKG_ERROR; }
-    // piece boundaries: halves from the top, the lowest one split once more -> n/8, n/8, n/4, n/2 for four pieces
-    size_t cut[9]; int P = max_pieces;
-    cut[P] = n;
-    for (int k = P - 1; k >= 1; --k) cut[k] = (cut[k + 1] / 2) & ~(size_t)255;
-    cut[0] = 0;
-    if (const char *e = getenv("ZKG_MSM_CUTS")) {                              // tuning aid: the piece boundaries in 64ths of n, e.g. "8,32" -> n/8, 3n/8, n/2
-        int k = 1; const char *q = e;
-        while (*q && k < 8) { const long v = strtol(q, const_cast<char **>(&q), 10); if (v <= 0 || v >= 64) break; cut[k++] = (n * (size_t)v / 64) & ~(size_t)255; if (*q == ',') ++q; }
-        if (k > 1) { P = k; cut[P] = n; for (int i = 1; i < P; ++i) if (cut[i] < cut[i - 1]) cut[i] = cut[i - 1]; }
-    }
+    if (T.ensure()) return ZKG_ERROR;
+    size_t cut[9]; const int P = host_scalars_cuts(n, max_pieces, cut);
     for (int k = 0; k < P; ++k) {
-        ZK_HIP(hipMemcpyAsync(d_sc + 8 * cut[k], h_scalars + 8 * cut[k], (cut[k + 1] - cut[k]) * 32, hipMemcpyHostToDevice, J.copy));
-        ZK_HIP(hipEventRecord(J.ev_piece[k], J.copy));
+        ZK_HIP(hipMemcpyAsync(d_sc + 8 * cut[k], h_scalars + 8 * cut[k], (cut[k + 1] - cut[k]) * 32, hipMemcpyHostToDevice, T.copy));
+        ZK_HIP(hipEventRecord(T.ev_piece[k], T.copy));
     }
-    // Pieces alternate between two jobs — two sets of sort buffers, ONE set of buckets, all accumulations in order on the caller's stream —
+    // Pieces alternate between two sort workspaces — the default job's and the step's — over ONE set of buckets, all accumulations in order on the caller's stream —
     // and every piece's digit sort runs on a high-priority stream of its own beside the accumulation of the piece before it: the sort's
     // small dependent launches and single-workgroup scans stand a third of a step when alone and cost the accumulation little beside it
     // (without the priority they crawl: k_rx_count 134 us instead of 11; and they only run BESIDE it because the accumulation leaves a
     // quarter of each SIMD's registers free and the sort's wavefronts raise their own issue priority — ACC29_VGPRS, sort_wave_priority).  The bases' 29-bit records are made once for all pieces, on
     // the side stream, under the first upload.
-    MsmJob &K = g_piece_job;
-    if (!g_sort_hi) {
-        int lo = 0, hi = 0; (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-        // (confining this stream to 16 ... 128 compute units with a CU mask instead was measured: 2.11 -> 4.25 ... 2.70 ms — the sort needs the chip's width)
-        bool ok = hipStreamCreateWithPriority(&g_sort_hi, hipStreamNonBlocking, hi) == hipSuccess;
-        // (these events without their system-scope fence — hipEventDisableSystemFence — were measured: 1.994 against 1.998 ms, nothing; an A/B on one box.
-        //  Again for ev_acc_done alone once the host paced the accumulations: 1.7512 against 1.7549 ms over five alternating runs, nothing.  ev_sorted
-        //  needs its fence in any case: the host reads the heavy word behind it.)
-        for (MsmJob *w : {&J, &K}) ok = ok && hipEventCreateWithFlags(&w->ev_sorted, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&w->ev_acc_done, hipEventDisableTiming) == hipSuccess;
-        if (!ok) { g_sort_hi = nullptr; set_error("msm: sort stream"); return ZKG_ERROR; }
-    }
-    hipStream_t s_hi = g_sort_hi;
-    // all bases as 29-bit records, once (k_bases_to29 on the job's side stream: it runs under the first piece's upload)
-    if (!J.aux && (hipStreamCreateWithFlags(&J.aux, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&J.ev_fork, hipEventDisableTiming) != hipSuccess ||
-                   hipEventCreateWithFlags(&J.ev_join, hipEventDisableTiming) != hipSuccess)) { set_error("msm: side stream"); return ZKG_ERROR; }
-    if (J.group[0].bases29.reserve(n * sizeof(Rec64))) return ZKG_ERROR;
-    ZK_HIP(hipEventRecord(J.ev_fork, s));                                     // behind whatever the caller queued (the work that made the bases), and the last call's accumulation
-    ZK_HIP(hipStreamWaitEvent(J.aux, J.ev_fork, 0));
-    hipLaunchKernelGGL(k_bases_to29, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, J.aux, reinterpret_cast<const Affine<Fq> *>(d_bases), n, J.group[0].bases29.as<Rec64>());
-    ZK_HIP(hipEventRecord(J.ev_join, J.aux));                                 // (the calling thread waits for it before the first accumulation, below)
-    ZK_HIP(hipStreamWaitEvent(s_hi, J.ev_fork, 0));
-    const int c = (int)pick_geom(n, J.window_hint).c;                         // every piece under the whole job's window size
-    const int saved_hint = J.window_hint, saved_hint_k = K.window_hint;
-    J.window_hint = c; K.window_hint = c; K.bucket_owner = &J; K.w0 = 0; K.ws = 1; K.one_pass_sort = false; K.stream = s;
+    // all bases as 29-bit records, once, under the first piece's upload (the calling thread waits for ev_join before the first accumulation, below)
+    if (msm_job_convert_aside(&J, d_bases, n)) return ZKG_ERROR;
+    ZK_HIP(hipStreamWaitEvent(T.sort, J.ev_fork, 0));
+    mode.sort_stream = T.sort; mode.beside = true;
+    mode.window = (int)pick_geom(n, J.window_hint).c;                         // every piece under the whole job's window size
     // The calling thread paces the accumulations (it would only sleep in msm_job_finish otherwise): an accumulation is enqueued once the host has
     // seen its sort finish, so the caller's stream carries kernels and one event record per piece and no cross-stream wait — such a wait in front
     // of a kernel stood for 15 ... 23 us of idle chip even where the awaited sort had ended long before.  And the host then knows the piece's
@@ -2157,46 +2179,41 @@ int msm_g1_host_scalars(const G1Affine *d_bases, const uint32_t *h_scalars, size
     for (int k = 0; k < P; ++k) if (cut[k + 1] != cut[k] || k + 1 == P) run[R++] = k;      // (empty pieces are skipped; the last one always runs: it carries the reduction)
     MsmLaunchSets ls[2];
     int rc = ZKG_OK; bool used[2] = {false, false};
-    // pieces alternate over the two jobs by their position among the pieces that run; the last one is the default job's: it carries the reduction and the result
-    auto job_of = [&](int i) -> MsmJob & { return ((R - 1 - i) & 1) ? K : J; };
+    // pieces alternate over the two workspaces by their position among the pieces that run; the last one sorts into the default job's own
     auto enqueue_sort = [&](int i) {
         const int k = run[i], which = (R - 1 - i) & 1;
-        MsmJob &W = job_of(i);
         MsmBases piece = set; piece.p = reinterpret_cast<const char *>(d_bases) + cut[k] * sizeof(G1Affine);
         piece.p29 = J.group[0].bases29.as<Rec64>() + cut[k];
-        W.sort_stream = s_hi; W.heavy_out = J.heavy_words + i;
-        // after its scalars have landed, and after the accumulation that last read this job's sort buffers
-        if (hipStreamWaitEvent(s_hi, J.ev_piece[k], 0) != hipSuccess) return ZKG_ERROR;
-        if (used[which] && hipStreamWaitEvent(s_hi, W.ev_acc_done, 0) != hipSuccess) return ZKG_ERROR;
-        return msm_job_enqueue_sort(&W, &piece, 1, d_sc + 8 * cut[k], cut[k + 1] - cut[k], mont, nullptr, ls[which]);
+        mode.heavy_out = T.heavy_words + i;
+        // after its scalars have landed, and after the accumulation that last read this workspace
+        if (hipStreamWaitEvent(T.sort, T.ev_piece[k], 0) != hipSuccess) return ZKG_ERROR;
+        if (used[which] && hipStreamWaitEvent(T.sort, T.ev_acc_done[which], 0) != hipSuccess) return ZKG_ERROR;
+        if (msm_job_enqueue_sort(&J, which ? T.space : J.space, &piece, 1, d_sc + 8 * cut[k], cut[k + 1] - cut[k], mont, nullptr, mode, ls[which])) return ZKG_ERROR;
+        return !ls[which].empty && hipEventRecord(T.ev_sorted[which], T.sort) != hipSuccess ? ZKG_ERROR : ZKG_OK;
     };
     rc = enqueue_sort(0);
     for (int i = 0; i < R && rc == ZKG_OK; ++i) {
         const int which = (R - 1 - i) & 1;
-        MsmJob &W = job_of(i);
         if (i + 1 < R && (rc = enqueue_sort(i + 1)) != ZKG_OK) break;
         if (i == 0 && hipEventSynchronize(J.ev_join) != hipSuccess) { rc = ZKG_ERROR; break; }      // the bases' records
         uint32_t heavy = 0;
-        if (!W.empty) {
-            if (hipEventSynchronize(W.ev_sorted) != hipSuccess) { rc = ZKG_ERROR; break; }
-            heavy = *static_cast<volatile const uint32_t *>(J.heavy_words + i);
+        if (!ls[which].empty) {
+            if (hipEventSynchronize(T.ev_sorted[which]) != hipSuccess) { rc = ZKG_ERROR; break; }
+            heavy = *static_cast<volatile const uint32_t *>(T.heavy_words + i);
         }
-        W.resume = i > 0; W.defer_reduce = i + 1 < R;
-        rc = msm_job_enqueue_accumulate(&W, ls[which], nullptr, heavy != 0);
-        if (rc == ZKG_OK && hipEventRecord(W.ev_acc_done, s) != hipSuccess) rc = ZKG_ERROR;
+        mode.resume = i > 0; mode.defer_reduce = i + 1 < R; mode.heavy_pair = heavy != 0;
+        rc = msm_job_enqueue_accumulate(&J, ls[which], nullptr, mode);
+        if (rc == ZKG_OK && hipEventRecord(T.ev_acc_done[which], s) != hipSuccess) rc = ZKG_ERROR;
         used[which] = true;
-        g_hs_stats.heavy[i] = heavy; g_hs_stats.pair[i] = heavy != 0; g_hs_stats.pieces = (uint32_t)(i + 1);
+        T.stats.heavy[i] = heavy; T.stats.pair[i] = heavy != 0; T.stats.pieces = (uint32_t)(i + 1);
     }
-    g_hs_stats.waits = J.stream_waits + K.stream_waits;
-    J.resume = false; J.defer_reduce = false; J.window_hint = saved_hint; J.sort_stream = nullptr; J.heavy_out = nullptr;      // (the other entry points sort on the job's own stream)
-    K.resume = false; K.defer_reduce = false; K.window_hint = saved_hint_k; K.bucket_owner = nullptr; K.sort_stream = nullptr; K.stream = nullptr; K.heavy_out = nullptr;
-    if (rc != ZKG_OK) { (void)hipStreamSynchronize(J.copy); (void)hipStreamSynchronize(J.aux); (void)hipStreamSynchronize(s_hi); (void)hipStreamSynchronize(s); return ZKG_ERROR; }
+    if (rc != ZKG_OK) { (void)hipStreamSynchronize(T.copy); (void)hipStreamSynchronize(J.aux); (void)hipStreamSynchronize(T.sort); (void)hipStreamSynchronize(s); return ZKG_ERROR; }
     return msm_job_finish(&J, out, nullptr);
 }
 // out: pieces | stream waits | (heavy count, pair launched) per piece — at most n words; returns the words the record has (0: no call yet)
 int msm_host_scalars_stats(uint32_t *out, int n) {
     std::lock_guard<std::mutex> lk(g_default_job.mu);
-    const HostScalarsStats &st = g_hs_stats;
+    const HostScalarsStats &st = g_step.stats;
     if (!st.pieces) return 0;
     uint32_t rec[2 + 2 * 8] = {st.pieces, st.waits};
     for (uint32_t k = 0; k < st.pieces; ++k) { rec[2 + 2 * k] = st.heavy[k]; rec[3 + 2 * k] = st.pair[k]; }
@@ -2412,31 +2429,9 @@ int msm_configure() {
 }
 void msm_release_all() {
     fixed_tables_release();
-    MsmJob &j = g_default_job;
-    std::lock_guard<std::mutex> lk(j.mu);
-    for (DevBuf *b : {&j.digits, &j.hist, &j.counts, &j.offsets, &j.scan_sums, &j.class_hist, &j.order, &j.sorted, &j.rx_tmp, &j.rx_meta}) b->release();
-    for (auto &gr : j.group) gr.release();
-    if (j.aux) { (void)hipStreamSynchronize(j.aux); (void)hipStreamDestroy(j.aux); j.aux = nullptr; }      // (a later zkg_init may pick another device)
-    j.hs_scalars.release();
-    {
-        MsmJob &k = g_piece_job;
-        if (g_sort_hi) { (void)hipStreamSynchronize(g_sort_hi); (void)hipStreamDestroy(g_sort_hi); g_sort_hi = nullptr; }
-        for (DevBuf *b : {&k.digits, &k.hist, &k.counts, &k.offsets, &k.scan_sums, &k.class_hist, &k.order, &k.sorted, &k.rx_tmp, &k.rx_meta}) b->release();
-        for (auto &gr : k.group) gr.release();
-        if (k.aux) { (void)hipStreamSynchronize(k.aux); (void)hipStreamDestroy(k.aux); k.aux = nullptr; }
-        if (k.ev_fork) { (void)hipEventDestroy(k.ev_fork); k.ev_fork = nullptr; }
-        if (k.ev_join) { (void)hipEventDestroy(k.ev_join); k.ev_join = nullptr; }
-        for (MsmJob *w : {&j, &k}) {
-            if (w->ev_sorted) { (void)hipEventDestroy(w->ev_sorted); w->ev_sorted = nullptr; }
-            if (w->ev_acc_done) { (void)hipEventDestroy(w->ev_acc_done); w->ev_acc_done = nullptr; }
-        }
-        k.stream = nullptr;
-    }
-    if (j.copy) { (void)hipStreamSynchronize(j.copy); (void)hipStreamDestroy(j.copy); j.copy = nullptr; }
-    for (auto &e : j.ev_piece) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    if (j.heavy_words) { (void)hipHostFree(j.heavy_words); j.heavy_words = nullptr; }
-    if (j.ev_fork) { (void)hipEventDestroy(j.ev_fork); j.ev_fork = nullptr; }
-    if (j.ev_join) { (void)hipEventDestroy(j.ev_join); j.ev_join = nullptr; }
+    std::lock_guard<std::mutex> lk(g_default_job.mu);
+    g_default_job.release_device();       // (every handle is null afterwards: a later zkg_init may pick another device and recreates them)
+    g_step.release();
 }
 
 }  // namespace zk
