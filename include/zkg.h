@@ -247,7 +247,10 @@ int zkg_msm_g2_dev(const void *d_bases, const void *d_scalars, size_t n, int sca
  * run under the work: from 2^19 points on the job is cut by points into four pieces whose uploads overlap the sort and accumulation of the
  * pieces before them, all accumulating into one set of buckets (pageable memory works, without the overlap).  Same point as zkg_msm_g1_dev on
  * the uploaded vector, bit for bit.  `stream` as in zkg_msm_g1_dev; the result is in out_jac when the call returns.  The calling thread
- * is busy for the length of the call: it enqueues each piece's accumulation once that piece's sort has finished.                        */
+ * is busy for the length of the call: it enqueues each piece's accumulation once that piece's sort has finished.
+ * Ordering of `scalars`: page-locked scalars may be produced by work queued on `stream` before the call (a device-to-host copy, say) — at
+ * every n the uploads are ordered behind that work, and no wait is put on `stream` for it.  Pageable memory is read at call time, as
+ * hipMemcpyAsync reads it: it must hold the scalars when the call is made.                                                              */
 int zkg_msm_g1_host_scalars(const void *d_bases, const uint64_t *scalars, size_t n, int scalars_mont, uint64_t out_jac[12], void *stream);
 /* test hook: what the last zkg_msm_g1_host_scalars of the process did.  The calling thread paces a piece-wise job: it enqueues an accumulation
  * only once that piece's digit sort has finished, and reads the piece's count of heavy buckets (lists above the accumulation's threshold) from

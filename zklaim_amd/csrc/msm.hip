@@ -1860,18 +1860,18 @@ static MsmJob g_default_job;          // the synchronous entry points share one 
 // the heavy-bucket count the host read and whether the heavy pair was launched
 struct HostScalarsStats { uint32_t pieces = 0, waits = 0, heavy[8] = {0}, pair[8] = {0}; };
 // Everything msm_g1_host_scalars keeps between calls beside the default job (used under g_default_job's mutex): the device copy of the scalars,
-// the copy stream with one event per piece, the high-priority stream the pieces' digit sorts run on, the second sort workspace — pieces
+// the copy stream with one event per piece and ev_caller (what the caller's stream held when the call began: the uploads wait for it), the high-priority stream the pieces' digit sorts run on, the second sort workspace — pieces
 // alternate between the default job's and this one, [0] and [1] below — and per workspace ev_sorted (the sort into it has finished: the calling
 // thread waits for it, then enqueues the accumulation) and ev_acc_done (the accumulation that read it has finished: the next sort into it waits
 // for that on the device), eight words of pinned host memory, one per piece, for the sorts' heavy-bucket counts, and the stats record.
 struct PieceStep {
     DevBuf scalars; MsmSortSpace space;
     hipStream_t copy = nullptr, sort = nullptr;
-    hipEvent_t ev_piece[8] = {nullptr}, ev_sorted[2] = {nullptr}, ev_acc_done[2] = {nullptr};
+    hipEvent_t ev_piece[8] = {nullptr}, ev_sorted[2] = {nullptr}, ev_acc_done[2] = {nullptr}, ev_caller = nullptr;
     uint32_t *heavy_words = nullptr;
     HostScalarsStats stats;
     bool ready = false;                // streams, events and pinned words: all of them or none
-    template <class Fn> void each_event(Fn f) { for (hipEvent_t &e : ev_piece) f(e); for (hipEvent_t &e : ev_sorted) f(e); for (hipEvent_t &e : ev_acc_done) f(e); }
+    template <class Fn> void each_event(Fn f) { for (hipEvent_t &e : ev_piece) f(e); for (hipEvent_t &e : ev_sorted) f(e); for (hipEvent_t &e : ev_acc_done) f(e); f(ev_caller); }
     int ensure() {
         if (ready) return ZKG_OK;
         int lo = 0, hi = 0; (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
@@ -2121,7 +2121,7 @@ static int host_scalars_cuts(size_t n, int max_pieces, size_t cut[9]) {
 }
 // Bases resident, scalars in HOST memory: SURVEY.md section 8(d)'s step ("wall clock around the call incl. H2D of scalars; bases resident") as
 // one entry point.  The upload is 32 B x n over PCIe (0.6 ms at 2^20 points) against 1.9 ms of work that cannot start on a scalar it has not
-// seen — so the job is cut by POINTS into pieces (1/4, 1/4, 1/2 of them: a small first piece starts the chip early, and every later
+// seen — so the job is cut by POINTS into pieces (1/8, 1/8, 1/4, 1/2 of them, host_scalars_cuts: a small first piece starts the chip early, and every later
 // piece's upload is shorter than the work of the piece before it), each piece sorted and accumulated as it lands, all pieces into ONE set of
 // buckets (k_bucket_accum29's `resume`: a lane picks its bucket's 29-bit accumulator up where the last piece left it), and one reduction at
 // the end.  Same point as msm_g1 on the uploaded vector: the buckets hold the same sums, whatever the order of the additions.
@@ -2153,6 +2153,14 @@ int msm_g1_host_scalars(const G1Affine *d_bases, const uint32_t *h_scalars, size
     }
     if (T.ensure()) return ZKG_ERROR;
     size_t cut[9]; const int P = host_scalars_cuts(n, max_pieces, cut);
+    // The uploads run on a stream of their own, and the contract is the single launch's, whose upload is on `s` itself: pinned scalars may be
+    // written by work queued on `s` before the call.  So the copy stream waits for what `s` holds now — the copy stream, not the caller's: no
+    // wait goes onto `s`.  A stream that has drained has nothing to wait for, and the first upload then starts without a wait in front of it.
+    if (hipStreamQuery(s) != hipSuccess) {
+        (void)hipGetLastError();                                                // (hipErrorNotReady is an answer, not a failure of the launches below)
+        ZK_HIP(hipEventRecord(T.ev_caller, s));
+        ZK_HIP(hipStreamWaitEvent(T.copy, T.ev_caller, 0));
+    }
     for (int k = 0; k < P; ++k) {
         ZK_HIP(hipMemcpyAsync(d_sc + 8 * cut[k], h_scalars + 8 * cut[k], (cut[k + 1] - cut[k]) * 32, hipMemcpyHostToDevice, T.copy));
         ZK_HIP(hipEventRecord(T.ev_piece[k], T.copy));
