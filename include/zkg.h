@@ -555,6 +555,25 @@ zkg_keypair *zkg_groth16_setup(const zkg_r1cs *cs, const uint64_t *trapdoor);
  * (beta At + alpha Bt + Ct) / gamma and / delta combinations from one kernel, and the fixed-base batches read those device buffers.  NULL with
  * zkg_last_error set: no zkg_init, a system zkg_qap_new refuses, a trapdoor whose t lies on the evaluation domain.                            */
 zkg_keypair *zkg_groth16_setup_dev(const zkg_r1cs *cs, const uint64_t *trapdoor /* as zkg_groth16_setup; NULL = random */);
+/* r1cs_gg_ppzksnark_generator with the key left where it is made.  trapdoor as zkg_groth16_setup (NULL: fresh randomness).
+ * *pk_blob / *vk_blob: the bytes zkg_keypair_pk_blob / zkg_keypair_vk_blob write for zkg_groth16_setup under the same trapdoor, byte for byte,
+ * malloc'ed (zkg_free).  *crs (optional, NULL: an issuer that keeps nothing on the GPU): the resident key, ready for every zkg_groth16_prove*
+ * entry, the same key zkg_crs_upload_blob(*pk_blob) would load — proofs are byte-identical.  No scalar vector and no query point exists on
+ * the host: the scalars are computed as zkg_groth16_setup_dev computes them, the B query's non-zero list by a ballot / scan / scatter of
+ * three launches over the device Bt, and the points come back only as the blob's compressed records.  ZKG_ERROR with zkg_last_error set and
+ * nothing allocated (the out-pointers are left alone): no zkg_init; a null cs, pk_blob, pk_len, vk_blob or vk_len; a system zkg_qap_new
+ * refuses; a trapdoor whose t lies on the evaluation domain.  Safe to call from several threads at once. */
+int  zkg_groth16_setup_resident(const zkg_r1cs *cs, const uint64_t *trapdoor, uint8_t **pk_blob, size_t *pk_len,
+                                uint8_t **vk_blob, size_t *vk_len, zkg_crs **crs);
+void zkg_free(void *p);
+/* the calling thread's last zkg_groth16_setup_resident or libsnark_trusted_setup: out[0] 1 if the scalars were computed on the device,
+ * out[1] entries of the B query's non-zero list, out[2] Fr scalars uploaded from host memory for the query batches (0 on the device path).
+ * Counters, not clocks. */
+void zkg_setup_resident_stats(size_t out[3]);
+/* test hook: positions of the non-zero elements of n raw Fr (HOST pointer, 4 limbs each, any representative below 2r, nothing normalised),
+ * ascending.  where 0: a plain host loop (no GPU, no zkg_init); 1: the generator's kernels.  idx_out holds up to n entries; only *count of
+ * them are written.  n <= 2^28. */
+int zkg_fr_nonzero_index(const uint64_t *fr, size_t n, int where, uint32_t *idx_out, size_t *count);
 void zkg_keypair_free(zkg_keypair *kp);
 const zkg_pk *zkg_keypair_pk(const zkg_keypair *kp);               /* flat arrays, valid until zkg_keypair_free              */
 int zkg_keypair_swapped(const zkg_keypair *kp);                    /* 1 if swap_AB_if_beneficial exchanged A and B          */

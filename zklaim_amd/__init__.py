@@ -11,4 +11,5 @@ from .api import (ZkgError, device_info, evaluation_domain_size, fixed_base_g1_d
                   libsnark_trusted_setup, libsnark_prove, libsnark_verify, zklaim_prove_batch, zklaim_verify_batch, zklaim_verify_batch_stats, proof_decode_gpu, zklaim_input_sums_gpu, zklaim_input_map_mirror, ctx_blob, COMPAT_SYMBOLS, field_op, fr29_op, FR29_OPS, fq29_op, FQ29_OPS, g1_add_quad29, g1_add_pair29, curve_op, CURVE_OPS, OK, ERROR, UNSATISFIED, init_multi, MsmShards, pk_blob_inspect, ResidentBases, msm_g1_host_scalars, msm_host_scalars_stats, msm_resident_async_stats, msm_combine_gpu, ResidentBasesG2, msm_combine_g2_gpu,
                   groth16_verify_each, verify_each_stats, verify_each_set_chunk, pairing_each, final_exp, fq12_op, FQ12_OPS,
                   point_decompress, point_compress, zklaim_verify_each, zklaim_verify_each_stats, zklaim_ic_each,
-                  Domain, domain_stats, Qap, qap_stats, qap_instance_stats)
+                  Domain, domain_stats, Qap, qap_stats, qap_instance_stats,
+                  groth16_setup_resident, setup_resident_stats, fr_nonzero_index)

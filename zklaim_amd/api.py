@@ -43,6 +43,7 @@ DECLARED_SYMBOLS = [
     "zkg_qap_witness_h_async", "zkg_qap_stats",
     "zkg_qap_instance_async", "zkg_qap_set_column_segment", "zkg_qap_instance_stats", "zkg_groth16_setup_dev",
     "zkg_msm_host_scalars_stats",
+    "zkg_groth16_setup_resident", "zkg_free", "zkg_setup_resident_stats", "zkg_fr_nonzero_index",
 ]
 # the reference's own seam, exported with its original names (zklaim.h:257-259)
 COMPAT_SYMBOLS = ["libsnark_trusted_setup", "libsnark_prove", "libsnark_verify"]
@@ -632,9 +633,13 @@ def make_pk(cs, arrays, log_m, keep, domain_size=0):
 class Crs:
     """Device-resident proving key (zkg_crs_upload): parsed once, reused for every proof."""
 
-    def __init__(self, pk=None, blob=None, m=None):
-        """from a zkg_pk struct of flat arrays, or from a libsnark pk byte blob (ctx->pk)"""
-        if blob is not None:
+    def __init__(self, pk=None, blob=None, m=None, handle=None):
+        """from a zkg_pk struct of flat arrays, from a libsnark pk byte blob (ctx->pk), or around a zkg_crs handle made elsewhere
+        (groth16_setup_resident), which this object then owns"""
+        if handle is not None:
+            self._h = int(handle)
+            self.m = m
+        elif blob is not None:
             buf = (C.c_ubyte * len(blob)).from_buffer_copy(blob)
             self._h = lib().zkg_crs_upload_blob(C.cast(buf, C.c_void_p), C.c_size_t(len(blob)))
             self.m = m
@@ -905,6 +910,45 @@ class Keypair:
             self.free()
         except Exception:
             pass
+
+
+def groth16_setup_resident(cs, trapdoor=None, want_crs=True):
+    """zkg_groth16_setup_resident: the key generated on the device and left there -> (pk_blob, vk_blob, Crs or None); the blobs are
+    Keypair(cs, trapdoor)'s byte for byte, the Crs is the key Crs(blob=pk_blob) would load"""
+    L = lib()
+    L.zkg_groth16_setup_resident.argtypes = [C.c_void_p] * 7
+    L.zkg_free.argtypes = [C.c_void_p]; L.zkg_free.restype = None
+    td = None if trapdoor is None else _u64(trapdoor)
+    pk = C.c_void_p(None); vk = C.c_void_p(None); crs = C.c_void_p(None); pk_len = C.c_size_t(0); vk_len = C.c_size_t(0)
+    rc = L.zkg_groth16_setup_resident(C.byref(cs), _p(td), C.byref(pk), C.byref(pk_len), C.byref(vk), C.byref(vk_len), C.byref(crs) if want_crs else None)
+    if rc != OK:
+        assert not pk.value and not vk.value and not crs.value, "a failed zkg_groth16_setup_resident wrote an out-pointer"
+        _check(rc, "zkg_groth16_setup_resident")
+    try:
+        blobs = C.string_at(pk.value, pk_len.value), C.string_at(vk.value, vk_len.value)
+    finally:
+        L.zkg_free(pk); L.zkg_free(vk)
+    return blobs[0], blobs[1], (Crs(handle=crs.value, m=pk_blob_inspect(blobs[0])["domain_size"]) if want_crs else None)
+
+
+def setup_resident_stats():
+    """[scalars computed on the device (1 / 0), entries of the B query's non-zero list, Fr scalars uploaded for the query batches] of this
+    thread's last groth16_setup_resident or libsnark_trusted_setup"""
+    out = (C.c_size_t * 3)()
+    lib().zkg_setup_resident_stats.argtypes = [C.c_void_p]
+    lib().zkg_setup_resident_stats(out)
+    return [int(v) for v in out]
+
+
+def fr_nonzero_index(fr, where=1):
+    """zkg_fr_nonzero_index: ascending positions of the elements of fr (raw limbs, any representative below 2r) that are not zero mod r;
+    where 0: a host loop, 1: the generator's kernels"""
+    fr = _u64(fr).reshape(-1, 4); n = fr.shape[0]
+    out = np.zeros(max(n, 1), np.uint32); count = C.c_size_t(0)
+    L = lib()
+    L.zkg_fr_nonzero_index.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
+    _check(L.zkg_fr_nonzero_index(_p(fr) if n else None, C.c_size_t(n), int(where), _p(out), C.byref(count)), "zkg_fr_nonzero_index")
+    return out[:count.value].copy()
 
 
 def groth16_verify(vk_blob, primary_input, proof):

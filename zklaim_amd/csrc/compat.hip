@@ -38,8 +38,9 @@ size_t zkg_keypair_vk_blob(const zkg_keypair *kp, uint8_t *out, size_t cap);
 int zkg_groth16_verify(const uint8_t *vk_blob, size_t vk_len, const uint64_t *primary_input, size_t n_inputs, const uint8_t *proof, size_t proof_len);
 }
 
-int seam_keygen(const zkg_r1cs *cs, zk::OwnedCsr *owned, const std::function<void()> &under_gpu, unsigned char **pk_out, size_t *pk_len,
-                unsigned char **vk_out, size_t *vk_len, zkg_crs **crs_out, const std::function<void(const unsigned char *, size_t)> &on_blob);    // setup_verify.hip
+int setup_resident_core(const zkg_r1cs *cs, const uint64_t *trapdoor, zk::OwnedCsr *owned, const std::function<void()> &under_gpu,
+                        unsigned char **pk_out, size_t *pk_len, unsigned char **vk_out, size_t *vk_len, zkg_crs **crs_out,
+                        const std::function<void(const unsigned char *, size_t)> &on_blob);                                  // setup_verify.hip
 void seam_keygen_quiesce();                                                                                              // setup_verify.hip
 void circuit_release_csr(zkg_circuit *c, zk::OwnedCsr &out);                                                            // zklaim_circuit.hip
 int seam_verify_batch(const zklaim_ctx *const *ctxs, size_t count, int *rc, int front_end);                              // setup_verify.hip
@@ -171,8 +172,9 @@ static int libsnark_trusted_setup_impl(zklaim_ctx *ctx) {
     uint64_t key = 0; Digest128 full;
     // the reference's protocol proves with the key it has just generated (main_benchmark.c:113-140): the generator's points stay on the GPU
     // as that key, already resident when libsnark_prove looks ctx->pk up — by the digests of the very bytes handed to the caller
-    const int rc_gen = seam_keygen(&cs, &csr, [&] { zkg_circuit_free(ck); freed = true; }, &pk, &pk_len, &vk, &vk_len, &crs,
-                                   [&](const unsigned char *blob, size_t len) { key = sampled_digest(blob, len); full = full_digest(blob, len); });
+    // (zkg_groth16_setup_resident's core: fresh randomness, every scalar computed on the device)
+    const int rc_gen = setup_resident_core(&cs, nullptr, &csr, [&] { zkg_circuit_free(ck); freed = true; }, &pk, &pk_len, &vk, &vk_len, &crs,
+                                           [&](const unsigned char *blob, size_t len) { key = sampled_digest(blob, len); full = full_digest(blob, len); });
     if (!freed) zkg_circuit_free(ck);                            // the generator failed before its GPU phase
     if (rc_gen != ZKG_OK) return ZKLAIM_ERROR;
     lap("keys generated");

@@ -42,10 +42,11 @@ struct zkg_keypair {
     std::vector<G2Affine> B_g2;
     Fq12 alpha_beta;
     zkg_pk pk_view;
-    // the seam's generator (seam_keygen) leaves the five queries on the DEVICE instead (they become the resident key of the proofs that
+    // the resident generator (setup_resident_core) leaves the five queries on the DEVICE instead (they become the resident key of the proofs that
     // follow): the host vectors above stay empty, pk_view's query pointers are device pointers, b_idx lists the B query's non-zero entries
-    bool on_device = false; DevBuf dA, dB1, dB2, dH, dL; std::vector<uint32_t> b_idx;
-    ~zkg_keypair() { for (DevBuf *b : {&dA, &dB1, &dB2, &dH, &dL}) b->release(); }
+    // (host copy, for the blob's decimal text) and dBidx holds the same list on the device (for compress_kc_records)
+    bool on_device = false; DevBuf dA, dB1, dB2, dH, dL, dBidx; std::vector<uint32_t> b_idx;
+    ~zkg_keypair() { for (DevBuf *b : {&dA, &dB1, &dB2, &dH, &dL, &dBidx}) b->release(); }
 };
 
 namespace {
@@ -98,14 +99,16 @@ int batch_points(FN fixed_base_fn, const A &base, const Scalars &scalars, std::v
 template <class A, class FN>
 int batch_points(FN fixed_base_fn, const A &base, const std::vector<Fr> &scalars, std::vector<A> &out) { return batch_points(fixed_base_fn, base, Scalars(scalars), out); }
 
-// the same batch with its result left on the device
+// the same batch with its result left on the device; `uploaded` counts the scalars that came from host memory
 template <class A, class FN>
-int batch_points_dev(FN fixed_base_fn, const A &base, const std::vector<Fr> &scalars, DevBuf &d_out) {
+int batch_points_dev(FN fixed_base_fn, const A &base, const Scalars &scalars, DevBuf &d_out, size_t &uploaded) {
     const size_t n = scalars.size();
     if (d_out.reserve(n * sizeof(A) + 16)) return ZKG_ERROR;
     if (!n) return ZKG_OK;
+    if (!scalars.host) return fixed_base_fn(base, reinterpret_cast<const uint32_t *>(scalars.dev), n, d_out.as<A>(), nullptr, true);
     ScopedDevBuf d_s;
-    if (d_s.reserve(n * 32) || !hip_ok(hipMemcpy(d_s.p, scalars.data(), n * 32, hipMemcpyHostToDevice), "H2D", __FILE__, __LINE__)) return ZKG_ERROR;
+    if (d_s.reserve(n * 32) || !hip_ok(hipMemcpy(d_s.p, scalars.host->data(), n * 32, hipMemcpyHostToDevice), "H2D", __FILE__, __LINE__)) return ZKG_ERROR;
+    uploaded += n;
     return fixed_base_fn(base, d_s.as<uint32_t>(), n, d_out.as<A>(), nullptr, true);
 }
 
@@ -128,6 +131,69 @@ __global__ __launch_bounds__(256) void k_setup_abc_scalars(const Fr *abc, size_t
     out[j] = (v * (j <= l ? ginv : dinv)).normalized();
 }
 
+// ---- the ordered non-zero index of an Fr vector (the B query's entries that are not the point at infinity): three dependent launches and
+//      no wait between workgroups.  One element per thread: a wavefront takes NZ_WAVE elements and counts them with one ballot, a workgroup
+//      takes NZ_BLOCK; k_nonzero_count leaves one count per workgroup, k_nonzero_scan — ONE workgroup that walks all the counts NZ_SCAN at a
+//      time with a running carry, so the scan has no levels — turns them into offsets and the total, k_nonzero_scatter takes the ballots
+//      again and writes each position at offset + waves before + lanes before.  Zero is the lazy layer's: 0 or r, nothing normalised.
+constexpr unsigned NZ_WAVE = 64, NZ_BLOCK = 256, NZ_SCAN = 1024;
+constexpr size_t NZ_MAX = (size_t)1 << 28;
+__global__ __launch_bounds__(NZ_BLOCK) void k_nonzero_count(const Fr *v, size_t n, uint32_t *block_count) {
+    __shared__ uint32_t wcnt[NZ_BLOCK / NZ_WAVE];
+    const size_t i = (size_t)blockIdx.x * NZ_BLOCK + threadIdx.x;
+    const bool nz = i < n && !v[i].is_zero();
+    const unsigned long long mask = __ballot(nz);
+    if ((threadIdx.x & (NZ_WAVE - 1)) == 0) wcnt[threadIdx.x / NZ_WAVE] = (uint32_t)__popcll(mask);
+    __syncthreads();
+    if (threadIdx.x == 0) { uint32_t c = 0; for (unsigned w = 0; w < NZ_BLOCK / NZ_WAVE; ++w) c += wcnt[w]; block_count[blockIdx.x] = c; }
+}
+__global__ __launch_bounds__(NZ_SCAN) void k_nonzero_scan(uint32_t *block_count, size_t nblocks, uint32_t *total) {   // counts -> exclusive offsets, in place
+    __shared__ uint32_t wsum[NZ_SCAN / NZ_WAVE];
+    const unsigned lane = threadIdx.x & (NZ_WAVE - 1), wave = threadIdx.x / NZ_WAVE;
+    uint32_t carry = 0;
+    for (size_t base = 0; base < nblocks; base += NZ_SCAN) {               // (the trip count is the same for every thread)
+        const size_t i = base + threadIdx.x;
+        const uint32_t c = i < nblocks ? block_count[i] : 0;
+        uint32_t incl = c;
+        for (unsigned d = 1; d < NZ_WAVE; d <<= 1) { const uint32_t up = __shfl_up(incl, d, NZ_WAVE); if (lane >= d) incl += up; }
+        if (lane == NZ_WAVE - 1) wsum[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+        for (unsigned w = 0; w < NZ_SCAN / NZ_WAVE; ++w) { const uint32_t s = wsum[w]; if (w < wave) before += s; all += s; }
+        if (i < nblocks) block_count[i] = carry + before + incl - c;
+        carry += all;
+        __syncthreads();                                                   // wsum is written again by the next round
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+__global__ __launch_bounds__(NZ_BLOCK) void k_nonzero_scatter(const Fr *v, size_t n, const uint32_t *block_offset, uint32_t *idx) {
+    __shared__ uint32_t wcnt[NZ_BLOCK / NZ_WAVE];
+    const size_t i = (size_t)blockIdx.x * NZ_BLOCK + threadIdx.x;
+    const unsigned lane = threadIdx.x & (NZ_WAVE - 1), wave = threadIdx.x / NZ_WAVE;
+    const bool nz = i < n && !v[i].is_zero();
+    const unsigned long long mask = __ballot(nz);
+    if (lane == 0) wcnt[wave] = (uint32_t)__popcll(mask);
+    __syncthreads();
+    if (!nz) return;
+    uint32_t at = block_offset[blockIdx.x] + (uint32_t)__popcll(mask & ((1ull << lane) - 1));
+    for (unsigned w = 0; w < wave; ++w) at += wcnt[w];
+    idx[at] = (uint32_t)i;                                                  // at < the total <= n: idx holds n entries
+}
+// d_idx: n entries; d_count: one word; d_blocks: nonzero_index_blocks(n) words of workspace.  Queued on s, nothing waits.
+size_t nonzero_index_blocks(size_t n) { return (n + NZ_BLOCK - 1) / NZ_BLOCK; }
+int nonzero_index_dev(const Fr *d_v, size_t n, uint32_t *d_idx, uint32_t *d_count, uint32_t *d_blocks, hipStream_t s) {
+    if (n > NZ_MAX) { set_error("nonzero index: more than 2^28 elements"); return ZKG_ERROR; }
+    if (!n) { ZK_HIP(hipMemsetAsync(d_count, 0, 4, s)); return ZKG_OK; }
+    const unsigned nblocks = (unsigned)nonzero_index_blocks(n);
+    hipLaunchKernelGGL(k_nonzero_count, dim3(nblocks), dim3(NZ_BLOCK), 0, s, d_v, n, d_blocks);
+    hipLaunchKernelGGL(k_nonzero_scan, dim3(1), dim3(NZ_SCAN), 0, s, d_blocks, (size_t)nblocks, d_count);
+    hipLaunchKernelGGL(k_nonzero_scatter, dim3(nblocks), dim3(NZ_BLOCK), 0, s, d_v, n, (const uint32_t *)d_blocks, d_idx);
+    if (hipGetLastError() != hipSuccess) { set_error("nonzero index: kernel launch failed"); return ZKG_ERROR; }
+    return ZKG_OK;
+}
+// what the last generator of this thread that leaves its key on the device did (zkg_setup_resident_stats)
+thread_local size_t t_setup_resident_stats[3] = {0, 0, 0};
+
 }  // namespace
 
 extern "C" {
@@ -135,12 +201,16 @@ extern "C" {
 // The generator proper.  The constraint system comes either as the ABI's view (copied) or — `owned` — as CSR vectors the caller gives up
 // (the seam's circuit: 100 MB at 20 payloads that would otherwise be copied and then freed twice); `under_gpu` runs on a thread of its own
 // while the GPU turns the scalars into points (the seam destroys its circuit there).
-// keep_on_device: the seam's variant (seam_keygen below).  after_csr(kp) runs when the generator's host loops are done and its GPU phase
+// mode: where the scalars are computed and where the queries end up (Resident: setup_resident_core below).
+// after_csr(kp) runs when the generator's host loops are done and its GPU phase
 // begins (kp holds the constraint system it will store) — the seam starts writing the pk blob's constraint rows there; before_delete()
 // runs before a failing generator deletes kp (whatever after_csr started must have let go of it).
-static zkg_keypair *groth16_setup_impl(const zkg_r1cs *cs, const uint64_t *trapdoor, OwnedCsr *owned, const std::function<void()> &under_gpu, bool keep_on_device = false,
-                                       const std::function<void(zkg_keypair *)> &after_csr = nullptr, const std::function<void()> &before_delete = nullptr,
-                                       bool dev_scalars = false) {
+enum class SetupMode { Host,          // zkg_groth16_setup: scalars from the host loops, the key in host vectors
+                       DevScalars,    // zkg_groth16_setup_dev: every scalar computed on the device, the key in host vectors
+                       Resident };    // zkg_groth16_setup_resident, the seam: every scalar computed on the device, the queries left there
+static zkg_keypair *groth16_setup_impl(const zkg_r1cs *cs, const uint64_t *trapdoor, OwnedCsr *owned, const std::function<void()> &under_gpu, SetupMode mode = SetupMode::Host,
+                                       const std::function<void(zkg_keypair *)> &after_csr = nullptr, const std::function<void()> &before_delete = nullptr) {
+    const bool dev_scalars = mode != SetupMode::Host, keep_on_device = mode == SetupMode::Resident;
     if (!cs || (!owned && (!cs->a_rowptr || !cs->b_rowptr || !cs->c_rowptr))) { set_error("zkg_groth16_setup: null constraint system"); return nullptr; }
     zkg_keypair *kp = new zkg_keypair();
     static const bool dbg = getenv("ZKG_DEBUG_TIMING") != nullptr;
@@ -180,7 +250,6 @@ static zkg_keypair *groth16_setup_impl(const zkg_r1cs *cs, const uint64_t *trapd
     if (dev_scalars) {
         // ---- zkg_groth16_setup_dev: the instance map on a zkg_qap handle over the system as it is stored (swapped or not), H's scalars from
         //      powers_table, IC's and L's from one kernel — all queued on the null stream, where the fixed-base batches follow them
-        if (keep_on_device) { set_error("zkg_groth16_setup_dev: no device-resident key"); return drop(); }
         zkg_r1cs view; memset(&view, 0, sizeof(view));
         view.num_variables = kp->n; view.num_inputs = kp->l; view.num_constraints = kp->C;
         view.a_rowptr = kp->rp[0].data(); view.a_col = kp->col[0].data(); view.a_val = kp->val[0].data();
@@ -196,6 +265,12 @@ static zkg_keypair *groth16_setup_impl(const zkg_r1cs *cs, const uint64_t *trapd
         if (powers_table(d_h, m - 1, t, zd, nullptr)) { set_error("zkg_groth16_setup_dev: kernel launch failed"); return drop(); }   // t^i Z(t) / delta
         hipLaunchKernelGGL(k_setup_abc_scalars, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, nullptr, (const Fr *)d_abc, n + 1, n + 1, (uint32_t)l, alpha, beta, ginv, dinv, d_icl);
         if (hipGetLastError() != hipSuccess) { set_error("zkg_groth16_setup_dev: kernel launch failed"); return drop(); }
+        // the B query's non-zero list, behind the instance map on the same stream: n + 1 indices | their count | the scan's workspace
+        if (keep_on_device) {
+            if (kp->dBidx.reserve((n + 2 + nonzero_index_blocks(n + 1)) * 4 + 16)) return drop();
+            uint32_t *d_idx = kp->dBidx.as<uint32_t>();
+            if (nonzero_index_dev(d_abc + (n + 1), n + 1, d_idx, d_idx + (n + 1), d_idx + (n + 2), nullptr)) return drop();
+        }
         if (dbg) (void)hipStreamSynchronize(nullptr);                      // the lap then holds the kernels, not their enqueue
         lap("qap instance + scalars (device)");
     } else {
@@ -255,12 +330,22 @@ static zkg_keypair *groth16_setup_impl(const zkg_r1cs *cs, const uint64_t *trapd
         // the seam: ~4n + m points computed into device buffers and left there; only the 8 key elements and the l + 1 points of the
         // verification key come back
         kp->on_device = true;
-        for (size_t i = 0; i < Bt.size(); ++i) if (!Bt[i].is_zero()) kp->b_idx.push_back((uint32_t)i);       // zero scalar <=> point at infinity
+        size_t uploaded = 0;
         const bool okd = batch_points<G1Affine>(fixed_base_g1, g1, {alpha, beta, delta}, small1) == 0 && batch_points<G2Affine>(fixed_base_g2, g2, {beta, delta, gamma}, small2) == 0 &&
-                         batch_points_dev<G1Affine>(fixed_base_g1, g1, At, kp->dA) == 0 && batch_points_dev<G1Affine>(fixed_base_g1, g1, Bt, kp->dB1) == 0 &&
-                         batch_points_dev<G2Affine>(fixed_base_g2, g2, Bt, kp->dB2) == 0 && batch_points_dev<G1Affine>(fixed_base_g1, g1, Hs, kp->dH) == 0 &&
-                         batch_points_dev<G1Affine>(fixed_base_g1, g1, Ls, kp->dL) == 0 && batch_points<G1Affine>(fixed_base_g1, g1, ICs, kp->IC) == 0;
+                         batch_points_dev<G1Affine>(fixed_base_g1, g1, sAt, kp->dA, uploaded) == 0 && batch_points_dev<G1Affine>(fixed_base_g1, g1, sBt, kp->dB1, uploaded) == 0 &&
+                         batch_points_dev<G2Affine>(fixed_base_g2, g2, sBt, kp->dB2, uploaded) == 0 && batch_points_dev<G1Affine>(fixed_base_g1, g1, sHs, kp->dH, uploaded) == 0 &&
+                         batch_points_dev<G1Affine>(fixed_base_g1, g1, sLs, kp->dL, uploaded) == 0 && batch_points<G1Affine>(fixed_base_g1, g1, sICs, kp->IC) == 0;
         if (!okd) return drop();
+        // the B query's non-zero list (zero scalar <=> point at infinity): compress_kc_records reads it where k_nonzero_* left it, behind the
+        // instance map and long finished by now; the blob's decimal text needs it on the host — its count and its entries come back here,
+        // after the batches, so that this copy, the one host wait the device scalars cost, never holds the GPU's queue up
+        const uint32_t *d_idx = kp->dBidx.as<uint32_t>();
+        uint32_t count = 0;
+        if (!hip_ok(hipMemcpy(&count, d_idx + (n + 1), 4, hipMemcpyDeviceToHost), "D2H", __FILE__, __LINE__)) return drop();
+        if (count > n + 1) { set_error("zkg_groth16_setup_resident: non-zero count above n + 1"); return drop(); }
+        kp->b_idx.resize(count);
+        if (count && !hip_ok(hipMemcpy(kp->b_idx.data(), d_idx, (size_t)count * 4, hipMemcpyDeviceToHost), "D2H", __FILE__, __LINE__)) return drop();
+        t_setup_resident_stats[0] = 1; t_setup_resident_stats[1] = count; t_setup_resident_stats[2] = uploaded;
     } else {
     if (!no_prefault) host_parallel_for(5, [&](int i) {
         if (i == 0) kp->B_g2.resize(sBt.size()); else if (i == 1) kp->A_query.resize(sAt.size()); else if (i == 2) kp->B_g1.resize(sBt.size());
@@ -299,7 +384,7 @@ zkg_keypair *zkg_groth16_setup(const zkg_r1cs *cs, const uint64_t *trapdoor /* 5
 zkg_keypair *zkg_groth16_setup_dev(const zkg_r1cs *cs, const uint64_t *trapdoor) {
     return c_boundary<zkg_keypair *>("zkg_groth16_setup_dev", nullptr, [&]() -> zkg_keypair * {
         if (initialised_device() < 0) { set_error("zkg_init not called"); return nullptr; }
-        return groth16_setup_impl(cs, trapdoor, nullptr, nullptr, false, nullptr, nullptr, true);
+        return groth16_setup_impl(cs, trapdoor, nullptr, nullptr, SetupMode::DevScalars);
     });
 }
 
@@ -1561,18 +1646,23 @@ static void keypair_discard(zkg_keypair *kp, int device) {
     discard_thread() = std::thread([kp, device] { (void)hipSetDevice(device); delete kp; });
 }
 
-// libsnark_trusted_setup's generator (zklaim/libsnark_wrapper.cpp:195-215) as the seam runs it.  The reference's protocol is setup -> ONE
-// prove -> verify per key (src/main_benchmark.c:113-148), so the key this call generates is the key the next libsnark_prove needs:
-// the ~4n + m query points are computed into device buffers and stay there as the resident key (zkg_crs, H table included); the pk blob
-// the C caller receives is assembled from GPU-compressed records (34 / 100 bytes per point instead of 64 / 192 over PCIe, no host point
-// vectors at all) around the constraint rows' text, which the host pool writes meanwhile.  Same bytes as zkg_keypair_pk_blob writes.
-// pk / vk: malloc'd (the caller's to free).  on_blob runs on a thread of its own as soon as the pk blob is complete (the seam hashes it).
-int seam_keygen(const zkg_r1cs *cs, zk::OwnedCsr *owned, const std::function<void()> &under_gpu, unsigned char **pk_out, size_t *pk_len,
-                unsigned char **vk_out, size_t *vk_len, zkg_crs **crs_out, const std::function<void(const unsigned char *, size_t)> &on_blob) {
+// The generator that leaves its key where it is made: zkg_groth16_setup_resident (a copied CSR, a trapdoor, no hooks) and
+// libsnark_trusted_setup's generator (zklaim/libsnark_wrapper.cpp:195-215: an owned CSR, fresh randomness, under_gpu and on_blob) are this
+// one function.  The reference's protocol is setup -> ONE prove -> verify per key (src/main_benchmark.c:113-148), so the key this call
+// generates is the key the next proof needs: every scalar is computed on the device (as zkg_groth16_setup_dev computes them), the ~4n + m
+// query points are computed into device buffers and stay there as the resident key (zkg_crs, H table included); the pk blob the caller
+// receives is assembled from GPU-compressed records (34 / 100 bytes per point instead of 64 / 192 over PCIe, no host point vectors at
+// all) around the constraint rows' text, which the host pool writes meanwhile.  Same bytes as zkg_keypair_pk_blob writes.
+// pk / vk: malloc'd (the caller's to free).  crs_out NULL: no resident key is built.  on_blob runs on a thread of its own as soon as the pk
+// blob is complete (the seam hashes it).
+int setup_resident_core(const zkg_r1cs *cs, const uint64_t *trapdoor, zk::OwnedCsr *owned, const std::function<void()> &under_gpu,
+                        unsigned char **pk_out, size_t *pk_len, unsigned char **vk_out, size_t *vk_len, zkg_crs **crs_out,
+                        const std::function<void(const unsigned char *, size_t)> &on_blob) {
     static const bool dbg = getenv("ZKG_DEBUG_TIMING") != nullptr;
     auto t_begin = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) { if (dbg) fprintf(stderr, "[zkg seam keygen] %-26s %8.3f ms\n", what, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count()); };
-    *pk_out = *vk_out = nullptr; *crs_out = nullptr;
+    *pk_out = *vk_out = nullptr; if (crs_out) *crs_out = nullptr;
+    t_setup_resident_stats[0] = t_setup_resident_stats[1] = t_setup_resident_stats[2] = 0;
     // ---- the constraint rows' text starts as soon as the generator has fixed the system it stores (a thread of its own that fans out over
     //      the host pool): it is the longest host-only part of the blob and needs nothing the GPU computes
     int device = 0; (void)hipGetDevice(&device);                               // threads started below bind to the caller's device
@@ -1580,7 +1670,7 @@ int seam_keygen(const zkg_r1cs *cs, zk::OwnedCsr *owned, const std::function<voi
     std::vector<ser::Writer> rows_part; bool rows_ok = true;
     std::thread rows_thread;
     struct Join { std::thread &t; ~Join() { if (t.joinable()) t.join(); } } join_rows{rows_thread};
-    kp.reset(groth16_setup_impl(cs, nullptr, owned, under_gpu, true,
+    kp.reset(groth16_setup_impl(cs, trapdoor, owned, under_gpu, SetupMode::Resident,
         [&](zkg_keypair *k) { rows_thread = std::thread([&rows_part, &rows_ok, k] { try { constraint_rows_text(k, rows_part); } catch (...) { rows_ok = false; } }); },
         [&] { if (rows_thread.joinable()) rows_thread.join(); }));
     if (!kp) return ZKG_ERROR;
@@ -1588,7 +1678,8 @@ int seam_keygen(const zkg_r1cs *cs, zk::OwnedCsr *owned, const std::function<voi
     // ---- the resident key is built from the device queries on a thread of its own (null stream: H table, constraint system upload, comb
     //      tables, domain, prover slot) while this thread turns the same queries into the blob's records on a stream of its own
     zkg_crs *crs = nullptr;
-    std::thread crs_thread([&] { try { (void)hipSetDevice(device); crs = crs_upload_device_queries(&kp->pk_view, nullptr); } catch (...) { crs = nullptr; } });
+    std::thread crs_thread;
+    if (crs_out) crs_thread = std::thread([&] { try { (void)hipSetDevice(device); crs = crs_upload_device_queries(&kp->pk_view, nullptr); } catch (...) { crs = nullptr; } });
     struct JoinCrs { std::thread &t; zkg_crs *&c; bool keep = false; ~JoinCrs() { if (t.joinable()) t.join(); if (!keep && c) { zkg_crs_free(c); c = nullptr; } } } join_crs{crs_thread, crs};
     // ---- layout: everything before the constraint rows has a known size
     const size_t nA = (size_t)kp->n + 1, nidx = kp->b_idx.size(), nH = kp->m - 1, nL = (size_t)kp->n - kp->l;
@@ -1604,22 +1695,21 @@ int seam_keygen(const zkg_r1cs *cs, zk::OwnedCsr *owned, const std::function<voi
     size_t terms = 0; for (int k = 0; k < 3; ++k) terms += kp->col[k].size();
     const size_t rows_bound = terms * 44 + (size_t)kp->C * 3 * 12 + 64;        // an index is at most 10 digits + '\n', a count likewise
     unsigned char *pk = (unsigned char *)malloc(rows_at + rows_bound);          // (untouched pages of the bound cost nothing; shrunk below)
-    if (!pk) { set_error("seam_keygen: out of memory"); return ZKG_ERROR; }
+    if (!pk) { set_error("resident generator: out of memory"); return ZKG_ERROR; }
     struct FreeOnExit { unsigned char *&p; ~FreeOnExit() { free(p); } } free_pk{pk};
     for (int i = 0; i < 5; ++i) memcpy(pk + at_seg[i], seg[i].buf.data(), seg[i].buf.size());
     // ---- the GPU compresses the points into the blob's records; they come back, run by run, straight into the blob
     {
-        ScopedDevBuf d_rec, d_idx;
+        ScopedDevBuf d_rec;
         hipStream_t st = nullptr;
         if (!hip_ok(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreate", __FILE__, __LINE__)) return ZKG_ERROR;
         struct DropStream { hipStream_t s; ~DropStream() { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } drop_stream{st};
         size_t off[4], total = 0;
         for (int i = 0; i < 4; ++i) { off[i] = total; total += (run[i] + 15) & ~(size_t)15; }
-        if (d_rec.reserve(total + 16) || d_idx.reserve(nidx * 4 + 16) ||
-            (nidx && !hip_ok(hipMemcpyAsync(d_idx.p, kp->b_idx.data(), nidx * 4, hipMemcpyHostToDevice, st), "H2D", __FILE__, __LINE__))) return ZKG_ERROR;
+        if (d_rec.reserve(total + 16)) return ZKG_ERROR;
         uint8_t *r = d_rec.as<uint8_t>();
-        if (compress_g1_records(kp->dA.as<G1Affine>(), nA, r + off[0], st) || compress_kc_records(kp->dB2.as<G2Affine>(), kp->dB1.as<G1Affine>(), d_idx.as<uint32_t>(), nidx, r + off[1], st) ||
-            compress_g1_records(kp->dH.as<G1Affine>(), nH, r + off[2], st) || compress_g1_records(kp->dL.as<G1Affine>(), nL, r + off[3], st)) { set_error("seam_keygen: compression launch failed"); return ZKG_ERROR; }
+        if (compress_g1_records(kp->dA.as<G1Affine>(), nA, r + off[0], st) || compress_kc_records(kp->dB2.as<G2Affine>(), kp->dB1.as<G1Affine>(), kp->dBidx.as<uint32_t>(), nidx, r + off[1], st) ||
+            compress_g1_records(kp->dH.as<G1Affine>(), nH, r + off[2], st) || compress_g1_records(kp->dL.as<G1Affine>(), nL, r + off[3], st)) { set_error("resident generator: compression launch failed"); return ZKG_ERROR; }
         for (int i = 0; i < 4; ++i)
             if (run[i] && !hip_ok(hipMemcpyAsync(pk + at_run[i], r + off[i], run[i], hipMemcpyDeviceToHost, st), "D2H", __FILE__, __LINE__)) return ZKG_ERROR;
         if (!hip_ok(hipStreamSynchronize(st), "sync", __FILE__, __LINE__)) return ZKG_ERROR;
@@ -1634,7 +1724,7 @@ int seam_keygen(const zkg_r1cs *cs, zk::OwnedCsr *owned, const std::function<voi
         if (rows_len > rows_bound) rows_ok = false;
         else host_parallel_for((int)rows_part.size(), [&](int i) { if (!rows_part[i].buf.empty()) memcpy(pk + at[i], rows_part[i].buf.data(), rows_part[i].buf.size()); });
     }
-    if (!rows_ok) { set_error("seam_keygen: constraint rows failed"); return ZKG_ERROR; }
+    if (!rows_ok) { set_error("resident generator: constraint rows failed"); return ZKG_ERROR; }
     const size_t len = rows_at + rows_len;
     { unsigned char *shrunk = (unsigned char *)realloc(pk, len); if (shrunk) pk = shrunk; }
     lap("pk blob complete");
@@ -1644,16 +1734,74 @@ int seam_keygen(const zkg_r1cs *cs, zk::OwnedCsr *owned, const std::function<voi
     // ---- vk (l + 1 points, host)
     const size_t vlen = zkg_keypair_vk_blob(kp.get(), nullptr, 0);
     unsigned char *vk = (unsigned char *)malloc(vlen);
-    if (!vk || zkg_keypair_vk_blob(kp.get(), vk, vlen) != vlen) { free(vk); set_error("seam_keygen: vk blob failed"); return ZKG_ERROR; }
-    crs_thread.join();
+    if (!vk || zkg_keypair_vk_blob(kp.get(), vk, vlen) != vlen) { free(vk); set_error("resident generator: vk blob failed"); return ZKG_ERROR; }
+    if (crs_thread.joinable()) crs_thread.join();
     lap("resident key built");
-    if (!crs) { free(vk); return ZKG_ERROR; }
+    if (crs_out && !crs) { free(vk); return ZKG_ERROR; }
     if (blob_thread.joinable()) blob_thread.join();
     join_crs.keep = true;
     // the keypair's host vectors (the constraint system, 100 MB at 20 payloads) and device queries go back to their allocators on a thread
     // of their own: nothing below needs them
     keypair_discard(kp.release(), device);
-    *pk_out = pk; *pk_len = len; *vk_out = vk; *vk_len = vlen; *crs_out = crs;
+    *pk_out = pk; *pk_len = len; *vk_out = vk; *vk_len = vlen; if (crs_out) *crs_out = crs;
     pk = nullptr;                                                               // handed over
     return ZKG_OK;
 }
+
+extern "C" {
+
+int zkg_groth16_setup_resident(const zkg_r1cs *cs, const uint64_t *trapdoor, uint8_t **pk_blob, size_t *pk_len, uint8_t **vk_blob, size_t *vk_len, zkg_crs **crs) {
+    return c_boundary("zkg_groth16_setup_resident", ZKG_ERROR, [&] {
+        if (!cs || !pk_blob || !pk_len || !vk_blob || !vk_len) { set_error("zkg_groth16_setup_resident: null argument"); return ZKG_ERROR; }
+        if (initialised_device() < 0) { set_error("zkg_groth16_setup_resident: zkg_init not called"); return ZKG_ERROR; }
+        unsigned char *pk = nullptr, *vk = nullptr; size_t plen = 0, vlen = 0; zkg_crs *key = nullptr;
+        if (setup_resident_core(cs, trapdoor, nullptr, nullptr, &pk, &plen, &vk, &vlen, crs ? &key : nullptr, nullptr) != ZKG_OK) {
+            set_error(std::string("zkg_groth16_setup_resident: ") + zkg_last_error());       // the out-pointers are left alone
+            return ZKG_ERROR;
+        }
+        *pk_blob = pk; *pk_len = plen; *vk_blob = vk; *vk_len = vlen;
+        if (crs) *crs = key;
+        return ZKG_OK;
+    });
+}
+void zkg_free(void *p) { free(p); }
+void zkg_setup_resident_stats(size_t out[3]) { if (out) for (int i = 0; i < 3; ++i) out[i] = t_setup_resident_stats[i]; }
+
+// test hook: the generator's non-zero index (where 1) against a plain host loop (where 0) on raw limbs — any representative below 2r
+int zkg_fr_nonzero_index(const uint64_t *fr, size_t n, int where, uint32_t *idx_out, size_t *count) {
+    return c_boundary("zkg_fr_nonzero_index", ZKG_ERROR, [&] {
+        if (!count || (n && (!fr || !idx_out)) || (where != 0 && where != 1)) { set_error("zkg_fr_nonzero_index: bad argument"); return ZKG_ERROR; }
+        if (n > NZ_MAX) { set_error("zkg_fr_nonzero_index: more than 2^28 elements"); return ZKG_ERROR; }
+        if (where == 0) {
+            size_t c = 0;
+            for (size_t i = 0; i < n; ++i) {
+                uint32_t v[8]; memcpy(v, fr + 4 * i, 32);
+                uint32_t o = 0, q = 0;
+                for (int k = 0; k < 8; ++k) { o |= v[k]; q |= v[k] ^ FrParams::P[k]; }
+                if (o != 0 && q != 0) idx_out[c++] = (uint32_t)i;
+            }
+            *count = c;
+            return ZKG_OK;
+        }
+        if (initialised_device() < 0) { set_error("zkg_fr_nonzero_index: zkg_init not called"); return ZKG_ERROR; }
+        if (!n) { *count = 0; return ZKG_OK; }
+        // idx: n entries and a guard of 64 behind them, all ones before the kernels run — whatever lies behind the count must still be so
+        const size_t guard = 64, words = n + guard;
+        ScopedDevBuf d_v, d_w;
+        if (d_v.reserve(n * 32) || d_w.reserve((words + 1 + nonzero_index_blocks(n)) * 4)) return ZKG_ERROR;
+        uint32_t *d_idx = d_w.as<uint32_t>(), *d_count = d_idx + words, *d_blocks = d_count + 1;
+        ZK_HIP(hipMemcpy(d_v.p, fr, n * 32, hipMemcpyHostToDevice));
+        ZK_HIP(hipMemsetAsync(d_idx, 0xff, (words + 1) * 4, nullptr));
+        if (nonzero_index_dev(d_v.as<Fr>(), n, d_idx, d_count, d_blocks, nullptr)) return ZKG_ERROR;
+        std::vector<uint32_t> back(words + 1);
+        ZK_HIP(hipMemcpy(back.data(), d_idx, (words + 1) * 4, hipMemcpyDeviceToHost));
+        const size_t c = back[words];
+        if (c > n) { set_error("zkg_fr_nonzero_index: count above n"); return ZKG_ERROR; }
+        for (size_t i = c; i < words; ++i) if (back[i] != 0xffffffffu) { set_error("zkg_fr_nonzero_index: an entry behind the count was written"); return ZKG_ERROR; }
+        memcpy(idx_out, back.data(), c * 4);
+        *count = c;
+        return ZKG_OK;
+    });
+}
+
+}  // extern "C"
