@@ -1,12 +1,13 @@
 """CPU suite: the single-proof zklaim entry without a GPU.  k_zklaim_witness_par's device code compiled for the host
 (zkg_zklaim_witness_mirror_parallel: the plain SHA-256 value pass, then every slice of the trace on its own from the derived plan, last
-slice first) against the host witness pass and the serial mirror, byte for byte; and zkg_groth16_prove_zklaim's argument failures."""
+slice first) against the host witness pass and the serial mirror, byte for byte, up to the 64 payloads the generator serves; and
+zkg_groth16_prove_zklaim's argument failures."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-from zklaim_witness_cases import N_SPECS, assert_same_witness, host_pass, payloads
+from zklaim_witness_cases import KS_LARGE, N_SPECS, assert_same_witness, host_pass, large_cases, payloads
 
 
 def _zkg():
@@ -35,6 +36,18 @@ def test_slices_in_reverse_order_equal_the_host_pass_and_the_serial_mirror(k, sp
         got = zkg.zklaim_witness_mirror_parallel(ctx)
         assert_same_witness(got, host_pass(zkg, ctx), (k, spec, "host pass"))
         assert_same_witness(got, zkg.zklaim_witness_mirror(ctx), (k, spec, "serial mirror"))
+
+
+@pytest.mark.parametrize("k", KS_LARGE)
+def test_slices_equal_the_host_pass_at_large_counts(k):
+    """more than one round of candidates (the mixed and banded credentials, the full-width pre-images, at 13 the sweeps over the 1 / c table)"""
+    zkg = _zkg()
+    cases = large_cases(zkg, k)
+    assert {"mixed0", "random", "ones", "banded1"} <= set(cases) and (k != 13 or {"sweep", "sweep_reversed"} <= set(cases))
+    for name, (ctx, want) in cases.items():
+        got = zkg.zklaim_witness_mirror_parallel(ctx)
+        assert_same_witness(got, want, (k, name, "host pass"))
+        assert_same_witness(got, zkg.zklaim_witness_mirror(ctx), (k, name, "serial mirror"))
 
 
 def test_broken_payload_list_is_an_error():
