@@ -464,6 +464,64 @@ int zkg_groth16_prove_batch_dev(const zkg_crs *crs, const void *d_witnesses, siz
 /* the calling thread's last zkg_groth16_prove_dev / zkg_groth16_prove_batch_dev: out[0] witnesses split on the device from the caller's buffer,
  * out[1] witnesses staged through host memory (0 on every path).  Counters, not clocks. */
 void zkg_prove_dev_stats(size_t out[2]);
+/* ---- proofs that stay on the caller's stream and on the device: a prover handle on a resident key.  One call takes `count` witnesses in DEVICE
+ *      memory and leaves `count` proofs of ZKG_PROOF_BYTES in DEVICE memory, queued behind the caller's stream with no wait on the host and no
+ *      arithmetic on the host; the bytes are those of zkg_groth16_prove_dev for the same (key, witness, r, s).  The synchronous entries above
+ *      keep their own tuned paths (subset tables, flat sums over the ones, host finish) and remain the default.
+ *      zkg_prover_new(crs): from a resident key of any source (zkg_crs_upload, zkg_crs_upload_blob, zkg_groth16_setup_resident), on the calling
+ *      thread's device, which must be the key's and the zkg_init device.  The handle BORROWS the key — its H per-window table, its queries, its
+ *      domain tables: free the prover before the key.  A key whose H query is sharded (zkg_crs_shard_h) is refused, and zkg_crs_shard_h refuses
+ *      a key that has a live prover handle.  NULL on failure, with zkg_last_error set (no zkg_init, a null key, a failed allocation).
+ *      What the handle builds once: a QAP handle over a device copy of the key's constraint system; per-window tables over the WHOLE witness
+ *      queries — A[1..n], B_g1[1..n], L padded to n points (infinity for the l public inputs, so that the three G1 sets share indices) and
+ *      B_g2[1..n], window size by n (8, 12 or 16 bits); three multi-exponentiation jobs with a device epilogue (one launch for the three G1 sets,
+ *      one for G2, one for H); the constant column's points A[0], B_g1[0], B_g2[0] and alpha, beta; the fixed-base tables of alpha_1, beta_1,
+ *      delta_1, delta_2 (64 x 15 affine multiples each) in device memory.  Memory beside the key: 64 B x levels x n per G1 table (these launches
+ *      read no 29-bit records, so none are built) and 128 B x levels x n for G2 — 320 B x 16 x n at 16-bit windows, 1.1 GB for an
+ *      eight-payload credential key (n = 219 338) — plus per proof of a group 32 (m + 1) B of coefficients, the QAP handle's 216 m B and the
+ *      jobs' buckets: at 16-bit windows 128 MiB for the G2 job (the capped one: 1 GiB for a group of 8), 3 x 64 MiB for the three G1 sets
+ *      of the A / B_1 / L job (1.5 GiB for a group of 8) and 32 MiB for H, whose rows are merged in pairs (0.25 GiB); at 12-bit windows a sixteenth of that per proof.
+ *      zkg_prover_free waits for the handle's pending work; NULL is accepted; callable from any device.
+ *      zkg_prover_prove_async: witness i is n Montgomery Fr at d_witnesses + i * stride * 32 bytes, stride >= n (zkg_groth16_prove_batch_dev's
+ *      layout), read in place; what lies between n and the stride is never read.  d_rs: (r, s) of item i as 8 limbs r | s, Montgomery Fr, in
+ *      DEVICE memory.  Proof i goes to d_proofs + i * proof_stride; bytes between ZKG_PROOF_BYTES and proof_stride are never written and no
+ *      alignment is asked of d_proofs.  Every word of d_status is written: ZKG_OK, or ZKG_UNSATISFIED when check_satisfied != 0 and the witness
+ *      violates a row — nothing is then written at that item's proof position and the other items are not affected; with check_satisfied == 0
+ *      the proof is written as zkg_groth16_prove_dev writes it.
+ *      The items are cut into groups of at most zkg_prover_batch_max — the largest p <= 16 that the three multi launches' sort geometry allows,
+ *      capped by the QAP handle's group and by 1 GiB of G2 buckets (zkg_msm_g2_resident_batch_max's rule).  Per group: the QAP handle's launch
+ *      sequence (coefficients_for_H and the unsatisfied words) and H over it on the handle's main stream; beside it, from the call's fork event,
+ *      the A / B_1 / L launch, the B_2 launch and the key-only part of the epilogue on three more streams; then the epilogue (three stages:
+ *      the products with r, s, rs from the fixed-base tables; s (W_a + A_0) and r (W_b1 + B1_0) as 4-bit windowed ladders side by side, behind
+ *      the G1 job; the sums, one normalisation per point and the three records).
+ *      Ordering: everything is ordered behind what is on `stream` (NULL: the null stream) at the time of the call, and before returning the call
+ *      makes `stream` wait for its last kernel: later work on `stream` sees proofs and status, and the host synchronises `stream` before it reads
+ *      them.  The caller keeps all four buffers alive and unchanged until then.  A handle serves its calls in call order whatever streams they
+ *      name (the enqueue is under the handle's mutex, on the handle's own streams).  The workspace only grows: a call that needs more of it
+ *      drains the handle's work first and counts one host wait per buffer set that grew; a call at a group size the handle has served makes no
+ *      host wait and no allocation.
+ *      Refused with ZKG_ERROR before any launch, nothing written: a null argument; stride < n or proof_stride < ZKG_PROOF_BYTES; more than 2^24
+ *      items, or a stride (either) above 2^32; a calling thread on another device than the key's; any of the four pointers that is not device
+ *      memory of that device, is misaligned (16 bytes for d_witnesses and d_rs, 4 for d_status) or runs past its allocation; ranges that
+ *      overlap.  count == 0 is ZKG_OK and touches nothing.  Safe from several threads, and beside every synchronous prove entry on the same key
+ *      (it shares only read-only key data).                                                                                                  */
+typedef struct zkg_prover zkg_prover;
+zkg_prover *zkg_prover_new(const zkg_crs *crs);
+void   zkg_prover_free(zkg_prover *p);
+size_t zkg_prover_batch_max(const zkg_prover *p);         /* proofs one launch sequence takes; >= 1, 0 for NULL */
+void   zkg_prover_set_batch_max(zkg_prover *p, size_t k); /* test hook: k proofs per launch sequence from now on; 0 restores the default, a larger k is clamped to it */
+int    zkg_prover_prove_async(zkg_prover *p, const void *d_witnesses, size_t stride /* Fr elements between items, >= n */, size_t count,
+                              const void *d_rs /* DEVICE, count x 8 limbs: r | s */, int check_satisfied,
+                              void *d_proofs /* DEVICE */, size_t proof_stride /* bytes, >= ZKG_PROOF_BYTES */,
+                              uint32_t *d_status /* DEVICE, count words */, void *stream);
+/* test hook: the calling thread's last zkg_prover_prove_async — out[0] proofs enqueued, out[1] launch groups, out[2] host waits.  Counters, not clocks. */
+void   zkg_prover_stats(size_t out[3]);
+/* test hook: the proof epilogue alone, on points the caller makes up.  key_points: alpha_g1 | beta_g1 | delta_g1 | A_0 | B1_0 (8 limbs each) |
+ * beta_g2 | delta_g2 | B2_0 (16 each), affine Montgomery, all-zero = infinity.  points: per proof W_a | W_b1 | L | H (12 limbs each, normalised
+ * jac) | W_b2 (24 limbs) — the sums over the witness WITHOUT the constant column, which the epilogue adds; rs: per proof r | s.  HOST pointers;
+ * proofs_out: count x ZKG_PROOF_BYTES.  where 0: the host's assembly (no GPU, no zkg_init) — the specification; 1: the epilogue kernels (needs
+ * zkg_init).  count <= 2^16.  Synchronous.                                                                                                 */
+int    zkg_proof_assemble(const uint64_t *key_points, const uint64_t *points, const uint64_t *rs, size_t count, int where, uint8_t *proofs_out);
 /* ---- many zklaim credentials of ONE resident key, their witnesses generated on the GPU.  ctxs[i] is a zklaim_ctx (include/zklaim_abi.h) whose
  *      payload count is the key's; rs holds (r, s) per item, 8 limbs: r | s, Montgomery Fr.  status[i] and the proof bytes are exactly those of
  *      zkg_groth16_prove_sparse on the host witness of ctxs[i] (zkg_zklaim_witness_new + zkg_circuit_sparse_witness) with the same (r, s).

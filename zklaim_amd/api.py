@@ -44,6 +44,8 @@ DECLARED_SYMBOLS = [
     "zkg_qap_instance_async", "zkg_qap_set_column_segment", "zkg_qap_instance_stats", "zkg_groth16_setup_dev",
     "zkg_msm_host_scalars_stats",
     "zkg_groth16_setup_resident", "zkg_free", "zkg_setup_resident_stats", "zkg_fr_nonzero_index",
+    "zkg_prover_new", "zkg_prover_free", "zkg_prover_batch_max", "zkg_prover_set_batch_max", "zkg_prover_prove_async", "zkg_prover_stats",
+    "zkg_proof_assemble",
 ]
 # the reference's own seam, exported with its original names (zklaim.h:257-259)
 COMPAT_SYMBOLS = ["libsnark_trusted_setup", "libsnark_prove", "libsnark_verify"]
@@ -386,6 +388,64 @@ def qap_stats():
     out = (C.c_size_t * 3)()
     lib().zkg_qap_stats(out)
     return tuple(int(v) for v in out)
+
+
+class Prover:
+    """zkg_prover: proofs of a resident key on the caller's stream — witnesses in device memory in, 134-byte proofs in device memory out, no wait
+    on the host.  The handle borrows `crs` (a Crs, or a raw zkg_crs pointer): free the prover before the key."""
+
+    def __init__(self, crs):
+        L = lib()
+        L.zkg_prover_new.restype = C.c_void_p
+        L.zkg_prover_new.argtypes = [C.c_void_p]
+        L.zkg_prover_free.argtypes = [C.c_void_p]
+        L.zkg_prover_batch_max.restype = C.c_size_t
+        L.zkg_prover_batch_max.argtypes = [C.c_void_p]
+        L.zkg_prover_set_batch_max.argtypes = [C.c_void_p, C.c_size_t]
+        L.zkg_prover_prove_async.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        self._crs = crs                                       # keeps the key alive while the handle lives
+        self._h = L.zkg_prover_new(C.c_void_p(getattr(crs, "_h", crs) or 0))
+        if not self._h:
+            raise ZkgError("zkg_prover_new failed: " + L.zkg_last_error().decode())
+
+    def prove_async(self, d_ptr, stride, count, d_rs, d_proofs, proof_stride, d_status, check_satisfied=True, stream=0):
+        """zkg_prover_prove_async: `count` witnesses of n Montgomery Fr, `stride` elements apart at the device address d_ptr, and (r, s) per item
+        at d_rs (8 limbs: r | s) -> proof i at d_proofs + i * proof_stride and its status word at d_status + 4 i, all DEVICE addresses.  Returns
+        without waiting: synchronise `stream` before reading the result on the host."""
+        _check(lib().zkg_prover_prove_async(C.c_void_p(self._h), _vp(d_ptr), C.c_size_t(stride), C.c_size_t(count), _vp(d_rs), 1 if check_satisfied else 0,
+                                            _vp(d_proofs), C.c_size_t(proof_stride), _vp(d_status), _vp(stream)), "zkg_prover_prove_async")
+
+    def batch_max(self):
+        return int(lib().zkg_prover_batch_max(C.c_void_p(self._h)))
+
+    def set_batch_max(self, k):
+        """test hook: k proofs per launch sequence from now on (0: the default; a larger k is clamped to it)"""
+        lib().zkg_prover_set_batch_max(C.c_void_p(self._h), C.c_size_t(k))
+
+    def free(self):
+        if self._h:
+            lib().zkg_prover_free(C.c_void_p(self._h)); self._h = None
+
+
+def prover_stats():
+    """(proofs enqueued, launch groups, host waits) of the calling thread's last Prover.prove_async"""
+    out = (C.c_size_t * 3)()
+    lib().zkg_prover_stats(out)
+    return tuple(int(v) for v in out)
+
+
+def proof_assemble(key_points, points, rs, where):
+    """zkg_proof_assemble: the proof epilogue alone.  key_points: 88 limbs (alpha_g1 | beta_g1 | delta_g1 | A_0 | B1_0 | beta_g2 | delta_g2 | B2_0,
+    affine); points: count x 72 limbs (W_a | W_b1 | L | H normalised jac, W_b2); rs: count x 8 limbs.  where 0: the host's assemble_proof (no
+    GPU), 1: the epilogue kernels.  Returns count x 134 bytes."""
+    kp, pt, r = _u64(key_points).reshape(-1), _u64(points).reshape(-1, 72), _u64(rs).reshape(-1, 8)
+    if kp.size != 88 or pt.shape[0] != r.shape[0]:
+        raise ZkgError("zkg_proof_assemble: key_points is 88 limbs, points and rs one row per proof")
+    out = np.zeros((pt.shape[0], 134), np.uint8)
+    L = lib()
+    L.zkg_proof_assemble.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    _check(L.zkg_proof_assemble(_p(kp), _p(pt), _p(r), C.c_size_t(pt.shape[0]), int(where), _p(out)), "zkg_proof_assemble")
+    return out
 
 
 def qap_instance_stats():

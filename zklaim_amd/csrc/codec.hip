@@ -18,6 +18,7 @@
 //   linear_combination             : #terms '\n' , (index '\n' coeff(32 B))*
 #include "common.hpp"
 #include "sqrt.hip.hpp"
+#include "record.hip.hpp"
 #include "host/serialize.hpp"
 #include "../../include/zkg.h"
 #include <chrono>
@@ -109,19 +110,7 @@ static int decompress_dev(K kernel, const uint8_t *host_rec, size_t stride, size
 //      resident key of the proofs that follow) and only these records — 34 / 100 bytes instead of 64 / 192 — travel to the host.
 //      A workgroup assembles its 256 records in LDS (byte stores) and writes them out as whole words: a run of records starts 16-byte
 //      aligned in the staging buffer and 256 records are a multiple of four bytes.
-ZK_D void put_fq_bytes(uint8_t *p, const Fq &x) {
-    for (int i = 0; i < 8; ++i) { p[4 * i] = (uint8_t)x.v[i]; p[4 * i + 1] = (uint8_t)(x.v[i] >> 8); p[4 * i + 2] = (uint8_t)(x.v[i] >> 16); p[4 * i + 3] = (uint8_t)(x.v[i] >> 24); }
-}
-ZK_D void put_g1_record(uint8_t *o, const G1Affine &a) {                  // ser::put_g1
-    const bool inf = a.is_inf();
-    const Fq x = inf ? Fq::zero() : a.x.normalized(), y = inf ? Fq::one() : a.y;
-    o[0] = inf ? '1' : '0'; put_fq_bytes(o + 1, x); o[33] = (y.from_mont().v[0] & 1u) ? '1' : '0';
-}
-ZK_D void put_g2_record(uint8_t *o, const G2Affine &a) {                  // ser::put_g2
-    const bool inf = a.is_inf();
-    const Fq2 x = inf ? Fq2::zero() : a.x.normalized(); const Fq y0 = inf ? Fq::one() : a.y.c0;
-    o[0] = inf ? '1' : '0'; put_fq_bytes(o + 1, x.c0); put_fq_bytes(o + 33, x.c1); o[65] = (y0.from_mont().v[0] & 1u) ? '1' : '0';
-}
+//      (put_g1_record / put_g2_record: record.hip.hpp, shared with the proof epilogue of prove_async.hip)
 // REC = 34: record i = G1 in1[i].  REC = 100: record j = G2 in2[idx[j]] then G1 in1[idx[j]] (a knowledge commitment of the sparse B query)
 template <int REC>
 __global__ __launch_bounds__(256) void k_compress_records(const G1Affine *in1, const G2Affine *in2, const uint32_t *idx, size_t n, uint8_t *out) {

@@ -238,6 +238,14 @@ int fixed_base_g2(const G2Affine &base, const uint32_t *d_scalars, size_t n, G2A
 void msm_release_all();
 int msm_configure();
 
+// ---------------- the QAP handle's launch sequence without its argument checks (qap.hip) ----------------
+// zkg_qap_witness_h_async for a caller inside the library whose buffers are its own: same launches, same ordering and growth; stats receives
+// witnesses enqueued, launch groups and host waits, and the calling thread's zkg_qap_stats stay as they are.
+}  // namespace zk
+struct zkg_qap;
+namespace zk {
+int qap_witness_h_enqueue(zkg_qap *q, const void *d_witnesses, size_t stride, size_t count, void *d_h, size_t h_stride, uint32_t *d_unsat, hipStream_t s, size_t stats[3]);
+
 // ---------------- key blobs (codec.hip) ----------------
 // affine points on the device -> the pk blob's compressed records (34 bytes per G1; 100 per knowledge commitment G2 | G1 of the sparse
 // B query, entry idx[j]); d_out: 16-byte aligned device staging for n x 34 (nidx x 100) bytes

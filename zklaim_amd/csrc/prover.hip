@@ -14,6 +14,7 @@
 // sharing one digit sort); the prover randomness (r, s) is an explicit input.
 #include "common.hpp"
 #include "r1cs.hip.hpp"
+#include "proof_assemble.hpp"
 #include "../../include/zkg.h"
 #include "../../include/zklaim_abi.h"
 #include <algorithm>
@@ -112,41 +113,7 @@ struct BatchWs {
     hipEvent_t ev_split = nullptr, ev_flags = nullptr, ev_gathered = nullptr;      // the split's words landed; the mat-vec's flags landed; the witness jobs' scalars gathered
 };
 
-// Host-side fixed-base table of one key element P (alpha_1, beta_1, delta_1, delta_2): entry [j][d-1] = d * 16^j * P, affine.  k * P for a
-// 254-bit k is then 64 mixed additions and no doubling (~20 us for G1) instead of 254 doublings + ~127 additions (~130 us): the products
-// r*delta, s*delta, rs*delta, s*alpha, r*beta that every proof needs cost less than one variable-base multiplication together.
-template <class F> struct CombTable {
-    std::vector<zk::Affine<F>> t;               // 64 x 15
-    void build(const zk::Affine<F> &base) {
-        // all 960 multiples in XYZZ first, then ONE inversion for the lot (Montgomery's trick over their ZZZ): a to_affine per entry was
-        // 960 Fermat inversions, 10 - 25 ms of every key load
-        std::vector<zk::XYZZ<F>> p(64 * 15);
-        zk::XYZZ<F> row = zk::XYZZ<F>::from_affine(base);                        // 16^j * P
-        for (int j = 0; j < 64; ++j) {
-            zk::XYZZ<F> cur = row;
-            for (int d = 1; d <= 15; ++d) { p[j * 15 + d - 1] = cur; cur.add(row); }
-            for (int k = 0; k < 4; ++k) row = row.dbl();
-        }
-        t.assign(64 * 15, zk::Affine<F>::inf());
-        std::vector<F> pre(p.size());
-        F run = F::one();
-        for (size_t i = 0; i < p.size(); ++i) { pre[i] = run; if (!p[i].is_inf()) run = run * p[i].zzz; }
-        F inv = run.inverse();
-        for (size_t i = p.size(); i-- > 0;) {
-            if (p[i].is_inf()) continue;
-            F zi = inv * pre[i];                                                 // 1 / ZZZ_i
-            inv = inv * p[i].zzz;
-            F z1 = zi * p[i].zz, zi2 = z1.sqr();                                 // ZZ / ZZZ = 1 / Z;  1 / ZZ
-            t[i] = zk::Affine<F>{p[i].x * zi2, p[i].y * zi};
-        }
-    }
-    zk::XYZZ<F> mul(const uint32_t k[8]) const {                                  // canonical little-endian scalar
-        zk::XYZZ<F> acc = zk::XYZZ<F>::inf();
-        for (int j = 0; j < 64; ++j) { uint32_t d = (k[j >> 3] >> (4 * (j & 7))) & 15u; if (d) acc.madd(t[j * 15 + d - 1]); }
-        return acc;
-    }
-};
-
+// (CombTable, the fixed-base tables of alpha_1, beta_1, delta_1, delta_2: proof_assemble.hpp, shared with prove_async.hip)
 struct zkg_crs {
     uint32_t n = 0, l = 0, C = 0, log_m = 0; size_t m = 0;
     zk::DevCsr A, B, Cm;
@@ -171,7 +138,7 @@ struct zkg_crs {
     } sub;
     int c_w = 8, c_w_forced = 0;                // window bits of the witness tables (set when they are built), ZKG_TABLE_C_W override
     zk::G1Affine alpha_g1, beta_g1, delta_g1; zk::G2Affine beta_g2, delta_g2;
-    CombTable<zk::Fq> alpha1_comb, beta1_comb, delta1_comb; CombTable<zk::Fq2> delta2_comb;
+    zk::CombTable<zk::Fq> alpha1_comb, beta1_comb, delta1_comb; zk::CombTable<zk::Fq2> delta2_comb;
     zk::NttDomain *dom = nullptr;               // basic_radix2_domain (m = 2^log_m) ...
     zk::StepDomain *sdom = nullptr;             // ... or step_radix2_domain (m = 2^(log_m-1) + 2^b); exactly one is set
     zk::DevBuf coset_over_m, coset_over_m29;    // g^i / m : iFFT post-scale fused with the next cosetFFT's pre-scale (and its 29-bit records)
@@ -190,6 +157,7 @@ struct zkg_crs {
     // zkg_groth16_prove_batch: one chunk workspace per key; batch callers take turns on it (batch_mu, always taken BEFORE a slot lease)
     BatchWs batch; std::mutex batch_mu;
     int device = 0;                             // the device the key was uploaded on (the *_dev prove entries refuse a caller on another one)
+    int provers = 0;                            // live zkg_prover handles (under mu): they hold H_query, so zkg_crs_shard_h refuses while there is one
 };
 
 namespace zk {
@@ -668,6 +636,39 @@ static void slot_destroy(ProverSlot &S) {
     S.ev_ok = false;
     if (S.flag_host) (void)hipHostFree(S.flag_host);
     S.flag_host = nullptr; S.ready = false;
+}
+
+// proof bytes from the four multi-exponentiations' results (W1: A, B_1, L over the whole witness; the same algebra as prove_finish); proof_assemble.hpp
+void assemble_proof(const ProofKey &key, const Fr &r, const Fr &s, const G1 W1[3], const G2 &Wb2, const G1 &Ht, uint8_t *out) {
+    uint32_t rc[8], sc[8], rsc[8];
+    canonical_limbs(r, rc); canonical_limbs(s, sc); canonical_limbs(r * s, rsc);
+    G1 gA = G1::from_affine(key.alpha_g1); gA.add(key.delta1->mul(rc)); gA.add(W1[0]);                   // alpha + r delta + W_a
+    G2 gB2 = G2::from_affine(key.beta_g2); gB2.add(key.delta2->mul(sc)); gB2.add(Wb2);                   // beta + s delta + W_b
+    G1 gC = key.alpha1->mul(sc); gC.add(key.beta1->mul(rc)); gC.add(key.delta1->mul(rsc));               // s alpha + r beta_1 + rs delta
+    gC.add(W1[0].mul(sc, 8)); gC.add(W1[1].mul(rc, 8)); gC.add(W1[2]); gC.add(Ht);                       // + s W_a + r W_b + L + H
+    size_t off = ser_g1(out, gA);
+    off += ser_g2(out + off, gB2);
+    ser_g1(out + off, gC);
+}
+static ProofKey proof_key_of(const zkg_crs *crs) {
+    ProofKey k; k.alpha_g1 = crs->alpha_g1; k.beta_g2 = crs->beta_g2;
+    k.alpha1 = &crs->alpha1_comb; k.beta1 = &crs->beta1_comb; k.delta1 = &crs->delta1_comb; k.delta2 = &crs->delta2_comb;
+    return k;
+}
+// ---- what a zkg_prover handle (prove_async.hip) borrows from the key
+void crs_prover_view(const zkg_crs *crs, CrsProverView &v) {
+    v.n = crs->n; v.l = crs->l; v.C = crs->C; v.m = crs->m; v.device = crs->device; v.h_sharded = !crs->h_shards.empty();
+    const DevCsr *mtx[3] = {&crs->A, &crs->B, &crs->Cm};
+    for (int k = 0; k < 3; ++k) { v.rp[k] = mtx[k]->rowptr.as<uint32_t>(); v.col[k] = mtx[k]->col.as<uint32_t>(); v.val[k] = mtx[k]->val.as<uint64_t>(); v.nnz[k] = mtx[k]->nnz; }
+    v.H = &crs->H_query; v.h_row_merge = h_row_merge(crs);
+    v.A_query = crs->A_query.as<G1Affine>(); v.B_g1 = crs->B_g1.as<G1Affine>(); v.L_query = crs->L_query.as<G1Affine>(); v.B_g2 = crs->B_g2.as<G2Affine>();
+    v.key = proof_key_of(crs);
+}
+bool crs_prover_ref(zkg_crs *crs, int delta) {
+    std::lock_guard<std::mutex> lk(crs->mu);
+    if (delta > 0 && !crs->h_shards.empty()) return false;
+    crs->provers += delta;
+    return true;
 }
 
 }  // namespace zk
@@ -1348,18 +1349,6 @@ static size_t dense_to_sparse(const uint64_t *w, size_t n, uint8_t *tags, uint32
     }
     return cnt;
 }
-// proof bytes from the four multi-exponentiations' results (W1: A, B_1, L over the whole witness; the same algebra as prove_finish)
-static void assemble_proof(const zkg_crs *crs, const Fr &r, const Fr &s, const G1 W1[3], const G2 &Wb2, const G1 &Ht, uint8_t *out) {
-    uint32_t rc[8], sc[8], rsc[8];
-    canonical_limbs(r, rc); canonical_limbs(s, sc); canonical_limbs(r * s, rsc);
-    G1 gA = G1::from_affine(crs->alpha_g1); gA.add(crs->delta1_comb.mul(rc)); gA.add(W1[0]);             // alpha + r delta + W_a
-    G2 gB2 = G2::from_affine(crs->beta_g2); gB2.add(crs->delta2_comb.mul(sc)); gB2.add(Wb2);             // beta + s delta + W_b
-    G1 gC = crs->alpha1_comb.mul(sc); gC.add(crs->beta1_comb.mul(rc)); gC.add(crs->delta1_comb.mul(rsc)); // s alpha + r beta_1 + rs delta
-    gC.add(W1[0].mul(sc, 8)); gC.add(W1[1].mul(rc, 8)); gC.add(W1[2]); gC.add(Ht);                       // + s W_a + r W_b + L + H
-    size_t off = ser_g1(out, gA);
-    off += ser_g2(out + off, gB2);
-    ser_g1(out + off, gC);
-}
 static thread_local size_t t_batch_stats[3] = {0, 0, 0};
 
 // Where a batch's witnesses come from (what WitnessSrc is to a single proof), one kind per entry:
@@ -1554,6 +1543,7 @@ static int prove_chunk(zkg_crs *crs, BatchWs &B, ProverSlot &S, const ChunkSourc
     for (hipStream_t w : B.wst) ZK_HIP(hipStreamSynchronize(w));
     if (jobs && (msm_job_finish_multi(B.job_w1, Wg1.data(), nullptr) || msm_job_finish_multi(B.job_w2, nullptr, Wg2.data()))) return ZKG_ERROR;
     lap("witness jobs landed");
+    const ProofKey pkey = proof_key_of(crs);
     host_parallel_for((int)P, [&](int p) {
         if (!good[p]) return;
         if (check && hw_flags[(size_t)p * BATCH_WORDS]) { status[p] = ZKG_UNSATISFIED; return; }
@@ -1561,7 +1551,7 @@ static int prove_chunk(zkg_crs *crs, BatchWs &B, ProverSlot &S, const ChunkSourc
         for (int i = 0; i < 3; ++i) W1[i].add(B.ones_g1.g1(3 * p + i));
         Wb2.add(B.ones_g2.g2pt(p));
         Fr r, sv; memcpy(r.v, src.r((size_t)p), 32); memcpy(sv.v, src.s((size_t)p), 32);
-        assemble_proof(crs, r, sv, W1, Wb2, Ht[p], proofs_out + (size_t)p * ZKG_PROOF_BYTES);
+        assemble_proof(pkey, r, sv, W1, Wb2, Ht[p], proofs_out + (size_t)p * ZKG_PROOF_BYTES);
         status[p] = ZKG_OK;
     });
     lap("proofs assembled");
@@ -1753,6 +1743,7 @@ static int crs_shard_h_impl(zkg_crs *crs, const int *devices, int ndev) {
     for (int i = 0; i < ndev; ++i) if (devices[i] < 0 || devices[i] >= count) { set_error("zkg_crs_shard_h: bad device index"); return ZKG_ERROR; }
     std::unique_lock<std::mutex> lk(crs->mu);
     if (crs->leases) { set_error("zkg_crs_shard_h: a proof of this key is in flight"); return ZKG_ERROR; }
+    if (crs->provers) { set_error("zkg_crs_shard_h: the key has a live zkg_prover handle (it holds the H table); free it first"); return ZKG_ERROR; }
     int cur = 0; (void)hipGetDevice(&cur);
     struct Restore { int d; ~Restore() { (void)hipSetDevice(d); } } restore{cur};
     crs->home_device = cur;

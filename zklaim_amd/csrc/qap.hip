@@ -305,7 +305,16 @@ static int qap_witness_h_async_impl(zkg_qap *q, const void *d_witnesses, size_t 
         (d_unsat && (ranges_overlap(d_unsat, u_bytes, d_witnesses, w_bytes) || ranges_overlap(d_unsat, u_bytes, d_h, h_bytes)))) {
         set_error(std::string(who) + ": the input and output ranges overlap"); return ZKG_ERROR;
     }
-    hipStream_t s = (hipStream_t)stream;
+    size_t stats[3] = {0, 0, 0};
+    const int rc = zk::qap_witness_h_enqueue(q, d_witnesses, stride, count, d_h, h_stride, d_unsat, (hipStream_t)stream, stats);
+    for (int i = 0; i < 3; ++i) t_qap_stats[i] = stats[i];
+    return rc;
+}
+// The launch sequence alone, for arguments that have been checked: zkg_qap_witness_h_async behind its refusals, and the prover handle
+// (prove_async.hip) on buffers of its own.  stats: witnesses enqueued, launch groups, host waits; no thread-local counter is touched.
+int zk::qap_witness_h_enqueue(zkg_qap *q, const void *d_witnesses, size_t stride, size_t count, void *d_h, size_t h_stride, uint32_t *d_unsat, hipStream_t s, size_t stats[3]) {
+    static const char *who = "zkg_qap_witness_h_async";
+    const size_t m = q->sh.m, u_bytes = count * 4;
     std::lock_guard<std::mutex> lk(q->mu);                              // held for the enqueue only
     NttDomain *nd = nullptr; StepDomain *sd = nullptr;                  // looked up per call (a map find): zkg_shutdown releases them under a live handle
     if (q->sh.step) sd = step_domain(m, s); else nd = ntt_domain(q->sh.log_m, s);
@@ -352,7 +361,7 @@ static int qap_witness_h_async_impl(zkg_qap *q, const void *d_witnesses, size_t 
         if (rc == ZKG_OK && hipGetLastError() != hipSuccess) { set_error(std::string(who) + ": kernel launch failed"); rc = ZKG_ERROR; }
         if (rc == ZKG_OK) { done += g; ++groups; }
     }
-    t_qap_stats[0] = done; t_qap_stats[1] = groups; t_qap_stats[2] = waits;
+    stats[0] = done; stats[1] = groups; stats[2] = waits;
     if (rc == ZKG_OK) { q->order.carried(s); return ZKG_OK; }
     if (enqueued) q->order.record(s);                                   // a failure: what was enqueued before it still runs
     return ZKG_ERROR;
