@@ -56,6 +56,7 @@
 // value there before it compares it with the budget ("amdgpu-num-vgpr" counts the unified file): half the wanted number of VGPRs goes in.
 #define ZK_VGPR_CAP(n) __attribute__((amdgpu_num_vgpr((n) / 2)))
 static constexpr int ACC29_VGPRS = 192;
+static constexpr int ACC29_WG = 64;          // threads per workgroup of k_bucket_accum29: one wavefront (see the kernel)
 
 namespace zk {
 
@@ -664,18 +665,31 @@ __global__ __launch_bounds__(1024) void k_class_hist(const uint32_t *counts, con
 // heavy_out (may be null): a word of pinned host memory that gets the count of heavy buckets — class heavy_t + 1, the lists the accumulation
 // hands to k_heavy_parts / k_heavy_merge under the same threshold — so that a host that paces the launches knows whether that pair has work
 // (msm_g1_host_scalars).
+// recs (may be null: no 29-bit accumulation reads this sort): beside order[p] = gb the kernel leaves a LaneRec at position p — the bucket, where
+// its list starts, how long it is (bit 31: heavy, decided HERE under the threshold the class histogram was counted with) and the list's first
+// entry — everything k_bucket_accum29's lane p needs before its first base, in one coalesced 16-byte load instead of the chain order[p] ->
+// offsets[gb], offsets[gb + 1] -> sorted[start] behind a threshold worked out in every wavefront.  `sorted` is complete when this kernel
+// starts (k_rx_fine / k_place run before it on the same stream).  One coalesced load (offsets[gb]), one gather (sorted[start], requested
+// before the class scan and waited for after it) and one 16-byte store per bucket are all it adds.
+struct alignas(16) LaneRec { uint32_t gb, start, len /* bit 31: heavy */, first /* sorted[start]; 0 for an empty list */; };
+static constexpr uint32_t LANE_HEAVY = 0x80000000u;
 __global__ __launch_bounds__(1024) void k_order_place(const uint32_t *counts, const uint32_t *offsets, size_t total, const uint32_t *class_hist, uint32_t *class_cursor,
-                                                       uint32_t *order, uint32_t *heavy_out) {
+                                                       uint32_t *order, uint32_t *heavy_out, const uint32_t *sorted, LaneRec *recs) {
     sort_wave_priority();
     __shared__ uint32_t h[HEAVY_T_MAX + 2], first[HEAVY_T_MAX + 2], wave_total[16], threshold;
     const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63;
     for (uint32_t i = t; i < HEAVY_T_MAX + 2; i += 1024) h[i] = 0;
     if (t == 0) threshold = heavy_threshold_dev(offsets, total, 1);
+    size_t gb = (size_t)blockIdx.x * 1024 + t;
+    uint32_t c = 0, start = 0, head = 0;
+    if (gb < total) {
+        c = counts[gb];
+        if (recs) { start = offsets[gb]; if (c) head = sorted[start]; }
+    }
     __syncthreads();
     const uint32_t heavy_t = threshold, nc = heavy_t + 2;
-    size_t gb = (size_t)blockIdx.x * 1024 + t;
     uint32_t cls = 0, rank = 0;
-    if (gb < total) { uint32_t c = counts[gb]; cls = c > heavy_t ? heavy_t + 1 : c; rank = atomicAdd(&h[cls], 1u); }
+    if (gb < total) { cls = c > heavy_t ? heavy_t + 1 : c; rank = atomicAdd(&h[cls], 1u); }
     // HEAVY_T_MAX + 2 = 1026 classes at most: thread t takes positions 2t and 2t + 1 of the reversed order
     uint32_t v0 = 0, v1 = 0, incl = 0;
     if (128 * wave < nc) {                                              // (uniform in the wavefront)
@@ -699,7 +713,11 @@ __global__ __launch_bounds__(1024) void k_order_place(const uint32_t *counts, co
     __syncthreads();
     for (uint32_t i = t; i < nc; i += 1024) if (h[i]) h[i] = first[i] + atomicAdd(&class_cursor[i], h[i]);      // reserve a range per class
     __syncthreads();
-    if (gb < total) order[h[cls] + rank] = (uint32_t)gb;
+    if (gb < total) {
+        const uint32_t p = h[cls] + rank;
+        order[p] = (uint32_t)gb;
+        if (recs) *reinterpret_cast<uint4 *>(recs + p) = make_uint4((uint32_t)gb, start, c | (c > heavy_t ? LANE_HEAVY : 0u), head);
+    }
 }
 
 // ---- 6. bucket accumulation (dominant kernel) -------------------------------------------------------------
@@ -762,18 +780,26 @@ ZK_D Rec64 load29_raw(const Rec64 *bases, uint32_t e) { return load_rec64_raw(ba
 // (table launches: the fold in between works on 32-bit limbs).  resume (OUT29 only): the buckets hold the sums of the job's earlier pieces
 // (piece-wise multi-exponentiation, msm_g1_host_scalars): a lane continues its bucket's accumulator, an empty list leaves it alone, and a
 // heavy bucket's old value joins its parts in k_heavy_merge.
+// A lane starts from its LaneRec (k_order_place): no threshold is worked out here (two 64-bit divisions in every wavefront, ~250 scalar
+// instructions in front of the first load of order[]), and the chain order[] -> offsets[] -> sorted[] -> base, four round trips behind the
+// one for the threshold, is two: the record, then the first base with the second index and the bucket.  Counters, one launch alone: 17 - 30 %
+// fewer wave cycles spent waiting, 1 - 4 % fewer wave cycles; the launches' durations fall by 3 - 5 us each, not by the ~60 us per launch
+// that a fit over the four pieces' durations leaves unexplained: the prologue was not that cost.
+// ACC29_WG: the kernel has no LDS and no barrier, so a workgroup is only what the dispatcher hands out and takes back: with four wavefronts
+// a slot is refilled once all four lists are done; one wavefront per workgroup refills each as it ends (traced: the four launches of a step
+// 1366 -> 1292 us with the records, 1366 -> 1347 us without them).
 template <int WAVES, bool OUT29>
-__global__ __launch_bounds__(256, WAVES) ZK_VGPR_CAP(ACC29_VGPRS) void k_bucket_accum29(const Rec64 *bases, size_t level_stride, uint32_t B, const uint32_t *sorted, const uint32_t *offsets, const uint32_t *order,
-                                                         size_t lanes, void *buckets_, HeavyItem *items, HeavyBucket *heavy, uint32_t *counters, SetLayout L, int flags /* 1: resume, 2: critical path */) {
+__global__ __launch_bounds__(ACC29_WG, WAVES) ZK_VGPR_CAP(ACC29_VGPRS) void k_bucket_accum29(const Rec64 *bases, size_t level_stride, uint32_t B, const uint32_t *sorted, const LaneRec *recs,
+                                                         size_t lanes, void *buckets_, HeavyItem *items, HeavyBucket *heavy, uint32_t *counters, int flags /* 1: resume, 2: critical path */) {
     crit_wave_priority(flags & 2);
     const int resume = flags & 1;
     size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (tid >= lanes) return;
-    const uint32_t heavy_t = heavy_threshold_dev(offsets, L.buckets, 1);
-    const uint32_t gb = order[tid];
+    const uint4 rec = *reinterpret_cast<const uint4 *>(recs + tid);             // LaneRec {gb, start, len | heavy flag, first entry}: the lane's first memory instruction
+    const uint32_t gb = rec.x, len = rec.z & ~LANE_HEAVY;
     if (level_stride) bases += (size_t)(gb / B) * level_stride;
-    uint32_t k = offsets[gb], end = offsets[gb + 1];
-    if (end - k > heavy_t) {                                                    // as k_bucket_accum: long lists go to k_heavy_parts / k_heavy_merge
+    uint32_t k = rec.y, end = k + len;
+    if (rec.z & LANE_HEAVY) {                                                   // as k_bucket_accum: long lists go to k_heavy_parts / k_heavy_merge (k_order_place applied the threshold)
         uint32_t nparts = (end - k + HEAVY_S - 1) / HEAVY_S;
         uint32_t first = atomicAdd(&counters[0], nparts);
         const bool single = nparts == 1 && !resume;                             // a lone part may write its bucket itself only when nothing is there yet
@@ -783,6 +809,12 @@ __global__ __launch_bounds__(256, WAVES) ZK_VGPR_CAP(ACC29_VGPRS) void k_bucket_
     }
     XYZZ29 acc; bool inf = true;
     acc.x = acc.y = acc.zz = acc.zzz = Fq29::zero();
+    // Everything the first addition needs is requested on the record alone, before anything is waited for: the first entry came with the
+    // record, so its base, the second index and, under resume, the bucket go out together — two round trips in front of the first addition
+    // (the loop's first turn requests the third index before it waits for the second)
+    uint32_t e = rec.w, e_next = 0;
+    Rec64 p;                                                                    // (kept packed while in flight: unpacked when its addition starts)
+    if (k < end) { if (k + 1 < end) e_next = sorted[k + 1]; p = load29_raw(bases, e); }
     if constexpr (OUT29) {
         if (resume) {
             if (k >= end) return;                                               // nothing of this piece lands here: the bucket keeps its sum
@@ -796,8 +828,6 @@ __global__ __launch_bounds__(256, WAVES) ZK_VGPR_CAP(ACC29_VGPRS) void k_bucket_
     if (k < end) {
         // two loads deep: under the addition of entry k the base of entry k + 1 arrives (its address came from an index loaded one
         // addition earlier) and the index of entry k + 2 — neither the index nor the base is ever waited for right after it was requested
-        uint32_t e = sorted[k], e_next = k + 1 < end ? sorted[k + 1] : 0;
-        Rec64 p = load29_raw(bases, e);                                         // (kept packed while in flight: unpacked when its addition starts)
         while (true) {
             const Rec64 curw = p; const uint32_t ce = e;
             ++k;
@@ -1396,8 +1426,9 @@ struct MsmGroup {                   // the base sets of one field in a launch: a
 // the heavy-list counters of the launch's two fields — the sort's first kernel clears them (ZeroList), so they go with the sort's buffers: a sort
 // that runs beside the accumulation of the launch before it (msm_g1_host_scalars) must not clear the counters that one is filling.
 struct MsmSortSpace {
-    DevBuf digits, hist, counts, offsets, scan_sums, class_hist, order, sorted, rx_tmp, rx_meta, heavy_counters[2];
-    void release() { for (DevBuf *b : {&digits, &hist, &counts, &offsets, &scan_sums, &class_hist, &order, &sorted, &rx_tmp, &rx_meta, &heavy_counters[0], &heavy_counters[1]}) b->release(); }
+    DevBuf digits, hist, counts, offsets, scan_sums, class_hist, order, lane_recs, sorted, rx_tmp, rx_meta, heavy_counters[2];
+    bool has_lane_recs = false;        // the sort enqueued last wrote lane_recs (a lone G1 set: what k_bucket_accum29 can follow)
+    void release() { for (DevBuf *b : {&digits, &hist, &counts, &offsets, &scan_sums, &class_hist, &order, &lane_recs, &sorted, &rx_tmp, &rx_meta, &heavy_counters[0], &heavy_counters[1]}) b->release(); }
 };
 // What belongs to ONE launch and not to the job: passed by value through both halves of a launch, nothing of it is kept on the job.
 struct MsmLaunchMode {
@@ -1515,7 +1546,8 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmLaunchSets &ls,
     // — where the rows are few (8 after the row merge of the large tables: a bucket's rows are added in sequence, 4 us each; a one-payload key's 22
     // rows of 2048 buckets keep the 32-bit fold, a tree over the rows: 0.75 against 0.83 ms per proof)
     const bool out29 = use29 && (stride29 == 0 ? !gr.table : (gr.table && ns == 1 && Wp <= 8));
-    const int resume = mode.resume ? 1 : 0;                                     // (msm_g1_host_scalars' pieces: one plain G1 set with its records, so use29 and out29 hold)
+    if (use29 && !sp.has_lane_recs) { set_error("msm: the sort left no lane records for the 29-bit accumulation"); return ZKG_ERROR; }
+    const int resume = mode.resume ? 1 : 0;                                   // (msm_g1_host_scalars' pieces: one plain G1 set with its records, so use29 and out29 hold)
     if (time_it) g_dominant_timer.begin(s);
     if constexpr (sizeof(F) == sizeof(Fq)) {
         // wavefronts per SIMD: three (168 registers; the loop has no spill either way) when the launch has the chip to itself — a plain set sorted on
@@ -1526,9 +1558,9 @@ static int launch_accumulate(MsmJob *job, MsmGroup &gr, const MsmLaunchSets &ls,
         //  alternating runs each, one of the three pairs the other way round — inside the runs' own spread, so it keeps the two)
         const int waves29 = waves_env ? waves_env : (mode.beside || gr.table) ? 2 : 3;
         auto launch29 = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, rec29, stride29, BP, sp.sorted.as<uint32_t>(),
-                               sp.offsets.as<uint32_t>(), sp.order.as<uint32_t>(), lanes, (void *)buckets, gr.heavy_items.as<HeavyItem>(),
-                               gr.heavy_buckets.as<HeavyBucket>(), heavy_counters, L, resume | (job->critical ? 2 : 0));
+            hipLaunchKernelGGL(kern, dim3((unsigned)((lanes + ACC29_WG - 1) / ACC29_WG)), dim3(ACC29_WG), 0, s, rec29, stride29, BP, sp.sorted.as<uint32_t>(),
+                               sp.lane_recs.as<LaneRec>(), lanes, (void *)buckets, gr.heavy_items.as<HeavyItem>(),
+                               gr.heavy_buckets.as<HeavyBucket>(), heavy_counters, resume | (job->critical ? 2 : 0));
         };
         if (use29 && waves29 == 3) { if (out29) launch29(k_bucket_accum29<3, true>); else launch29(k_bucket_accum29<3, false>); }
         else if (use29) { if (out29) launch29(k_bucket_accum29<2, true>); else launch29(k_bucket_accum29<2, false>); }
@@ -1760,6 +1792,9 @@ static int sort_digits(MsmJob *job, MsmLaunchSets &ls, const uint32_t *d_scalars
     if (sp.digits.reserve(std::max<size_t>(1, n * g.W) * 4) || sp.hist.reserve((size_t)g.W * S * g.B * 4) || sp.counts.reserve(total * 4) ||
         sp.offsets.reserve((total + 1) * 4) || sp.scan_sums.reserve(1024 * 4) || sp.class_hist.reserve((CLASS_HIST_COPIES + 1) * (HEAVY_T_MAX + 2) * 4) ||
         sp.order.reserve(total * 4) || sp.sorted.reserve(std::max<size_t>(1, n * g.W) * 4)) return ZKG_ERROR;
+    // a lone G1 set is what the 29-bit accumulation takes (launch_accumulate): only then does k_order_place write the lanes' records
+    sp.has_lane_recs = job->group[0].nsets == 1;
+    if (sp.has_lane_recs && sp.lane_recs.reserve(total * sizeof(LaneRec))) return ZKG_ERROR;
     uint32_t *digits = sp.digits.as<uint32_t>(), *hist = sp.hist.as<uint32_t>(), *counts = sp.counts.as<uint32_t>(),
              *offsets = sp.offsets.as<uint32_t>(), *sums = sp.scan_sums.as<uint32_t>(), *chist = sp.class_hist.as<uint32_t>();
     uint32_t cbits = 6;
@@ -1825,7 +1860,8 @@ static int sort_digits(MsmJob *job, MsmLaunchSets &ls, const uint32_t *d_scalars
     hipLaunchKernelGGL(k_place, dim3(S, g.W), dim3(SORT_THREADS), g.B * 4, s, digits, n, g.B, S, slice_len, hist, offsets, sp.sorted.as<uint32_t>());
     hipLaunchKernelGGL(k_class_hist, dim3((unsigned)((total + 1023) / 1024)), dim3(1024), 0, s, counts, offsets, total, chist);
     }
-    hipLaunchKernelGGL(k_order_place, dim3((unsigned)((total + 1023) / 1024)), dim3(1024), 0, s, counts, offsets, total, chist, chist + CLASS_HIST_COPIES * (HEAVY_T_MAX + 2), sp.order.as<uint32_t>(), mode.heavy_out);
+    hipLaunchKernelGGL(k_order_place, dim3((unsigned)((total + 1023) / 1024)), dim3(1024), 0, s, counts, offsets, total, chist, chist + CLASS_HIST_COPIES * (HEAVY_T_MAX + 2), sp.order.as<uint32_t>(), mode.heavy_out,
+                       sp.sorted.as<uint32_t>(), sp.has_lane_recs ? sp.lane_recs.as<LaneRec>() : nullptr);
     if (hipGetLastError() != hipSuccess) { set_error("msm sort launch failed"); return ZKG_ERROR; }
     return ZKG_OK;
 }
